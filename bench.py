@@ -18,7 +18,13 @@ ranks, barrier + synchronize on both sides).  Weak scaling: every rank owns its 
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the configuration, the
+last step's loss).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): its losses and
+statistics (`out.*`, of the step's last micro-batch) and every parameter and gradient after it (`param.*`, `grad.*`; about
+10 MB); the inputs depend only on the arguments, so two builds can be compared array for array.  Everything else below is
+measured only with `--full`.
+
+Extra objects on the JSON line with --full:
   roofline     -- the dominant kernel FAMILY of the step: the MLP matrix kernels (gemm_f16_kernel / gemm_split_kernel activation GEMMs with
                   their epilogues + wgrad_split_kernel weight gradients, ~90 % of the step).  `achieved` = ISSUED matrix-instruction TFLOP/s
                   (three fp16 piece products per fp32 product) over the time of the family's launches, by HIP events recorded on the launch
@@ -126,8 +132,18 @@ def parse_args():
     ap.add_argument("--lib", default=None, help="developer A/B: another build of librqhip.so (same ABI) instead of the in-tree one")
     ap.add_argument("--no-narrow", action="store_true", help="A/B: layers of 128 (mod 256) columns on the library instead of the split kernel's 128-column tile")
     ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="if the K timed steps took less, also time a longer region and report it as `long_run`")
-    return ap.parse_args()
+                    help="--full: if the K timed steps took less, also time a longer region and report it as `long_run`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (untimed): HIP-event records in the timed region, "
+                         "long_run, rooflines, per-kernel figures, breakdown, secondary scopes, box calibration, parity gate, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.pmc_window and not args.full:
+        ap.error("--pmc-window is a profiling leg of --full")
+    return args
 
 
 def build_model(device, x_init, levels, codes):
@@ -360,6 +376,22 @@ def _sha256_file(path):
     return h.hexdigest()
 
 
+def dump_outputs(path, out, model):
+    """--dump-outputs: what a caller of the step receives from its last call -- the RqVaeComputedLosses it returns and the
+    parameters and gradients it leaves -- one DIR/<name>.npy each, float32 (float64 arrays stay float64)."""
+    import numpy as np
+    import torch
+    arrays = {f"out.{k}": v for k, v in out._asdict().items() if v is not None}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def main():
     args = parse_args()
     n_ranks = args.dry_ranks if args.dry_ranks > 1 else args.gpus
@@ -448,39 +480,104 @@ def main():
 
     for _ in range(args.warmup):
         out = step()
-    # the timed region records the kernels that ARE the step -- the MLP GEMM / weight-gradient family -- in its FIRST n_rec steps only:
-    # ~21 event pairs per step cost 5 % of a 2.8 ms step (K-step 2.90 ms vs 2.76 ms unrecorded, profiles/r05_bench_n1.json's long_run)
-    n_rec = min(steps, 4 if steps >= 100 else 2)     # (short regions -- the driver's K = 20 -- record two steps: the pairs are 1 % of such a region)
-    n_fam = n_rec * n_micro * 26 + 64
-    ops.profile_enable(n_fam)
-    ops.profile_select("gemm_split", "wgrad")
-    if world > 1:
-        reducer.enable_timing()
+    if args.full:
+        # the timed region records the kernels that ARE the step -- the MLP GEMM / weight-gradient family -- in its FIRST n_rec steps only:
+        # ~21 event pairs per step cost 5 % of a 2.8 ms step (K-step 2.90 ms vs 2.76 ms unrecorded, profiles/r05_bench_n1.json's long_run)
+        n_rec = min(steps, 4 if steps >= 100 else 2)     # (short regions -- K = 20 -- record two steps: the pairs are 1 % of such a region)
+        n_fam = n_rec * n_micro * 26 + 64
+        ops.profile_enable(n_fam)
+        ops.profile_select("gemm_split", "wgrad")
+        if world > 1:
+            reducer.enable_timing()
     rqdist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for si in range(steps):
-        if si == n_rec:
+        if args.full and si == n_rec:
             ops.profile_select("none")      # (a host-side flag: no further records, no synchronisation)
         out = step()
     torch.cuda.synchronize()
     rqdist.barrier()
     elapsed = time.perf_counter() - t0
-    exposed = reducer.exposed_ms() if world > 1 else []
-    reducer.enable_timing(False)
-    exposed_all = None
-    if world > 1:    # every rank's mean exposed all-reduce time (device events, host clock), gathered on all ranks
-        mine = torch.tensor([float(np.mean([d for d, _ in exposed])) if exposed else 0.0,
-                             float(np.mean([h for _, h in exposed])) if exposed else 0.0], device=device, dtype=torch.float64)
-        parts = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(parts, mine)
-        exposed_all = [[round(float(p[0]), 4), round(float(p[1]), 4)] for p in parts]
-    fam_records = ops.profile_read_tagged(n_fam)
-    ops.profile_enable(0)
+    if args.full:
+        exposed = reducer.exposed_ms() if world > 1 else []
+        reducer.enable_timing(False)
+        exposed_all = None
+        if world > 1:    # every rank's mean exposed all-reduce time (device events, host clock), gathered on all ranks
+            mine = torch.tensor([float(np.mean([d for d, _ in exposed])) if exposed else 0.0,
+                                 float(np.mean([h for _, h in exposed])) if exposed else 0.0], device=device, dtype=torch.float64)
+            parts = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine)
+            exposed_all = [[round(float(p[0]), 4), round(float(p[1]), 4)] for p in parts]
+        fam_records = ops.profile_read_tagged(n_fam)
+        ops.profile_enable(0)
     if dist.is_initialized():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    value = B * world * steps / elapsed
+    ms_per_step = elapsed / steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
+
+    # ---- the headline line: all a plain run reports ------------------------------------------------------------------
+    line = None
+    if rank == 0:
+        from rqhip import _lib as _rqlib
+        lib_sha = _sha256_file(os.path.abspath(args.lib) if args.lib else _rqlib.SO_PATH)
+        workload = {
+            "c2": "C2: synthetic 100000x768 unit-norm items per GPU -> RQ-VAE 768-[512,256,128]-32, 3x256 codebooks, "
+                  "STE (Gumbel off), one fwd+bwd+allreduce+AdamW step per HBM-resident batch",
+            "c4": "C4: synthetic 10Mx768 items sharded over 8 GPUs = 1250000 rows per GPU (seed 1234+rank) -> RQ-VAE "
+                  "768-[512,256,128]-32, 4x1024 codebooks, STE; one step = the whole shard as 10 micro-batches of "
+                  "125000 rows (gradient accumulation), one flat gradient all-reduce, one AdamW update",
+        }[args.config]
+        line = {
+            "metric": "item-embeddings quantized/sec (RQ-VAE fwd+bwd)",
+            "value": round(value, 1), "unit": "items/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": {"split": "f32 (MLP GEMMs f16x2-emulated)", "split6": "f32 (MLP GEMMs bf16x3-emulated)", "library": "f32"}[args.mlp],
+            "data": "synthetic",
+            "config": {"workload": workload, "name": args.config, "rows_per_gpu_per_step": B, "micro_batch_rows": micro,
+                       "levels": LEVELS, "codebook_size": CODES, "embed_dim": EMBED,
+                       "parallelism": f"row-shard x{world}, 1 flat grad all-reduce per step (RCCL)"},
+            "arithmetic": {"split": "f16x2: MLP GEMMs and weight gradients as two fp16 pieces per fp32 operand (11 + 11 significant "
+                                    "bits + sign) under exact power-of-two row / column scales, products hh + hm + mh on "
+                                    "v_mfma_f32_32x32x16_f16, fp32 accumulation -- an emulation of fp32 GEMMs held to `max error "
+                                    "vs fp64 <= the library fp32 GEMM's` on every operand family of tests/test_gpu_gemm_split.py; "
+                                    "the RQ kernels are fp32 (bit-exact vs the oracle)",
+                           "split6": "bf16x3: three exact bf16 pieces per operand, six products (round 3)",
+                           "library": "fp32 library GEMMs + fp32-MFMA weight gradients (round 2)"}[args.mlp],
+            "rccl_ranks": 0 if dry else world,
+            "dry_ranks": world if dry else 0,
+            "mlp_gemms": (f"--mlp {args.mlp} (see `arithmetic`); layers of 128 (mod 128) output columns on the split kernels"
+                          + (" (128 (mod 256) on the library: --no-narrow)" if args.no_narrow else "")
+                          + ("; the 32-wide layers either side of the quantiser: the seam kernel (rqhip_rq_seam: fused with the levels in the "
+                             "forward, stand-alone with the ReLU backward / maxima epilogues as the data gradients; fp32 FMA chains), their weight "
+                             "gradients fp32-MFMA kernels" if (not args.no_seam and micro >= 4096 and args.mlp != "library") else
+                             "; the 32-wide layers: PyTorch-ROCm fp32 GEMMs (matmul precision highest), TunableOp selections "
+                             + ("loaded" if tuned else "off"))),
+            "input_scales": ("the per-row maxima the fp16-split GEMMs scale by come with the resident item matrix (computed once per corpus, "
+                             "data/processed.py:ItemData._corpus_maxima; the first layer's weight gradient uses corpus-wide column bounds): no maxima "
+                             "pass over the input batch inside the step" if (not args.no_input_scales and args.mlp == "split" and micro >= 4096)
+                             else "a maxima pass over the input batch inside every step (round 4; --no-input-scales)"),
+            "final_loss": round(float(out.loss.detach()), 6), "p_unique_ids": round(float(out.p_unique_ids), 6),
+            "librqhip_sha256": lib_sha,
+        }
+        if dry:
+            line["config"]["parallelism"] = f"DRY RUN: {world} ranks on ONE GPU over gloo -- plumbing rehearsal, not a scaling number"
+            line["n_physical_gpus"] = 1
+    if not args.full:
+        if rank == 0:
+            json_out.write(json.dumps(line) + "\n")
+            json_out.flush()
+        rqdist.barrier()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here --------------------------------------------------------------------------------------------
     # a K-step region shorter than --min-seconds (the driver's K = 20 at 5 ms) is re-measured over a longer one, same
     # protocol; every rank takes the same decision from the reduced time
     long_run = None
@@ -623,9 +720,6 @@ def main():
         kmeans_only_s = time.perf_counter() - tk
 
     if rank == 0:
-        items = B * world * steps
-        value = items / elapsed
-        ms_per_step = elapsed / steps * 1e3
         flops_per_row = LEVELS * (2 * EMBED * CODES + 5 * EMBED)            # 49 632 (c2), 262 784 (c4)
         mlp_fwd = 2 * 2 * (INPUT_DIM * HIDDEN[0] + HIDDEN[0] * HIDDEN[1] + HIDDEN[1] * HIDDEN[2] + HIDDEN[2] * EMBED)
         # backward = 2 x forward minus the first layer's input gradient, which is never formed
@@ -639,8 +733,6 @@ def main():
             bytes_per_row = 4 * 128 + 4 * EMBED + 8 * LEVELS + 4 * EMBED + 4 + 4 * LEVELS + 4 * 128
             achieved = rq_flops_row * Bm / (mean_ms * 1e-3) / 1e12
         traffic, traffic_src = None, None
-        from rqhip import _lib as _rqlib
-        lib_sha = _sha256_file(os.path.abspath(args.lib) if args.lib else _rqlib.SO_PATH)
         import glob as _glob
         def _newest(pattern):     # profiles/r0N_<pattern>: the newest round first
             return sorted(_glob.glob(os.path.join(ROOT, "profiles", pattern)), reverse=True)
@@ -773,23 +865,7 @@ def main():
                                if fam_cov else pmc_k_src),
             "dominant_member": dom,
         }
-        workload = {
-            "c2": "C2: synthetic 100000x768 unit-norm items per GPU -> RQ-VAE 768-[512,256,128]-32, 3x256 codebooks, "
-                  "STE (Gumbel off), one fwd+bwd+allreduce+AdamW step per HBM-resident batch",
-            "c4": "C4: synthetic 10Mx768 items sharded over 8 GPUs = 1250000 rows per GPU (seed 1234+rank) -> RQ-VAE "
-                  "768-[512,256,128]-32, 4x1024 codebooks, STE; one step = the whole shard as 10 micro-batches of "
-                  "125000 rows (gradient accumulation), one flat gradient all-reduce, one AdamW update",
-        }[args.config]
-        line = {
-            "metric": "item-embeddings quantized/sec (RQ-VAE fwd+bwd)",
-            "value": round(value, 1), "unit": "items/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"split": "f32 (MLP GEMMs f16x2-emulated)", "split6": "f32 (MLP GEMMs bf16x3-emulated)", "library": "f32"}[args.mlp],
-            "data": "synthetic",
-            "config": {"workload": workload, "name": args.config, "rows_per_gpu_per_step": B, "micro_batch_rows": micro,
-                       "levels": LEVELS, "codebook_size": CODES, "embed_dim": EMBED,
-                       "parallelism": f"row-shard x{world}, 1 flat grad all-reduce per step (RCCL)"},
+        line.update({
             "roofline": roofline_family,
             "roofline_rq": {"kernel": (f"rq_seam_kernel<STE> = 128->{EMBED} GEMM + rq_forward's filtered scan ({LEVELS}x{CODES}) + {EMBED}->128 GEMM + ReLU, "
                                        f"{Bm} rows/launch (csrc/rq_forward.hip)" if seam_fused
@@ -830,20 +906,11 @@ def main():
                                                 "fp32_equivalent_frac: all GEMM + RQ FLOPs of fwd+bwd per GPU / ms_per_step / "
                                                 "157.3 -- above 1 is possible, the kernels do not use the fp32 pipe"}},
             "roofline_kernels": roofline_kernels,
-            "arithmetic": {"split": "f16x2: MLP GEMMs and weight gradients as two fp16 pieces per fp32 operand (11 + 11 significant "
-                                    "bits + sign) under exact power-of-two row / column scales, products hh + hm + mh on "
-                                    "v_mfma_f32_32x32x16_f16, fp32 accumulation -- an emulation of fp32 GEMMs held to `max error "
-                                    "vs fp64 <= the library fp32 GEMM's` on every operand family of tests/test_gpu_gemm_split.py; "
-                                    "the RQ kernels are fp32 (bit-exact vs the oracle)",
-                           "split6": "bf16x3: three exact bf16 pieces per operand, six products (round 3)",
-                           "library": "fp32 library GEMMs + fp32-MFMA weight gradients (round 2)"}[args.mlp],
             "breakdown_ms": {"rows": Bm, "encoder_fwd": round(enc_ms, 3), "rq_forward_call": round(rq_ms, 3),
                              "model_fwd_total": round(fwd_ms, 3), "backward_total": round(bwd_ms, 3),
                              "allreduce_ms": round(allreduce_ms, 4), "adamw": round(opt_ms, 3),
                              "first_forward_with_kmeans_init_s": round(kmeans_s, 3),
                              "kmeans_init_s": round(kmeans_only_s, 4)},
-            "rccl_ranks": 0 if dry else world,
-            "dry_ranks": world if dry else 0,
             "allreduce": {"exposed_ms_per_rank_device_host": exposed_all,
                           "overlap_launches": reducer_overlaps,
                           "what": "per rank, mean over the timed steps: the part of the step's gradient reduction that is NOT hidden under the "
@@ -855,25 +922,10 @@ def main():
                           "tokenize_items_per_s": round(Bm / tok_ms * 1e3, 1), "tokenize_ms": round(tok_ms, 4),
                           "note": "per GPU; S-rq = HIP quantisation stack fwd+bwd on 32-d latents, tokenize = "
                                   "get_semantic_ids (encoder GEMMs + HIP RQ, eval)"},
-            "mlp_gemms": (f"--mlp {args.mlp} (see `arithmetic`); layers of 128 (mod 128) output columns on the split kernels"
-                          + (" (128 (mod 256) on the library: --no-narrow)" if args.no_narrow else "")
-                          + ("; the 32-wide layers either side of the quantiser: the seam kernel (rqhip_rq_seam: fused with the levels in the "
-                             "forward, stand-alone with the ReLU backward / maxima epilogues as the data gradients; fp32 FMA chains), their weight "
-                             "gradients fp32-MFMA kernels" if (not args.no_seam and micro >= 4096 and args.mlp != "library") else
-                             "; the 32-wide layers: PyTorch-ROCm fp32 GEMMs (matmul precision highest), TunableOp selections "
-                             + ("loaded" if tuned else "off"))),
-            "input_scales": ("the per-row maxima the fp16-split GEMMs scale by come with the resident item matrix (computed once per corpus, "
-                             "data/processed.py:ItemData._corpus_maxima; the first layer's weight gradient uses corpus-wide column bounds): no maxima "
-                             "pass over the input batch inside the step" if (not args.no_input_scales and args.mlp == "split" and micro >= 4096)
-                             else "a maxima pass over the input batch inside every step (round 4; --no-input-scales)"),
             "final_loss": round(final_loss, 6), "p_unique_ids": round(p_unique, 6),
-            "librqhip_sha256": lib_sha,
-        }
+        })
         if long_run is not None:
             line["long_run"] = long_run
-        if dry:
-            line["config"]["parallelism"] = f"DRY RUN: {world} ranks on ONE GPU over gloo -- plumbing rehearsal, not a scaling number"
-            line["n_physical_gpus"] = 1
         del model, opt, reducer, batches, X
         torch.cuda.empty_cache()
         line["box"] = box_calibration(device)

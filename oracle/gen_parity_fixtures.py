@@ -40,6 +40,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle import gen_golden  # noqa: E402
 from oracle import rq_oracle as o  # noqa: E402
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+import parity_gate  # noqa: E402  (the fixture layout: files below 1 MiB)
 
 OUT = os.path.join(HERE, "..", "tests", "golden")
 INPUT_DIM, HIDDEN, EMBED, BETA = 768, [512, 256, 128], 32, 0.25
@@ -207,9 +209,9 @@ def make_case(tag: str, n_rows: int, K: int, L: int, n_latent_rows: int, q, r, k
           f"{[float(f'{m:.2e}') for m in marg]}", flush=True)
     assert (marg < TAU).all()
 
-    path = os.path.join(OUT, f"parity_{tag}.npz")
-    np.savez_compressed(path, **save)
-    print(f"[{tag}] wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB, {time.time() - t0:.0f} s)", flush=True)
+    paths = parity_gate.save_fixture(tag, save, OUT)
+    print(f"[{tag}] wrote {len(paths)} files under {OUT} ({sum(os.path.getsize(p) for p in paths) / 1024:.0f} KiB, "
+          f"{time.time() - t0:.0f} s)", flush=True)
 
 
 def main():

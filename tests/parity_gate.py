@@ -34,8 +34,45 @@ def sha(a) -> str:
     return hashlib.sha256(a.view(np.uint8).reshape(-1)).hexdigest()
 
 
+# No committed file may exceed 1 MiB: save_fixture moves every array larger than PIECE_BYTES out of parity_<tag>.npz into
+# parity_<tag>.<name>.<i>.npz, cut along its first axis into pieces of at most PIECE_BYTES; load_fixture joins them again.
+FILE_LIMIT_BYTES = 1 << 20
+PIECE_BYTES = 768 << 10
+
+
 def load_fixture(tag: str) -> Dict[str, np.ndarray]:
-    return dict(np.load(os.path.join(GOLDEN_DIR, f"parity_{tag}.npz")))
+    fx = dict(np.load(os.path.join(GOLDEN_DIR, f"parity_{tag}.npz")))
+    pieces: Dict[str, Dict[int, np.ndarray]] = {}
+    prefix = f"parity_{tag}."
+    for f in os.listdir(GOLDEN_DIR):
+        if f.startswith(prefix) and f.endswith(".npz") and f.count(".") == 3:
+            name, i = f[len(prefix):-len(".npz")].split(".")
+            with np.load(os.path.join(GOLDEN_DIR, f)) as z:
+                pieces.setdefault(name, {})[int(i)] = z[name]
+    for name, p in pieces.items():
+        assert name not in fx and sorted(p) == list(range(len(p))), (tag, name, sorted(p))
+        fx[name] = np.concatenate([p[i] for i in range(len(p))])
+    return fx
+
+
+def save_fixture(tag: str, arrays: Dict[str, np.ndarray], out_dir: str = GOLDEN_DIR) -> list:
+    """Write `arrays` in the layout load_fixture reads; returns the paths written (each checked to be below 1 MiB)."""
+    main, paths = {}, []
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.nbytes <= PIECE_BYTES or a.ndim == 0:
+            main[name] = a
+            continue
+        assert "." not in name, name
+        n = -(-a.nbytes // PIECE_BYTES)
+        for i, piece in enumerate(np.array_split(a, n)):
+            paths.append(os.path.join(out_dir, f"parity_{tag}.{name}.{i}.npz"))
+            np.savez_compressed(paths[-1], **{name: piece})
+    paths.append(os.path.join(out_dir, f"parity_{tag}.npz"))
+    np.savez_compressed(paths[-1], **main)
+    for p in paths:
+        assert os.path.getsize(p) < FILE_LIMIT_BYTES, (p, os.path.getsize(p))
+    return paths
 
 
 def synthetic_items(n: int, seed: int = 1234) -> torch.Tensor:

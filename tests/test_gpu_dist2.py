@@ -318,7 +318,7 @@ def test_bench_dry_ranks_line_is_consistent():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-ranks", "2", "--batch", "8192", "--steps", "4", "--warmup", "1",
-           "--no-cpu-baseline", "--no-parity", "--no-small-batch", "--min-seconds", "0.3"]
+           "--full", "--no-cpu-baseline", "--no-parity", "--no-small-batch", "--min-seconds", "0.3"]
     pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=540, env=env)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]

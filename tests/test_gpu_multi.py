@@ -41,7 +41,7 @@ def _clean_env():
 def test_bench_two_gpus_line():
     """(i) The driver's SCALE command at N = 2 (`python bench.py --gpus 2` relaunches itself under torch.distributed.run)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--batch", "16384",
-           "--no-cpu-baseline", "--no-parity", "--no-small-batch", "--min-seconds", "0.3"]
+           "--full", "--no-cpu-baseline", "--no-parity", "--no-small-batch", "--min-seconds", "0.3"]
     pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=800, env=_clean_env())
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]

@@ -264,6 +264,23 @@ def test_bench_relaunches_itself_under_torchrun_for_multi_gpu(monkeypatch):
     assert bench.CONFIGS["c4"]["rows"] == 1_250_000 and bench.CONFIGS["c4"]["codes"] == 1024
 
 
+def test_bench_options_of_the_plain_run(monkeypatch):
+    """`python bench.py` measures only its headline unless --full is given; --steps sets the timed steps; --pmc-window is a --full leg."""
+    import importlib
+    import sys
+    import pytest
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "outs"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, "outs")
+    for bad in (["--pmc-window", "tags.json"], ["--steps", "0"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *bad])
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--pmc-window", "tags.json"])
+    assert bench.parse_args().full
+
+
 def test_loss_scale_hint_nests_and_restores():
     """rqhip.autograd.loss_scale: the hint for the speculative reconstruction-loss gradient is a plain nesting context
     manager -- restored on exit and on exceptions (a stale value would only cost speed, but it must not leak)."""

@@ -3,7 +3,7 @@
 REPO="${GRAFT_REPO_ROOT:-$(pwd)}"; OUT="$REPO/gpurun_out/prof_c2ab_r06"; mkdir -p "$OUT"; cd /tmp && export TMPDIR=/tmp
 for arm in seam noseam; do
   flag=""; [ $arm = noseam ] && flag="--no-seam"
-  timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$arm" -o c2 -- python "$REPO/bench.py" --steps 40 --warmup 3 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 $flag > "$OUT/$arm.json" 2> "$OUT/$arm.err"
+  timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$arm" -o c2 -- python "$REPO/bench.py" --full --steps 40 --warmup 3 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 $flag > "$OUT/$arm.json" 2> "$OUT/$arm.err"
   f=$(find "$OUT/$arm" -name "*kernel_stats.csv" | head -1)
   echo "== $arm"; python - "$f" <<'PY'
 import csv, sys

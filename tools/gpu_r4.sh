@@ -6,7 +6,7 @@ O=gpurun_out/$TAG; mkdir -p $O; R=$GRAFT_REPO_ROOT
 TESTS=${@:-tests/test_gpu_gemm_split.py tests/test_gpu_wgrad.py tests/test_gpu_modules.py}
 timeout 900 python -m pytest $TESTS -x -q > $O/pytest.log 2>&1; tail -15 $O/pytest.log
 for arm in split split6; do
-timeout 300 python bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-parity --min-seconds 0 --mlp $arm 2>$O/bench_$arm.err | tail -1 > $O/bench_$arm.json
+timeout 300 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-parity --min-seconds 0 --mlp $arm 2>$O/bench_$arm.err | tail -1 > $O/bench_$arm.json
 python - $O/bench_$arm.json $arm <<'PY'
 import json, sys
 try:
@@ -23,7 +23,7 @@ except Exception as ex:
 PY
 done 2>&1 | tee $O/bench_step.log
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_step -o p -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-parity --min-seconds 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_step -o p -- python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-parity --min-seconds 0 > /dev/null 2>&1
 python - $R/$O/prof_step <<'PY' | tee $R/$O/step_kernels.log
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):

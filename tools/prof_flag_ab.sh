@@ -1,11 +1,12 @@
 #!/bin/bash
 # usage: prof_flag_ab.sh "<bench flags of arm B>"  -- rocprofv3 kernel stats of the default step and of the step with the flags, top kernels side by side
 F=$1; R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
+P=$(mktemp -d)   # the two profiles, removed at the end
 for arm in A B; do
   fl=""; [ $arm = B ] && fl="$F"
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/pf_$arm -o t -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 $fl > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/pf_$arm -o t -- python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 $fl > /dev/null 2>&1
 done
-python - $R/gpurun_out/pf_A $R/gpurun_out/pf_B <<'PY'
+python - $P/pf_A $P/pf_B <<'PY'
 import csv, glob, sys
 def load(d):
     f = glob.glob(d + "/**/*kernel_stats.csv", recursive=True)[0]
@@ -17,4 +18,4 @@ for n in names[:30]:
     x, y = a.get(n, (0, 0, 0)), b.get(n, (0, 0, 0))
     print(f"{n.replace('void ', '').replace('rqhip::', '')[:64]:64} {x[0]:5d} {x[1]:9.1f} {y[1]:9.1f} {x[2]:9.2f} {y[2]:9.2f}")
 PY
-rm -rf $R/gpurun_out/pf_A $R/gpurun_out/pf_B
+rm -rf $P

@@ -14,12 +14,12 @@ sha256sum "$REPO/rq-vae-recommender_amd/csrc/librqhip.so" > "$OUT/librqhip.sha25
 cd /tmp && export TMPDIR=/tmp
 # (a short line first: tools/summarize_profile.py wants one; the DEFAULT line is taken at the end, after the counter passes have been
 # summarised on this box, so that its `roofline.traffic` finds the PMC file of the very library it loaded)
-timeout -k 5 200 python "$REPO/bench.py" --config $CFG --no-cpu-baseline --no-parity --no-small-batch --no-strict > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+timeout -k 5 200 python "$REPO/bench.py" --full --config $CFG --no-cpu-baseline --no-parity --no-small-batch --no-strict > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- \
-    python "$REPO/bench.py" --config $CFG --steps $([ $CFG = c2 ] && echo 20 || echo 3) --warmup 3 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
+    python "$REPO/bench.py" --full --config $CFG --steps $([ $CFG = c2 ] && echo 20 || echo 3) --warmup 3 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 5 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/pmc_$c" -o pmc -- \
-        python "$REPO/bench.py" --config $CFG --steps $([ $CFG = c2 ] && echo 5 || echo 1) --warmup 2 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 \
+        python "$REPO/bench.py" --full --config $CFG --steps $([ $CFG = c2 ] && echo 5 || echo 1) --warmup 2 --no-cpu-baseline --no-parity --no-small-batch --no-strict --min-seconds 0 \
             --pmc-window "$OUT/window_tags_$c.json" > /dev/null 2> "$OUT/pmc_$c.err"
 done
 # keep what summarize_profile.py reads (gpurun copies back at most 64 MiB): the stats table, and the counter rows
@@ -42,7 +42,7 @@ find "$OUT" -name "*kernel_trace.csv" -delete
 find "$OUT" -type f ! -name "*.csv" ! -name "*.json" ! -name "*.err" ! -name "*.sha256" -delete
 find "$OUT" -name "*.csv" -size +8M -delete
 ( cd "$REPO" && python tools/summarize_profile.py $TAG $CFG > "$OUT/summarize_on_box.log" 2>&1 )
-timeout -k 5 400 python "$REPO/bench.py" --config $CFG > "$OUT/bench_n1.json.new" 2> "$OUT/bench_n1.err"   # the default line: parity gate, CPU baseline, secondaries
+timeout -k 5 400 python "$REPO/bench.py" --full --config $CFG > "$OUT/bench_n1.json.new" 2> "$OUT/bench_n1.err"   # the --full line: parity gate, CPU baseline, secondaries
 [ -s "$OUT/bench_n1.json.new" ] && mv "$OUT/bench_n1.json.new" "$OUT/bench_n1.json"
 du -sh "$OUT"; tail -3 "$OUT/stats.err"
 find "$OUT" -name "*.csv" | sed "s#$REPO/##"

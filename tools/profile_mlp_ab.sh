@@ -10,12 +10,12 @@ mkdir -p "$OUT"
 sha256sum "$REPO/rq-vae-recommender_amd/csrc/librqhip.so" > "$OUT/librqhip.sha256"
 cd /tmp && export TMPDIR=/tmp
 for arm in split split6 library split split6 library; do     # un-profiled wall clock first, alternating (clock state drifts)
-    timeout -k 5 200 python "$REPO/bench.py" --mlp $arm --steps 100 --warmup 5 --no-cpu-baseline --no-parity --min-seconds 0 \
+    timeout -k 5 200 python "$REPO/bench.py" --full --mlp $arm --steps 100 --warmup 5 --no-cpu-baseline --no-parity --min-seconds 0 \
         >> "$OUT/$arm.json" 2>> "$OUT/$arm.err"
 done
 for arm in split split6 library; do
     timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$arm" -o ab -- \
-        python "$REPO/bench.py" --mlp $arm --steps 20 --warmup 3 --no-cpu-baseline --no-parity --min-seconds 0 \
+        python "$REPO/bench.py" --full --mlp $arm --steps 20 --warmup 3 --no-cpu-baseline --no-parity --min-seconds 0 \
         > "$OUT/${arm}_under_rocprof.json" 2> "$OUT/prof_$arm.err"
     cp $(find "$OUT/prof_$arm" -name "*kernel_stats.csv" | head -1) "$OUT/$arm.stats.csv"
     rm -rf "$OUT/prof_$arm"

@@ -35,7 +35,7 @@ stats = one("stats/**/*kernel_stats.csv")
 shutil.copyfile(stats, os.path.join(DST, f"{PRE}_bench_kernel_stats.csv"))
 rows = list(csv.DictReader(open(stats)))
 with open(os.path.join(DST, f"{PRE}_bench_kernel_stats_summary.txt"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats of `python bench.py --config {CFG} --steps {20 if CFG == 'c2' else 3} --warmup 3 --no-cpu-baseline --no-parity` (MI355X, {TAG}; librqhip.so sha256 {str(lib_sha)[:16]})\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats of `python bench.py --full --config {CFG} --steps {20 if CFG == 'c2' else 3} --warmup 3 --no-cpu-baseline --no-parity` (MI355X, {TAG}; librqhip.so sha256 {str(lib_sha)[:16]})\n")
     f.write(f"# bench line of the same build: profiles/{PRE}_bench_n1.json ({bench['value'] / 1e6:.2f} M items/s, "
             f"{bench['ms_per_step']:.2f} ms/step; roofline launch mean {bench['roofline_rq']['launch_ms_mean'] * 1e3:.1f} us by HIP events)\n")
     f.write(f"# top kernels by total time; names shortened; full CSV: {PRE}_bench_kernel_stats.csv\n\n")
@@ -51,7 +51,7 @@ with open(os.path.join(DST, f"{PRE}_bench_kernel_stats_summary.txt"), "w") as f:
 
 cfg_name = bench["config"].get("name", "c2")
 pmc = {"librqhip_sha256": lib_sha,   # of the library the counters were collected on (bench.py checks it before using them)
-       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --steps 5 "
+       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --full --steps 5 "
                   "--warmup 2 --no-cpu-baseline --no-parity   (tools/profile_bench.sh)",
        "note": "KB per launch; max = the B=100000 launches (mean includes the 20000-row k-means warm-up launch). gfx950 "
                "correction from MI355X_MICROARCH.md (HBM section): FETCH_SIZE under-reports coalesced streaming reads by "
