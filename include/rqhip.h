@@ -258,6 +258,28 @@ int rqhip_prefix_lookup(const void *index, size_t index_bytes, const int64_t *co
 int rqhip_topk_first_match(const int64_t *actual, const int64_t *top_k, int64_t B, int K, int D,
                            int64_t *rank, rqhip_stream_t stream);
 
+/* Beam step -- one hierarchy step of EncoderDecoderRetrievalModel.generate (modules/model.py) in one launch: softmax,
+ * sampling without replacement, log, prefix validity, masked_fill, sort and gathers.  Row r of the B * beams_in rows
+ * (beams_in = 1 at h = 0, else the k beams of the previous step; row b * beams_in + beam):
+ *   p = softmax(logits[r]) (fp32, row max subtracted); samples[r, 0..n) = indices of the n largest p[c] / noise[r, c]
+ *   in descending order, equal keys to the lower code (ATen's multinomial(p, n, replacement=False) with its Exp(1) draw
+ *   q passed as `noise` [B * beams_in, K], dense); lp = logf(p[sample]).
+ *   Candidate j = beam * n + s of user b: score = lp + parent_scores[b, beam] (lp alone at h = 0), or -inf unless
+ *   parent_ids[b, beam, 0:h] ++ sample is a prefix of some corpus row (the exact test of rqhip_prefix_lookup against an
+ *   index built by rqhip_prefix_index_build from corpus / N / H / ld).
+ *   Per user the k best candidates, descending, equal scores (-inf included) to the lower j:
+ *   out_ids [B, k, h+1] = parent ids ++ sample, out_scores [B, k], out_parent [B, k] = b * beams_in + beam.
+ * logits [B * beams_in, K] with row stride ld_logits; parent_scores [B, beams_in] and parent_ids [B, beams_in, h]
+ * dense (NULL at h = 0).  Limits: K <= 4096, n_cands <= min(64, K), k <= 64 and k <= beams_in * n_cands,
+ * beams_in <= 64, h + 1 <= min(H, RQHIP_MAX_PREFIX_LEN); outside them RQHIP_EUNSUPPORTED / RQHIP_EARG with the limit
+ * named in rqhip_last_error().  Deterministic; no allocation, copy or sync (graph-capturable). */
+size_t rqhip_beam_step_workspace_bytes(int64_t B, int beams_in, int K, int n_cands, int k);
+int rqhip_beam_step(const float *logits, int64_t ld_logits, const float *noise, const float *parent_scores,
+                    const int64_t *parent_ids, int h, int64_t B, int beams_in, int K, int n_cands, int k,
+                    const void *index, size_t index_bytes, const int64_t *corpus, int64_t N, int H, int64_t ld,
+                    int64_t *out_ids, float *out_scores, int64_t *out_parent, void *workspace, size_t workspace_bytes,
+                    rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

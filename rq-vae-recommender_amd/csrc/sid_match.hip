@@ -14,35 +14,9 @@
 // bound integer work, nothing to put on the matrix cores.  The index costs 8 bytes per corpus row and prefix
 // length (load factor <= 1/2), i.e. 320 MB for 10 M items x 4 levels: resident in HBM for the run.
 #include "rqhip_common.h"
+#include "sid_hash.h"
 
 namespace rqhip {
-
-__device__ __forceinline__ unsigned sid_mix(unsigned h, unsigned v) {
-    h ^= v + 0x9e3779b9u + (h << 6) + (h >> 2);
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    return h;
-}
-
-__device__ __forceinline__ unsigned sid_hash_step(unsigned h, int64_t v) {
-    h = sid_mix(h, (unsigned)(unsigned long long)v);
-    const unsigned hi = (unsigned)((unsigned long long)v >> 32);
-    return hi ? sid_mix(h, hi ^ 0x5bd1e995u) : h;  // ids are small non-negative numbers: the high word is 0
-}
-
-__device__ __forceinline__ unsigned sid_hash_final(unsigned h) {
-    h ^= h >> 16;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 15;
-    return h;
-}
-
-static unsigned long long slots_for(long long N) {
-    unsigned long long p = 64;
-    const unsigned long long want = 2ull * (unsigned long long)(N > 0 ? N : 1);
-    while (p < want) p <<= 1;
-    return p;
-}
 
 // one thread per corpus row; inserts its H prefixes (hash extended incrementally)
 __global__ __launch_bounds__(256) void prefix_build_kernel(const int64_t *__restrict__ corpus, long long N, int H,
@@ -51,7 +25,7 @@ __global__ __launch_bounds__(256) void prefix_build_kernel(const int64_t *__rest
     if (i >= N) return;
     const int64_t *mine = corpus + (size_t)i * ld;
     const size_t slots = (size_t)mask + 1;
-    unsigned hsh = 0x9747b28cu;
+    unsigned hsh = kSidHashSeed;
     for (int h = 1; h <= H; ++h) {
         hsh = sid_hash_step(hsh, mine[h - 1]);
         int *tab = table + (size_t)(h - 1) * slots;
@@ -79,7 +53,7 @@ __global__ __launch_bounds__(256) void prefix_lookup_kernel(const int *__restric
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= P) return;
     const int64_t *mine = prefix + (size_t)q * ldp;
-    unsigned hsh = 0x9747b28cu;
+    unsigned hsh = kSidHashSeed;
     for (int c = 0; c < h; ++c) hsh = sid_hash_step(hsh, mine[c]);
     const int *tab = table + (size_t)(h - 1) * ((size_t)mask + 1);
     unsigned s = sid_hash_final(hsh) & mask;

@@ -1,0 +1,247 @@
+"""Generative retrieval model (TIGER): a T5 encoder over a user's semantic-id history, a T5 decoder that emits the
+next item's ids one hierarchy level at a time.  API and state dict of the reference's modules/model.py
+(EncoderDecoderRetrievalModel), so a checkpoint trained there loads here with strict=True.
+
+The T5 body runs on torch operators (modules/t5.py).  Each hierarchy step of `generate` is the decoder on one new
+token per beam, the head's F.linear and ONE HIP launch (ops.beam_step, csrc/beam_step.hip) that does the reference's
+softmax, multinomial sampling, log, prefix-validity mask, sort and gathers.  After the encoder nothing is read back to
+the host and no allocation depends on data, so a whole `generate` can be captured into a graph.
+
+Sampling: the reference's `torch.multinomial(probas, n, replacement=False)` is ATen's exponential race
+`topk(p / q, n)` with `q = empty_like(p).exponential_(1)`.  `_exponential_like` draws the same q from the same
+generator, so a seeded `generate` consumes the RNG as the reference's does.
+"""
+from typing import List, NamedTuple, Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch import Tensor
+
+from data.schemas import TokenizedSeqBatch
+from modules.sid_prefix import SemIdPrefixIndex
+from modules.t5 import T5Config, T5EncoderModel, T5Stack
+from rqhip import ops
+from rqhip._lib import RqHipError
+
+
+class ModelOutput(NamedTuple):
+    loss: Tensor
+    logits: Tensor
+    loss_d: Tensor
+
+
+class GenerationOutput(NamedTuple):
+    sem_ids: Tensor
+    log_probas: Tensor
+
+
+def _strip_dedup_col(tensor: Tensor, sem_ids_dim: int, n_layers: int) -> Tensor:
+    """[B, N * sem_ids_dim] (n_layers ids + the tokenizer's dedup column per item) -> [B, N * n_layers]."""
+    B, total = tensor.shape
+    N = total // sem_ids_dim
+    return tensor.view(B, N, sem_ids_dim)[:, :, :n_layers].contiguous().view(B, N * n_layers)
+
+
+def _exponential_like(probas: Tensor) -> Tensor:
+    """The Exp(1) draw of torch.multinomial without replacement, from the current device generator."""
+    return torch.empty_like(probas).exponential_(1)
+
+
+class EncoderDecoderRetrievalModel(nn.Module):
+    def __init__(
+        self,
+        codebooks: Tensor,
+        num_hierarchies: int,
+        num_embeddings_per_hierarchy: int,
+        t5_d_model: int = 128,
+        t5_num_heads: int = 6,
+        t5_d_ff: int = 1024,
+        t5_num_layers: int = 4,
+        top_k_for_generation: int = 10,
+        should_add_sep_token: bool = True,
+        num_user_bins: Optional[int] = None,
+    ):
+        super().__init__()
+        self.num_hierarchies = num_hierarchies
+        self.num_embeddings_per_hierarchy = num_embeddings_per_hierarchy
+        self.top_k_for_generation = top_k_for_generation
+        self.register_buffer("codebooks", codebooks)
+
+        vocab = num_embeddings_per_hierarchy * num_hierarchies
+        self.encoder = T5EncoderModel(T5Config(vocab, d_model=t5_d_model, num_heads=t5_num_heads, d_ff=t5_d_ff,
+                                               num_layers=t5_num_layers, is_decoder=False))
+        self.t5_decoder = T5Stack(T5Config(vocab, d_model=t5_d_model, num_heads=t5_num_heads, d_ff=t5_d_ff,
+                                           num_layers=t5_num_layers, is_decoder=True))
+        self.bos_token = nn.Parameter(torch.randn(1, t5_d_model), requires_grad=True)
+        self.decoder_mlp = nn.ModuleList(
+            [nn.Linear(t5_d_model, num_embeddings_per_hierarchy, bias=False) for _ in range(num_hierarchies)])
+        # one table for all hierarchies: level h, code t -> row h * codebook_size + t
+        self.item_sid_embedding_table = nn.Embedding(num_embeddings=vocab, embedding_dim=t5_d_model)
+        self.user_embedding = nn.Embedding(num_user_bins, t5_d_model) if num_user_bins else None
+        self.sep_token = (nn.Parameter(torch.randn(1, t5_d_model), requires_grad=True)
+                          if should_add_sep_token else None)
+
+        self._prefix_index: Optional[SemIdPrefixIndex] = None
+        self._prefix_key = None
+
+    @property
+    def device(self) -> torch.device:
+        return next(self.parameters()).device
+
+    def _add_repeating_offset_to_rows(self, input_sids: Tensor, codebook_size: int, num_hierarchies: int,
+                                      attention_mask: Optional[Tensor] = None) -> Tensor:
+        """Add per-hierarchy offsets so a single embedding table covers all hierarchies (times the mask: the
+        tokenizer's -1 padding becomes row 0)."""
+        if input_sids.ndim != 2:
+            raise ValueError("Input tensor must be 2-dimensional.")
+        num_cols = input_sids.shape[1]
+        offsets = torch.arange(num_hierarchies, device=input_sids.device) * codebook_size
+        num_repeats = (num_cols + num_hierarchies - 1) // num_hierarchies
+        result = input_sids + offsets.repeat(num_repeats)[:num_cols]
+        if attention_mask is not None:
+            result = result * attention_mask
+        return result
+
+    def _inject_sep_token_between_sids(self, id_embeddings: Tensor, attention_mask: Tensor, sep_token: Tensor,
+                                       num_hierarchies: int):
+        """Append the separator embedding after each item's group of ids (the mask copies the item's last column)."""
+        batch_size, seq_len, emb_dim = id_embeddings.size()
+        item_count = seq_len // num_hierarchies
+        emb = id_embeddings.view(batch_size, item_count, num_hierarchies, -1)
+        mask = attention_mask.view(batch_size, item_count, num_hierarchies)
+        sep = sep_token.unsqueeze(0).expand(batch_size, item_count, -1).unsqueeze(-2)
+        id_embeddings = torch.cat([emb, sep], dim=-2)
+        attention_mask = torch.cat([mask, mask[:, :, -1:]], dim=-1)  # a slice, not a host index: capturable
+        return id_embeddings.reshape(batch_size, -1, emb_dim), attention_mask.reshape(batch_size, -1)
+
+    def _prefix_index_for_codebooks(self) -> SemIdPrefixIndex:
+        """The corpus' prefix index, built on first use on a device and rebuilt whenever the `codebooks` buffer
+        changes (load_state_dict copies into it and bumps its version; .to() replaces it)."""
+        cb = self.codebooks
+        key = (cb.data_ptr(), cb.device, cb._version, tuple(cb.shape))
+        if self._prefix_index is None or self._prefix_key != key:
+            self._prefix_index = SemIdPrefixIndex(cb)
+            self._prefix_key = key
+        return self._prefix_index
+
+    def _check_valid_prefix(self, prefix: Tensor, batch_size: int = 100000) -> Tensor:
+        """Boolean mask: which rows of prefix [P, h] occur as the first h ids of a corpus row."""
+        if prefix.device != self.codebooks.device:
+            self.codebooks = self.codebooks.to(prefix.device)
+        return self._prefix_index_for_codebooks().check_valid_prefix(prefix, batch_size)
+
+    def encoder_forward_pass(self, attention_mask, input_ids, user_id=None):
+        shifted = self._add_repeating_offset_to_rows(input_sids=input_ids,
+                                                     codebook_size=self.num_embeddings_per_hierarchy,
+                                                     num_hierarchies=self.num_hierarchies,
+                                                     attention_mask=attention_mask)
+        inputs_embeds = self.item_sid_embedding_table(shifted)
+        if self.sep_token is not None:
+            inputs_embeds, attention_mask = self._inject_sep_token_between_sids(
+                id_embeddings=inputs_embeds, attention_mask=attention_mask, sep_token=self.sep_token,
+                num_hierarchies=self.num_hierarchies)
+        if user_id is not None and self.user_embedding is not None:
+            user_embeds = self.user_embedding(torch.remainder(user_id[:, 0], self.user_embedding.num_embeddings))
+            inputs_embeds = torch.cat([user_embeds.unsqueeze(1), inputs_embeds], dim=1)
+            attention_mask = torch.cat(
+                [torch.ones(attention_mask.size(0), 1, device=attention_mask.device), attention_mask], dim=1)
+        encoder_output = self.encoder(inputs_embeds=inputs_embeds, attention_mask=attention_mask)
+        return encoder_output, attention_mask
+
+    def decoder_forward_pass(self, attention_mask=None, future_ids=None, encoder_output=None,
+                             attention_mask_for_encoder=None, use_cache=False, past_key_values=None):
+        """BOS followed by the embedded future ids (or BOS alone); with a cache (the list this returns when use_cache)
+        only the last future id is run.  Returns the hidden states, and the self-attention cache when use_cache."""
+        if future_ids is not None:
+            shifted = self._add_repeating_offset_to_rows(
+                input_sids=future_ids, codebook_size=self.num_embeddings_per_hierarchy,
+                num_hierarchies=self.num_hierarchies,
+                attention_mask=torch.ones_like(future_ids) if attention_mask is None else attention_mask)
+            inputs_embeds = self.item_sid_embedding_table(shifted)
+            if not past_key_values:
+                bos = self.bos_token.unsqueeze(0).expand(future_ids.size(0), 1, -1)
+                inputs_embeds = torch.cat([bos, inputs_embeds], dim=1)
+                if attention_mask is not None:
+                    attention_mask = torch.cat(
+                        [torch.ones(future_ids.size(0), 1, device=future_ids.device), attention_mask], dim=1)
+            else:
+                inputs_embeds = inputs_embeds[:, -1:, :]
+        else:
+            inputs_embeds = self.bos_token.unsqueeze(0).expand(encoder_output.size(0), 1, -1)
+        return self.t5_decoder(inputs_embeds, attention_mask=attention_mask, encoder_hidden_states=encoder_output,
+                               encoder_attention_mask=attention_mask_for_encoder,
+                               past_key_values=past_key_values or None, use_cache=use_cache)
+
+    def forward(self, batch: TokenizedSeqBatch) -> ModelOutput:
+        sem_ids_dim = self.num_hierarchies + 1
+        input_ids = _strip_dedup_col(batch.sem_ids, sem_ids_dim, self.num_hierarchies)
+        attention_mask = _strip_dedup_col(batch.seq_mask.long(), sem_ids_dim, self.num_hierarchies)
+        fut_ids = batch.sem_ids_fut[:, : self.num_hierarchies]
+        encoder_output, attention_mask_for_encoder = self.encoder_forward_pass(
+            attention_mask=attention_mask, input_ids=input_ids, user_id=batch.user_ids)
+        decoder_output = self.decoder_forward_pass(
+            future_ids=fut_ids, encoder_output=encoder_output,
+            attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False)[:, :-1]
+        total_loss = torch.tensor(0.0, device=decoder_output.device)
+        loss_d = []
+        for h in range(self.num_hierarchies):
+            logits = self.decoder_mlp[h](decoder_output[:, h])
+            h_loss = F.cross_entropy(logits, fut_ids[:, h].long())
+            total_loss = total_loss + h_loss
+            loss_d.append(h_loss.detach())
+        return ModelOutput(loss=total_loss, logits=None, loss_d=torch.stack(loss_d))
+
+    @torch.no_grad()
+    def generate(self, attention_mask, input_ids, user_id=None):
+        """Sampling beam search over the hierarchy levels.
+
+        Step 0 decodes BOS on the B users and keeps the best k of n_cands = min(64, K) samples; every later step runs
+        the B * k beams' newest id through the decoder (self-attention cache reordered by parent beam; cross-attention
+        K/V computed once on the B users) and one ops.beam_step.
+
+        Returns generated_ids [B, k, num_hierarchies] int64 and log_probas [B, k] fp32 (-inf for beams without a valid
+        corpus prefix)."""
+        k = self.top_k_for_generation
+        n_cands = min(64, self.num_embeddings_per_hierarchy)
+        if k > n_cands:
+            raise ValueError(f"top_k_for_generation={k} exceeds the n_cands={n_cands} samples of the first step "
+                             f"(min(64, num_embeddings_per_hierarchy))")
+        if not self.codebooks.is_cuda or not input_ids.is_cuda:
+            raise RqHipError("generate needs ROCm device tensors: the beam step is a HIP kernel with no CPU path")
+        if input_ids.device != self.codebooks.device:
+            self.codebooks = self.codebooks.to(input_ids.device)
+        index = self._prefix_index_for_codebooks()
+        index.to(input_ids.device)
+
+        enc_out, enc_mask = self.encoder_forward_pass(attention_mask=attention_mask, input_ids=input_ids,
+                                                      user_id=user_id)
+        dec = self.t5_decoder
+        cross_kv = dec.cross_kv(enc_out)
+        B = enc_out.shape[0]
+        K = self.num_embeddings_per_hierarchy
+
+        x = self.bos_token.unsqueeze(0).expand(B, 1, -1)
+        self_kv: Optional[List] = None
+        ids = scores = None
+        for h in range(self.num_hierarchies):
+            if h > 0:
+                rows = parent.flatten()
+                self_kv = [(kk.index_select(0, rows), vv.index_select(0, rows)) for kk, vv in self_kv]
+                x = self.item_sid_embedding_table(ids[:, :, h - 1].reshape(-1, 1) + (h - 1) * K)
+            hidden, self_kv = dec(x, encoder_attention_mask=enc_mask, past_key_values=self_kv, use_cache=True,
+                                  cross_kv=cross_kv)
+            logits = F.linear(hidden[:, -1], self.decoder_mlp[h].weight)
+            noise = _exponential_like(logits)
+            ids, scores, parent = ops.beam_step(logits, noise, scores, ids, index._index, index._corpus, n_cands, k)
+        return ids, scores
+
+    @torch.no_grad()
+    def generate_next_sem_id(self, batch: TokenizedSeqBatch, top_k: bool = True,
+                             temperature: int = 1) -> GenerationOutput:
+        sem_ids_dim = self.num_hierarchies + 1
+        input_ids = _strip_dedup_col(batch.sem_ids, sem_ids_dim, self.num_hierarchies)
+        attention_mask = _strip_dedup_col(batch.seq_mask.long(), sem_ids_dim, self.num_hierarchies)
+        generated_ids, log_probas = self.generate(attention_mask=attention_mask, input_ids=input_ids,
+                                                  user_id=batch.user_ids)
+        return GenerationOutput(sem_ids=generated_ids, log_probas=log_probas)

@@ -1,0 +1,293 @@
+"""T5 encoder / decoder stacks for the retrieval model (modules/model.py), in torch operators.
+
+The reference builds its retrieval model from HuggingFace's `T5EncoderModel` and `T5Stack` with `T5Config` defaults
+for everything it does not set.  This module is written for this project and reproduces what those defaults give,
+with the same module tree, so a reference checkpoint loads by its state-dict names:
+
+- d_kv = 64: each attention's inner width is heads * 64, not d_model; q/k/v/o have no bias.
+- No 1/sqrt(d) scaling of the scores; a relative-position bias (32 buckets, max distance 128) lives in block 0 and is
+  shared by the later blocks; bidirectional in the encoder, causal in the decoder's self-attention; none in the
+  cross-attention.
+- Masks are added as finfo(dtype).min; softmax in fp32.
+- RMS layer norm (no mean, no bias), variance in fp32, eps 1e-6.
+- ReLU feed-forward.
+- Dropout 0.1 on the input embeddings, each sub-layer output, inside the feed-forward, on the attention weights and
+  after the final norm.
+
+The decoder can run incrementally: `T5Stack.forward` takes and returns a self-attention cache (one (K, V) pair per
+block, [rows, heads, t, 64]) and accepts precomputed cross-attention K/V (`cross_kv`) on fewer rows than the queries:
+rows r = b * beams + beam all read user b's encoder output, as the beams of a beam search do.
+"""
+import math
+from typing import List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch import Tensor
+
+KV = Tuple[Tensor, Tensor]
+
+
+class T5Config:
+    def __init__(self, vocab_size: int, d_model: int = 512, num_heads: int = 8, d_ff: int = 2048, num_layers: int = 6,
+                 d_kv: int = 64, relative_attention_num_buckets: int = 32, relative_attention_max_distance: int = 128,
+                 dropout_rate: float = 0.1, layer_norm_epsilon: float = 1e-6, is_decoder: bool = False) -> None:
+        self.vocab_size = vocab_size
+        self.d_model = d_model
+        self.num_heads = num_heads
+        self.d_ff = d_ff
+        self.num_layers = num_layers
+        self.d_kv = d_kv
+        self.relative_attention_num_buckets = relative_attention_num_buckets
+        self.relative_attention_max_distance = relative_attention_max_distance
+        self.dropout_rate = dropout_rate
+        self.layer_norm_epsilon = layer_norm_epsilon
+        self.is_decoder = is_decoder
+
+
+def additive_mask(mask: Tensor, dtype: torch.dtype) -> Tensor:
+    """[B, S] keep-mask (1 = attend) -> [B, 1, 1, S] additive mask: 0 where kept, finfo.min where masked."""
+    return (1.0 - mask[:, None, None, :].to(dtype)) * torch.finfo(dtype).min
+
+
+class T5LayerNorm(nn.Module):
+    def __init__(self, d_model: int, eps: float = 1e-6) -> None:
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(d_model))
+        self.variance_epsilon = eps
+
+    def forward(self, x: Tensor) -> Tensor:
+        variance = x.to(torch.float32).pow(2).mean(-1, keepdim=True)
+        x = x * torch.rsqrt(variance + self.variance_epsilon)
+        return self.weight * x
+
+
+def relative_position_bucket(relative_position: Tensor, bidirectional: bool, num_buckets: int,
+                             max_distance: int) -> Tensor:
+    """T5's bucketing of memory_position - query_position: exact buckets for small distances, logarithmic bins up to
+    max_distance; bidirectional halves the buckets between the two signs, causal clamps positive offsets to 0."""
+    buckets = torch.zeros_like(relative_position)
+    if bidirectional:
+        num_buckets //= 2
+        buckets = buckets + (relative_position > 0).to(torch.long) * num_buckets
+        relative_position = relative_position.abs()
+    else:
+        relative_position = -torch.min(relative_position, torch.zeros_like(relative_position))
+    max_exact = num_buckets // 2
+    is_small = relative_position < max_exact
+    large = max_exact + (torch.log(relative_position.float() / max_exact) / math.log(max_distance / max_exact)
+                         * (num_buckets - max_exact)).to(torch.long)
+    large = torch.min(large, torch.full_like(large, num_buckets - 1))
+    return buckets + torch.where(is_small, relative_position, large)
+
+
+def _attend(module: nn.Module, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], mask: Optional[Tensor]) -> Tensor:
+    scores = torch.matmul(q, k.transpose(-1, -2))
+    if bias is not None:
+        scores = scores + bias
+    if mask is not None:
+        scores = scores + mask
+    weights = F.softmax(scores.float(), dim=-1).type_as(scores)
+    weights = F.dropout(weights, p=module.dropout, training=module.training)
+    return torch.matmul(weights, v)
+
+
+class T5Attention(nn.Module):
+    def __init__(self, config: T5Config, has_relative_attention_bias: bool = False) -> None:
+        super().__init__()
+        self.is_decoder = config.is_decoder
+        self.has_relative_attention_bias = has_relative_attention_bias
+        self.num_buckets = config.relative_attention_num_buckets
+        self.max_distance = config.relative_attention_max_distance
+        self.n_heads = config.num_heads
+        self.d_kv = config.d_kv
+        self.dropout = config.dropout_rate
+        inner = self.n_heads * self.d_kv
+        self.q = nn.Linear(config.d_model, inner, bias=False)
+        self.k = nn.Linear(config.d_model, inner, bias=False)
+        self.v = nn.Linear(config.d_model, inner, bias=False)
+        self.o = nn.Linear(inner, config.d_model, bias=False)
+        if has_relative_attention_bias:
+            self.relative_attention_bias = nn.Embedding(self.num_buckets, self.n_heads)
+
+    def compute_bias(self, query_length: int, key_length: int, past: int = 0) -> Tensor:
+        """[1, heads, query_length, key_length] bias for queries at positions past .. past + query_length - 1."""
+        dev = self.relative_attention_bias.weight.device
+        context = torch.arange(query_length, dtype=torch.long, device=dev)[:, None] + past
+        memory = torch.arange(key_length, dtype=torch.long, device=dev)[None, :]
+        bucket = relative_position_bucket(memory - context, bidirectional=not self.is_decoder,
+                                          num_buckets=self.num_buckets, max_distance=self.max_distance)
+        return self.relative_attention_bias(bucket).permute(2, 0, 1).unsqueeze(0)
+
+    def _heads(self, x: Tensor) -> Tensor:  # [R, T, inner] -> [R, heads, T, d_kv]
+        return x.view(x.shape[0], x.shape[1], self.n_heads, self.d_kv).transpose(1, 2)
+
+    def project_kv(self, x: Tensor) -> KV:
+        return self._heads(self.k(x)), self._heads(self.v(x))
+
+    def self_attention(self, x: Tensor, bias: Optional[Tensor], mask: Optional[Tensor],
+                       past: Optional[KV]) -> Tuple[Tensor, KV]:
+        q = self._heads(self.q(x))
+        k, v = self.project_kv(x)
+        if past is not None:
+            k, v = torch.cat([past[0], k], dim=2), torch.cat([past[1], v], dim=2)
+        out = _attend(self, q, k, v, bias, mask)
+        return self.o(out.transpose(1, 2).reshape(x.shape[0], x.shape[1], -1)), (k, v)
+
+    def cross_attention(self, x: Tensor, kv: KV, mask: Optional[Tensor]) -> Tensor:
+        """Queries x [R, T, d] with R = B * beams over keys / values [B, heads, S, d_kv] of B rows."""
+        R, T = x.shape[0], x.shape[1]
+        B = kv[0].shape[0]
+        beams = R // B
+        q = self._heads(self.q(x))  # [R, H, T, dk]
+        if beams != 1:
+            q = q.view(B, beams, self.n_heads, T, self.d_kv).transpose(1, 2).reshape(B, self.n_heads, beams * T,
+                                                                                      self.d_kv)
+        out = _attend(self, q, kv[0], kv[1], None, mask)
+        if beams != 1:
+            out = out.view(B, self.n_heads, beams, T, self.d_kv).transpose(1, 2).reshape(R, self.n_heads, T, self.d_kv)
+        return self.o(out.transpose(1, 2).reshape(R, T, -1))
+
+
+class T5LayerSelfAttention(nn.Module):
+    def __init__(self, config: T5Config, has_relative_attention_bias: bool = False) -> None:
+        super().__init__()
+        self.SelfAttention = T5Attention(config, has_relative_attention_bias)
+        self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
+        self.dropout = nn.Dropout(config.dropout_rate)
+
+    def forward(self, x, bias, mask, past):
+        out, kv = self.SelfAttention.self_attention(self.layer_norm(x), bias, mask, past)
+        return x + self.dropout(out), kv
+
+
+class T5LayerCrossAttention(nn.Module):
+    def __init__(self, config: T5Config) -> None:
+        super().__init__()
+        self.EncDecAttention = T5Attention(config, has_relative_attention_bias=False)
+        self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
+        self.dropout = nn.Dropout(config.dropout_rate)
+
+    def forward(self, x, kv, mask):
+        return x + self.dropout(self.EncDecAttention.cross_attention(self.layer_norm(x), kv, mask))
+
+
+class T5DenseReluDense(nn.Module):
+    def __init__(self, config: T5Config) -> None:
+        super().__init__()
+        self.wi = nn.Linear(config.d_model, config.d_ff, bias=False)
+        self.wo = nn.Linear(config.d_ff, config.d_model, bias=False)
+        self.dropout = nn.Dropout(config.dropout_rate)
+
+    def forward(self, x):
+        return self.wo(self.dropout(F.relu(self.wi(x))))
+
+
+class T5LayerFF(nn.Module):
+    def __init__(self, config: T5Config) -> None:
+        super().__init__()
+        self.DenseReluDense = T5DenseReluDense(config)
+        self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
+        self.dropout = nn.Dropout(config.dropout_rate)
+
+    def forward(self, x):
+        return x + self.dropout(self.DenseReluDense(self.layer_norm(x)))
+
+
+class T5Block(nn.Module):
+    def __init__(self, config: T5Config, has_relative_attention_bias: bool = False) -> None:
+        super().__init__()
+        layers = [T5LayerSelfAttention(config, has_relative_attention_bias)]
+        if config.is_decoder:
+            layers.append(T5LayerCrossAttention(config))
+        layers.append(T5LayerFF(config))
+        self.layer = nn.ModuleList(layers)
+
+
+class T5Stack(nn.Module):
+    def __init__(self, config: T5Config, embed_tokens: Optional[nn.Embedding] = None) -> None:
+        super().__init__()
+        self.config = config
+        self.is_decoder = config.is_decoder
+        # the stacks are driven with inputs_embeds; the table is kept for the state-dict layout
+        self.embed_tokens = embed_tokens if embed_tokens is not None else nn.Embedding(config.vocab_size,
+                                                                                       config.d_model)
+        self.block = nn.ModuleList([T5Block(config, has_relative_attention_bias=(i == 0))
+                                    for i in range(config.num_layers)])
+        self.final_layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
+        self.dropout = nn.Dropout(config.dropout_rate)
+        init_t5_weights(self, config)
+
+    def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
+        """Cross-attention K/V of every block, computed once per encoder output."""
+        return [blk.layer[1].EncDecAttention.project_kv(encoder_hidden_states) for blk in self.block]
+
+    def forward(self, inputs_embeds: Tensor, attention_mask: Optional[Tensor] = None,
+                encoder_hidden_states: Optional[Tensor] = None, encoder_attention_mask: Optional[Tensor] = None,
+                past_key_values: Optional[List[KV]] = None, use_cache: bool = False,
+                cross_kv: Optional[List[KV]] = None):
+        """inputs_embeds [R, T, d]; attention_mask [R, past + T] keep-mask (encoder: [R, T]); encoder_attention_mask
+        [B, S] keep-mask of the encoder output (B rows, R = B * beams).  Returns the hidden states, and with use_cache
+        the per-block self-attention (K, V) including these T positions."""
+        R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
+        dtype = inputs_embeds.dtype
+        past = 0 if past_key_values is None else past_key_values[0][0].shape[2]
+        keys = past + T
+        keep = None if attention_mask is None else attention_mask[:, None, None, :].bool()
+        if self.is_decoder and T > 1:
+            causal = torch.ones(T, keys, dtype=torch.bool, device=inputs_embeds.device).tril(diagonal=past)[None, None]
+            keep = causal if keep is None else keep & causal
+        mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
+        bias = self.block[0].layer[0].SelfAttention.compute_bias(T, keys, past)
+        if self.is_decoder:
+            if cross_kv is None:
+                cross_kv = self.cross_kv(encoder_hidden_states)
+            cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
+
+        x = self.dropout(inputs_embeds)
+        new_kv = []
+        for i, blk in enumerate(self.block):
+            x, kv = blk.layer[0](x, bias, mask, None if past_key_values is None else past_key_values[i])
+            new_kv.append(kv)
+            if self.is_decoder:
+                x = blk.layer[1](x, cross_kv[i], cross_mask)
+            x = blk.layer[-1](x)
+        x = self.dropout(self.final_layer_norm(x))
+        return (x, new_kv) if use_cache else x
+
+
+class T5EncoderModel(nn.Module):
+    """`shared` table + encoder stack, the layout of HuggingFace's T5EncoderModel (the stack's embed_tokens IS
+    `shared`, so both names appear in the state dict)."""
+
+    def __init__(self, config: T5Config) -> None:
+        super().__init__()
+        self.shared = nn.Embedding(config.vocab_size, config.d_model)
+        self.encoder = T5Stack(config, embed_tokens=self.shared)
+        nn.init.normal_(self.shared.weight, mean=0.0, std=1.0)
+
+    def forward(self, inputs_embeds: Tensor, attention_mask: Optional[Tensor] = None) -> Tensor:
+        return self.encoder(inputs_embeds, attention_mask=attention_mask)
+
+
+@torch.no_grad()
+def init_t5_weights(stack: T5Stack, config: T5Config) -> None:
+    """T5's initialisation (initializer_factor 1): normal with the fan-in scales of the mesh-tensorflow T5."""
+    d, dk, H = config.d_model, config.d_kv, config.num_heads
+    nn.init.normal_(stack.embed_tokens.weight, mean=0.0, std=1.0)
+    for blk in stack.block:
+        for layer in blk.layer:
+            layer.layer_norm.weight.fill_(1.0)
+            att = getattr(layer, "SelfAttention", None) or getattr(layer, "EncDecAttention", None)
+            if att is not None:
+                att.q.weight.normal_(0.0, (d * dk) ** -0.5)
+                att.k.weight.normal_(0.0, d ** -0.5)
+                att.v.weight.normal_(0.0, d ** -0.5)
+                att.o.weight.normal_(0.0, (H * dk) ** -0.5)
+                if att.has_relative_attention_bias:
+                    att.relative_attention_bias.weight.normal_(0.0, d ** -0.5)
+            else:
+                layer.DenseReluDense.wi.weight.normal_(0.0, d ** -0.5)
+                layer.DenseReluDense.wo.weight.normal_(0.0, config.d_ff ** -0.5)
+    stack.final_layer_norm.weight.fill_(1.0)

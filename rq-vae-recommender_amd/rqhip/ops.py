@@ -490,6 +490,55 @@ def topk_first_match(actual: Tensor, top_k: Tensor) -> Tensor:
     return rank
 
 
+def beam_step(logits: Tensor, noise: Tensor, parent_scores: Optional[Tensor], parent_ids: Optional[Tensor],
+              index: Tensor, corpus: Tensor, n_cands: int, k: int):
+    """One hierarchy step of the retrieval model's beam search in one launch (rqhip_beam_step).
+
+    logits [B * beams_in, K] fp32 (unit column stride), noise [B * beams_in, K] Exp(1) draws, parent_scores [B, beams_in]
+    fp32 and parent_ids [B, beams_in, h] int64, both None at the first step (beams_in = 1); index / corpus as from
+    prefix_index_build.  Returns ids [B, k, h+1] int64, scores [B, k] fp32 and parent [B, k] int64 (the global row
+    b * beams_in + beam each kept candidate came from).  Shapes decide every allocation; nothing is read back."""
+    _need_gpu(logits, noise, parent_scores, parent_ids, index, corpus)
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise RqHipError(f"beam_step: logits must be a float32 [rows, K] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    rows, K = logits.shape
+    noise = _f32c(noise, "noise")
+    if tuple(noise.shape) != (rows, K):
+        raise RqHipError(f"beam_step: noise must be [{rows}, {K}], got {tuple(noise.shape)}")
+    if parent_ids is None:
+        if parent_scores is not None:
+            raise RqHipError("beam_step: parent_scores without parent_ids")
+        h, beams_in = 0, 1
+    else:
+        if parent_ids.dtype != torch.int64 or parent_ids.dim() != 3 or parent_scores is None:
+            raise RqHipError("beam_step: parent_ids must be int64 [B, beams_in, h] and come with parent_scores")
+        beams_in, h = parent_ids.shape[1], parent_ids.shape[2]
+        parent_ids = parent_ids.contiguous()
+        parent_scores = _f32c(parent_scores, "parent_scores")
+    if rows % beams_in != 0:
+        raise RqHipError(f"beam_step: {rows} logit rows are not B * beams_in with beams_in = {beams_in}")
+    B = rows // beams_in
+    if parent_ids is not None and (parent_ids.shape[0] != B or tuple(parent_scores.shape) != (B, beams_in)):
+        raise RqHipError(f"beam_step: parent_ids {tuple(parent_ids.shape)} / parent_scores {tuple(parent_scores.shape)} "
+                         f"do not match B = {B}, beams_in = {beams_in}")
+    corpus = _i64_rows(corpus, "corpus")
+    N, H = corpus.shape
+    dev = logits.device
+    with torch.cuda.device(dev):
+        ids = torch.empty((B, k, h + 1), dtype=torch.int64, device=dev)
+        scores = torch.empty((B, k), dtype=torch.float32, device=dev)
+        parent = torch.empty((B, k), dtype=torch.int64, device=dev)
+        l = _lib.lib()
+        rc = l.rqhip_beam_step(_ptr(logits), int(logits.stride(0)) if rows > 1 else K, _ptr(noise), _ptr(parent_scores),
+                               _ptr(parent_ids), h, B, beams_in, K, int(n_cands), int(k), _ptr(index), index.numel(),
+                               _ptr(corpus), N, H, _row_stride(corpus), _ptr(ids), _ptr(scores), _ptr(parent), None, 0,
+                               _stream())
+        check(rc, "rqhip_beam_step")
+    return ids, scores, parent
+
+
 def gumbel_matrix_path_min_rows(set_to: int = 0) -> int:
     """Query (set_to <= 0) or set the batch size from which the Gumbel level runs on the matrix instructions
     (rqhip_gumbel_matrix_path_min_rows); returns the previous value."""
