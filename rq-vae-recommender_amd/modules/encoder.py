@@ -85,17 +85,18 @@ class _MLPStack(torch.autograd.Function):
       * a data gradient applies the ReLU backward of the layer below in its epilogue (RQHIP_EPI_MASK), so the masked
         gradient is written once, with its maxima, and the weight-gradient kernels read it unmasked.
     Same kernels, maxima and therefore result bits as the per-layer Functions above (tests/test_gpu_modules.py).
-    forward(x, target, relus, zero_bias, *weights): relus[i] = layer i is followed by a ReLU; zero_bias(n, like) -> zeros
-    [n] for the library GEMM's fused-ReLU call.  Returns the last layer's output, or the loss rows [M] when target is given
-    (then the last layer has no ReLU and takes the split kernel: the caller checks)."""
+    forward(x, target, relus, zero_bias, given, defer, *weights): relus[i] = layer i is followed by a ReLU; zero_bias(n, like) -> zeros
+    [n] for the library GEMM's fused-ReLU call; given: the maxima that came with x (rqhip/linear.py:attached_scales -- an argument because
+    the node may be handed an alias of the caller's tensor object, and attributes do not survive that) or None; defer: this node's batched
+    weight gradients may wait for a later node's launch (rqhip/linear.py:WgradQueue).  Returns the last layer's output, or the loss rows
+    [M] when target is given (then the last layer has no ReLU and takes the split kernel: the caller checks)."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, target, relus, zero_bias, *weights):
+    def forward(ctx, x: Tensor, target, relus, zero_bias, given, defer, *weights):
         from rqhip import _lib
         from rqhip import autograd as _ag
         n, M = len(weights), x.shape[0]
-        given = _lin.take_scales()          # maxima that came with the input (rqhip/linear.py:attach_scales), or None
-        need_w = [bool(f) for f in ctx.needs_input_grad[4:]]
+        need_w = [bool(f) for f in ctx.needs_input_grad[6:]]
         need_in = [bool(ctx.needs_input_grad[0]) or any(need_w[:i]) for i in range(n)]   # gradient wrt layer i's input wanted
         # the 128 <-> 32 layers either side of the quantiser: the seam kernel's GEMMs (rqhip/linear.py:chain_*), forward and data gradient
         aligned = x.data_ptr() % 16 == 0 and M > 0
@@ -153,7 +154,7 @@ class _MLPStack(torch.autograd.Function):
         ctx.acts_mid, ctx.scs, ctx.relus = (acts[1:] if ctx.has_target else acts[1:-1]), scs, tuple(relus)
         ctx.img_t, ctx.dg_split, ctx.wg_f16, ctx.need_in, ctx.need_w, ctx.chain = img_t, dg_split, wg_f16, need_in, need_w, chain
         ctx.small = small
-        ctx.defer = _lin.take_defer_flag()
+        ctx.defer = bool(defer)
         ctx.g_recon, ctx.g_scales, ctx.consumed = g_recon, g_scales, False
         return out
 
@@ -189,10 +190,9 @@ class _MLPStack(torch.autograd.Function):
         # batches below the split kernels' row count: every weight gradient of the stack in ONE launch after the data gradients
         # (csrc/wgrad_jobs.hip; same bits as the per-layer path, which runs the same kernel with one job)
         deferred = g.is_cuda and _lin.wgrad_jobs_ok(g.shape[0], [tuple(w.shape) for i, w in enumerate(weights) if need_w[i]])
-        pending = []
         # split-kernel batches: the weight gradients of the layers tiled 256 x 256 whose gradient arrives masked wait for ONE launch at the
         # end of the stack (rqhip_linear_wgrad_f16_batch: one workgroup's partial block per CU for all of them instead of per layer)
-        batched = []
+        own = []        # (layer, rqhip/linear.py:WgradJob) of either kind: a stack's row count decides which
         for i in range(n - 1, -1, -1):
             w, a = weights[i], acts[i]
             y = acts[i + 1] if (relus[i] and not premasked) else None
@@ -203,10 +203,10 @@ class _MLPStack(torch.autograd.Function):
             if need_w[i] and deferred:
                 if y is not None:
                     g, gsc = torch.ops.aten.threshold_backward(g, y, 0.0), _lin.Scales()
-                pending.append((i, g, a, _grad_sink(w)))
+                own.append((i, _lin.WgradJob(w, g, a, None, None, _grad_sink(w))))
             elif need_w[i] and y is None and g.is_cuda and wg_f16[i] and _lin.wgrad_batch_shape_ok(w.shape[0], w.shape[1], g.shape[0]):
                 gsc = _lin.ensure_scales(g, gsc, False, True)
-                batched.append((i, g, a, gsc.cols, _lin.ensure_scales(a, scs[i], False, True).cols, _grad_sink(w)))
+                own.append((i, _lin.WgradJob(w, g, a, gsc.cols, _lin.ensure_scales(a, scs[i], False, True).cols, _grad_sink(w))))
             elif need_w[i]:
                 sink = _grad_sink(w)
                 gw, g, gsc = _lin.weight_grad(g, y, a, w, out=sink, want_masked=need_in[i] and not mask_on_load, g_scales=gsc,
@@ -248,45 +248,16 @@ class _MLPStack(torch.autograd.Function):
             else:
                 g, gsc = g.mm(w), _lin.Scales()
                 premasked = not lower_relu
-        waiting = _lin.xstack_take() if g_out.is_cuda else []      # an earlier stack's weight gradients that waited for this launch
-        if batched or waiting:
-            M = g_out.shape[0]
-            sunk = all(sk is not None for *_, sk in batched)
-            if batched and not waiting and ctx.defer and sunk and _lin.xstack_ok():
-                # (this stack's turn to wait: a later node, or the engine's end-of-backward callback, launches them into the flat buffer)
-                _lin.xstack_push([(weights[i], gm, a, gc, xc, sk) for i, gm, a, gc, xc, sk in batched])
-                for i, *_, sk in batched:
-                    gws[i] = _adopt(sk, sk)
-            elif sunk:
-                _lin._launch_wgrads(waiting + [(weights[i], gm, a, gc, xc, sk) for i, gm, a, gc, xc, sk in batched])
-                for i, *_, sk in batched:
-                    gws[i] = _adopt(sk, sk)
-            else:       # (some gradient has no slice of a flat buffer to land in: fresh tensors, launched now)
-                _lin._launch_wgrads(waiting)
-                full = [b for b in batched if weights[b[0]].shape[0] % 256 == 0 and weights[b[0]].shape[1] % 256 == 0]
-                for group in (full, [b for b in batched if b not in full]):
-                    if len(group) >= 2 and ops.linear_wgrad_f16_batch_ranges(M, [tuple(weights[i].shape) for i, *_ in group]) >= 1:
-                        dws = ops.linear_wgrad_f16_batch([(gm, a, gc, xc) for _, gm, a, gc, xc, _ in group], outs=[sk for *_, sk in group])
-                        for (i, *_, sk), gw in zip(group, dws):
-                            gws[i] = _adopt(gw, sk)
-                    else:
-                        for i, gm, a, gc, xc, sk in group:
-                            gw, _, _ = _lin.weight_grad(gm, None, a, weights[i], out=sk, want_masked=False, g_scales=_lin.Scales(None, gc),
-                                                        x_scales=_lin.Scales(None, xc), premasked=True)
-                            gws[i] = _adopt(gw, sk)
-        waiting_small = _lin.xsmall_take() if g_out.is_cuda else []      # an earlier stack's job-table weight gradients
-        if pending or waiting_small:
-            sunk = all(sk is not None for *_, sk in pending)
-            if pending and not waiting_small and ctx.defer and sunk and _lin.xsmall_ok():
-                _lin.xsmall_push([(gm, a, sk) for _, gm, a, sk in pending])      # (a later stack's launch, or the end-of-backward callback)
-                for i, *_, sk in pending:
-                    gws[i] = _adopt(sk, sk)
-            else:
-                outs = [sk if sk is not None else torch.empty_like(weights[i]) for (i, _, _, sk) in pending]
-                _lin._launch_small(waiting_small + [(gm, a, o) for (_, gm, a, _), o in zip(pending, outs)])
-                for (i, _, _, sk), o in zip(pending, outs):
-                    gws[i] = _adopt(o, sk)
-        return (g if ctx.needs_input_grad[0] else None), None, None, None, *gws
+        waited = _lin.wgrad_queue.take() if g_out.is_cuda else []       # an earlier stack's weight gradients that waited for this launch
+        jobs = [j for _, j in own]
+        if jobs and not waited and ctx.defer and _lin.wgrad_queue.may_park(jobs):
+            _lin.wgrad_queue.park(jobs)      # (this stack's turn to wait: what it returns meanwhile is the sinks -- rqhip/linear.py:WgradQueue)
+            dws = [j.sink for j in jobs]
+        else:
+            dws = _lin.launch_wgrads(jobs, waited)
+        for (i, j), dw in zip(own, dws):
+            gws[i] = _adopt(dw, j.sink)
+        return (g if ctx.needs_input_grad[0] else None), None, None, None, None, None, *gws
 
 
 class MLP(nn.Module):
@@ -333,12 +304,7 @@ class MLP(nn.Module):
             relus.append(relu)
             i += 2 if relu else 1
         if weights:
-            _lin.handoff_scales(_lin.attached_scales(x))
-            _lin.mark_next_stack_defers(getattr(self, "_defer_wgrads", False))
-            try:
-                x = _MLPStack.apply(x, target, tuple(relus), self._zero_bias, *weights)
-            finally:
-                _lin.mark_next_stack_defers(False)
+            x = _MLPStack.apply(x, target, tuple(relus), self._zero_bias, _lin.attached_scales(x), getattr(self, "_defer_wgrads", False), *weights)
         return self._run_layerwise(x, layers[i:]) if i < len(layers) else x
 
     def _run_layerwise(self, x: Tensor, layers) -> Tensor:

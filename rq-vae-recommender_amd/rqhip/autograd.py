@@ -120,7 +120,7 @@ class RqSeamFunction(torch.autograd.Function):
             if need_wout:
                 if jobs:
                     g_dm = torch.ops.aten.threshold_backward(g_d, d, 0.0)     # (the job-table kernel takes the masked gradient as a tensor)
-                    pending.append(("out", g_dm, emb_sum, claim_grad_sink(w_out), w_out))
+                    pending.append(_lin.WgradJob(w_out, g_dm, emb_sum, None, None, claim_grad_sink(w_out)))
                 else:
                     sink = claim_grad_sink(w_out)
                     gw, gp, _ = _lin.weight_grad(g_d, d, emb_sum, w_out, out=sink, want_masked=False)
@@ -148,19 +148,17 @@ class RqSeamFunction(torch.autograd.Function):
         g_h = None
         if g_res0 is not None and need_win:
             if jobs:
-                pending.append(("in", g_res0, h, claim_grad_sink(w_in), w_in))
+                pending.append(_lin.WgradJob(w_in, g_res0, h, None, None, claim_grad_sink(w_in)))
             else:
                 sink = claim_grad_sink(w_in)
                 gw, _, _ = _lin.weight_grad(g_res0, None, h, w_in, out=sink)
                 gw_in = gw.view_as(gw) if sink is not None else gw
-        if pending:
-            outs = [sk if sk is not None else torch.empty_like(w) for (_, _, _, sk, w) in pending]
-            for (which, _, _, sk, _), gw in zip(pending, ops.linear_wgrad_jobs([(gm, a) for _, gm, a, _, _ in pending], outs=outs)):
-                gw = gw.view_as(gw) if sk is not None else gw
-                if which == "out":
-                    gw_out = gw
-                else:
-                    gw_in = gw
+        for j, gw in zip(pending, _lin.launch_wgrads(pending)):
+            gw = gw.view_as(gw) if j.sink is not None else gw
+            if j.w is w_out:
+                gw_out = gw
+            else:
+                gw_in = gw
         if g_res0 is not None and need_h:
             cols = None
             if ctx.want_scales:      # the forward's spare half, once; a second backward through a retained graph zeroes its own

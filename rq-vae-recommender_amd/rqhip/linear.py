@@ -10,8 +10,13 @@ a caller that has none gets them from one `ops.maxima` pass -- same maxima, same
 when the reconstruction loss's upstream gradient is not the announced 1 / B -- `ops.recon_rescale_rows` -- rows that were scaled DOWN leave
 the column maxima of that gradient too large: still a valid scale, one low-order bit of the fp16 low piece per binade of overestimate,
 and not the bits a fresh maxima pass would give.  No shipped training loop takes that path: the loss is a mean.)
-`use_arith("bf16x3")` keeps round 3's three-piece bf16 kernels for A/B (bench.py --mlp split6)."""
-from typing import List, Optional, Tuple
+`use_arith("bf16x3")` keeps round 3's three-piece bf16 kernels for A/B (bench.py --mlp split6).
+
+What the host side of a step tells itself across autograd nodes, and how: the maxima that came with a stack's input (`attached_scales`) and
+whether the stack may park its weight gradients are ARGUMENTS of `_MLPStack.apply`; weight-gradient jobs are `WgradJob`s, launched by
+`launch_wgrads` and parked in `wgrad_queue` (the contract: `WgradQueue`); the one remaining call-order slot is `handoff_grad`, which
+carries pointer, shape and version of the gradient it speaks about."""
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import os
 
@@ -88,20 +93,6 @@ def attached_scales(t: Tensor) -> Optional[Scales]:
     return Scales(sc.rows if ok_r else None, sc.cols if ok_c else None)
 
 
-_HANDOFF: List[Optional[Scales]] = [None]
-
-
-def handoff_scales(sc: Optional[Scales]) -> None:
-    """The scales of the tensor the NEXT `_MLPStack.apply` receives as its input (set by MLP._run right before the call, taken by the
-    node's forward: an autograd Function may be handed an alias of the caller's tensor object, attributes do not survive that)."""
-    _HANDOFF[0] = sc
-
-
-def take_scales() -> Optional[Scales]:
-    sc, _HANDOFF[0] = _HANDOFF[0], None
-    return sc
-
-
 # ---- zeroed int32 slices for column maxima ---------------------------------------------------------------------------------------------
 # Every kernel that emits column maxima accumulates them with atomic maxima into a buffer the caller zeroed; a training step at 100 000
 # rows asked for six such buffers, each a `torch.zeros` = one 4 us fill launch (28 us of a 2.7 ms step).  They are cut from a pool that
@@ -146,15 +137,17 @@ _GRAD_HANDOFF: List[Optional[tuple]] = [None]
 
 
 def handoff_grad(g: Tensor, sc: Scales) -> None:
-    """The NEXT `_MLPStack.backward` that receives `g` (same storage, same shape) as its upstream gradient may take it as already masked by
-    its last layer's ReLU, with these maxima (set by the backward of modules/rqvae.py's seam node, whose epilogue did both)."""
-    _GRAD_HANDOFF[0] = (g.data_ptr(), tuple(g.shape), sc)
+    """The NEXT `_MLPStack.backward` that receives `g` (same storage, same shape, not written since) as its upstream gradient may take it
+    as already masked by its last layer's ReLU, with these maxima (set by the backward of modules/rqvae.py's seam node, whose epilogue did
+    both).  The version is part of the proof: a second consumer of the hidden activation makes autograd's input buffer add its gradient
+    into `g` in place -- same pointer, another version, and a sum that is neither masked nor under these maxima."""
+    _GRAD_HANDOFF[0] = (g.data_ptr(), tuple(g.shape), g._version, sc)
 
 
 def take_grad_handoff(g: Tensor) -> Optional[Scales]:
     slot, _GRAD_HANDOFF[0] = _GRAD_HANDOFF[0], None     # one shot: whoever asks next clears it, match or not
-    if slot is not None and slot[0] == g.data_ptr() and slot[1] == tuple(g.shape):
-        return slot[2]
+    if slot is not None and slot[:3] == (g.data_ptr(), tuple(g.shape), g._version):
+        return slot[3]
     return None
 
 
@@ -223,125 +216,115 @@ def use_wgrad_batch(on: bool = True) -> bool:
     return before
 
 
-# ---- ... and of TWO stacks in one launch: the decoder's wait for the encoder's (single rank, eager, gradients in a flat buffer) ----------
-# The decoder's backward runs first; its 256 x 256-tiled weight gradients (with the encoder's: 16 tiles x 16 row ranges instead of twice
-# 8 x 32) are launched at the end of the encoder stack's backward, or by a callback the autograd engine runs when the backward pass ends
-# (an encoder without gradients, a stack used on its own).  What the decoder's node returns for those weights meanwhile is the parameter's
-# slice of the flat gradient buffer (rqhip/dist.py:claim_grad_sink), which the launch fills before anything on the stream reads it.  NOT
-# with several ranks: the decoder's gradients go on the wire under the encoder's backward there (FlatGradReducer.boundary_hook).
-_XSTACK_ON = True
-_XSTACK: List[tuple] = []            # (w, g, x, g_cols, x_cols, sink) waiting for a later stack of the same backward pass
-_DEFER_NEXT = [False]
+# ---- weight-gradient jobs: one record, one launcher, one waiting list -------------------------------------------------------------------
+class WgradJob(NamedTuple):
+    """dW [n_out, n_in] = g^T x of one layer: `w` (for its shape), `g` [M, n_out] already masked by the layer's ReLU, `x` [M, n_in], the
+    column maxima of both for the fp16 split kernel (None, None: a job of the job-table kernel, batches below 4096 rows), `sink`: the
+    tensor to write (the parameter's slice of a flat gradient buffer) or None = a fresh one."""
+    w: Tensor
+    g: Tensor
+    x: Tensor
+    g_cols: Optional[Tensor]
+    x_cols: Optional[Tensor]
+    sink: Optional[Tensor]
+
+
+def _launch_group(jobs: List[WgradJob]) -> List[Tensor]:
+    if jobs[0].g_cols is None:
+        return ops.linear_wgrad_jobs([(j.g, j.x) for j in jobs], outs=[j.sink for j in jobs])
+    if len(jobs) >= 2 and ops.linear_wgrad_f16_batch_ranges(jobs[0].g.shape[0], [tuple(j.w.shape) for j in jobs]) >= 1:
+        return ops.linear_wgrad_f16_batch([(j.g, j.x, j.g_cols, j.x_cols) for j in jobs], outs=[j.sink for j in jobs])
+    return [weight_grad(j.g, None, j.x, j.w, out=j.sink, want_masked=False, g_scales=Scales(None, j.g_cols), x_scales=Scales(None, j.x_cols),
+                        premasked=True)[0] for j in jobs]
+
+
+def launch_wgrads(jobs: List[WgradJob], waited: Sequence[WgradJob] = ()) -> List[Tensor]:
+    """Launch `jobs` and return their dW in order.  fp16 jobs first: the layers tiled 256 x 256 together, the half-tiled ones (128 x 256 /
+    256 x 128) together, at most 4 per launch, one batched launch where the plan allows, else per layer; then the job-table jobs, at most
+    ops.WGRAD_JOBS_MAX per launch.  `waited`: an earlier stack's jobs (`WgradQueue.take`), launched in the same groups as `jobs` when every
+    one of `jobs` has a sink and both have the same row count and device -- a batched launch cuts its layers into a number of row ranges
+    that depends on which layers share it, so the grouping decides result bits -- else on their own, first."""
+    if waited and not (jobs and all(j.sink is not None for j in jobs)
+                       and (waited[0].g.shape[0], waited[0].g.device) == (jobs[0].g.shape[0], jobs[0].g.device)):
+        launch_wgrads(waited)
+        waited = ()
+    todo = [*waited, *jobs]
+    dws: List[Optional[Tensor]] = [None] * len(todo)
+    groups = ([], [], [])       # indices of: fp16 jobs tiled 256 x 256, fp16 jobs half-tiled, job-table jobs
+    for i, j in enumerate(todo):
+        groups[2 if j.g_cols is None else 0 if (j.w.shape[0] % 256 == 0 and j.w.shape[1] % 256 == 0) else 1].append(i)
+    for idx, per_launch in zip(groups, (4, 4, ops.WGRAD_JOBS_MAX)):
+        for c in range(0, len(idx), per_launch):
+            part = idx[c:c + per_launch]
+            for i, dw in zip(part, _launch_group([todo[i] for i in part])):
+                dws[i] = dw
+    return dws[len(waited):]
+
+
+_CROSS_STACK = True
 
 
 def use_wgrad_cross_stack(on: bool = True) -> bool:
     """A/B (round 6): the decoder's batched weight gradients wait for the encoder's launch (default) or are launched per stack."""
-    global _XSTACK_ON
-    before, _XSTACK_ON = _XSTACK_ON, bool(on)
+    global _CROSS_STACK
+    before, _CROSS_STACK = _CROSS_STACK, bool(on)
     return before
 
 
-def mark_next_stack_defers(on: bool = True) -> None:
-    """modules/encoder.py:MLP._run for a module tagged `_defer_wgrads` (RqVae's decoder): the stack node created next may hand its
-    batched weight gradients to a later node's launch."""
-    _DEFER_NEXT[0] = bool(on)
+class WgradQueue:
+    """Weight-gradient jobs of one stack that wait for a later stack's launch in the same backward pass (`wgrad_queue`, the only instance).
 
+    Why: the decoder's backward runs before the encoder's.  At split-kernel batches one rqhip_linear_wgrad_f16_batch over both stacks' layers
+    (16 tiles x 16 row ranges instead of twice 8 x 32) beats one per stack; below 4096 rows one job-table launch serves both stacks (also
+    inside a hipGraph capture: the engine's callback runs inside the captured region like everything else of the step).
 
-def take_defer_flag() -> bool:
-    f, _DEFER_NEXT[0] = _DEFER_NEXT[0], False
-    return f
+    Who may park: a `_MLPStack` node whose module is tagged `_defer_wgrads` (RqVae's decoder), when nothing waits already and `may_park`
+    holds -- one rank (with several the decoder's gradients go on the wire under the encoder's backward: FlatGradReducer.boundary_hook), the
+    A/B switches on, every job with a slice of the flat gradient buffer to land in (rqhip/dist.py:claim_grad_sink), no hook on a weight.
+    Who launches: the next `_MLPStack.backward` of the pass (`take`, then `launch_wgrads(own, waited)`), or the callback the autograd engine
+    runs when the pass ends (an encoder without gradients, a stack used on its own) -- on the stream the parking backward ran on, which
+    need not be current on the thread that called backward().
+    What the parked dW is until then: the node has returned an alias of the sink, autograd has made it `.grad`, and it still holds the
+    PREVIOUS step's values; the launch fills it before anything later on the stream reads it.  Whatever reads a gradient between the node
+    and the launch -- a tensor hook, a post-accumulate-grad hook -- would see stale values, hence no parking for a hooked weight.
+    A pass that ended in an exception leaves its jobs here: `clear` (RqVae.forward) drops them."""
 
+    def __init__(self) -> None:
+        self._jobs: List[WgradJob] = []
+        self._stream = None
 
-def xstack_ok() -> bool:
-    from . import dist as _dist
-    return bool(_XSTACK_ON and _WGRAD_BATCH and _dist.world_size() == 1 and not torch.cuda.is_current_stream_capturing())
+    def waiting(self) -> bool:
+        return bool(self._jobs)
 
+    def may_park(self, jobs: List[WgradJob]) -> bool:
+        from . import dist as _dist
+        kind_ok = _WGRAD_JOBS if jobs[0].g_cols is None else (_WGRAD_BATCH and not torch.cuda.is_current_stream_capturing())
+        return bool(_CROSS_STACK and kind_ok and _dist.world_size() == 1 and all(j.sink is not None for j in jobs)
+                    and not any(j.w._backward_hooks or j.w._post_accumulate_grad_hooks for j in jobs))
 
-def _launch_wgrads(jobs: List[tuple]) -> None:
-    """jobs = [(w, g, x, g_cols, x_cols, sink), ...]: batched launches where the plan allows (layers tiled 256 x 256 together, layers tiled
-    128 x 256 / 256 x 128 together; at most 4 per launch), else per layer."""
-    full = [j for j in jobs if j[0].shape[0] % 256 == 0 and j[0].shape[1] % 256 == 0]
-    half = [j for j in jobs if not (j[0].shape[0] % 256 == 0 and j[0].shape[1] % 256 == 0)]
-    for group in (full, half):
-        _launch_wgrad_group(group)
+    def park(self, jobs: List[WgradJob]) -> None:
+        if not self._jobs:
+            torch.autograd.Variable._execution_engine.queue_callback(self._flush)
+            self._stream = torch.cuda.current_stream()
+        self._jobs.extend(jobs)
 
+    def take(self) -> List[WgradJob]:
+        jobs, self._jobs = self._jobs, []
+        return jobs
 
-def _launch_wgrad_group(jobs: List[tuple]) -> None:
-    while jobs:
-        take, jobs = jobs[:4], jobs[4:]
-        M = take[0][1].shape[0]
-        if len(take) >= 2 and ops.linear_wgrad_f16_batch_ranges(M, [tuple(w.shape) for w, *_ in take]) >= 1:
-            ops.linear_wgrad_f16_batch([(g, x, gc, xc) for _, g, x, gc, xc, _ in take], outs=[sk for *_, sk in take])
-        else:
-            for w, g, x, gc, xc, sk in take:
-                weight_grad(g, None, x, w, out=sk, want_masked=False, g_scales=Scales(None, gc), x_scales=Scales(None, xc), premasked=True)
+    def clear(self) -> None:
+        self._jobs = []
 
-
-_XSTACK_STREAM: List = [None]      # the stream the waiting stack's backward ran on
-
-
-def xstack_flush() -> None:
-    """Launch whatever still waits: the autograd engine's end-of-backward callback.  It runs on the thread that called backward(), whose
-    current stream need not be the one the backward nodes ran on -- the launch goes to THAT stream (recorded by xstack_push)."""
-    if _XSTACK:
-        jobs, _XSTACK[:] = list(_XSTACK), []
-        st = _XSTACK_STREAM[0]
-        if st is not None and st != torch.cuda.current_stream(st.device):
+    def _flush(self) -> None:
+        jobs, st = self.take(), self._stream
+        if jobs and st is not None and st != torch.cuda.current_stream(st.device):
             with torch.cuda.stream(st):
-                _launch_wgrads(jobs)
-        else:
-            _launch_wgrads(jobs)
+                launch_wgrads(jobs)
+        elif jobs:
+            launch_wgrads(jobs)
 
 
-def xstack_push(jobs: List[tuple]) -> None:
-    if not _XSTACK:
-        torch.autograd.Variable._execution_engine.queue_callback(xstack_flush)
-        _XSTACK_STREAM[0] = torch.cuda.current_stream()
-    _XSTACK.extend(jobs)
-
-
-def xstack_take() -> List[tuple]:
-    jobs, _XSTACK[:] = list(_XSTACK), []
-    return jobs
-
-
-# ---- the same for the job-table launch of the reference's batch sizes (< 4096 rows, csrc/wgrad_jobs.hip): one launch for BOTH stacks' layers --------
-# (also inside a hipGraph capture: the engine's end-of-backward callback runs inside the captured region like everything else of the step)
-_XSMALL: List[tuple] = []            # (g, x, sink)
-
-
-def xsmall_ok() -> bool:
-    from . import dist as _dist
-    return bool(_XSTACK_ON and _WGRAD_JOBS and _dist.world_size() == 1)
-
-
-def _launch_small(jobs: List[tuple]) -> None:
-    while jobs:
-        take, jobs = jobs[:ops.WGRAD_JOBS_MAX], jobs[ops.WGRAD_JOBS_MAX:]
-        ops.linear_wgrad_jobs([(g, x) for g, x, _ in take], outs=[sk for *_, sk in take])
-
-
-def xsmall_flush() -> None:
-    if _XSMALL:
-        jobs, _XSMALL[:] = list(_XSMALL), []
-        st = _XSTACK_STREAM[0]
-        if st is not None and st != torch.cuda.current_stream(st.device):
-            with torch.cuda.stream(st):
-                _launch_small(jobs)
-        else:
-            _launch_small(jobs)
-
-
-def xsmall_push(jobs: List[tuple]) -> None:
-    if not _XSMALL:
-        torch.autograd.Variable._execution_engine.queue_callback(xsmall_flush)
-        _XSTACK_STREAM[0] = torch.cuda.current_stream()
-    _XSMALL.extend(jobs)
-
-
-def xsmall_take() -> List[tuple]:
-    jobs, _XSMALL[:] = list(_XSMALL), []
-    return jobs
+wgrad_queue = WgradQueue()
 
 
 def wgrad_batch_shape_ok(n_out: int, n_in: int, rows: int) -> bool:

@@ -531,7 +531,7 @@ def test_batched_weight_gradients_across_the_two_stacks(frozen_encoder, monkeypa
             out = m(batch, 0.2)
             out.loss.backward()
             torch.cuda.synchronize()
-            assert not linear._XSTACK
+            assert not linear.wgrad_queue.waiting()
             res[arm] = (out.loss.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.requires_grad}, list(calls))
         finally:
             linear.use_wgrad_batch(b0)
@@ -544,6 +544,125 @@ def test_batched_weight_gradients_across_the_two_stacks(frozen_encoder, monkeypa
         for n, gref in res["per_layer"][1].items():
             got = res[arm][1][n]
             assert (got - gref).abs().max().item() <= 4e-6 * gref.abs().max().item() + 1e-12, (arm, n)
+
+
+@pytest.mark.parametrize("rows", [8192, 640])
+@pytest.mark.parametrize("hook", ["tensor", "post_accumulate"])
+def test_hook_on_a_decoder_weight_sees_this_steps_gradient(hook, rows):
+    """rqhip/linear.py:WgradQueue: a parked weight gradient is an alias of the flat-buffer slice that the launch fills LATER, so a stack does
+    not park when one of its weights has a tensor hook or a post-accumulate-grad hook -- it launches at once, as the per-stack arm does.
+    The hook on a 256 x 256-tiled decoder weight therefore sees the second step's gradient (another batch), bit for bit the per-stack arm's."""
+    from data.schemas import SeqBatch
+    from rqhip import linear
+    from rqhip.dist import FlatGradReducer
+    batches = [SeqBatch(None, None, None, torch.nn.functional.normalize(
+        torch.randn(rows, 768, device="cuda", generator=torch.Generator("cuda").manual_seed(s)), dim=-1), None, None) for s in (1, 2)]
+
+    def run(cross, hooked):
+        m = _rqvae_768()
+        red = FlatGradReducer(m.parameters()).attach(m)
+        w, seen = m.decoder.mlp[4].weight, []
+        assert tuple(w.shape) == (512, 256)
+        if hooked and hook == "tensor":
+            w.register_hook(lambda g: seen.append(g.clone()))
+        elif hooked:
+            w.register_post_accumulate_grad_hook(lambda p: seen.append(p.grad.clone()))
+        before = linear.use_wgrad_cross_stack(cross)
+        try:
+            for b in batches:
+                red.zero_()
+                m(b, 0.2).loss.backward()
+                torch.cuda.synchronize()
+                assert not linear.wgrad_queue.waiting()
+        finally:
+            linear.use_wgrad_cross_stack(before)
+        return seen, w.grad.clone()
+
+    seen, _ = run(True, True)
+    _, ref = run(False, False)
+    assert len(seen) == 2 and not torch.equal(seen[0], seen[1])
+    assert torch.equal(seen[1], ref)
+
+
+def test_waiting_weight_gradients_meet_a_stack_of_another_row_count(monkeypatch):
+    """rqhip/linear.py:launch_wgrads: jobs that waited are merged into the next stack's launch only when row count and device agree.  Two
+    MLPs under one loss on 8192 and 4096 rows, the one whose backward runs first (the one applied last) tagged `_defer_wgrads`: its parked
+    jobs are launched on their own, nothing is lost, nothing is left waiting, every gradient is the untagged run's bit for bit."""
+    from modules.encoder import MLP
+    from rqhip import linear
+    from rqhip.dist import FlatGradReducer
+    gen = torch.Generator("cuda").manual_seed(4)
+    xa = torch.nn.functional.normalize(torch.randn(4096, 768, device="cuda", generator=gen), dim=-1)
+    xb = torch.nn.functional.normalize(torch.randn(8192, 768, device="cuda", generator=gen), dim=-1)
+    parked = []
+    real_park = linear.wgrad_queue.park
+    monkeypatch.setattr(linear.wgrad_queue, "park", lambda jobs: (parked.append(len(jobs)), real_park(jobs))[1])
+
+    def run(tagged):
+        torch.manual_seed(7)
+        a, b = MLP(768, [512, 256, 128], 32).cuda(), MLP(768, [512, 256, 128], 32).cuda()
+        if tagged:
+            b._defer_wgrads = True
+        params = [*a.parameters(), *b.parameters()]
+        FlatGradReducer(params).attach().zero_()
+        (a(xa).square().mean() + b(xb).square().mean()).backward()
+        torch.cuda.synchronize()
+        assert not linear.wgrad_queue.waiting()
+        return [p.grad.clone() for p in params]
+
+    ref = run(False)
+    assert not parked
+    got = run(True)
+    assert parked == [3], "the tagged stack did not park: the case under test did not occur"
+    for u, v in zip(got, ref):
+        assert torch.equal(u, v)
+
+
+def test_seam_hand_over_meets_a_second_gradient_of_the_hidden_activation(monkeypatch):
+    """rqhip/linear.py:handoff_grad: the seam node's "this gradient is masked, here are its maxima" holds for the tensor as it was handed
+    over.  With a second consumer of the encoder's hidden activation autograd's input buffer adds that gradient to g_h -- in place when g_h
+    arrived first (same pointer, another version), which is why the second consumer's term is built inside the wrapper, BEFORE the seam
+    node exists: the engine runs later-created nodes first, so the seam's g_h reaches the buffer first.  The stack must then mask the sum
+    and take its maxima itself: every gradient equals the run without any hand-over.  Without the second consumer the hand-over IS taken."""
+    from data.schemas import SeqBatch
+    from modules.quantize import QuantizeForwardMode
+    from rqhip import linear
+    from test_gpu_seam import _model
+    x = torch.nn.functional.normalize(torch.randn(8192, 768, generator=torch.Generator().manual_seed(11)), dim=-1).cuda()
+    taken = []
+    real_take = linear.take_grad_handoff
+
+    def counting_take(g):
+        sc = real_take(g)
+        taken.append(sc is not None)
+        return sc
+    monkeypatch.setattr(linear, "take_grad_handoff", counting_take)
+
+    def run(second_consumer, hand_over=True):
+        m = _model(QuantizeForwardMode.STE).train()
+        assert m._seam_weights(x) is not None
+        side, real = [], m.encoder.run_before_tail
+
+        def keeping(t):
+            h = real(t)
+            side.append(h.sum() * 1e-5)
+            return h
+        m.encoder.run_before_tail = keeping
+        with monkeypatch.context() as mp:
+            if not hand_over:
+                mp.setattr(linear, "handoff_grad", lambda g, sc: None)
+            del taken[:]
+            out = m(SeqBatch(None, None, None, x, None, None), 0.2)
+            (out.loss + side[0] if second_consumer else out.loss).backward()
+        return {k: p.grad.detach().clone() for k, p in m.named_parameters()}, list(taken)
+
+    _, took = run(False)
+    assert any(took), "the seam's hand-over was not taken on the plain path: the version check never matches"
+    got, _ = run(True)
+    ref, took = run(True, hand_over=False)
+    assert not any(took)
+    for k in ref:
+        assert torch.equal(got[k], ref[k]), k
 
 
 def test_split_gemms_follow_the_optimizer():

@@ -33,7 +33,7 @@ if "--no-seam" in sys.argv:      # A/B: round 5's library GEMMs for the 128 <-> 
 if "--no-small" in sys.argv:     # A/B: round 5's library GEMMs + threshold_backward launches instead of csrc/mlp_small.hip
     from rqhip import linear as _linear
     _linear.use_small_kernels(False)
-if "--no-cross-stack" in sys.argv:   # A/B: one job-table weight-gradient launch per MLP stack instead of one for both (rqhip/linear.py:xsmall_*)
+if "--no-cross-stack" in sys.argv:   # A/B: one job-table weight-gradient launch per MLP stack instead of one for both (rqhip/linear.py:WgradQueue)
     from rqhip import linear as _linear
     _linear.use_wgrad_cross_stack(False)
 ARGS = [a for a in sys.argv[1:] if a not in ("--json", "--no-jobs", "--no-seam", "--no-small", "--no-cross-stack")]
