@@ -280,6 +280,27 @@ int rqhip_beam_step(const float *logits, int64_t ld_logits, const float *noise, 
                     int64_t *out_ids, float *out_scores, int64_t *out_parent, void *workspace, size_t workspace_bytes,
                     rqhip_stream_t stream);
 
+/* T5 attention for inference (modules/t5.py:_attend) in one launch, fp32 throughout (csrc/t5_attention.hip):
+ *   out[r, i, h*64 : h*64+64] = softmax_j(q[r, i, h] . k[b, j, h] + bias + mask) . v[b, :, h]      b = r / (R / Rk)
+ * with T5's semantics: no 1/sqrt(d) scaling, d_kv = 64, masked scores get finfo(float32).min ADDED (a row with every key
+ * masked is the uniform average of V).  Token (r, i) of q / out is row r * Tq + i with row stride ld_q / ld_out (elements),
+ * head h at columns h*64 ..: the q Linear's output and the o Linear's input as they are, no transposes.
+ *   K/V, dense (anc NULL): token (b, j) of k / v is row b * Tk + j with row stride ld_kv; the R / Rk query rows
+ *     b * (R / Rk) .. read group b (the beams of a user in cross-attention), whose K/V are staged once per (b, h).
+ *   K/V, cached decode step (anc [R, ld_anc] int32, Tq = 1, Rk = R, Tk = past + 1): k / v are per-position slabs, row
+ *     t * slab_rows + x with row stride ld_kv; key t < past of row r is slab row x = anc[r * ld_anc + t], key `past` is
+ *     the row's own x = r.  No cache tensor is copied.
+ *   bias_by_delta [n_delta, H] (or NULL): table[(j - i - past) + bias_offset][h] is added; the caller gathers it from
+ *     the relative-position embedding, the kernel computes no bucket.
+ *   key_mask [Rk, Tk] bytes (or NULL; 0 = masked); causal != 0 keeps j <= i + past.
+ * Limits (rqhip_t5_attention_supported): d_kv = 64, 1 <= Tq, Tk <= 256, any H >= 1; else RQHIP_EUNSUPPORTED.  Pointers
+ * 16-byte aligned, strides multiples of 4.  Deterministic; no allocation, copy or sync (graph-capturable). */
+int rqhip_t5_attention_supported(int d_kv, int H, int Tq, int Tk);
+int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, int64_t R, int64_t Rk,
+                       int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta, int bias_offset,
+                       const uint8_t *key_mask, int causal, int past, const int32_t *anc, int64_t ld_anc,
+                       int64_t slab_rows, float *out, int64_t ld_out, rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

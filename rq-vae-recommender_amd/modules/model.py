@@ -2,9 +2,12 @@
 next item's ids one hierarchy level at a time.  API and state dict of the reference's modules/model.py
 (EncoderDecoderRetrievalModel), so a checkpoint trained there loads here with strict=True.
 
-The T5 body runs on torch operators (modules/t5.py).  Each hierarchy step of `generate` is the decoder on one new
-token per beam, the head's F.linear and ONE HIP launch (ops.beam_step, csrc/beam_step.hip) that does the reference's
-softmax, multinomial sampling, log, prefix-validity mask, sort and gathers.  After the encoder nothing is read back to
+The T5 body runs on torch operators (modules/t5.py), or, with `model.attention_impl = "hip"` (a plain attribute, default
+"torch"; inference only, see modules/t5.py), with every attention call as one HIP launch (ops.t5_attention) and the
+decoder's self-attention history of `generate` in per-position slabs that are never copied.
+Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
+(ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
+mask, sort and gathers.  After the encoder nothing is read back to
 the host and no allocation depends on data, so a whole `generate` can be captured into a graph.
 
 Sampling: the reference's `torch.multinomial(probas, n, replacement=False)` is ATen's exponential race
@@ -84,6 +87,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
         self._prefix_index: Optional[SemIdPrefixIndex] = None
         self._prefix_key = None
+        self.attention_impl = "torch"  # or "hip"; handed to both T5 stacks whenever they are run
 
     @property
     def device(self) -> torch.device:
@@ -131,7 +135,11 @@ class EncoderDecoderRetrievalModel(nn.Module):
             self.codebooks = self.codebooks.to(prefix.device)
         return self._prefix_index_for_codebooks().check_valid_prefix(prefix, batch_size)
 
+    def _push_attention_impl(self) -> None:
+        self.encoder.encoder.attention_impl = self.t5_decoder.attention_impl = self.attention_impl
+
     def encoder_forward_pass(self, attention_mask, input_ids, user_id=None):
+        self._push_attention_impl()
         shifted = self._add_repeating_offset_to_rows(input_sids=input_ids,
                                                      codebook_size=self.num_embeddings_per_hierarchy,
                                                      num_hierarchies=self.num_hierarchies,
@@ -153,6 +161,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
                              attention_mask_for_encoder=None, use_cache=False, past_key_values=None):
         """BOS followed by the embedded future ids (or BOS alone); with a cache (the list this returns when use_cache)
         only the last future id is run.  Returns the hidden states, and the self-attention cache when use_cache."""
+        self._push_attention_impl()
         if future_ids is not None:
             shifted = self._add_repeating_offset_to_rows(
                 input_sids=future_ids, codebook_size=self.num_embeddings_per_hierarchy,
@@ -198,7 +207,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
         Step 0 decodes BOS on the B users and keeps the best k of n_cands = min(64, K) samples; every later step runs
         the B * k beams' newest id through the decoder (self-attention cache reordered by parent beam; cross-attention
-        K/V computed once on the B users) and one ops.beam_step.
+        K/V computed once on the B users) and one ops.beam_step.  With attention_impl = "hip" the self-attention cache
+        is a T5DecodeCache instead: each step's K/V are projected straight into that position's slab and the parent
+        beams reorder a small ancestor table, never the K/V.
 
         Returns generated_ids [B, k, num_hierarchies] int64 and log_probas [B, k] fp32 (-inf for beams without a valid
         corpus prefix)."""
@@ -223,14 +234,23 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
         x = self.bos_token.unsqueeze(0).expand(B, 1, -1)
         self_kv: Optional[List] = None
+        slabs = None
+        if dec.hip_attention_active(enc_out, 1, self.num_hierarchies, enc_out.shape[1]):
+            slabs = dec.new_decode_cache(self.num_hierarchies, B * k, enc_out.device)
         ids = scores = None
         for h in range(self.num_hierarchies):
             if h > 0:
-                rows = parent.flatten()
-                self_kv = [(kk.index_select(0, rows), vv.index_select(0, rows)) for kk, vv in self_kv]
                 x = self.item_sid_embedding_table(ids[:, :, h - 1].reshape(-1, 1) + (h - 1) * K)
-            hidden, self_kv = dec(x, encoder_attention_mask=enc_mask, past_key_values=self_kv, use_cache=True,
-                                  cross_kv=cross_kv)
+            if slabs is not None:
+                if h > 0:
+                    slabs.reorder(parent)
+                hidden = dec(x, encoder_attention_mask=enc_mask, cross_kv=cross_kv, decode_cache=slabs)
+            else:
+                if h > 0:
+                    rows = parent.flatten()
+                    self_kv = [(kk.index_select(0, rows), vv.index_select(0, rows)) for kk, vv in self_kv]
+                hidden, self_kv = dec(x, encoder_attention_mask=enc_mask, past_key_values=self_kv, use_cache=True,
+                                      cross_kv=cross_kv)
             logits = F.linear(hidden[:, -1], self.decoder_mlp[h].weight)
             noise = _exponential_like(logits)
             ids, scores, parent = ops.beam_step(logits, noise, scores, ids, index._index, index._corpus, n_cands, k)

@@ -17,6 +17,14 @@ with the same module tree, so a reference checkpoint loads by its state-dict nam
 The decoder can run incrementally: `T5Stack.forward` takes and returns a self-attention cache (one (K, V) pair per
 block, [rows, heads, t, 64]) and accepts precomputed cross-attention K/V (`cross_kv`) on fewer rows than the queries:
 rows r = b * beams + beam all read user b's encoder output, as the beams of a beam search do.
+
+Attention implementation: a stack's `attention_impl` is "torch" (the default: the operators above) or "hip": every
+attention call is then ONE launch of ops.t5_attention (csrc/t5_attention.hip), fed the q / k / v Linears' outputs as
+they are and a [n_delta, heads] table of the relative-position bias by j - i.  "hip" is taken only for fp32 device
+tensors with grad disabled, dropout inactive (eval mode), no operator-format cache passed in and a shape the kernel
+supports; otherwise the operators run, silently.  The incremental decoder of the "hip" path keeps its self-attention
+K/V in per-position slabs (`T5DecodeCache`) that are written once and never copied: a beam search reorders an int32
+ancestor table instead of the cache.
 """
 import math
 from typing import List, Optional, Tuple
@@ -26,7 +34,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch import Tensor
 
+from rqhip import ops
+
 KV = Tuple[Tensor, Tensor]
+ATTENTION_IMPLS = ("torch", "hip")
+MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
 class T5Config:
@@ -82,6 +94,37 @@ def relative_position_bucket(relative_position: Tensor, bidirectional: bool, num
     return buckets + torch.where(is_small, relative_position, large)
 
 
+class T5DecodeCache:
+    """Self-attention K/V of an incremental decode on the "hip" path.  Block i owns two slabs [steps, rows, heads * 64]:
+    position t's projections of every row alive at step t, written once.  `anc` [rows, steps] int32 says where a row's
+    history lives: its key at position t < pos is row anc[r, t] of slab t (its own key at `pos` is row r of slab
+    `pos`).  `reorder(parent)` moves to the next position after a beam step: new row r continues old row parent[r]."""
+
+    def __init__(self, num_blocks: int, steps: int, rows: int, inner: int, device) -> None:
+        self.slabs = [(torch.empty(steps, rows, inner, device=device), torch.empty(steps, rows, inner, device=device))
+                      for _ in range(num_blocks)]
+        self.anc = torch.zeros(rows, steps, dtype=torch.int32, device=device)
+        self.steps, self.rows, self.pos = steps, rows, 0
+
+    def reorder(self, parent: Tensor) -> None:
+        self.anc = advance_ancestors(self.anc, parent, self.pos)
+        self.pos += 1
+
+
+def advance_ancestors(anc: Tensor, parent: Tensor, pos: int) -> Tensor:
+    """The ancestor table after position `pos`: row r of the result continues old row parent[r] -- its columns < pos
+    are that row's (one small gather), column `pos` is parent[r] itself."""
+    parent = parent.reshape(-1)
+    out = anc.index_select(0, parent)
+    out[:, pos] = parent
+    return out
+
+
+class _HipPlan:
+    """What a stack forward on the "hip" path computes once for all its blocks."""
+    __slots__ = ("table", "offset", "key_mask", "causal", "past", "cross_mask", "cache")
+
+
 def _attend(module: nn.Module, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], mask: Optional[Tensor]) -> Tensor:
     scores = torch.matmul(q, k.transpose(-1, -2))
     if bias is not None:
@@ -110,6 +153,7 @@ class T5Attention(nn.Module):
         self.o = nn.Linear(inner, config.d_model, bias=False)
         if has_relative_attention_bias:
             self.relative_attention_bias = nn.Embedding(self.num_buckets, self.n_heads)
+        self._delta_buckets = {}  # (lowest delta, highest + 1, device) -> integer buckets of that range of j - i - past
 
     def compute_bias(self, query_length: int, key_length: int, past: int = 0) -> Tensor:
         """[1, heads, query_length, key_length] bias for queries at positions past .. past + query_length - 1."""
@@ -119,6 +163,24 @@ class T5Attention(nn.Module):
         bucket = relative_position_bucket(memory - context, bidirectional=not self.is_decoder,
                                           num_buckets=self.num_buckets, max_distance=self.max_distance)
         return self.relative_attention_bias(bucket).permute(2, 0, 1).unsqueeze(0)
+
+    def delta_table(self, query_length: int, key_length: int, past: int = 0) -> Tuple[Tensor, int]:
+        """(table [n_delta, heads], offset) with table[(j - i - past) + offset, h] == compute_bias(...)[0, h, i, j]: the
+        bias depends on j - i - past alone.  The integer buckets (relative_position_bucket, on the weight's device as
+        in compute_bias) are kept per shape; the table is one gather of the embedding weight."""
+        dev = self.relative_attention_bias.weight.device
+        lo, hi = -(query_length - 1) - past, key_length - past  # the deltas lo .. hi - 1 decide the buckets
+        key = (lo, hi, dev)
+        bucket = self._delta_buckets.get(key)
+        if bucket is None:
+            delta = torch.arange(lo, hi, dtype=torch.long, device=dev)
+            bucket = relative_position_bucket(delta, bidirectional=not self.is_decoder, num_buckets=self.num_buckets,
+                                              max_distance=self.max_distance)
+            if not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+                if len(self._delta_buckets) >= MAX_DELTA_BUCKETS:  # variable lengths: start over, never grow
+                    self._delta_buckets.clear()
+                self._delta_buckets[key] = bucket  # memory of a graph's pool must not outlive the capture
+        return self.relative_attention_bias(bucket), query_length - 1 + past
 
     def _heads(self, x: Tensor) -> Tensor:  # [R, T, inner] -> [R, heads, T, d_kv]
         return x.view(x.shape[0], x.shape[1], self.n_heads, self.d_kv).transpose(1, 2)
@@ -149,6 +211,29 @@ class T5Attention(nn.Module):
             out = out.view(B, self.n_heads, beams, T, self.d_kv).transpose(1, 2).reshape(R, self.n_heads, T, self.d_kv)
         return self.o(out.transpose(1, 2).reshape(R, T, -1))
 
+    def self_attention_hip(self, x: Tensor, plan: _HipPlan, block: int) -> Tuple[Tensor, KV]:
+        """self_attention as one launch; with plan.cache the K/V projections go straight into their slabs."""
+        R = x.shape[0]
+        q = self.q(x)
+        if plan.cache is None:
+            k, v = self.k(x), self.v(x)
+            out = ops.t5_attention(q, k, v, self.n_heads, bias_by_delta=plan.table, bias_offset=plan.offset,
+                                   key_mask=plan.key_mask, causal=plan.causal)
+            return self.o(out), (self._heads(k), self._heads(v))
+        ks, vs = plan.cache.slabs[block]
+        pos = plan.cache.pos
+        x2 = x.reshape(R, -1)
+        torch.mm(x2, self.k.weight.t(), out=ks[pos, :R])
+        torch.mm(x2, self.v.weight.t(), out=vs[pos, :R])
+        out = ops.t5_attention(q, ks, vs, self.n_heads, bias_by_delta=plan.table, bias_offset=plan.offset, past=pos,
+                               anc=plan.cache.anc[:R])
+        return self.o(out), (ks, vs)
+
+    def cross_attention_hip(self, x: Tensor, kv: KV, plan: _HipPlan) -> Tensor:
+        """cross_attention as one launch: the beams of a user are the query rows of one K/V group."""
+        k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in kv)  # a view of the Linear's output
+        return self.o(ops.t5_attention(self.q(x), k, v, self.n_heads, key_mask=plan.cross_mask))
+
 
 class T5LayerSelfAttention(nn.Module):
     def __init__(self, config: T5Config, has_relative_attention_bias: bool = False) -> None:
@@ -157,8 +242,11 @@ class T5LayerSelfAttention(nn.Module):
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
 
-    def forward(self, x, bias, mask, past):
-        out, kv = self.SelfAttention.self_attention(self.layer_norm(x), bias, mask, past)
+    def forward(self, x, bias, mask, past, hip=None, block=0):
+        if hip is not None:
+            out, kv = self.SelfAttention.self_attention_hip(self.layer_norm(x), hip, block)
+        else:
+            out, kv = self.SelfAttention.self_attention(self.layer_norm(x), bias, mask, past)
         return x + self.dropout(out), kv
 
 
@@ -169,7 +257,9 @@ class T5LayerCrossAttention(nn.Module):
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
 
-    def forward(self, x, kv, mask):
+    def forward(self, x, kv, mask, hip=None):
+        if hip is not None:
+            return x + self.dropout(self.EncDecAttention.cross_attention_hip(self.layer_norm(x), kv, hip))
         return x + self.dropout(self.EncDecAttention.cross_attention(self.layer_norm(x), kv, mask))
 
 
@@ -217,21 +307,75 @@ class T5Stack(nn.Module):
                                     for i in range(config.num_layers)])
         self.final_layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
+        self.attention_impl = "torch"  # or "hip": see the module docstring
         init_t5_weights(self, config)
 
     def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
         """Cross-attention K/V of every block, computed once per encoder output."""
         return [blk.layer[1].EncDecAttention.project_kv(encoder_hidden_states) for blk in self.block]
 
+    def hip_attention_active(self, x: Tensor, query_length: int, key_length: int,
+                             cross_length: Optional[int] = None) -> bool:
+        """Whether a forward of x with these lengths takes the "hip" path (module docstring)."""
+        if self.attention_impl not in ATTENTION_IMPLS:
+            raise ValueError(f"attention_impl must be one of {ATTENTION_IMPLS}, got {self.attention_impl!r}")
+        if self.attention_impl != "hip" or not x.is_cuda or torch.is_grad_enabled():
+            return False
+        if self.training and self.config.dropout_rate > 0:
+            return False
+        cfg = self.config
+        ok = ops.t5_attention_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, key_length)
+        if ok and cross_length is not None:
+            ok = ops.t5_attention_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, cross_length)
+        return ok
+
+    def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
+        return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
+
+    def _forward_hip(self, inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache, decode_cache):
+        """forward on the "hip" path: the bias table and the byte masks are built once, every attention is one launch."""
+        T = inputs_embeds.shape[1]
+        plan = _HipPlan()
+        plan.cache = decode_cache
+        plan.past = 0 if decode_cache is None else decode_cache.pos
+        plan.table, plan.offset = self.block[0].layer[0].SelfAttention.delta_table(T, plan.past + T, plan.past)
+        plan.key_mask = None if attention_mask is None else attention_mask.bool()
+        plan.causal = self.is_decoder and T > 1
+        plan.cross_mask = None if encoder_attention_mask is None else encoder_attention_mask.bool()
+        x = self.dropout(inputs_embeds)
+        new_kv = []
+        for i, blk in enumerate(self.block):
+            x, kv = blk.layer[0](x, None, None, None, hip=plan, block=i)
+            new_kv.append(kv)
+            if self.is_decoder:
+                x = blk.layer[1](x, cross_kv[i], None, hip=plan)
+            x = blk.layer[-1](x)
+        x = self.dropout(self.final_layer_norm(x))
+        return (x, new_kv) if use_cache else x
+
     def forward(self, inputs_embeds: Tensor, attention_mask: Optional[Tensor] = None,
                 encoder_hidden_states: Optional[Tensor] = None, encoder_attention_mask: Optional[Tensor] = None,
                 past_key_values: Optional[List[KV]] = None, use_cache: bool = False,
-                cross_kv: Optional[List[KV]] = None):
+                cross_kv: Optional[List[KV]] = None, decode_cache: Optional[T5DecodeCache] = None):
         """inputs_embeds [R, T, d]; attention_mask [R, past + T] keep-mask (encoder: [R, T]); encoder_attention_mask
         [B, S] keep-mask of the encoder output (B rows, R = B * beams).  Returns the hidden states, and with use_cache
-        the per-block self-attention (K, V) including these T positions."""
+        the per-block self-attention (K, V) including these T positions.  decode_cache ("hip" path, T = 1) holds the
+        self-attention history instead of past_key_values: this position's K/V are written into it."""
         R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
         dtype = inputs_embeds.dtype
+        if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
+            if self.is_decoder and cross_kv is None:
+                cross_kv = self.cross_kv(encoder_hidden_states)
+            past = 0 if decode_cache is None else decode_cache.pos
+            if self.hip_attention_active(inputs_embeds, T, past + T, cross_kv[0][0].shape[2] if self.is_decoder else None):
+                if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
+                                                 or past >= decode_cache.steps or R > decode_cache.rows):
+                    raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
+                                     "past_key_values or attention_mask")
+                return self._forward_hip(inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache,
+                                         decode_cache)
+            if decode_cache is not None:
+                raise ValueError('decode_cache belongs to the "hip" attention path, which is not active here')
         past = 0 if past_key_values is None else past_key_values[0][0].shape[2]
         keys = past + T
         keep = None if attention_mask is None else attention_mask[:, None, None, :].bool()

@@ -98,6 +98,9 @@ SIGNATURES = {
     "rqhip_beam_step_workspace_bytes": (_sz, [_i64, _int, _int, _int, _int]),
     "rqhip_beam_step": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _vp, _sz, _vp, _i64, _int,
                                _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rqhip_t5_attention_supported": (_int, [_int, _int, _int, _int]),
+    "rqhip_t5_attention": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _int, _int, _vp, _int,
+                                  _int, _vp, _i64, _i64, _vp, _i64, _vp]),
     "rqhip_recon_loss_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp]),
     "rqhip_recon_loss_backward": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
     "rqhip_recon_loss_forward_spec": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _f32, _vp, _vp, _vp]),

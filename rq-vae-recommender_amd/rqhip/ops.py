@@ -539,6 +539,77 @@ def beam_step(logits: Tensor, noise: Tensor, parent_scores: Optional[Tensor], pa
     return ids, scores, parent
 
 
+def t5_attention_supported(dtype: torch.dtype, d_kv: int, n_heads: int, Tq: int, Tk: int) -> bool:
+    """Whether t5_attention implements this shape (rqhip_t5_attention_supported): fp32, d_kv = 64, Tq and Tk <= 256."""
+    return dtype == torch.float32 and bool(
+        _lib.lib().rqhip_t5_attention_supported(int(d_kv), int(n_heads), int(Tq), int(Tk)))
+
+
+def _token_rows(t: Tensor, name: str, copy: bool = True) -> Tensor:
+    """A float32 [rows, T, inner] tensor whose tokens lie at one row stride (unit column stride); copies otherwise, or
+    raises when `copy` is False (the K/V slabs: the point of them is that nothing copies them)."""
+    if t.dtype != torch.float32 or t.dim() != 3:
+        raise RqHipError(f"t5_attention: {name} must be a float32 [rows, T, heads * 64] tensor, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    if t.stride(2) != 1 or t.stride(1) % 4 != 0 or t.stride(0) != t.shape[1] * t.stride(1) or t.data_ptr() % 16 != 0:
+        if not copy:
+            raise RqHipError(f"t5_attention: {name} must be a 16-byte aligned [positions, rows, heads * 64] slab with "
+                             f"one row stride (a multiple of 4), got strides {tuple(t.stride())}")
+        t = t.contiguous()
+    return t
+
+
+def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
+                 bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False, past: int = 0,
+                 anc: Optional[Tensor] = None) -> Tensor:
+    """softmax(q k^T + bias + mask) v for every row and head in one launch (rqhip_t5_attention), T5 semantics, fp32.
+
+    q [R, Tq, n_heads * 64] as the q Linear wrote it; returns [R, Tq, n_heads * 64] as the o Linear reads it.
+    Dense K/V: k, v [Rk, Tk, n_heads * 64], R a multiple of Rk (rows b * R / Rk .. read group b).  Cached decode step
+    (anc [R, >= past] int32, Tq = 1): k, v are the position slabs [positions, slab_rows, n_heads * 64]; key t < past of
+    row r is row anc[r, t] of slab t, key `past` is row r of slab `past`.
+    bias_by_delta [n_delta, n_heads]: table[(j - i - past) + bias_offset] is added.  key_mask [Rk, Tk] bool / uint8
+    (0 = masked), causal keeps j <= i + past; masked scores get finfo(float32).min added."""
+    _need_gpu(q, k, v, bias_by_delta, key_mask, anc)
+    q = _token_rows(q, "q")
+    R, Tq, inner = q.shape
+    if inner != n_heads * 64:
+        raise RqHipError(f"t5_attention: q has {inner} columns, not n_heads * 64 = {n_heads * 64}")
+    if k.shape != v.shape or k.shape[-1] != inner:
+        raise RqHipError(f"t5_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    k, v = _token_rows(k, "k", copy=anc is None), _token_rows(v, "v", copy=anc is None)
+    if k.stride(1) != v.stride(1):
+        if anc is not None:
+            raise RqHipError("t5_attention: the k and v slabs must share one row stride")
+        k, v = k.contiguous(), v.contiguous()
+    if anc is not None:
+        if (anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < past or anc.stride(1) != 1
+                or k.shape[0] <= past or k.shape[1] < R):
+            raise RqHipError("t5_attention: anc must be an int32 [R, >= past] table with unit column stride, and the "
+                             "slabs must hold position `past` and at least R rows")
+        Rk, Tk, slab_rows, ld_anc = R, past + 1, k.shape[1], int(anc.stride(0))
+    else:
+        Rk, Tk, slab_rows, ld_anc = k.shape[0], k.shape[1], 0, 0
+    if bias_by_delta is not None:
+        bias_by_delta = _f32c(bias_by_delta, "bias_by_delta")
+        if bias_by_delta.dim() != 2 or bias_by_delta.shape[1] != n_heads:
+            raise RqHipError(f"t5_attention: bias_by_delta must be [n_delta, {n_heads}], got {tuple(bias_by_delta.shape)}")
+    if key_mask is not None:
+        if key_mask.dtype not in (torch.bool, torch.uint8) or tuple(key_mask.shape) != (Rk, Tk):
+            raise RqHipError(f"t5_attention: key_mask must be bool / uint8 [{Rk}, {Tk}], got {key_mask.dtype} "
+                             f"{tuple(key_mask.shape)}")
+        key_mask = key_mask.contiguous()
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention(
+            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
+            _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
+            _ptr(key_mask), int(bool(causal)), int(past), _ptr(anc), ld_anc, slab_rows, _ptr(out), inner, _stream())
+        check(rc, "rqhip_t5_attention")
+    return out
+
+
 def gumbel_matrix_path_min_rows(set_to: int = 0) -> int:
     """Query (set_to <= 0) or set the batch size from which the Gumbel level runs on the matrix instructions
     (rqhip_gumbel_matrix_path_min_rows); returns the previous value."""

@@ -1,0 +1,469 @@
+"""The fused T5 attention on the GPU: ops.t5_attention (csrc/t5_attention.hip) against `_attend`'s operator sequence in
+fp64, and the retrieval model with attention_impl = "hip" against the reference's recorded values, the cache-free
+operator generate, itself (seeded replay) and its own graph capture.
+
+Kernel gate: e = max|out - out64| / max|out64| for the kernel and for the operators in fp32 on the same inputs;
+e_kernel <= 4 e_torch (one rounding for another summation order and one for another exp, over the operators' own
+error), equality when Tk = 1 (both are exact).  Measured ratios: profiles/retrieval_generate.txt."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+from test_gpu_retrieval import (GAP, _cache_free_generate, _close, _default_model_and_batch, _Replay, compare_beams)
+from test_retrieval_model import CASES, build_model, fixture_batch
+
+pytestmark = pytest.mark.gpu
+
+_EVAL = types.SimpleNamespace(dropout=0.0, training=False)
+
+
+def _operators(q, k, v, H, bias, keep, dtype):
+    """modules/t5.py's sequence (head transposes, _attend, transpose back) in `dtype`.  q [R, Tq, H*64], k / v
+    [R, Tk, H*64], bias [1, H, Tq, Tk] or None, keep [R, 1, Tq or 1, Tk] bool or None."""
+    from modules.t5 import _attend
+
+    def heads(x):
+        return x.to(dtype).view(x.shape[0], x.shape[1], H, 64).transpose(1, 2)
+
+    mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
+    bias = None if bias is None else bias.to(dtype)
+    if dtype == torch.float32:
+        out = _attend(_EVAL, heads(q), heads(k), heads(v), bias, mask)
+    else:  # _attend's sequence with its softmax in `dtype` too (its `.float()` is the identity in fp32 only)
+        scores = torch.matmul(heads(q), heads(k).transpose(-1, -2))
+        if bias is not None:
+            scores = scores + bias
+        if mask is not None:
+            scores = scores + mask
+        out = torch.matmul(torch.softmax(scores, dim=-1), heads(v))
+    return out.transpose(1, 2).reshape(q.shape[0], q.shape[1], -1)
+
+
+def _gate(name, out, q, k, v, H, bias, keep):
+    """Prints and asserts the gate of the module docstring; k / v already expanded to one K/V per query row."""
+    out64 = _operators(q, k, v, H, bias, keep, torch.float64)
+    out32 = _operators(q, k, v, H, bias, keep, torch.float32)
+    scale = out64.abs().max()
+    e_kernel = float((out.double() - out64).abs().max() / scale)
+    e_torch = float((out32.double() - out64).abs().max() / scale)
+    smax = float(torch.einsum("rihd,rjhd->rhij", q.double().view(*q.shape[:2], H, 64),
+                              k.double().view(*k.shape[:2], H, 64)).abs().max())
+    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
+    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f} max|score| {smax:.1f}")
+    assert torch.isfinite(out).all()
+    if k.shape[1] == 1:
+        assert e_kernel == e_torch
+    else:
+        assert e_kernel <= 4 * e_torch
+    return smax
+
+
+def _inputs(R, Tq, Rk, Tk, H, seed):
+    g = torch.Generator().manual_seed(seed)
+    dev = torch.device("cuda")
+    q = (torch.randn(R, Tq, H * 64, generator=g) * 1.5).to(dev)   # no 1/sqrt(d): scores reach 30 and beyond
+    k = torch.randn(Rk, Tk, H * 64, generator=g).to(dev)
+    v = torch.randn(Rk, Tk, H * 64, generator=g).to(dev)
+    return q, k, v, g
+
+
+def _bias_module(H, is_decoder, seed):
+    from modules.t5 import T5Attention, T5Config
+    torch.manual_seed(seed)
+    att = T5Attention(T5Config(64, d_model=32, num_heads=H, is_decoder=is_decoder), has_relative_attention_bias=True)
+    torch.nn.init.normal_(att.relative_attention_bias.weight)
+    return att.to("cuda")
+
+
+def _padding(R, T, g):
+    """Keep-mask [R, T] with padded tails of every length; row 1 (if any) is fully masked."""
+    keep = torch.arange(T)[None, :] < torch.randint(1, T + 1, (R, 1), generator=g)
+    keep[0] = True
+    if R > 1:
+        keep[1] = False
+    return keep.to("cuda")
+
+
+@pytest.mark.parametrize("H", [1, 6, 8])
+@pytest.mark.parametrize("T", [1, 7, 81, 101, 256])
+def test_encoder_attention_matches_operators(T, H):
+    from rqhip import ops
+    R = 5
+    q, k, v, g = _inputs(R, T, R, T, H, 100 * T + H)
+    att = _bias_module(H, False, T + H)
+    keep = _padding(R, T, g)
+    with torch.no_grad():
+        table, offset = att.delta_table(T, T, 0)
+        out = ops.t5_attention(q, k, v, H, bias_by_delta=table, bias_offset=offset, key_mask=keep)
+        smax = _gate(f"encoder T={T} H={H}", out, q, k, v, H, att.compute_bias(T, T), keep[:, None, None, :])
+        if T >= 81:
+            assert smax > 30
+        # the fully masked row is the uniform average of V, as with the operators
+        if R > 1 and T > 1:
+            np.testing.assert_allclose(out[1].cpu().numpy(), v[1].mean(dim=0, keepdim=True).expand(T, -1).cpu().numpy(),
+                                       rtol=0, atol=1e-5)
+        again = ops.t5_attention(q, k, v, H, bias_by_delta=table, bias_offset=offset, key_mask=keep)
+    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+
+
+@pytest.mark.parametrize("H", [1, 6, 8])
+@pytest.mark.parametrize("T", [2, 4])
+def test_causal_attention_matches_operators(T, H):
+    from rqhip import ops
+    R = 9
+    q, k, v, _ = _inputs(R, T, R, T, H, 7 * T + H)
+    att = _bias_module(H, True, T)
+    causal = torch.ones(T, T, dtype=torch.bool, device="cuda").tril()[None, None]
+    with torch.no_grad():
+        table, offset = att.delta_table(T, T, 0)
+        out = ops.t5_attention(q, k, v, H, bias_by_delta=table, bias_offset=offset, causal=True)
+        _gate(f"causal T={T} H={H}", out, q, k, v, H, att.compute_bias(T, T), causal)
+        # the first query sees one key: exact
+        assert torch.equal(out[:, 0], v[:, 0])
+        again = ops.t5_attention(q, k, v, H, bias_by_delta=table, bias_offset=offset, causal=True)
+    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+
+
+@pytest.mark.parametrize("H", [1, 6, 8])
+@pytest.mark.parametrize("beams,Tq", [(1, 1), (1, 4), (10, 1), (10, 3)])
+def test_cross_attention_matches_operators(beams, Tq, H):
+    from rqhip import ops
+    B, S = 6, 81
+    q, k, v, g = _inputs(B * beams, Tq, B, S, H, 31 * beams + Tq + H)
+    keep = _padding(B, S, g)
+    with torch.no_grad():
+        out = ops.t5_attention(q, k, v, H, key_mask=keep)
+        _gate(f"cross beams={beams} Tq={Tq} H={H}", out, q, k.repeat_interleave(beams, 0), v.repeat_interleave(beams, 0),
+              H, None, keep.repeat_interleave(beams, 0)[:, None, None, :])
+        unmasked = ops.t5_attention(q, k, v, H)
+        _gate(f"cross beams={beams} Tq={Tq} H={H} no mask", unmasked, q, k.repeat_interleave(beams, 0),
+              v.repeat_interleave(beams, 0), H, None, None)
+        again = ops.t5_attention(q, k, v, H, key_mask=keep)
+    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+
+
+@pytest.mark.parametrize("H", [1, 6, 8])
+@pytest.mark.parametrize("past", [1, 2, 3])
+def test_cached_step_through_ancestors_matches_cat_and_index_select(past, H):
+    from rqhip import ops
+    R, rows, steps = 50, 64, 4
+    g = torch.Generator().manual_seed(13 * past + H)
+    dev = torch.device("cuda")
+    q = (torch.randn(R, 1, H * 64, generator=g) * 1.5).to(dev)
+    ks = torch.randn(steps, rows, H * 64, generator=g).to(dev)
+    vs = torch.randn(steps, rows, H * 64, generator=g).to(dev)
+    anc = torch.randint(0, rows, (R, steps), generator=g).to(torch.int32).to(dev)
+    att = _bias_module(H, True, past)
+    # the operators' cache: index_select per earlier position, cat with the row's own newest key
+    k = torch.cat([ks[t].index_select(0, anc[:, t].long())[:, None] for t in range(past)] + [ks[past, :R, None]], dim=1)
+    v = torch.cat([vs[t].index_select(0, anc[:, t].long())[:, None] for t in range(past)] + [vs[past, :R, None]], dim=1)
+    with torch.no_grad():
+        table, offset = att.delta_table(1, past + 1, past)
+        out = ops.t5_attention(q, ks, vs, H, bias_by_delta=table, bias_offset=offset, past=past, anc=anc)
+        _gate(f"cached past={past} H={H}", out, q, k, v, H, att.compute_bias(1, past + 1, past), None)
+        dense = ops.t5_attention(q, k, v, H, bias_by_delta=table, bias_offset=offset, past=past)
+        again = ops.t5_attention(q, ks, vs, H, bias_by_delta=table, bias_offset=offset, past=past, anc=anc)
+        # the gathered cache through the dense form (the matrix kernel) meets the same gate
+        _gate(f"cached past={past} H={H} dense form", dense, q, k, v, H, att.compute_bias(1, past + 1, past), None)
+    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+
+
+def test_wrapper_rejects_host_tensors_and_unsupported_shapes():
+    from rqhip import ops
+    from rqhip._lib import RqHipError
+    dev = torch.device("cuda")
+    with pytest.raises(RqHipError):
+        ops.t5_attention(torch.zeros(2, 3, 64), torch.zeros(2, 3, 64), torch.zeros(2, 3, 64), 1)
+    with pytest.raises(RqHipError, match="<= 256"):
+        ops.t5_attention(torch.zeros(1, 1, 64, device=dev), torch.zeros(1, 257, 64, device=dev),
+                         torch.zeros(1, 257, 64, device=dev), 1)
+    with pytest.raises(RqHipError, match="multiple"):
+        ops.t5_attention(torch.zeros(5, 1, 64, device=dev), torch.zeros(2, 8, 64, device=dev),
+                         torch.zeros(2, 8, 64, device=dev), 1)
+
+
+# ---- the model with attention_impl = "hip"
+
+
+def _count_attention(monkeypatch):
+    """Counts ops.t5_attention launches as modules.t5 makes them."""
+    import modules.t5 as t5
+    calls = []
+    orig = t5.ops.t5_attention
+
+    def counted(*a, **kw):
+        calls.append(1)
+        return orig(*a, **kw)
+
+    monkeypatch.setattr(t5.ops, "t5_attention", counted)
+    return calls
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_forward_no_grad_matches_reference_with_hip_attention(case, monkeypatch):
+    fx = load_golden(f"retrieval_{case}.npz")
+    dev = torch.device("cuda")
+    model = build_model(fx, dev).eval()
+    batch = fixture_batch(fx, dev)
+    model.attention_impl = "hip"
+    calls = _count_attention(monkeypatch)
+    with torch.no_grad():
+        out = model(batch)
+    layers = int(fx["config"][5])
+    assert len(calls) == 3 * layers                       # encoder, decoder self- and cross-attention of every block
+    np.testing.assert_allclose(out.loss.item(), float(fx["loss"]), rtol=1e-5)
+    np.testing.assert_allclose(out.loss_d.cpu().numpy(), fx["loss_d"], rtol=1e-5)
+    # under grad the operators run
+    del calls[:]
+    model(batch).loss.backward()
+    assert not calls
+
+
+def _sampling_boundary_users(model, batch, monkeypatch):
+    """One generate on the operators' attention; per user, whether at some step the n-th and the (n+1)-th sampling key
+    of one of its rows lie within GAP (which codes are sampled is then open to any other correct fp32 evaluation)."""
+    import modules.model as mm
+    orig = mm.ops.beam_step
+    tied = []
+
+    def recording(logits, noise, parent_scores, parent_ids, index, corpus, n, k):
+        beams_in = 1 if parent_ids is None else parent_ids.shape[1]
+        keys = torch.softmax(logits, dim=-1) / noise
+        kv = torch.sort(keys, dim=-1, descending=True, stable=True).values
+        if n < keys.shape[1]:
+            tied.append((_close(kv[:, n - 1], kv[:, n]) & (kv[:, n - 1] > 0)).reshape(-1, beams_in).any(dim=1))
+        return orig(logits, noise, parent_scores, parent_ids, index, corpus, n, k)
+
+    monkeypatch.setattr(mm.ops, "beam_step", recording)
+    model.attention_impl = "torch"
+    model.generate_next_sem_id(batch)
+    monkeypatch.setattr(mm.ops, "beam_step", orig)
+    return torch.stack(tied).any(dim=0) if tied else None
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_generate_matches_reference_with_recorded_noise_hip_attention(case, monkeypatch):
+    import modules.model as mm
+    fx = load_golden(f"retrieval_{case}.npz")
+    dev = torch.device("cuda")
+    model = build_model(fx, dev).eval()
+    batch = fixture_batch(fx, dev)
+    L = int(fx["config"][0])
+    noise = [torch.from_numpy(fx[f"noise{h}"]).to(dev) for h in range(L)]
+    monkeypatch.setattr(mm, "_exponential_like", _Replay(noise))
+    boundary = _sampling_boundary_users(model, batch, monkeypatch)
+    monkeypatch.setattr(mm, "_exponential_like", _Replay(noise))
+    model.attention_impl = "hip"
+    calls = _count_attention(monkeypatch)
+    out = model.generate_next_sem_id(batch)
+    layers = int(fx["config"][5])
+    assert len(calls) == layers + 2 * layers * L
+    r_ids = torch.from_numpy(fx["sem_ids"]).to(dev)
+    r_lp = torch.from_numpy(fx["log_probas"]).to(dev)
+    fin = torch.isfinite(r_lp)
+    differs = ((torch.isfinite(out.log_probas) != fin) | (fin & ((out.log_probas - r_lp).abs() > 1e-5))
+               | (fin & (out.sem_ids != r_ids).any(dim=-1))).any(dim=1)
+    dlp = torch.where(fin, (out.log_probas - r_lp).abs(), torch.zeros_like(r_lp))
+    print(f"fixture {case}: max |log_proba - recorded| {float(dlp.max()):.3e}, users with other ids "
+          f"{int((fin & (out.sem_ids != r_ids).any(dim=-1)).any(dim=1).sum())}, -inf pattern differs "
+          f"{int((torch.isfinite(out.log_probas) != fin).any(dim=1).sum())}")
+    # a user that differs sits on a sampling boundary of the operator run, and only such a user is set aside
+    if bool(differs.any()):
+        assert boundary is not None and bool(boundary[differs].all()), "a user differs away from a sampling boundary"
+    keep = ~differs
+    amb = (_close(r_lp[:, :-1], r_lp[:, 1:]) & torch.isfinite(r_lp[:, :-1])).any(dim=1)
+    n_amb = compare_beams(out.sem_ids[keep], out.log_probas[keep], None, r_ids[keep], r_lp[keep], None, amb[keep], 1e-5)
+    print(f"fixture {case}: {n_amb} users inside the gap, {int(differs.sum())} of {differs.numel()} users set aside on a "
+          f"sampling boundary (gap {GAP:g})")
+    assert n_amb == 0 and int(amb.sum()) == 0
+
+
+def test_generate_hip_attention_default_config(monkeypatch):
+    import modules.model as mm
+    dev = torch.device("cuda")
+    model, batch = _default_model_and_batch(dev)
+    L, k = model.num_hierarchies, model.top_k_for_generation
+    B = batch.sem_ids.shape[0]
+    drawn = []
+    orig = mm._exponential_like
+
+    def record(p):
+        q = orig(p)
+        drawn.append(q.clone())
+        return q
+
+    model.attention_impl = "hip"
+    monkeypatch.setattr(mm, "_exponential_like", record)
+    calls = _count_attention(monkeypatch)
+    torch.manual_seed(7)
+    out = model.generate_next_sem_id(batch)
+    monkeypatch.setattr(mm, "_exponential_like", orig)
+    assert len(calls) == 28                              # 4 encoder blocks + 3 levels x 4 decoder blocks x 2
+    assert out.sem_ids.shape == (B, k, L) and out.log_probas.shape == (B, k)
+    # the ambiguity mask comes from the operator run alone
+    model.attention_impl = "torch"
+    r_ids, r_lp, amb = _cache_free_generate(model, batch, drawn)
+    n_amb = compare_beams(out.sem_ids, out.log_probas, None, r_ids, r_lp, None, amb, 1e-5, 1e-5)
+    print(f"default config, hip attention: {n_amb}/{B} users inside the gap, {int(torch.isfinite(r_lp).sum())} finite beams")
+    assert n_amb <= B // 8
+    assert torch.isfinite(out.log_probas).any()
+    # a seeded generate replays bit for bit
+    model.attention_impl = "hip"
+    torch.manual_seed(7)
+    again = model.generate_next_sem_id(batch)
+    assert torch.equal(again.sem_ids, out.sem_ids)
+    assert torch.equal(again.log_probas.view(torch.int32), out.log_probas.view(torch.int32))
+
+
+def test_generate_hip_attention_makes_no_cache_copies(monkeypatch):
+    """No index_select, cat or contiguous() copy touches a K/V tensor: the K/V that reach the kernel are the slabs and
+    the cross-attention Linears' outputs themselves, and the only index_select of a generate is the ancestor table's."""
+    import modules.t5 as t5
+    dev = torch.device("cuda")
+    model, batch = _default_model_and_batch(dev, B=16, N=3000, seed=2)
+    model.attention_impl = "hip"
+    model.generate_next_sem_id(batch)
+    selected, cats, copies, kv_ptrs, caches, cross = [], [], [], [], [], []
+    o_select, o_cat, o_contig, o_att = torch.Tensor.index_select, torch.cat, torch.Tensor.contiguous, t5.ops.t5_attention
+    o_cache, o_cross = t5.T5Stack.new_decode_cache, t5.T5Stack.cross_kv
+
+    def spy_select(self, dim, index):
+        selected.append((self.dtype, self.dim()))
+        return o_select(self, dim, index)
+
+    def spy_cat(tensors, *a, **kw):
+        cats.append(int(tensors[0].shape[-1]) if tensors[0].dim() else 0)
+        return o_cat(tensors, *a, **kw)
+
+    def spy_contig(self, *a, **kw):
+        if self.dtype == torch.float32 and not self.is_contiguous():
+            copies.append(tuple(self.shape))
+        return o_contig(self, *a, **kw)
+
+    def spy_att(q, k, v, *a, **kw):
+        kv_ptrs.append((k.data_ptr(), v.data_ptr(), kw.get("anc") is not None, q.shape[1]))
+        return o_att(q, k, v, *a, **kw)
+
+    def spy_cache(self, *a, **kw):
+        caches.append(o_cache(self, *a, **kw))
+        return caches[-1]
+
+    def spy_cross(self, enc):
+        cross.append(o_cross(self, enc))
+        return cross[-1]
+
+    def install(on):
+        monkeypatch.setattr(torch.Tensor, "index_select", spy_select if on else o_select)
+        monkeypatch.setattr(torch, "cat", spy_cat if on else o_cat)
+        monkeypatch.setattr(torch.Tensor, "contiguous", spy_contig if on else o_contig)
+        monkeypatch.setattr(t5.ops, "t5_attention", spy_att if on else o_att)
+        monkeypatch.setattr(t5.T5Stack, "new_decode_cache", spy_cache if on else o_cache)
+        monkeypatch.setattr(t5.T5Stack, "cross_kv", spy_cross if on else o_cross)
+
+    install(True)
+    model.generate_next_sem_id(batch)
+    install(False)
+    L, blocks = model.num_hierarchies, len(model.t5_decoder.block)
+    assert selected == [(torch.int32, 2)] * (L - 1)
+    assert not copies, copies
+    # the encoder's input is assembled with cat (d_model wide); nothing as wide as a head or as the K/V rows is
+    inner = model.t5_decoder.config.num_heads * 64
+    assert inner != model.t5_decoder.config.d_model and not any(w in (64, inner) for w in cats), cats
+    slab_ptrs = {(ks.data_ptr(), vs.data_ptr()) for ks, vs in caches[0].slabs}
+    cross_ptrs = {(kk.data_ptr(), vv.data_ptr()) for kk, vv in cross[0]}
+    decoder = kv_ptrs[blocks:]                      # the encoder's calls come first
+    assert len(decoder) == 2 * blocks * L
+    for i, (kp, vp, has_anc, tq) in enumerate(decoder):
+        assert tq == 1
+        if i % 2 == 0:
+            assert has_anc and (kp, vp) in slab_ptrs
+        else:
+            assert not has_anc and (kp, vp) in cross_ptrs
+    # the operator path does reorder its cache
+    model.attention_impl = "torch"
+    del selected[:]
+    monkeypatch.setattr(torch.Tensor, "index_select", spy_select)
+    model.generate_next_sem_id(batch)
+    monkeypatch.setattr(torch.Tensor, "index_select", o_select)
+    assert any(dt == torch.float32 for dt, _ in selected)
+
+
+def test_slab_form_refuses_to_copy():
+    from rqhip import ops
+    from rqhip._lib import RqHipError
+    dev = torch.device("cuda")
+    q = torch.zeros(4, 1, 64, device=dev)
+    slabs = torch.zeros(3, 4, 128, device=dev)[:, :, ::2]           # column stride 2: would need a copy
+    anc = torch.zeros(4, 3, dtype=torch.int32, device=dev)
+    with pytest.raises(RqHipError, match="slab"):
+        ops.t5_attention(q, slabs, slabs, 1, past=1, anc=anc)
+
+
+_LDS_ORDER = """
+import sys
+sys.path[:0] = [{root!r}, {pkg!r}]
+import torch
+from rqhip import ops
+g = torch.Generator().manual_seed(1)
+outs = []
+for T in (128, 256):      # 70 KiB of LDS first, 139 KiB after it, in one process
+    q, k, v = (torch.randn(3, T, 128, generator=g).cuda() for _ in range(3))
+    out = ops.t5_attention(q, k, v, 2)
+    hq, hk, hv = (x.double().view(3, T, 2, 64).transpose(1, 2) for x in (q, k, v))
+    ref = torch.matmul(torch.softmax(torch.matmul(hq, hk.transpose(-1, -2)), dim=-1), hv).transpose(1, 2).reshape(3, T, 128)
+    torch.cuda.synchronize()
+    err = float((out.double() - ref).abs().max() / ref.abs().max())
+    assert err < 1e-4, (T, err)
+print("ok")
+"""
+
+
+def test_lds_limit_does_not_depend_on_the_order_of_lengths():
+    """A fresh process whose first long call is T = 128 must still run T = 256 (the LDS attribute is raised once)."""
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    code = _LDS_ORDER.format(root=ROOT, pkg=os.path.join(ROOT, "rq-vae-recommender_amd"))
+    pr = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                        timeout=300)
+    assert pr.returncode == 0 and pr.stdout.strip().endswith("ok"), pr.stdout[-2000:]
+
+
+def test_generate_hip_attention_under_graph_capture_equals_eager(monkeypatch):
+    import modules.model as mm
+    dev = torch.device("cuda")
+    model, batch = _default_model_and_batch(dev, B=32, N=5000, seed=3)
+    model.attention_impl = "hip"
+    L, K, k = model.num_hierarchies, model.num_embeddings_per_hierarchy, model.top_k_for_generation
+    B = batch.sem_ids.shape[0]
+    torch.manual_seed(11)
+    noise = [torch.empty(B * (1 if h == 0 else k), K, device=dev).exponential_(1) for h in range(L)]
+
+    class Static:
+        def __init__(self):
+            self.i = 0
+
+        def __call__(self, p):
+            q = noise[self.i % L]
+            self.i += 1
+            return q
+
+    monkeypatch.setattr(mm, "_exponential_like", Static())
+    eager = model.generate_next_sem_id(batch)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            model.generate_next_sem_id(batch)
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = model.generate_next_sem_id(batch)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(captured.sem_ids, eager.sem_ids)
+    assert torch.equal(captured.log_probas.view(torch.int32), eager.log_probas.view(torch.int32))

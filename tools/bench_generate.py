@@ -7,11 +7,16 @@ K = 256, L = 3, k = 10, batch 640, 20-item histories, a 12 101-item corpus), two
              torch.multinomial, gather, log, the [N, P, h] prefix-equality test in chunks of 100 000, masked_fill,
              sort, gathers and a cat)
 
+and, for the kernel path, with either attention implementation (--attention): "torch", the T5 operators, or "hip",
+one ops.t5_attention launch per attention call and slab K/V (modules/t5.py).  `--attention both` alternates the two
+arms --runs times in one process and ends with one summary line of the medians over the runs.
+
 Device events around each generate after a warm-up; prints one JSON line per path (ms per generate, users/s).
 Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --stats` run of this tool
-(--path one of them, --iters small).
+(--path one of them, one --attention arm, --iters small).
 
-    python tools/bench_generate.py [--path kernel|reference|both] [--warmup 3] [--iters 10]
+    python tools/bench_generate.py [--path kernel|reference|both] [--attention torch|hip|both] [--runs 5]
+                                   [--warmup 3] [--iters 10]
 """
 import argparse
 import json
@@ -99,14 +104,37 @@ def time_path(model, batch, warmup, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--path", choices=["kernel", "reference", "both"], default="both")
+    ap.add_argument("--path", choices=["kernel", "reference", "both"], default=None,
+                    help="default: both, or kernel with --attention both")
+    ap.add_argument("--attention", choices=["torch", "hip", "both"], default="torch")
+    ap.add_argument("--runs", type=int, default=5, help="alternations of the two arms with --attention both")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
+    if args.path is None:
+        args.path = "kernel" if args.attention == "both" else "both"
     dev = torch.device("cuda")
     model, batch = build(dev)
     B = batch.sem_ids.shape[0]
     paths = ["kernel", "reference"] if args.path == "both" else [args.path]
+    if args.attention == "both":
+        if args.path != "kernel":
+            ap.error("--attention both compares the two arms of --path kernel")
+        medians = {"torch": [], "hip": []}
+        for run in range(args.runs):
+            for arm in ("torch", "hip"):
+                model.attention_impl = arm
+                med, best = time_path(model, batch, args.warmup, args.iters)
+                medians[arm].append(med)
+                print(json.dumps({"path": "kernel", "attention": arm, "run": run, "batch": B,
+                                  "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),
+                                  "iters": args.iters}), flush=True)
+        mid = {arm: sorted(v)[len(v) // 2] for arm, v in medians.items()}
+        print(json.dumps({"path": "kernel", "attention": "both", "runs": args.runs, "batch": B,
+                          "ms_per_generate_torch": round(mid["torch"], 3), "ms_per_generate_hip": round(mid["hip"], 3),
+                          "hip_over_torch": round(mid["hip"] / mid["torch"], 4)}), flush=True)
+        return
+    model.attention_impl = args.attention
     for path in paths:
         if path == "reference":
             mm.ops.beam_step, saved = reference_beam_step(model.codebooks), mm.ops.beam_step
@@ -116,7 +144,8 @@ def main():
         finally:
             if path == "reference":
                 mm.ops.beam_step, mm._exponential_like = saved, saved_q
-        print(json.dumps({"path": path, "batch": B, "k": model.top_k_for_generation, "L": model.num_hierarchies,
+        print(json.dumps({"path": path, "attention": args.attention, "batch": B,
+                          "k": model.top_k_for_generation, "L": model.num_hierarchies,
                           "K": model.num_embeddings_per_hierarchy, "corpus": int(model.codebooks.shape[0]),
                           "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),
                           "users_per_s": round(B / (med / 1e3), 1), "iters": args.iters}), flush=True)
