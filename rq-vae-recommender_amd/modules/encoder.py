@@ -36,15 +36,20 @@ def _adopt(gw: Tensor, sink) -> Tensor:
     return gw.view_as(gw) if sink is not None else gw
 
 
+def _plain(layers) -> bool:
+    """Every module is a bias-free Linear or a ReLU."""
+    return all((isinstance(l, nn.Linear) and l.bias is None) or isinstance(l, nn.ReLU) for l in layers)
+
+
 class _LinearReLU(torch.autograd.Function):
-    """relu(x @ w.T) for 2-D fp32 tensors, one layer (the registered operators, stacks with dropout, CPU): ReLU fused into the
-    GEMM epilogue; backward by rqhip/linear.py:backward -- weight gradient with the ReLU mask, data gradient on the masked
-    gradient it hands over; shapes no kernel tiles keep the three library kernels autograd would run (mask, two GEMMs)."""
+    """relu(x @ w.T), or plain x @ w.T when zero_bias is None (the last layer of each MLP), for 2-D fp32 tensors, one layer (stacks with
+    dropout, CPU): ReLU fused into the GEMM epilogue; backward by rqhip/linear.py:backward -- weight gradient with the ReLU mask, data gradient on
+    the masked gradient it hands over; shapes no kernel tiles keep the three library kernels autograd would run (mask, two GEMMs)."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, w: Tensor, zero_bias: Tensor) -> Tensor:
-        y = _lin.forward(x, w, True, zero_bias)
-        ctx.save_for_backward(x, w, y)
+    def forward(ctx, x: Tensor, w: Tensor, zero_bias) -> Tensor:
+        y = _lin.forward(x, w, zero_bias is not None, zero_bias)
+        ctx.save_for_backward(x, w, y if zero_bias is not None else None)
         return y
 
     @staticmethod
@@ -54,23 +59,6 @@ class _LinearReLU(torch.autograd.Function):
         sink = _grad_sink(w) if need_w else None
         gx, gw = _lin.backward(gy, y, x, w, need_x, need_w, sink)
         return gx, (_adopt(gw, sink) if need_w else None), None
-
-
-class _LinearPlain(torch.autograd.Function):
-    """x @ w.T (the last layer of each MLP: no ReLU), one layer."""
-
-    @staticmethod
-    def forward(ctx, x: Tensor, w: Tensor) -> Tensor:
-        ctx.save_for_backward(x, w)
-        return _lin.forward(x, w, False)
-
-    @staticmethod
-    def backward(ctx, gy: Tensor):
-        x, w = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad
-        sink = _grad_sink(w) if need_w else None
-        gx, gw = _lin.backward(gy, None, x, w, need_x, need_w, sink)
-        return gx, (_adopt(gw, sink) if need_w else None)
 
 
 class _MLPStack(torch.autograd.Function):
@@ -84,7 +72,7 @@ class _MLPStack(torch.autograd.Function):
         it stores, so the only maxima PASS of a training step is the one over the input batch;
       * a data gradient applies the ReLU backward of the layer below in its epilogue (RQHIP_EPI_MASK), so the masked
         gradient is written once, with its maxima, and the weight-gradient kernels read it unmasked.
-    Same kernels, maxima and therefore result bits as the per-layer Functions above (tests/test_gpu_modules.py).
+    Same kernels (both read rqhip/linear.py:plan_layer), maxima and therefore result bits as the per-layer Function above (tests/test_gpu_modules.py).
     forward(x, target, relus, zero_bias, given, defer, *weights): relus[i] = layer i is followed by a ReLU; zero_bias(n, like) -> zeros
     [n] for the library GEMM's fused-ReLU call; given: the maxima that came with x (rqhip/linear.py:attached_scales -- an argument because
     the node may be handed an alias of the caller's tensor object, and attributes do not survive that) or None; defer: this node's batched
@@ -95,52 +83,42 @@ class _MLPStack(torch.autograd.Function):
     def forward(ctx, x: Tensor, target, relus, zero_bias, given, defer, *weights):
         from rqhip import _lib
         from rqhip import autograd as _ag
-        n, M = len(weights), x.shape[0]
+        n, M, R, aligned = len(weights), x.shape[0], _lin.Route, _lin.dense_f32(x)
         need_w = [bool(f) for f in ctx.needs_input_grad[6:]]
         need_in = [bool(ctx.needs_input_grad[0]) or any(need_w[:i]) for i in range(n)]   # gradient wrt layer i's input wanted
-        # the 128 <-> 32 layers either side of the quantiser: the seam kernel's GEMMs (rqhip/linear.py:chain_*), forward and data gradient
-        aligned = x.data_ptr() % 16 == 0 and M > 0
-        chain = [(_lin.chain_shape(w.shape[0], w.shape[1], M) if aligned else 0) for w in weights]
-        chain = [0 if (k == 1 and relus[i]) else k for i, k in enumerate(chain)]
-        # batches below 4096 rows: forward and data gradient on csrc/mlp_small.hip (exact fp32; ReLU / ReLU backward in the epilogue)
-        small = [aligned and w.is_contiguous() and w.data_ptr() % 16 == 0 and _lin.small_shape_ok(M, w.shape[0], w.shape[1])
-                 and _lin.small_shape_ok(M, w.shape[1], w.shape[0]) for w in weights]
-        fwd_split = [not chain[i] and _lin.split_shape_ok(M, w.shape[0], w.shape[1]) for i, w in enumerate(weights)]
-        dg_split = [not chain[i] and need_in[i] and _lin.split_shape_ok(M, w.shape[1], w.shape[0]) for i, w in enumerate(weights)]
-        wg_f16 = [need_w[i] and _lin.wgrad_f16_ok(w.shape[0], w.shape[1], M) for i, w in enumerate(weights)]
-        jobs = [(w, False) for i, w in enumerate(weights) if fwd_split[i]] + [(w, True) for i, w in enumerate(weights) if dg_split[i]]
-        imgs = iter(_lin.images(jobs))
-        img_f = [next(imgs) if fwd_split[i] else None for i in range(n)]
-        img_t = [next(imgs) if dg_split[i] else None for i in range(n)]
-        f16 = _lin.f16()
+        # which kernel every layer's forward, data gradient and weight gradient take: rqhip/linear.py:plan_layer, as on the per-layer path
+        # (below 4096 rows all weight gradients of the stack are ONE job-table launch, decided for the layers together)
+        stack_jobs = _lin.wgrad_jobs_ok(M, [tuple(w.shape) for i, w in enumerate(weights) if need_w[i]])
+        plans = [_lin.plan_layer(M, w.shape[0], w.shape[1], relu=relus[i], operands_aligned=aligned, weight_ok=_lin.dense_f32(w),
+                                 need_dgrad=need_in[i], need_wgrad=need_w[i], stack_jobs=stack_jobs) for i, w in enumerate(weights)]
+        imgs = iter(_lin.images([(w, False) for w, p in zip(weights, plans) if p.fwd == R.SPLIT]
+                                + [(w, True) for w, p in zip(weights, plans) if p.dgrad == R.SPLIT]))
+        img_f = [next(imgs) if p.fwd == R.SPLIT else None for p in plans]
+        img_t = [next(imgs) if p.dgrad == R.SPLIT else None for p in plans]
         # column maxima the epilogues emit in this forward: of layer i's output when layer i + 1's weight gradient wants them
         # (and of the reconstruction gradient for the last layer's own weight gradient) -- one zeroed arena
-        emit = [f16 and (fwd_split[i] or chain[i] == 2) and ((i + 1 < n and wg_f16[i + 1]) or (i + 1 == n and target is not None and wg_f16[i]))
-                for i in range(n)]
-        arena = _lin.zeros_i32(sum(w.shape[0] for i, w in enumerate(weights) if emit[i]), x.device) if any(emit) else None
-        off = 0
+        emit = [p.fwd in (R.SPLIT, R.SEAM_OUT) and (plans[i + 1].wgrad_f16 if i + 1 < n else (target is not None and p.wgrad_f16))
+                for i, p in enumerate(plans)]
+        col_outs = _lin.col_slices([w.shape[0] if e else 0 for w, e in zip(weights, emit)], x.device)
         acts, scs = [x], [given if given is not None else _lin.Scales()]
-        if f16 and (fwd_split[0] or wg_f16[0]):   # the input batch: the one maxima pass of the step -- unless its maxima came with it
-            _lin.ensure_scales(x, scs[0], fwd_split[0], wg_f16[0])
+        if _lin.f16() and (plans[0].fwd == R.SPLIT or plans[0].wgrad_f16):   # the input batch: the step's one maxima pass, unless they came with it
+            _lin.ensure_scales(x, scs[0], plans[0].fwd == R.SPLIT, plans[0].wgrad_f16)
         out = g_recon = g_scales = None
-        for i, w in enumerate(weights):
+        for i, (w, p) in enumerate(zip(weights, plans)):
             a, sc, last = acts[-1], scs[-1], i + 1 == n
-            col_out = None
-            if emit[i]:
-                col_out = arena[off:off + w.shape[0]]
-                off += w.shape[0]
+            want_rows = not last and plans[i + 1].fwd == R.SPLIT
             if last and target is not None:
                 one = torch.tensor(1.0, dtype=torch.float32)   # fp32 (loss scale) * fp32 (1 / B), as ReconLossFunction
                 ctx.row_scale = float(torch.tensor(_ag._LOSS_SCALE, dtype=torch.float32) * (one / M))
                 g_recon, out, g_scales = _lin.gemm(a, img_f[i], w.shape[0], epilogue=_lib.EPI_RECON, aux=target,
-                                                   row_scale=ctx.row_scale, a_scales=sc, want_rows=dg_split[i], col_out=col_out)
+                                                   row_scale=ctx.row_scale, a_scales=sc, want_rows=p.dgrad == R.SPLIT, col_out=col_outs[i])
                 break
-            if chain[i]:
-                y, ysc = _lin.chain_forward(a, w, relus[i], want_rows=not last and fwd_split[i + 1], col_out=col_out)
-            elif fwd_split[i]:
+            if p.fwd in (R.SEAM_IN, R.SEAM_OUT):
+                y, ysc = _lin.chain_forward(a, w, relus[i], want_rows=want_rows, col_out=col_outs[i])
+            elif p.fwd == R.SPLIT:
                 y, _, ysc = _lin.gemm(a, img_f[i], w.shape[0], epilogue=_lib.EPI_RELU if relus[i] else _lib.EPI_STORE,
-                                      a_scales=sc, want_rows=not last and fwd_split[i + 1], col_out=col_out)
-            elif small[i]:
+                                      a_scales=sc, want_rows=want_rows, col_out=col_outs[i])
+            elif p.fwd == R.SMALL:
                 y, ysc = _lin.small_forward(a, w, relus[i]), _lin.Scales()
             else:
                 y, ysc = _lin.library_forward(a, w, relus[i], zero_bias(w.shape[0], a) if relus[i] else None), _lin.Scales()
@@ -152,8 +130,7 @@ class _MLPStack(torch.autograd.Function):
         ctx.has_target = target is not None
         ctx.save_for_backward(x, *weights, target if ctx.has_target else out)
         ctx.acts_mid, ctx.scs, ctx.relus = (acts[1:] if ctx.has_target else acts[1:-1]), scs, tuple(relus)
-        ctx.img_t, ctx.dg_split, ctx.wg_f16, ctx.need_in, ctx.need_w, ctx.chain = img_t, dg_split, wg_f16, need_in, need_w, chain
-        ctx.small = small
+        ctx.plans, ctx.stack_jobs, ctx.img_t, ctx.need_in, ctx.need_w = plans, stack_jobs, img_t, need_in, need_w
         ctx.defer = bool(defer)
         ctx.g_recon, ctx.g_scales, ctx.consumed = g_recon, g_scales, False
         return out
@@ -162,11 +139,10 @@ class _MLPStack(torch.autograd.Function):
     def backward(ctx, g_out: Tensor):
         from rqhip import _lib
         x, weights, tail = ctx.saved_tensors[0], ctx.saved_tensors[1:-1], ctx.saved_tensors[-1]
-        n = len(weights)
+        n, R = len(weights), _lin.Route
         target = tail if ctx.has_target else None
         acts = [x] + list(ctx.acts_mid) + ([] if ctx.has_target else [tail])
-        scs, relus, need_in, need_w = ctx.scs, ctx.relus, ctx.need_in, ctx.need_w
-        dg_split, wg_f16, f16, chain, small = ctx.dg_split, ctx.wg_f16, _lin.f16(), ctx.chain, ctx.small
+        scs, relus, need_in, need_w, plans = ctx.scs, ctx.relus, ctx.need_in, ctx.need_w, ctx.plans
         g_out = g_out.contiguous()
         handed = _lin.take_grad_handoff(g_out) if target is None else None
         if handed is not None:       # the node above (modules/rqvae.py's seam) masked this gradient by our last ReLU and took its maxima
@@ -182,29 +158,27 @@ class _MLPStack(torch.autograd.Function):
             gsc = _lin.Scales()
         # column maxima the data-gradient epilogues emit: of the gradient wrt layer i - 1's output (masked) when that
         # layer's weight gradient wants them
-        emit = [f16 and (dg_split[i] or chain[i] == 1) and i > 0 and wg_f16[i - 1] for i in range(n)]
-        arena = _lin.zeros_i32(sum(w.shape[1] for i, w in enumerate(weights) if emit[i]), g.device) if any(emit) else None
-        off = 0
+        emit = [i > 0 and p.dgrad in (R.SPLIT, R.SEAM_OUT) and plans[i - 1].wgrad_f16 for i, p in enumerate(plans)]
+        col_outs = _lin.col_slices([w.shape[1] if e else 0 for w, e in zip(weights, emit)], g.device)
         premasked = (not relus[n - 1]) or handed is not None      # is g already masked by this layer's ReLU (or is there none)?
         gws = [None] * n
-        # batches below the split kernels' row count: every weight gradient of the stack in ONE launch after the data gradients
-        # (csrc/wgrad_jobs.hip; same bits as the per-layer path, which runs the same kernel with one job)
-        deferred = g.is_cuda and _lin.wgrad_jobs_ok(g.shape[0], [tuple(w.shape) for i, w in enumerate(weights) if need_w[i]])
-        # split-kernel batches: the weight gradients of the layers tiled 256 x 256 whose gradient arrives masked wait for ONE launch at the
-        # end of the stack (rqhip_linear_wgrad_f16_batch: one workgroup's partial block per CU for all of them instead of per layer)
-        own = []        # (layer, rqhip/linear.py:WgradJob) of either kind: a stack's row count decides which
+        # Weight gradients that wait for ONE launch at the end of the stack (rqhip/linear.py:WgradJob), of either kind -- a stack's row
+        # count decides which.  Below the split kernels' row count: every one of the stack (csrc/wgrad_jobs.hip; same bits as the per-layer
+        # path, which runs the same kernel with one job).  Split-kernel batches: those of the layers whose gradient arrives masked
+        # (rqhip_linear_wgrad_f16_batch: one workgroup's partial block per CU for all of them instead of per layer).
+        own = []        # (layer, job)
         for i in range(n - 1, -1, -1):
-            w, a = weights[i], acts[i]
+            w, a, p = weights[i], acts[i], plans[i]
             y = acts[i + 1] if (relus[i] and not premasked) else None
             # a 32 -> 128 seam layer applies its own ReLU backward on LOAD in its data gradient: the masked gradient is then only
             # written out when the job-table weight gradient needs it as a tensor
-            mask_on_load = chain[i] == 2 and need_in[i] and y is not None and g.data_ptr() % 16 == 0
+            mask_on_load = p.dgrad == R.SEAM_IN and y is not None and g.data_ptr() % 16 == 0
             g_unmasked = g
-            if need_w[i] and deferred:
+            if p.wgrad == R.JOBS and ctx.stack_jobs:
                 if y is not None:
                     g, gsc = torch.ops.aten.threshold_backward(g, y, 0.0), _lin.Scales()
                 own.append((i, _lin.WgradJob(w, g, a, None, None, _grad_sink(w))))
-            elif need_w[i] and y is None and g.is_cuda and wg_f16[i] and _lin.wgrad_batch_shape_ok(w.shape[0], w.shape[1], g.shape[0]):
+            elif p.wgrad == R.F16_SPLIT_BATCHED and y is None:
                 gsc = _lin.ensure_scales(g, gsc, False, True)
                 own.append((i, _lin.WgradJob(w, g, a, gsc.cols, _lin.ensure_scales(a, scs[i], False, True).cols, _grad_sink(w))))
             elif need_w[i]:
@@ -218,31 +192,22 @@ class _MLPStack(torch.autograd.Function):
                 g = None
                 break
             lower_relu = i > 0 and relus[i - 1]
-            if chain[i] and (g_unmasked if mask_on_load else g).data_ptr() % 16 == 0:
-                col_out = None
-                if emit[i]:
-                    col_out = arena[off:off + w.shape[1]]
-                    off += w.shape[1]
-                if chain[i] == 2:     # 32 -> 128 layer: gx [M, 32]; its own ReLU backward on load when the gradient is still unmasked
+            lower_split = i > 0 and plans[i - 1].dgrad == R.SPLIT
+            if p.dgrad in (R.SEAM_IN, R.SEAM_OUT) and (g_unmasked if mask_on_load else g).data_ptr() % 16 == 0:
+                if p.dgrad == R.SEAM_IN:     # 32 -> 128 layer: gx [M, 32]; its own ReLU backward on load when the gradient is still unmasked
                     src, msk = (g_unmasked, y) if (mask_on_load and (g is None or g is g_unmasked)) else (g, None)
                     g, gsc = _lin.chain_input_grad(src, w, g_mask=msk)
                     premasked = not lower_relu
-                else:                 # 128 -> 32 layer: gx [M, 128], the ReLU backward of the layer below in the epilogue, with its maxima
-                    g, gsc = _lin.chain_input_grad(g, w, out_mask=a if lower_relu else None,
-                                                   want_rows=i > 0 and dg_split[i - 1], col_out=col_out)
+                else:                        # 128 -> 32 layer: gx [M, 128], the ReLU backward of the layer below in the epilogue, with its maxima
+                    g, gsc = _lin.chain_input_grad(g, w, out_mask=a if lower_relu else None, want_rows=lower_split, col_out=col_outs[i])
                     premasked = True
-            elif dg_split[i]:
-                col_out = None
-                if emit[i]:
-                    col_out = arena[off:off + w.shape[1]]
-                    off += w.shape[1]
-                fuse = f16 and lower_relu              # the ReLU backward of the layer below in this GEMM's epilogue
+            elif p.dgrad == R.SPLIT:
+                fuse = _lin.f16() and lower_relu       # the ReLU backward of the layer below in this GEMM's epilogue
                 g, _, gsc = _lin.gemm(g, ctx.img_t[i], w.shape[1], epilogue=_lib.EPI_MASK if fuse else _lib.EPI_STORE,
-                                      aux=a if fuse else None, a_scales=gsc,
-                                      want_rows=i > 0 and dg_split[i - 1] and (fuse or not lower_relu),
-                                      col_out=col_out if (fuse or not lower_relu) else None)
+                                      aux=a if fuse else None, a_scales=gsc, want_rows=lower_split and (fuse or not lower_relu),
+                                      col_out=col_outs[i] if (fuse or not lower_relu) else None)
                 premasked = fuse or not lower_relu
-            elif small[i] and g.data_ptr() % 16 == 0:      # the ReLU backward of the layer below in the epilogue: no mask launch
+            elif p.dgrad == R.SMALL and g.data_ptr() % 16 == 0:      # the ReLU backward of the layer below in the epilogue: no mask launch
                 g, gsc = _lin.small_input_grad(g, w, a if lower_relu else None), _lin.Scales()
                 premasked = True
             else:
@@ -318,7 +283,7 @@ class MLP(nn.Module):
                      else _LinearReLU.apply(x, layer.weight, self._zero_bias(layer.out_features, x)))
                 i += 2
             elif isinstance(layer, nn.Linear) and layer.bias is None:
-                x = torch.ops.rqhip.linear_plain(x, layer.weight) if as_ops else _LinearPlain.apply(x, layer.weight)
+                x = torch.ops.rqhip.linear_plain(x, layer.weight) if as_ops else _LinearReLU.apply(x, layer.weight, None)
                 i += 1
             else:
                 x = layer(x)
@@ -333,7 +298,7 @@ class MLP(nn.Module):
         if (self.dropout == 0 and len(layers) >= 4 and isinstance(layers[-1], nn.Identity) and isinstance(layers[-2], nn.Linear)
                 and layers[-2].bias is None and isinstance(layers[-3], nn.ReLU)
                 and tuple(layers[-2].weight.shape) == (_lin.CHAIN_D, _lin.CHAIN_H)
-                and all((isinstance(l, nn.Linear) and l.bias is None) or isinstance(l, nn.ReLU) for l in layers[:-1])):
+                and _plain(layers[:-1])):
             return layers[-2].weight
         return None
 
@@ -343,7 +308,7 @@ class MLP(nn.Module):
         if (self.dropout == 0 and len(layers) >= 4 and isinstance(layers[0], nn.Linear) and layers[0].bias is None
                 and isinstance(layers[1], nn.ReLU) and isinstance(layers[2], nn.Linear)
                 and tuple(layers[0].weight.shape) == (_lin.CHAIN_H, _lin.CHAIN_D)
-                and all((isinstance(l, nn.Linear) and l.bias is None) or isinstance(l, nn.ReLU) for l in layers[:-1])):
+                and _plain(layers[:-1])):
             return layers[0].weight
         return None
 
@@ -361,19 +326,17 @@ class MLP(nn.Module):
         epilogue writes the gradient matrix the backward is going to ask for, so it only runs when a backward can follow.
         first: index of the first module of the stack to run (2: z is already behind the first Linear + ReLU -- the seam)."""
         layers = list(self.mlp)[first:]
-        lin = [l for l in layers[:-1]]
+        lin = layers[:-1]
         last = layers[-2] if len(layers) >= 2 else None
-        chain_ok = all((isinstance(l, nn.Linear) and l.bias is None) or isinstance(l, nn.ReLU) for l in lin) \
-            and not any(isinstance(a, nn.ReLU) and isinstance(b, nn.ReLU) for a, b in zip(lin, lin[1:]))
+        chain_ok = _plain(lin) and not any(isinstance(a, nn.ReLU) and isinstance(b, nn.ReLU) for a, b in zip(lin, lin[1:]))
         if not (isinstance(last, nn.Linear) and last.bias is None and isinstance(layers[-1], nn.Identity) and chain_ok
                 and isinstance(layers[0], nn.Linear)
-                and not torch_ops.enabled() and z.is_cuda and z.dim() == 2 and z.dtype == torch.float32
+                and not torch_ops.enabled() and _lin.dense_f32(z)
                 and torch.is_grad_enabled() and (z.requires_grad or any(l.weight.requires_grad for l in layers if isinstance(l, nn.Linear)))
-                and target.is_cuda and target.dtype == torch.float32 and not target.requires_grad
-                and tuple(target.shape) == (z.shape[0], last.out_features) and target.is_contiguous()
-                and target.data_ptr() % 16 == 0
+                and _lin.dense_f32(target) and not target.requires_grad and tuple(target.shape) == (z.shape[0], last.out_features)
                 and last.out_features % 256 == 0   # (the fused epilogue sums four 64-column waves: 256-column tiles only)
-                and _lin.split_shape_ok(z.shape[0], last.out_features, last.in_features)):
+                and _lin.plan_layer(z.shape[0], last.out_features, last.in_features, relu=False, operands_aligned=True,
+                                    need_dgrad=False, need_wgrad=False).fwd == _lin.Route.SPLIT):
             return None
         assert z.shape[-1] == layers[0].in_features, f"Invalid input dim: Expected {layers[0].in_features}, found {z.shape[-1]}"
-        return self._run(z if z.is_contiguous() else z.contiguous(), layers[:-1], target)
+        return self._run(z, layers[:-1], target)

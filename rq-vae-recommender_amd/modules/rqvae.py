@@ -169,8 +169,8 @@ class RqVae(nn.Module, PyTorchModelHubMixin):
         batch of 4096 rows or more; else None.  (Smaller batches are launch-bound and keep round 5's path: measured at batch 640, the
         fused node 0.233 ms per graph step against 0.198 -- its two weight gradients leave the MLP stacks' job tables and every GEMM
         output is a long chain of dependent fp32 matrix instructions; profiles/r06_seam.txt.)"""
-        if (not FUSE_SEAM or torch_ops.enabled() or not _lin._CHAIN or type(self.encoder) is not MLP or type(self.decoder) is not MLP
-                or not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] >= _lin._SPLIT_MIN_ROWS)
+        if (not FUSE_SEAM or torch_ops.enabled() or not _lin.chain_gemms_on() or type(self.encoder) is not MLP or type(self.decoder) is not MLP
+                or not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] >= _lin.SPLIT_MIN_ROWS)
                 or not self._can_fuse() or not all(layer.plain_codebook for layer in self.layers)
                 or self.embed_dim != _lin.CHAIN_D or not ops.rq_seam_supported(self.embed_dim, _lin.CHAIN_H, len(self.layers), self.codebook_size)):
             return None
@@ -232,7 +232,7 @@ class RqVae(nn.Module, PyTorchModelHubMixin):
             hidden = self.encoder.run_before_tail(xin)
             codebooks = torch.stack([layer.codebook() for layer in self.layers])
             sink = getattr(self, "_rq_cb_grad_sink", None)
-            want_scales = _lin.f16() and xin.shape[0] >= _lin._SPLIT_MIN_ROWS
+            want_scales = _lin.f16() and xin.shape[0] >= _lin.SPLIT_MIN_ROWS
             if reducer is not None and hidden.requires_grad:
                 # multi-GPU: when the gradient of `hidden` exists, the decoder's, the codebooks' and every other gradient that is not an
                 # encoder parameter's has been accumulated -- their all-reduce starts under the rest of the encoder's backward

@@ -1,6 +1,8 @@
-"""Kernel selection for the bias-free Linear(+ReLU) layers of the MLPs, shared by the autograd Functions of
-modules/encoder.py and the registered operators of rqhip/torch_ops.py (both must run the same kernels: the tests compare
-them bit for bit).
+"""Kernel selection for the bias-free Linear(+ReLU) layers of the MLPs.  Which kernel a layer's forward, data gradient and weight
+gradient take is decided in ONE place, `plan_layer`: a function of row count, widths and switches.  The whole-stack autograd node of
+modules/encoder.py (`_MLPStack`) and the per-layer path (`forward` / `input_grad` / `weight_grad` / `backward` here, run by the
+per-layer Function and the registered operators of rqhip/torch_ops.py) both dispatch on it, which is why the tests can compare them
+bit for bit; the two places where they decide differently are arguments of `plan_layer` (`relu`, `stack_jobs`).
 
 The large layers run on the 16-bit matrix cores with fp32's accuracy (csrc/gemm_split.hip, csrc/wgrad_split.hip).  Round 4's
 product arithmetic is `f16x2`: every row (column, for the weight gradients) is scaled by an exact power of two and split into
@@ -16,9 +18,8 @@ What the host side of a step tells itself across autograd nodes, and how: the ma
 whether the stack may park its weight gradients are ARGUMENTS of `_MLPStack.apply`; weight-gradient jobs are `WgradJob`s, launched by
 `launch_wgrads` and parked in `wgrad_queue` (the contract: `WgradQueue`); the one remaining call-order slot is `handoff_grad`, which
 carries pointer, shape and version of the gradient it speaks about."""
+from enum import IntEnum
 from typing import List, NamedTuple, Optional, Sequence, Tuple
-
-import os
 
 import torch
 from torch import Tensor
@@ -29,7 +30,7 @@ from . import _lib, ops
 # Measured at 100 000 rows against the tuned library fp32 GEMM of the same layer (tools/bench_gemm_split.py, and in the
 # step: profiles/r04_*): every supported forward and data gradient is faster.  Small batches are launch-bound and stay with
 # the library.
-_SPLIT_MIN_ROWS = 4096
+SPLIT_MIN_ROWS = 4096
 _SPLIT_GEMMS = True
 _ARITH = ops.F16X2
 _FP32 = -1   # no split kernels at all: library fp32 GEMMs, fp32-MFMA weight gradients (round 2's step, bench.py --mlp library)
@@ -133,6 +134,13 @@ def zeros_i32(n: int, device) -> Tensor:
     return out
 
 
+def col_slices(widths: Sequence[int], device) -> List[Optional[Tensor]]:
+    """One zeroed int32 [n] slice per width n > 0 (None for 0), all cut from one `zeros_i32` arena: where the epilogues of a stack's
+    GEMMs put the column maxima of what they store."""
+    arena = zeros_i32(sum(widths), device) if any(widths) else None
+    return [arena[sum(widths[:i]):sum(widths[:i + 1])] if n else None for i, n in enumerate(widths)]
+
+
 _GRAD_HANDOFF: List[Optional[tuple]] = [None]
 
 
@@ -164,14 +172,6 @@ def ensure_scales(a: Tensor, sc: Optional[Scales], rows: bool, cols: bool) -> Sc
     return sc
 
 
-def split_ok(x: Tensor, n_cols: int, n_red: int, forward_relu: bool = False) -> bool:
-    """Does this GEMM (x [M, n_red] against a weight image of n_cols columns) take the split kernel?"""
-    del forward_relu   # (round 3 excluded the first encoder layer's forward here)
-    return bool(_SPLIT_GEMMS and _ARITH != _FP32 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-                and x.shape[0] >= _SPLIT_MIN_ROWS and x.is_contiguous() and _wide(n_cols)
-                and ops.gemm_split_supported(n_cols, n_red))
-
-
 def _wide(n_cols: int) -> bool:
     """Layers of 128 (mod 128) output columns: 256-column tiles (the product kernel) or, for 128 (mod 256) columns, the staged
     loop's 128-column tile.  Round 3 left the latter to the library (HBM-bound shapes, measured level: 100 000 x 256 -> 128
@@ -190,18 +190,12 @@ def use_narrow_tiles(on: bool = True) -> bool:
     return before
 
 
-def split_shape_ok(rows: int, n_cols: int, n_red: int) -> bool:
-    """`split_ok` for a contiguous fp32 ROCm operand of `rows` rows that does not exist yet."""
-    return bool(_SPLIT_GEMMS and _ARITH != _FP32 and rows >= _SPLIT_MIN_ROWS and _wide(n_cols)
-                and ops.gemm_split_supported(n_cols, n_red))
-
-
-def wgrad_f16_ok(n_out: int, n_in: int, rows: int = _SPLIT_MIN_ROWS) -> bool:
+def wgrad_f16_ok(n_out: int, n_in: int, rows: int = SPLIT_MIN_ROWS) -> bool:
     """Does the weight gradient of an [n_out, n_in] layer over `rows` batch rows run on the fp16 split kernel (and therefore
     want column maxima)?  The shapes csrc/wgrad_split.hip tiles: both multiples of 128, one of them of 256 -- and batches of
     4096 rows and more: below that a step is launch-bound, and the maxima passes / zeroed arenas the scales need are launches
     (batch 640: 71 device activities per step with them, 1.55 ms; the fused-mask kernels of csrc/wgrad.hip need none)."""
-    return bool(f16() and rows >= _SPLIT_MIN_ROWS and n_out % 128 == 0 and n_in % 128 == 0 and (n_out % 256 == 0 or n_in % 256 == 0))
+    return bool(f16() and rows >= SPLIT_MIN_ROWS and n_out % 128 == 0 and n_in % 128 == 0 and (n_out % 256 == 0 or n_in % 256 == 0))
 
 
 _WGRAD_BATCH = True
@@ -327,11 +321,6 @@ class WgradQueue:
 wgrad_queue = WgradQueue()
 
 
-def wgrad_batch_shape_ok(n_out: int, n_in: int, rows: int) -> bool:
-    """May this layer's weight gradient wait for the stack's batched launch?"""
-    return bool(_WGRAD_BATCH and wgrad_f16_ok(n_out, n_in, rows))      # (tiled 256 x 256, 128 x 256 or 256 x 128: ops.linear_wgrad_f16_batch)
-
-
 _WGRAD_JOBS = True
 
 
@@ -347,7 +336,7 @@ def use_wgrad_jobs(on: bool = True) -> bool:
 def wgrad_jobs_ok(rows: int, shapes) -> bool:
     """Do the weight gradients of layers `shapes` = [(n_out, n_in), ...] over `rows` batch rows run as ONE job-table launch?"""
     shapes = list(shapes)
-    return bool(_WGRAD_JOBS and _ARITH != _FP32 and 0 < rows < _SPLIT_MIN_ROWS and 0 < len(shapes) <= ops.WGRAD_JOBS_MAX
+    return bool(_WGRAD_JOBS and _ARITH != _FP32 and 0 < rows < SPLIT_MIN_ROWS and 0 < len(shapes) <= ops.WGRAD_JOBS_MAX
                 and all(ops.linear_wgrad_jobs_supported(n, k) for n, k in shapes))
 
 
@@ -402,7 +391,9 @@ def _tile_code(n_cols: int, n_red: int, epilogue: int) -> int:
 # The encoder's last Linear (128 -> 32) and the decoder's first (32 -> 128), forward and data gradient, run on csrc/rq_forward.hip's seam
 # kernel (rqhip_rq_seam): every output is ONE fp32 FMA chain over the input features on the fp32 matrix pipe -- no library call, the ReLU /
 # ReLU backward and the maxima the neighbouring split kernels scale by in the same launch, and the same bits in the fused launch
-# RqVae.forward uses (modules/rqvae.py), which is this kernel with the quantisation levels switched on.  Batches of 4096 rows and more.
+# RqVae.forward uses (modules/rqvae.py), which is this kernel with the quantisation levels switched on.  Batches of 4096 rows and more:
+# every output is a 64- or 16-deep chain of dependent fp32 matrix instructions over 32 rows at a time -- at the reference's batch 640, 20
+# such chains on 20 SIMDs, 9.3 us per launch against 4.6-5.9 us for the library's 16 x 16 tiles (profiles/r06_seam.txt); see SMALL below.
 _CHAIN = True
 CHAIN_D, CHAIN_H = 32, ops.SEAM_H
 
@@ -415,39 +406,19 @@ def use_chain_gemms(on: bool = True) -> bool:
     return before
 
 
-def chain_shape(n_out: int, n_in: int, rows: int = _SPLIT_MIN_ROWS) -> int:
-    """0: not a seam layer; 1: 128 -> 32 (rows enter the input GEMM); 2: 32 -> 128 (rows leave through the output GEMM).
-    Batches of 4096 rows and more, like the split kernels: every output of these GEMMs is a 64- or 16-deep chain of dependent fp32
-    matrix instructions over 32 rows at a time -- at the reference's batch 640 that is 20 such chains on 20 SIMDs, 9.3 us per
-    launch against 4.6-5.9 us for the library's 16 x 16 tiles (profiles/r06_seam.txt): small batches take rqhip_linear_small (below),
-    which splits every reduction over four waves per tile."""
-    if not _CHAIN or rows < _SPLIT_MIN_ROWS:
-        return 0
-    return 1 if (n_out, n_in) == (CHAIN_D, CHAIN_H) else 2 if (n_out, n_in) == (CHAIN_H, CHAIN_D) else 0
-
-
-def chain_kind(x: Tensor, n_out: int, n_in: int) -> int:
-    """chain_shape for an operand that exists: a 2-D fp32 ROCm tensor of n_in columns with at least one row, 16-byte aligned rows."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0 and x.shape[1] == n_in
-            and x.data_ptr() % 16 == 0):
-        return 0
-    return chain_shape(n_out, n_in, x.shape[0])
-
-
-def _chain_scales(r, col_out) -> "Scales":
-    return Scales(r.out_row_max if r.out_row_max is not None else None, col_out)
+def chain_gemms_on() -> bool:
+    return _CHAIN
 
 
 def chain_forward(x: Tensor, w: Tensor, relu: bool, want_rows: bool = False, col_out: Optional[Tensor] = None):
-    """(y, Scales of y) of y = [relu](x w^T) for a seam layer (chain_kind != 0; a ReLU only behind the 32 -> 128 layer)."""
-    kind = chain_kind(x, w.shape[0], w.shape[1])
+    """(y, Scales of y) of y = [relu](x w^T) for a seam layer (`plan_layer`: SEAM_IN / SEAM_OUT; a ReLU only behind the 32 -> 128 layer)."""
     x = x if x.is_contiguous() else x.contiguous()
-    if kind == 1:
+    if tuple(w.shape) == (CHAIN_D, CHAIN_H):
         assert not relu
         return ops.rq_seam(h=x, w_in=w.detach()).res0, Scales()
     r = ops.rq_seam(res0=x, w_out=w.detach(), epilogue=_lib.EPI_RELU if relu else _lib.EPI_STORE, want_row_max=want_rows and f16(),
                     col_max_out=col_out if f16() else None)
-    return r.out, _chain_scales(r, col_out if f16() else None)
+    return r.out, Scales(r.out_row_max, col_out if f16() else None)
 
 
 def chain_input_grad(g: Tensor, w: Tensor, *, g_mask: Optional[Tensor] = None, out_mask: Optional[Tensor] = None, want_rows: bool = False,
@@ -455,15 +426,14 @@ def chain_input_grad(g: Tensor, w: Tensor, *, g_mask: Optional[Tensor] = None, o
     """(gx, Scales of gx) of gx = g' w for a seam layer with weight w [n_out, n_in]; g' = g where g_mask > 0 (the layer's own ReLU
     backward, applied on load: 32 -> 128 layers only); gx is kept where out_mask > 0 (the ReLU backward of the layer below, in the
     epilogue: 128 -> 32 layers only)."""
-    kind = chain_kind(g, w.shape[1], w.shape[0])      # the data gradient maps n_out -> n_in
     g = g if g.is_contiguous() else g.contiguous()
-    if kind == 1:       # layer 32 -> 128, w [128, 32]: gx [B, 32] = g' [B, 128] . w
+    if tuple(w.shape) == (CHAIN_H, CHAIN_D):       # layer 32 -> 128, w [128, 32]: gx [B, 32] = g' [B, 128] . w
         assert out_mask is None
         return ops.rq_seam(h=g, h_mask=g_mask, w_in=w.detach(), w_in_transposed=True).res0, Scales()
-    assert kind == 2 and g_mask is None   # layer 128 -> 32, w [32, 128]: gx [B, 128] = g [B, 32] . w
+    assert g_mask is None                 # layer 128 -> 32, w [32, 128]: gx [B, 128] = g [B, 32] . w
     r = ops.rq_seam(res0=g, w_out=w.detach(), w_out_transposed=True, epilogue=_lib.EPI_MASK if out_mask is not None else _lib.EPI_STORE,
                     out_mask=out_mask, want_row_max=want_rows and f16(), col_max_out=col_out if f16() else None)
-    return r.out, _chain_scales(r, col_out if f16() else None)
+    return r.out, Scales(r.out_row_max, col_out if f16() else None)
 
 
 # ---- batches below 4096 rows: the layers' forward and data gradient on csrc/mlp_small.hip (rqhip_linear_small) -----------------------
@@ -480,24 +450,89 @@ def use_small_kernels(on: bool = True) -> bool:
     return before
 
 
-def small_shape_ok(rows: int, n_out: int, n_red: int) -> bool:
-    """Does out [rows, n_out] = a [rows, n_red] . B run on rqhip_linear_small?  (Not in the strict-fp32 arm, which means "library".)"""
-    return bool(_SMALL and _ARITH != _FP32 and 0 < rows < _SPLIT_MIN_ROWS and n_out % 32 == 0 and n_red % 32 == 0)
-
-
-def small_ok(a: Tensor, n_out: int, n_red: int) -> bool:
-    return bool(a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and a.shape[1] == n_red and a.data_ptr() % 16 == 0
-                and small_shape_ok(a.shape[0], n_out, n_red))
-
-
 def small_forward(x: Tensor, w: Tensor, relu: bool) -> Tensor:
-    """[relu](x w^T), small_ok(x, *w.shape)."""
+    """[relu](x w^T) on rqhip_linear_small (`plan_layer`: SMALL)."""
     return ops.linear_small(x, w.detach(), epilogue=_lib.EPI_RELU if relu else _lib.EPI_STORE)
 
 
 def small_input_grad(g: Tensor, w: Tensor, below: Optional[Tensor] = None) -> Tensor:
     """g w for w [n_out, n_in], kept where `below` [M, n_in] > 0 (the ReLU backward of the layer below) when given."""
     return ops.linear_small(g, w.detach(), w_kn=True, epilogue=_lib.EPI_MASK if below is not None else _lib.EPI_STORE, aux=below)
+
+
+# ---- the plan: which kernel a layer's forward, data gradient and weight gradient take ---------------------------------------------------
+class Route(IntEnum):
+    NONE = 0                # this direction is not computed (nobody wants the gradient)
+    LIBRARY = 1             # the library's fp32 GEMM (widths no kernel tiles, operands no kernel takes, the strict-fp32 arm)
+    SPLIT = 2               # csrc/gemm_split.hip: 4096 rows and more, 128 (mod 128) output columns
+    SEAM_IN = 3             # csrc/rq_forward.hip's seam kernel, a 128 -> 32 product (the rows enter through its input GEMM)
+    SEAM_OUT = 4            # ... a 32 -> 128 product (the rows leave through its output GEMM, which can emit maxima)
+    SMALL = 5               # csrc/mlp_small.hip: below 4096 rows
+    F16_SPLIT = 6           # weight gradient on csrc/wgrad_split.hip, one launch for the layer
+    F16_SPLIT_BATCHED = 7   # ... and the layer may wait for a launch it shares with other layers (`launch_wgrads`)
+    FP32_MFMA = 8           # weight gradient on csrc/wgrad.hip (round 3's kernels; oracle-ordered in the strict-fp32 arm)
+    JOBS = 9                # weight gradient on csrc/wgrad_jobs.hip: below 4096 rows
+
+
+class LayerPlan(NamedTuple):
+    fwd: Route
+    dgrad: Route
+    wgrad: Route
+
+    @property
+    def wgrad_f16(self) -> bool:        # the fp16 split kernel: the weight gradient wants column maxima of both its operands
+        return self.wgrad in (Route.F16_SPLIT, Route.F16_SPLIT_BATCHED)
+
+
+def dense_f32(t: Tensor) -> bool:
+    """The operand form the kernels take: a 2-D fp32 ROCm tensor, contiguous, rows 16-byte aligned."""
+    return bool(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.data_ptr() % 16 == 0)
+
+
+def _gemm_route(rows: int, n_cols: int, n_red: int, seam: bool, small: bool) -> Route:
+    """out [rows, n_cols] = a [rows, n_red] . B, a forward or a data gradient; seam / small: those kernels may be used."""
+    if rows >= SPLIT_MIN_ROWS:
+        if seam and (n_cols, n_red) == (CHAIN_D, CHAIN_H):
+            return Route.SEAM_IN
+        if seam and (n_cols, n_red) == (CHAIN_H, CHAIN_D):
+            return Route.SEAM_OUT
+        if _SPLIT_GEMMS and _ARITH != _FP32 and _wide(n_cols) and ops.gemm_split_supported(n_cols, n_red):
+            return Route.SPLIT
+    elif small and _ARITH != _FP32 and n_cols % 32 == 0 and n_red % 32 == 0:     # (strict fp32 means "library")
+        return Route.SMALL
+    return Route.LIBRARY
+
+
+def plan_layer(rows: int, n_out: int, n_in: int, *, relu: bool, operands_aligned: bool, weight_ok: bool = True,
+               need_dgrad: bool = True, need_wgrad: bool = True, stack_jobs: bool = False) -> LayerPlan:
+    """The kernels of a bias-free Linear n_in -> n_out over `rows` batch rows under the module's switches (ints and bools only: testable
+    without a device).  operands_aligned: activations and gradients have 16-byte aligned rows, which the seam kernel and rqhip_linear_small
+    need; weight_ok: the weight is `dense_f32` (rqhip_linear_small alone reads it as it lies).  The two places where the stack node and the per-layer path decide differently, kept as they are:
+    relu -- the layer is followed by a ReLU.  The seam kernel has no ReLU behind its input GEMM, so a 128 -> 32 layer with one stays off
+      it.  The stack says so for both directions; the per-layer `input_grad` is not told about the ReLU and passes False, so there the
+      data gradient of such a layer still takes the seam kernel.  (No shipped configuration has that layer.)
+    stack_jobs -- the caller is a stack whose layers TOGETHER pass `wgrad_jobs_ok`: one job-table launch for all of them, including
+      layers csrc/wgrad.hip does not tile (64 x 64), which the per-layer path, asking that kernel's shape rule first, leaves to the
+      library."""
+    if rows <= 0:
+        return LayerPlan(Route.LIBRARY, Route.LIBRARY if need_dgrad else Route.NONE, Route.LIBRARY if need_wgrad else Route.NONE)
+    seam = _CHAIN and operands_aligned and not (relu and (n_out, n_in) == (CHAIN_D, CHAIN_H))
+    small = _SMALL and operands_aligned and weight_ok
+    fwd = _gemm_route(rows, n_out, n_in, seam, small)
+    dgrad = _gemm_route(rows, n_in, n_out, seam, small) if need_dgrad else Route.NONE
+    if not need_wgrad:
+        wgrad = Route.NONE
+    elif stack_jobs:
+        wgrad = Route.JOBS
+    elif not ops.linear_wgrad_supported(n_out, n_in):
+        wgrad = Route.LIBRARY
+    elif wgrad_jobs_ok(rows, [(n_out, n_in)]):
+        wgrad = Route.JOBS
+    elif wgrad_f16_ok(n_out, n_in, rows):
+        wgrad = Route.F16_SPLIT_BATCHED if _WGRAD_BATCH else Route.F16_SPLIT
+    else:
+        wgrad = Route.FP32_MFMA
+    return LayerPlan(fwd, dgrad, wgrad)
 
 
 def images(jobs: List[Tuple[Tensor, bool]]) -> List[Tensor]:
@@ -529,26 +564,29 @@ def gemm(a: Tensor, image: Tensor, n_cols: int, *, epilogue: int = _lib.EPI_STOR
 
 
 def input_grad(g: Tensor, w: Tensor, *, g_scales: Optional[Scales] = None, image: Optional[Tensor] = None) -> Tensor:
-    """g [M, N] . w [N, K]: the split kernel with the image of w^T where it applies, else the library GEMM."""
+    """g [M, N] . w [N, K] on the kernel `plan_layer` names (the split kernel with the image of w^T)."""
     g = g if g.is_contiguous() else g.contiguous()
-    if chain_kind(g, w.shape[1], w.shape[0]):
+    # relu=False: nobody tells this function whether a ReLU follows the layer -- the first difference in `plan_layer`'s docstring
+    route = plan_layer(g.shape[0], w.shape[0], w.shape[1], relu=False, operands_aligned=True, weight_ok=dense_f32(w),
+                       need_wgrad=False).dgrad if dense_f32(g) else Route.LIBRARY
+    if route in (Route.SEAM_IN, Route.SEAM_OUT):
         return chain_input_grad(g, w)[0]
-    if split_ok(g, w.shape[1], w.shape[0], False):
+    if route == Route.SPLIT:
         return gemm(g, image if image is not None else planes(w, True), w.shape[1], a_scales=g_scales)[0]
-    if small_ok(g, w.shape[1], w.shape[0]) and w.is_contiguous() and w.data_ptr() % 16 == 0:
+    if route == Route.SMALL:
         return small_input_grad(g, w)
     return g.mm(w)
 
 
 def forward(x: Tensor, w: Tensor, relu: bool, zero_bias: Tensor = None) -> Tensor:
-    """relu(x w^T) or x w^T for 2-D fp32 ROCm tensors: the split kernel where it applies, else the library GEMM (with
-    the ReLU in the hipBLASLt epilogue)."""
-    kind = chain_kind(x, w.shape[0], w.shape[1])
-    if kind == 2 or (kind == 1 and not relu):
+    """relu(x w^T) or x w^T on the kernel `plan_layer` names; the library GEMM has the ReLU in the hipBLASLt epilogue."""
+    route = plan_layer(x.shape[0], w.shape[0], w.shape[1], relu=relu, operands_aligned=True, weight_ok=dense_f32(w),
+                       need_dgrad=False, need_wgrad=False).fwd if dense_f32(x) else Route.LIBRARY
+    if route in (Route.SEAM_IN, Route.SEAM_OUT):
         return chain_forward(x, w, relu)[0]
-    if split_ok(x, w.shape[0], w.shape[1], relu):
+    if route == Route.SPLIT:
         return gemm(x, planes(w, False), w.shape[0], epilogue=_lib.EPI_RELU if relu else _lib.EPI_STORE)[0]
-    if small_ok(x, w.shape[0], w.shape[1]) and x.is_contiguous() and w.is_contiguous() and w.data_ptr() % 16 == 0:
+    if route == Route.SMALL:
         return small_forward(x, w, relu)
     return library_forward(x, w, relu, zero_bias)
 
@@ -560,11 +598,6 @@ def library_forward(x: Tensor, w: Tensor, relu: bool, zero_bias: Tensor = None) 
     return x.mm(w.t())
 
 
-def hip_wgrad_ok(g: Tensor, w: Tensor) -> bool:
-    return bool(g.is_cuda and g.dtype == torch.float32 and g.dim() == 2 and g.shape[0] > 0
-                and ops.linear_wgrad_supported(w.shape[0], w.shape[1]))
-
-
 def weight_grad(g: Tensor, y: Optional[Tensor], x: Tensor, w: Tensor, *, out: Optional[Tensor] = None,
                 want_masked: bool = True, g_scales: Optional[Scales] = None, x_scales: Optional[Scales] = None,
                 premasked: bool = False):
@@ -573,17 +606,18 @@ def weight_grad(g: Tensor, y: Optional[Tensor], x: Tensor, w: Tensor, *, out: Op
     backward).  f16x2 arithmetic on the shapes csrc/wgrad_split.hip tiles: column scales of g_pre and x from `g_scales` /
     `x_scales` or from passes (for an unmasked g with y, ONE pass masks, writes g_pre and takes its maxima); otherwise the
     round-3 kernels (mask fused into the weight-gradient kernel).  Falls back to library GEMMs for shapes no kernel tiles."""
-    if not hip_wgrad_ok(g, w):
+    plan = plan_layer(g.shape[0] if dense_f32(g) else 0, w.shape[0], w.shape[1], relu=y is not None, operands_aligned=True, need_dgrad=False)
+    if plan.wgrad == Route.LIBRARY:
         gp = g if (y is None or premasked) else torch.ops.aten.threshold_backward(g, y, 0.0)
         gw = torch.mm(gp.t(), x, out=out) if out is not None else gp.t().mm(x)
         return gw, gp, None
     if premasked:
         y = None
-    if g.is_cuda and wgrad_jobs_ok(g.shape[0], [tuple(w.shape)]):     # small batches: the job-table kernel with one job
+    if plan.wgrad == Route.JOBS:     # small batches: the job-table kernel with one job
         gp = g if y is None else torch.ops.aten.threshold_backward(g, y, 0.0)
         gw = ops.linear_wgrad_jobs([(gp, x)], outs=[out] if out is not None else None)[0]
         return gw, gp, (g_scales if y is None else None)
-    if wgrad_f16_ok(w.shape[0], w.shape[1], g.shape[0]):
+    if plan.wgrad_f16:      # (batched or not: a call of this function is a launch of the layer's own)
         if y is not None:   # mask + maxima in one pass; the weight-gradient kernel then runs without a mask
             r, c, g = ops.maxima(g, y, rows=want_masked, cols=True, write_masked=True)
             g_scales = Scales(r, c)

@@ -238,7 +238,7 @@ def test_maxima_wide_rows_and_wide_mlp_layer(R):
     x = torch.randn(M, R, generator=g).cuda().requires_grad_(True)
     w = (torch.randn(256, R, generator=g) / R ** 0.5).cuda().requires_grad_(True)
     from modules.encoder import _LinearReLU
-    assert lin.split_ok(x.detach(), 256, R)
+    assert lin.plan_layer(M, 256, R, relu=True, operands_aligned=lin.dense_f32(x.detach())).fwd == lin.Route.SPLIT
     out = _LinearReLU.apply(x, w, torch.zeros(256, device="cuda"))
     gy = torch.randn(M, 256, generator=g).cuda()
     out.backward(gy)

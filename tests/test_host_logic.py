@@ -320,6 +320,67 @@ def test_grad_sink_is_claimed_once_per_parameter_and_epoch():
     assert claim_grad_sink(w) is None                      # a gradient is already there: autograd accumulates
 
 
+def test_layer_plan_for_the_shipped_stacks_and_every_switch():
+    """rqhip/linear.py:plan_layer is the one place that decides which kernel a Linear layer's forward, data gradient and weight gradient
+    take; it is a function of ints and switches (the support queries are host-side), so the table is pinned here without a GPU.  Expected
+    routes written by hand from DESIGN section 4: 4096 rows and more -- activation GEMMs of 128 (mod 128) output columns on the split
+    kernel (4.3), the 128 <-> 32 layers on the seam kernel's GEMMs (4.1b), weight gradients tiled 256 x 256 / 128 x 256 / 256 x 128 on
+    the fp16 split kernel and batched, the 32-wide ones on the fp32-MFMA kernel (4.4); below 4096 rows -- rqhip_linear_small (4.4c)
+    and the job table (4.4b)."""
+    from rqhip import linear
+    R = linear.Route
+    enc, dec = [768, 512, 256, 128, 32], [32, 128, 256, 512, 768]       # configuration 2; a ReLU behind every layer but the last
+
+    def plans(widths, rows, **kw):
+        n = len(widths) - 1
+        kw.setdefault("operands_aligned", True)
+        return [tuple(linear.plan_layer(rows, widths[i + 1], widths[i], relu=i + 1 < n, **kw)) for i in range(n)]
+
+    big = (R.SPLIT, R.SPLIT, R.F16_SPLIT_BATCHED)
+    for rows in (100_000, 4096):                                          # (4096: the first row count of the large-batch kernels)
+        assert plans(enc, rows) == [big, big, big, (R.SEAM_IN, R.SEAM_OUT, R.FP32_MFMA)], rows
+        assert plans(dec, rows) == [(R.SEAM_OUT, R.SEAM_IN, R.FP32_MFMA), big, big, big], rows
+    for rows in (4095, 640, 64):
+        for widths in (enc, dec):
+            assert plans(widths, rows) == [(R.SMALL, R.SMALL, R.JOBS)] * 4, (rows, widths)
+            shapes = list(zip(widths[1:], widths[:-1]))
+            assert plans(widths, rows, stack_jobs=linear.wgrad_jobs_ok(rows, shapes)) == [(R.SMALL, R.SMALL, R.JOBS)] * 4
+    # a width that is not a multiple of 32: the library everywhere, at either size
+    for rows in (100_000, 640):
+        assert plans([768, 500, 256], rows) == [(R.LIBRARY, R.LIBRARY, R.LIBRARY)] * 2, rows
+    # rows that are not 16-byte aligned (the seam kernel and rqhip_linear_small move them as vectors), no rows, directions nobody asks for
+    assert plans(enc, 100_000, operands_aligned=False) == [big, big, big, (R.LIBRARY, R.SPLIT, R.FP32_MFMA)]    # (32 -> 128: a 128-column split tile)
+    assert plans(enc, 640, operands_aligned=False) == [(R.LIBRARY, R.LIBRARY, R.JOBS)] * 4
+    assert tuple(linear.plan_layer(0, 512, 768, relu=True, operands_aligned=True)) == (R.LIBRARY, R.LIBRARY, R.LIBRARY)
+    assert tuple(linear.plan_layer(100_000, 512, 768, relu=True, operands_aligned=True, need_dgrad=False, need_wgrad=False)) \
+        == (R.SPLIT, R.NONE, R.NONE)
+    assert linear.plan_layer(640, 512, 768, relu=True, operands_aligned=True, weight_ok=False)[:2] == (R.LIBRARY, R.LIBRARY)
+    # the two places where the stack node and the per-layer path decide differently (plan_layer's docstring)
+    assert linear.plan_layer(100_000, 32, 128, relu=True, operands_aligned=True).fwd == R.LIBRARY            # the seam kernel has no ReLU there
+    assert linear.plan_layer(100_000, 32, 128, relu=True, operands_aligned=True).dgrad != R.SEAM_OUT         # ... the stack: neither direction
+    assert linear.plan_layer(100_000, 32, 128, relu=False, operands_aligned=True)[:2] == (R.SEAM_IN, R.SEAM_OUT)
+    assert linear.plan_layer(640, 64, 64, relu=True, operands_aligned=True, stack_jobs=True).wgrad == R.JOBS
+    assert linear.plan_layer(640, 64, 64, relu=True, operands_aligned=True).wgrad == R.LIBRARY               # csrc/wgrad.hip's rule first
+
+    def flipped(switch, value, rows, n_out, n_in):
+        before = switch(value)
+        try:
+            return tuple(linear.plan_layer(rows, n_out, n_in, relu=(n_out, n_in) != (32, 128), operands_aligned=True))
+        finally:
+            switch(before)
+
+    assert flipped(linear.use_arith, "fp32", 100_000, 512, 768) == (R.LIBRARY, R.LIBRARY, R.FP32_MFMA)
+    assert flipped(linear.use_arith, "fp32", 640, 512, 768) == (R.LIBRARY, R.LIBRARY, R.FP32_MFMA)
+    assert flipped(linear.use_arith, "bf16x3", 100_000, 512, 768) == (R.SPLIT, R.SPLIT, R.FP32_MFMA)       # round 3's weight-gradient kernels
+    assert flipped(linear.use_split_gemms, False, 100_000, 512, 768) == (R.LIBRARY, R.LIBRARY, R.F16_SPLIT_BATCHED)
+    assert flipped(linear.use_chain_gemms, False, 100_000, 32, 128)[0] == R.LIBRARY                         # 32 output columns: no split tile
+    assert flipped(linear.use_narrow_tiles, False, 100_000, 128, 256) == (R.LIBRARY, R.SPLIT, R.F16_SPLIT_BATCHED)
+    assert flipped(linear.use_small_kernels, False, 640, 512, 768) == (R.LIBRARY, R.LIBRARY, R.JOBS)
+    assert flipped(linear.use_wgrad_jobs, False, 640, 512, 768) == (R.SMALL, R.SMALL, R.FP32_MFMA)
+    assert flipped(linear.use_wgrad_batch, False, 100_000, 512, 768) == (R.SPLIT, R.SPLIT, R.F16_SPLIT)
+    assert plans(enc, 100_000)[0] == big and plans(enc, 640)[0] == (R.SMALL, R.SMALL, R.JOBS)              # every switch is back
+
+
 def test_small_batch_weight_gradient_routing_and_its_abi_argument_checks():
     """Which batches take the job-table weight-gradient kernel (csrc/wgrad_jobs.hip) is host logic: below the split kernels' 4096
     rows, at most eight supported layers, not under the strict fp32 arithmetic; and the C entry point refuses bad job tables before
