@@ -83,13 +83,14 @@ class _MLPStack(torch.autograd.Function):
     def forward(ctx, x: Tensor, target, relus, zero_bias, given, defer, *weights):
         from rqhip import _lib
         from rqhip import autograd as _ag
-        n, M, R, aligned = len(weights), x.shape[0], _lin.Route, _lin.dense_f32(x)
+        assert _lin.dense_f32(x), "_MLPStack takes a contiguous, 16-byte aligned fp32 ROCm matrix (MLP._run re-homes what is not)"
+        n, M, R = len(weights), x.shape[0], _lin.Route
         need_w = [bool(f) for f in ctx.needs_input_grad[6:]]
         need_in = [bool(ctx.needs_input_grad[0]) or any(need_w[:i]) for i in range(n)]   # gradient wrt layer i's input wanted
         # which kernel every layer's forward, data gradient and weight gradient take: rqhip/linear.py:plan_layer, as on the per-layer path
         # (below 4096 rows all weight gradients of the stack are ONE job-table launch, decided for the layers together)
         stack_jobs = _lin.wgrad_jobs_ok(M, [tuple(w.shape) for i, w in enumerate(weights) if need_w[i]])
-        plans = [_lin.plan_layer(M, w.shape[0], w.shape[1], relu=relus[i], operands_aligned=aligned, weight_ok=_lin.dense_f32(w),
+        plans = [_lin.plan_layer(M, w.shape[0], w.shape[1], relu=relus[i], operands_aligned=True, weight_ok=_lin.dense_f32(w),
                                  need_dgrad=need_in[i], need_wgrad=need_w[i], stack_jobs=stack_jobs) for i, w in enumerate(weights)]
         imgs = iter(_lin.images([(w, False) for w, p in zip(weights, plans) if p.fwd == R.SPLIT]
                                 + [(w, True) for w, p in zip(weights, plans) if p.dgrad == R.SPLIT]))
@@ -145,7 +146,9 @@ class _MLPStack(torch.autograd.Function):
         scs, relus, need_in, need_w, plans = ctx.scs, ctx.relus, ctx.need_in, ctx.need_w, ctx.plans
         g_out = g_out.contiguous()
         handed = _lin.take_grad_handoff(g_out) if target is None else None
-        if handed is not None:       # the node above (modules/rqvae.py's seam) masked this gradient by our last ReLU and took its maxima
+        if g_out.data_ptr() % 16 != 0:      # (the caller's gradient may be a view into a larger buffer: as the input in MLP._run; every
+            g_out = g_out.clone()           # gradient further down is written by this node's own launches into fresh allocations)
+        if handed is not None:      # the node above (modules/rqvae.py's seam) masked this gradient by our last ReLU and took its maxima
             g, gsc = g_out, handed
         elif target is None:
             g, gsc = g_out, _lin.Scales()
@@ -172,7 +175,7 @@ class _MLPStack(torch.autograd.Function):
             y = acts[i + 1] if (relus[i] and not premasked) else None
             # a 32 -> 128 seam layer applies its own ReLU backward on LOAD in its data gradient: the masked gradient is then only
             # written out when the job-table weight gradient needs it as a tensor
-            mask_on_load = p.dgrad == R.SEAM_IN and y is not None and g.data_ptr() % 16 == 0
+            mask_on_load = p.dgrad == R.SEAM_IN and y is not None
             g_unmasked = g
             if p.wgrad == R.JOBS and ctx.stack_jobs:
                 if y is not None:
@@ -193,7 +196,7 @@ class _MLPStack(torch.autograd.Function):
                 break
             lower_relu = i > 0 and relus[i - 1]
             lower_split = i > 0 and plans[i - 1].dgrad == R.SPLIT
-            if p.dgrad in (R.SEAM_IN, R.SEAM_OUT) and (g_unmasked if mask_on_load else g).data_ptr() % 16 == 0:
+            if p.dgrad in (R.SEAM_IN, R.SEAM_OUT):
                 if p.dgrad == R.SEAM_IN:     # 32 -> 128 layer: gx [M, 32]; its own ReLU backward on load when the gradient is still unmasked
                     src, msk = (g_unmasked, y) if (mask_on_load and (g is None or g is g_unmasked)) else (g, None)
                     g, gsc = _lin.chain_input_grad(src, w, g_mask=msk)
@@ -207,7 +210,7 @@ class _MLPStack(torch.autograd.Function):
                                       aux=a if fuse else None, a_scales=gsc, want_rows=lower_split and (fuse or not lower_relu),
                                       col_out=col_outs[i] if (fuse or not lower_relu) else None)
                 premasked = fuse or not lower_relu
-            elif p.dgrad == R.SMALL and g.data_ptr() % 16 == 0:      # the ReLU backward of the layer below in the epilogue: no mask launch
+            elif p.dgrad == R.SMALL:      # the ReLU backward of the layer below in the epilogue: no mask launch
                 g, gsc = _lin.small_input_grad(g, w, a if lower_relu else None), _lin.Scales()
                 premasked = True
             else:
@@ -269,7 +272,10 @@ class MLP(nn.Module):
             relus.append(relu)
             i += 2 if relu else 1
         if weights:
-            x = _MLPStack.apply(x, target, tuple(relus), self._zero_bias, _lin.attached_scales(x), getattr(self, "_defer_wgrads", False), *weights)
+            given = _lin.attached_scales(x)
+            if not _lin.dense_f32(x):       # (e.g. a view into a larger buffer: the kernels read rows as 16-byte vectors -- re-home it once, here)
+                x = x.clone(memory_format=torch.contiguous_format)
+            x = _MLPStack.apply(x, target, tuple(relus), self._zero_bias, given, getattr(self, "_defer_wgrads", False), *weights)
         return self._run_layerwise(x, layers[i:]) if i < len(layers) else x
 
     def _run_layerwise(self, x: Tensor, layers) -> Tensor:

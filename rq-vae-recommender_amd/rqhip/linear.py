@@ -606,8 +606,10 @@ def weight_grad(g: Tensor, y: Optional[Tensor], x: Tensor, w: Tensor, *, out: Op
     backward).  f16x2 arithmetic on the shapes csrc/wgrad_split.hip tiles: column scales of g_pre and x from `g_scales` /
     `x_scales` or from passes (for an unmasked g with y, ONE pass masks, writes g_pre and takes its maxima); otherwise the
     round-3 kernels (mask fused into the weight-gradient kernel).  Falls back to library GEMMs for shapes no kernel tiles."""
-    plan = plan_layer(g.shape[0] if dense_f32(g) else 0, w.shape[0], w.shape[1], relu=y is not None, operands_aligned=True, need_dgrad=False)
-    if plan.wgrad == Route.LIBRARY:
+    # operands no kernel takes (a misaligned g; a misaligned x: the per-layer forward sent that first-layer input to the library as well)
+    aligned = dense_f32(g) and x.data_ptr() % 16 == 0
+    plan = plan_layer(g.shape[0], w.shape[0], w.shape[1], relu=y is not None, operands_aligned=True, need_dgrad=False)
+    if plan.wgrad == Route.LIBRARY or not aligned:
         gp = g if (y is None or premasked) else torch.ops.aten.threshold_backward(g, y, 0.0)
         gw = torch.mm(gp.t(), x, out=out) if out is not None else gp.t().mm(x)
         return gw, gp, None

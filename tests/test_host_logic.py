@@ -381,6 +381,79 @@ def test_layer_plan_for_the_shipped_stacks_and_every_switch():
     assert plans(enc, 100_000)[0] == big and plans(enc, 640)[0] == (R.SMALL, R.SMALL, R.JOBS)              # every switch is back
 
 
+def test_mlp_route_cases_reach_every_route_and_every_hand_over():
+    """tests/mlp_route_cases.py is the table tests/test_gpu_mlp_routes.py runs against fp64; here, without a GPU: the plans of its cases,
+    computed as modules/encoder.py:_MLPStack.forward computes them, reach every route in every direction and every pair of neighbouring
+    routes across which the node hands state over (maxima, masks, job lists).  A pair no widths can reach is listed with its rule."""
+    import mlp_route_cases as mc
+    from rqhip import linear
+    R = linear.Route
+    f16 = "f16"     # F16_SPLIT or F16_SPLIT_BATCHED: the weight gradient that wants column maxima
+    fwd, dgrad, wgrad, dgrad_wgrad, fwd_fwd, plans_of = set(), set(), set(), set(), set(), {}
+    for case in mc.cases():
+        with mc.switched(case.switch):
+            plans, stack_jobs = mc.stack_plans(case)
+        plans_of[case.id] = (plans, stack_jobs)
+        for i, p in enumerate(plans):
+            fwd.add(p.fwd), dgrad.add(p.dgrad), wgrad.add(p.wgrad)
+            if i > 0:
+                dgrad_wgrad.add((p.dgrad, f16 if plans[i - 1].wgrad_f16 else plans[i - 1].wgrad))
+            if i + 1 < len(plans):
+                fwd_fwd.add((p.fwd, plans[i + 1].fwd))
+    assert len(plans_of) == len(mc.cases())                                     # ids are unique
+    assert linear.arith_name() == "f16x2" and linear.plan_layer(640, 512, 768, relu=True, operands_aligned=True) == (R.SMALL, R.SMALL, R.JOBS)
+    gemms = {R.LIBRARY, R.SPLIT, R.SEAM_IN, R.SEAM_OUT, R.SMALL}
+    assert fwd == gemms and dgrad == gemms | {R.NONE}
+    assert wgrad == {R.NONE, R.LIBRARY, R.F16_SPLIT, R.F16_SPLIT_BATCHED, R.FP32_MFMA, R.JOBS}
+    # data gradient of layer i x weight gradient of layer i - 1 (which reads what that data gradient wrote)
+    forbidden = {(R.SPLIT, R.JOBS), (R.SEAM_OUT, R.JOBS),      # split and seam kernels: 4096 rows and more; the job table: fewer
+                 (R.SMALL, f16)}                               # rqhip_linear_small: fewer than 4096 rows; the fp16 weight gradient: 4096 and more
+    want = {(d, w) for d in (R.SPLIT, R.LIBRARY, R.SEAM_OUT, R.SMALL) for w in (f16, R.FP32_MFMA, R.LIBRARY, R.JOBS)} - forbidden
+    assert want <= dgrad_wgrad, sorted(want - dgrad_wgrad)
+    assert not forbidden & dgrad_wgrad
+    # forward of layer i -> forward of layer i + 1 (which may want the row maxima of what layer i stores).  Not in the list, because no
+    # widths reach them: pairs across the 4096-row threshold (SMALL with SPLIT / SEAM_*: one row count per stack), and SEAM_IN ->
+    # anything (the seam kernel has no ReLU behind its input GEMM, so a 128 -> 32 layer on it is the last one).
+    assert {(R.LIBRARY, R.SPLIT), (R.SPLIT, R.LIBRARY), (R.SPLIT, R.SPLIT), (R.SPLIT, R.SEAM_IN), (R.SEAM_OUT, R.SPLIT), (R.LIBRARY, R.SEAM_IN),
+            (R.SEAM_OUT, R.LIBRARY), (R.SEAM_OUT, R.SEAM_IN), (R.LIBRARY, R.LIBRARY), (R.SMALL, R.SMALL), (R.SMALL, R.LIBRARY),
+            (R.LIBRARY, R.SMALL)} <= fwd_fwd
+    assert not any(a == R.SEAM_IN or (((a == R.SMALL) != (b == R.SMALL)) and R.LIBRARY not in (a, b)) for a, b in fwd_fwd)
+
+    # what the table says of its stacks, with the default switches (routes as (forward, data gradient, weight gradient))
+    def of(cid):
+        return [tuple(p) for p in plans_of[cid][0]]
+    big, small = (R.SPLIT, R.SPLIT, R.F16_SPLIT_BATCHED), (R.SMALL, R.SMALL, R.JOBS)
+    lib = (R.LIBRARY,) * 3
+    assert of("S3-4096-dx")[3] == (R.LIBRARY, R.SPLIT, R.FP32_MFMA) and of("S4-4097-dx")[0] == (R.SPLIT, R.LIBRARY, R.FP32_MFMA)
+    assert of("M1-4096-dx") == [big, (R.LIBRARY, R.SPLIT, R.LIBRARY), (R.SPLIT, R.LIBRARY, R.LIBRARY), (R.SEAM_IN, R.SEAM_OUT, R.FP32_MFMA)]
+    assert of("M2-640-dx") == [small] * 3 and plans_of["M2-640-dx"][1]                                   # (64 x 96, 32 x 64: jobs of the stack's table)
+    assert of("M2-4097-dx") == [(R.LIBRARY, R.SPLIT, R.FP32_MFMA), lib, lib]
+    assert of("M3-4095-dx") == [small, lib, lib, (R.SMALL, R.SMALL, R.LIBRARY)] and not plans_of["M3-4095-dx"][1]   # one-job launch beside the library
+    assert of("M3-4096-dx") == [big, lib, lib, lib]                                                      # library data gradient -> fp16 weight gradient
+    assert of("M4-4097-dx")[1] == (R.LIBRARY, R.SPLIT, R.FP32_MFMA) and of("M4-640-dx") == [small] * 3
+    assert of("M5-4095-dx") == [small] * 9 and not plans_of["M5-4095-dx"][1]                             # nine layers: no table for the stack
+    assert of("M5-4096-dx") == [(R.SPLIT, R.SPLIT, R.FP32_MFMA)] * 9
+    assert of("M6-4096-dx") == [lib, big, (R.LIBRARY, R.SPLIT, R.FP32_MFMA)]
+    assert of("M7-4096-dx") == [(R.SEAM_OUT, R.SEAM_IN, R.FP32_MFMA), (R.LIBRARY, R.SPLIT, R.FP32_MFMA)]
+    assert of("M8-4097-dx") == [(R.SEAM_OUT, R.SEAM_IN, R.FP32_MFMA), (R.SEAM_IN, R.SEAM_OUT, R.FP32_MFMA)]
+    assert of("S1-4096-nodx-frozen02") == [(R.SPLIT, R.NONE, R.NONE), (R.SPLIT, R.NONE, R.F16_SPLIT_BATCHED), (R.SPLIT, R.SPLIT, R.NONE),
+                                            (R.SEAM_IN, R.SEAM_OUT, R.FP32_MFMA)]
+    # where stack node and per-layer path run different kernels: exactly the two differences plan_layer documents
+    differ = {c.id for c in mc.cases() if c.switch is None and not mc.same_kernels(c)}
+    assert differ == {c.id for c in mc.cases() if c.switch is None and ((c.stack == "M4") or (c.stack == "M2" and c.rows < 4096))}
+
+
+def test_mlp_route_cases_zero_few_rows_for_relu_kinks():
+    """tests/mlp_route_cases.py:reference gives rows with a pre-activation within 2^-17 of zero (relative to its layer's largest) a zero
+    upstream gradient; that must stay a small part of every case -- a property of seeds and widths, checked here before any GPU runs."""
+    import mlp_route_cases as mc
+    for stack in mc.STACKS:
+        for rows in mc.ROWS:
+            zeroed = mc.reference(stack, rows).zeroed
+            assert zeroed <= mc.MAX_ZEROED, (stack, rows, zeroed)
+    assert mc.KINK_MARGIN == 2.0 ** -17 and mc.MAX_ZEROED == 0.10
+
+
 def test_small_batch_weight_gradient_routing_and_its_abi_argument_checks():
     """Which batches take the job-table weight-gradient kernel (csrc/wgrad_jobs.hip) is host logic: below the split kernels' 4096
     rows, at most eight supported layers, not under the strict fp32 arithmetic; and the C entry point refuses bad job tables before
