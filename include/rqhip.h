@@ -301,6 +301,42 @@ int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, const float
                        const uint8_t *key_mask, int causal, int past, const int32_t *anc, int64_t ld_anc,
                        int64_t slab_rows, float *out, int64_t ld_out, rqhip_stream_t stream);
 
+/* The same attention for training (csrc/t5_attention.hip): a forward that also writes the row log-sum-exp and applies the
+ * attention-weight dropout, and the backward.  Dense K/V with one K/V per query row only (Rk = R, else
+ * RQHIP_EUNSUPPORTED), no `past`; q, k, v, bias_by_delta, bias_offset, key_mask and causal as above.
+ *   Dropout (0 <= p < 1): weight (r, h, i, j) is kept iff hash(seed, ((r * H + h) * Tq + i) * Tk + j) >= round(p * 2^32)
+ *     and kept weights are scaled by 1 / (1 - p), AFTER the softmax's normalisation.  With x = the index, s = *seed and
+ *     fmix = murmur3's 32-bit finaliser:  hash = fmix((fmix(lo(s) ^ lo(x)) ^ hi(s) ^ hi(x) * 0x85EBCA6B) + 0x9E3779B9).
+ *     `seed` points to ONE int64 on the device (NULL allowed at p = 0); the host never reads it.  The forward and both
+ *     passes of the backward recompute the decision; no mask is stored (rqhip/ops.py:t5_attention_dropout_keep restates
+ *     it in torch).
+ *   rqhip_t5_attention_fwd_train: out as rqhip_t5_attention (bit for bit at p = 0) and lse [R, H, Tq] = max + log(sum)
+ *     of each row's scores.
+ *   rqhip_t5_attention_bwd: from d_out (row stride ld_do) writes d_q [R, Tq, H * 64], d_k and d_v [R, Tk, H * 64] (dense)
+ *     and, with a bias table, d_bias_by_delta [n_delta, H] (zero outside the deltas -(Tq - 1) .. Tk - 1 of the call)
+ *     through the scratch d_bias_partial [R * H, Tq + Tk - 1].  P is recomputed: dP = (dO V^T) o M / (1 - p),
+ *     D_i = dO_i . O_i, dS = P o (dP - D), dQ = dS K, dK = dS^T Q, dV = (P o M / (1 - p))^T dO, with no special case for
+ *     masked keys; nothing of size Tq x Tk is stored.  Two of the saved tensors are recomputed rather than read, for
+ *     accuracy.  Each row's max and sum come from q and k with the forward's bits, not from lse, which cannot carry
+ *     log(sum) beside max = -FLT_MAX (a row with every key masked keeps its uniform P and non-zero dS, as with the
+ *     operators).  D is evaluated as sum_j P_ij dP_ij, the same number as dO_i . O_i, from the very dP it is subtracted
+ *     from: the rounding of the 64-term products cancels in dP - D as in the operators' softmax backward, and a row
+ *     with one live key has dS = 0 exactly.  out and lse stay part of the call (what autograd saves) and must be
+ *     non-NULL.
+ * Limits (rqhip_t5_attention_bwd_supported, both functions): d_kv = 64, 1 <= Tq, Tk <= 256, any H >= 1, Tq <= Tk with
+ * a bias table or causal.  No float atomics, fixed reduction orders: the same bits on every run; no allocation, copy
+ * or sync. */
+int rqhip_t5_attention_bwd_supported(int d_kv, int H, int Tq, int Tk);
+int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, int64_t R,
+                                 int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta,
+                                 int bias_offset, const uint8_t *key_mask, int causal, double p, const int64_t *seed,
+                                 float *out, int64_t ld_out, float *lse, rqhip_stream_t stream);
+int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, const float *out,
+                           int64_t ld_out, const float *lse, const float *d_out, int64_t ld_do, int64_t R, int64_t Rk,
+                           int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta, int bias_offset,
+                           const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *d_q, float *d_k,
+                           float *d_v, float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

@@ -23,6 +23,7 @@
 // Fixed reduction orders, no atomics, no host sync: the same bits on every run; graph-capturable once the LDS
 // attribute has been raised by a first eager call, as everywhere in this library.
 #include <float.h>
+#include <math.h>
 
 #include "rqhip_common.h"
 
@@ -48,8 +49,33 @@ struct AttArgs {
     long long ld_anc, slab_rows;
 };
 
-template <int MT>
-__global__ __launch_bounds__(256) void t5_attention_kernel(AttArgs a) {
+// What the training forward adds to a call: the row log-sum-exp and the dropout of the normalised weights.
+struct AttTrain {
+    float *lse;               // [R, H, Tq]
+    const long long *seed;    // one int64 on the device (read only when thresh != 0)
+    unsigned thresh;          // round(p * 2^32): element kept when its hash >= thresh; 0 = no dropout
+    float inv_keep;           // 1 / (1 - p)
+};
+
+// The dropout decision of element idx = ((r * H + h) * Tq + i) * Tk + j: a pure function of the 64-bit seed and idx
+// (two rounds of the murmur3 finaliser).  rqhip/ops.py:t5_attention_dropout_keep restates it in torch integer operations.
+__device__ __forceinline__ unsigned att_fmix32(unsigned h) {
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
+__device__ __forceinline__ bool att_keep(unsigned long long seed, unsigned long long idx, unsigned thresh) {
+    unsigned h = att_fmix32((unsigned)seed ^ (unsigned)idx);
+    h = att_fmix32((h ^ (unsigned)(seed >> 32) ^ ((unsigned)(idx >> 32) * 0x85EBCA6Bu)) + 0x9E3779B9u);
+    return h >= thresh;
+}
+
+template <int MT, bool TRAIN>
+__device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
     extern __shared__ float att_lds[];
     const int ntiles = (a.Tk + 15) >> 4, Tkp = ntiles << 4;
     float *Ks = att_lds;
@@ -148,6 +174,22 @@ __global__ __launch_bounds__(256) void t5_attention_kernel(AttArgs a) {
         }
         sum = sum + __shfl_xor(sum, 16, RQ_WAVE);
         sum = sum + __shfl_xor(sum, 32, RQ_WAVE);
+        if constexpr (TRAIN) {
+            const size_t qh = ((size_t)(b * a.beams + beam) * (size_t)a.H + (size_t)h) * (size_t)a.Tq + (size_t)ti;
+            if (m < M && g == 0) t.lse[qh] = mx + logf(sum);
+            if (t.thresh) {  // dropout of the normalised weights: the dropped ones leave the product, the sum stays
+                const unsigned long long seed = (unsigned long long)*t.seed;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    if (mt < ntiles) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (!att_keep(seed, (unsigned long long)qh * a.Tk + (16 * mt + 4 * g + r), t.thresh))
+                                s[mt][r] = 0.f;
+                    }
+                }
+            }
+        }
 
         // ---- O^T = V^T P^T
         f32x4 o[4];
@@ -168,11 +210,27 @@ __global__ __launch_bounds__(256) void t5_attention_kernel(AttArgs a) {
         if (m < M) {
             float *op = a.out + qrow * (size_t)a.ld_out + (size_t)h * kAttD + 4 * g;
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                *reinterpret_cast<float4 *>(op + 16 * dt) =
-                    make_float4(o[dt][0] / sum, o[dt][1] / sum, o[dt][2] / sum, o[dt][3] / sum);
+            for (int dt = 0; dt < 4; ++dt) {
+                if constexpr (TRAIN)  // times 1 / (1 - p), which is 1.0f at p = 0: the bits of the inference kernel
+                    *reinterpret_cast<float4 *>(op + 16 * dt) =
+                        make_float4(o[dt][0] / sum * t.inv_keep, o[dt][1] / sum * t.inv_keep, o[dt][2] / sum * t.inv_keep,
+                                    o[dt][3] / sum * t.inv_keep);
+                else
+                    *reinterpret_cast<float4 *>(op + 16 * dt) =
+                        make_float4(o[dt][0] / sum, o[dt][1] / sum, o[dt][2] / sum, o[dt][3] / sum);
+            }
         }
     }
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void t5_attention_kernel(AttArgs a) {
+    att_body<MT, false>(a, AttTrain{});
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void t5_attention_train_kernel(AttArgs a, AttTrain t) {
+    att_body<MT, true>(a, t);
 }
 
 size_t att_lds_bytes(int Tq, int Tk, bool bias) {
@@ -193,6 +251,394 @@ int launch_att(const AttArgs &a, long long groups, int threads, size_t lds, hipS
     hipLaunchKernelGGL(t5_attention_kernel<MT>, dim3((unsigned)(groups * a.H)), dim3(threads), lds, s, a);
     RQ_CHECK_LAUNCH("t5_attention_kernel");
     return RQHIP_OK;
+}
+
+
+template <int MT>
+int launch_att_train(const AttArgs &a, const AttTrain &t, long long groups, int threads, size_t lds, hipStream_t s) {
+    if (lds > 64 * 1024) {
+        static LdsGrant grant;
+        RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_attention_train_kernel<MT>),
+                                      (int)att_lds_bytes(kAttMaxT, MT * 16 < kAttMaxT ? MT * 16 : kAttMaxT, true)));
+    }
+    hipLaunchKernelGGL(t5_attention_train_kernel<MT>, dim3((unsigned)(groups * a.H)), dim3(threads), lds, s, a, t);
+    RQ_CHECK_LAUNCH("t5_attention_train_kernel");
+    return RQHIP_OK;
+}
+
+// ---- backward
+//
+// One workgroup per (row, head), two passes over one LDS buffer; P is recomputed, nothing of size Tq x Tk is stored.
+//   pass 1, query-major: K and V staged as in the forward; a wave takes sixteen queries, recomputes their scores, row
+//     max and row sum exactly as the forward did (the bits of its P), then
+//       dP^T = V dO^T (o M / (1 - p)), D_i = sum_j P_ij dP_ij (= dO_i . O_i), dS = P o (dP - D), dQ^T += K^T dS^T
+//     in the forward's register layout (lane (g, i) holds keys 16 mt + 4 g + r of query i), and leaves max, sum and D
+//     of its queries in LDS.
+//   pass 2, key-major: Q and dO staged in the same buffer; a wave takes sixteen keys (K and V rows in registers) and
+//     loops over the query tiles, S = Q K^T and dP = dO V^T now with lane (g, c) holding queries 16 qt + 4 g + r of key
+//     c, and accumulates dK^T += Q^T dS, dV^T += dO^T (P o M / (1 - p)) in registers.
+//   bias gradient: the sums of dS along the diagonals j - i.  Pass 1 puts each 16 x 16 tile of dS through a per-wave LDS
+//     scratch, lane d < 31 adds diagonal d - 15 (queries ascending) into the wave's own [Tq + Tk - 1] row; the waves'
+//     rows are added in wave order into d_bias_partial[(r, h)], and t5_dbias_reduce_kernel adds the rows r in order.
+// The row's normaliser comes from pass 1, not from lse: max + log(sum) rounds log(sum) away when every key of a row is
+// masked (max = -FLT_MAX), and that row's P must still be uniform.  Nor is `out` read: D comes from P and dP (above).
+struct AttBwdArgs {
+    const float *q, *k, *v, *d_out;
+    float *dq, *dk, *dv, *dbias_part;
+    long long ld_q, ld_kv, ld_do;
+    int H, Tq, Tk, causal;
+    const float *bias;
+    int bias_base;
+    const unsigned char *key_mask;
+    const long long *seed;
+    unsigned thresh;
+    float inv_keep;
+};
+
+constexpr int kAttTileLd = 17;  // row stride of the per-wave 16 x 16 dS scratch
+
+struct AttBwdLds {
+    size_t big, madd, bias, mx, sum, dd, dbw, tile, total;  // offsets in floats
+};
+
+__host__ __device__ inline AttBwdLds att_bwd_lds(int Tq, int Tk, bool bias, int nw) {
+    const size_t Tqp = (size_t)((Tq + 15) / 16) * 16, Tkp = (size_t)((Tk + 15) / 16) * 16;
+    const size_t Tp = Tqp > Tkp ? Tqp : Tkp, nb = bias ? (size_t)(Tq + Tk - 1) : 0;
+    AttBwdLds l;
+    l.big = 0;
+    l.madd = 2 * Tp * kAttLd;
+    l.bias = l.madd + Tkp;
+    l.mx = l.bias + nb;
+    l.sum = l.mx + Tqp;
+    l.dd = l.sum + Tqp;
+    l.dbw = l.dd + Tqp;
+    l.tile = l.dbw + (size_t)nw * nb;
+    l.total = l.tile + (bias ? (size_t)nw * 16 * kAttTileLd : 0);
+    return l;
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
+    extern __shared__ float att_lds[];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int nw = nthr / RQ_WAVE, wave = tid / RQ_WAVE, lane = tid & (RQ_WAVE - 1);
+    const int i = lane & 15, g = lane >> 4;
+    const int ntiles = (a.Tk + 15) >> 4, Tkp = ntiles << 4, Tqp = ((a.Tq + 15) >> 4) << 4;
+    const int Tp = Tqp > Tkp ? Tqp : Tkp, nb = a.bias ? a.Tq + a.Tk - 1 : 0;
+    const AttBwdLds L = att_bwd_lds(a.Tq, a.Tk, a.bias != nullptr, nw);
+    float *Ks = att_lds, *Vs = Ks + (size_t)Tp * kAttLd;  // pass 2: Q and dO
+    float *madd = att_lds + L.madd, *bias_s = att_lds + L.bias;
+    float *mx_s = att_lds + L.mx, *sum_s = att_lds + L.sum, *dd_s = att_lds + L.dd;
+    float *dbw = att_lds + L.dbw + (size_t)wave * nb, *tile = att_lds + L.tile + (size_t)wave * 16 * kAttTileLd;
+
+    const long long b = blockIdx.x / a.H;
+    const int h = blockIdx.x - (int)b * a.H;
+    const unsigned long long seed = a.thresh ? (unsigned long long)*a.seed : 0ull;
+    const unsigned long long idx0 = ((unsigned long long)b * a.H + h) * (unsigned long long)a.Tq;  // + i, then * Tk + j
+
+    // ---- pass 1: stage K, V (zeros beyond Tk), the key mask, the head's bias column; clear the waves' bias rows
+    for (int idx = tid; idx < Tkp * 16; idx += nthr) {
+        const int j = idx >> 4, c = idx & 15;
+        float4 kk = make_float4(0.f, 0.f, 0.f, 0.f), vv = kk;
+        if (j < a.Tk) {
+            const size_t off = (size_t)(b * a.Tk + j) * (size_t)a.ld_kv + (size_t)h * kAttD + 4 * c;
+            kk = *reinterpret_cast<const float4 *>(a.k + off);
+            vv = *reinterpret_cast<const float4 *>(a.v + off);
+        }
+        *reinterpret_cast<float4 *>(Ks + j * kAttLd + 4 * c) = kk;
+        *reinterpret_cast<float4 *>(Vs + j * kAttLd + 4 * c) = vv;
+    }
+    for (int j = tid; j < Tkp; j += nthr)
+        madd[j] = j >= a.Tk ? -INFINITY : ((a.key_mask && !a.key_mask[b * a.Tk + j]) ? -FLT_MAX : 0.f);
+    for (int x = tid; x < nb; x += nthr) bias_s[x] = a.bias[(size_t)(a.bias_base + x) * a.H + h];
+    for (int x = tid; x < nw * nb; x += nthr) att_lds[L.dbw + x] = 0.f;
+    __syncthreads();
+
+    for (int qt = wave; qt * 16 < a.Tq; qt += nw) {
+        const int m = qt * 16 + i;
+        const int ti = m < a.Tq ? m : a.Tq - 1;  // lanes past the last query recompute it and contribute nothing
+        const size_t qrow = (size_t)b * (size_t)a.Tq + (size_t)ti;
+        const float *qp = a.q + qrow * (size_t)a.ld_q + (size_t)h * kAttD + g;
+        const float *dop = a.d_out + qrow * (size_t)a.ld_do + (size_t)h * kAttD + g;
+        float qreg[16], doreg[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) qreg[e] = qp[4 * e], doreg[e] = dop[4 * e];
+
+        // ---- scores, bias, masks, row max and row sum: the forward's sequence
+        f32x4 s[MT];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            s[mt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            if (mt < ntiles) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                const float *kp = Ks + (16 * mt + i) * kAttLd + g;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kp[4 * e], qreg[e], acc, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int j = 16 * mt + 4 * g + r;
+                    const float ma = madd[j];
+                    float sc = acc[r];
+                    if (ma == -INFINITY) {
+                        sc = -INFINITY;
+                    } else {
+                        if (a.bias) sc = sc + bias_s[j - ti + a.Tq - 1];
+                        if (ma != 0.f || (a.causal && j > ti)) sc = sc + -FLT_MAX;
+                    }
+                    s[mt][r] = sc;
+                    mx = fmaxf(mx, sc);
+                }
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, RQ_WAVE));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, RQ_WAVE));
+        float sum = 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            if (mt < ntiles) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = expf(s[mt][r] - mx);
+                    s[mt][r] = p;
+                    sum = sum + p;
+                }
+            }
+        }
+        sum = sum + __shfl_xor(sum, 16, RQ_WAVE);
+        sum = sum + __shfl_xor(sum, 32, RQ_WAVE);
+
+        // ---- dP = (dO V^T) o M / (1 - p) of the whole row, and D = sum_j P dP (the lane's keys in order, then the four
+        // lanes of the query).  D is dO . O, evaluated from the dP that dS subtracts it from: the rounding of the 64-term
+        // products then cancels in dP - D as it does in the operators' softmax backward, and a row with one live key
+        // (P = 1, the others exactly 0) has D = dP and dS = 0 exactly.
+        f32x4 dp[MT];
+        float D = 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            dp[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (mt < ntiles) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                const float *vp = Vs + (16 * mt + i) * kAttLd + g;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[4 * e], doreg[e], acc, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float d = acc[r];
+                    if (a.thresh)
+                        d = att_keep(seed, (idx0 + ti) * a.Tk + (16 * mt + 4 * g + r), a.thresh) ? d * a.inv_keep : 0.f;
+                    const float p = s[mt][r] / sum;
+                    s[mt][r] = p;
+                    dp[mt][r] = d;
+                    D = D + p * d;
+                }
+            }
+        }
+        D = D + __shfl_xor(D, 16, RQ_WAVE);
+        D = D + __shfl_xor(D, 32, RQ_WAVE);
+        if (m < a.Tq && g == 0) mx_s[m] = mx, sum_s[m] = sum, dd_s[m] = D;
+
+        // ---- per key tile: dS, the tile's diagonal sums, dQ
+        f32x4 dq[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            if (mt < ntiles) {
+                f32x4 ds;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float d = s[mt][r] * (dp[mt][r] - D);
+                    ds[r] = m < a.Tq ? d : 0.f;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float *kp = Ks + (16 * mt + 4 * g + r) * kAttLd + i;
+#pragma unroll
+                    for (int dt = 0; dt < 4; ++dt)
+                        dq[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kp[16 * dt], ds[r], dq[dt], 0, 0, 0);
+                }
+                if (a.bias) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) tile[i * kAttTileLd + 4 * g + r] = ds[r];
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the scratch and the row are this wave's only
+                    if (lane < 31) {
+                        const int dl = lane - 15;  // key - query inside the tile
+                        const int lo = dl < 0 ? -dl : 0, hi = dl > 0 ? 15 - dl : 15;
+                        float acc1 = 0.f;
+                        for (int ii = lo; ii <= hi; ++ii) acc1 = acc1 + tile[ii * kAttTileLd + ii + dl];
+                        const int x = 16 * (mt - qt) + dl + a.Tq - 1;
+                        if (x >= 0 && x < nb) dbw[x] = dbw[x] + acc1;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                }
+            }
+        }
+        if (m < a.Tq) {
+            float *dqp = a.dq + qrow * (size_t)a.H * kAttD + (size_t)h * kAttD + 4 * g;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                *reinterpret_cast<float4 *>(dqp + 16 * dt) = make_float4(dq[dt][0], dq[dt][1], dq[dt][2], dq[dt][3]);
+        }
+    }
+    __syncthreads();
+
+    // ---- the waves' bias rows in wave order; then Q and dO take the place of K and V (zeros beyond Tq)
+    for (int x = tid; x < nb; x += nthr) {
+        float acc1 = att_lds[L.dbw + x];
+        for (int w = 1; w < nw; ++w) acc1 = acc1 + att_lds[L.dbw + (size_t)w * nb + x];
+        a.dbias_part[(size_t)blockIdx.x * nb + x] = acc1;
+    }
+    float *Qs = Ks, *dOs = Vs;
+    for (int idx = tid; idx < Tqp * 16; idx += nthr) {
+        const int ii = idx >> 4, c = idx & 15;
+        float4 qq = make_float4(0.f, 0.f, 0.f, 0.f), dd = qq;
+        if (ii < a.Tq) {
+            const size_t row = (size_t)b * (size_t)a.Tq + (size_t)ii;
+            qq = *reinterpret_cast<const float4 *>(a.q + row * (size_t)a.ld_q + (size_t)h * kAttD + 4 * c);
+            dd = *reinterpret_cast<const float4 *>(a.d_out + row * (size_t)a.ld_do + (size_t)h * kAttD + 4 * c);
+        }
+        *reinterpret_cast<float4 *>(Qs + ii * kAttLd + 4 * c) = qq;
+        *reinterpret_cast<float4 *>(dOs + ii * kAttLd + 4 * c) = dd;
+    }
+    __syncthreads();
+
+    // ---- pass 2: lane (g, c) owns key 16 kt + c and, per query tile, queries 16 qt + 4 g + r
+    for (int kt = wave; kt * 16 < a.Tk; kt += nw) {
+        const int j = kt * 16 + i;
+        const int jc = j < a.Tk ? j : a.Tk - 1;
+        const size_t krow = (size_t)b * (size_t)a.Tk + (size_t)jc;
+        const float *kp = a.k + krow * (size_t)a.ld_kv + (size_t)h * kAttD + g;
+        const float *vp = a.v + krow * (size_t)a.ld_kv + (size_t)h * kAttD + g;
+        float kreg[16], vreg[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) kreg[e] = kp[4 * e], vreg[e] = vp[4 * e];
+        const float ma = madd[kt * 16 + i];
+        f32x4 dk[4], dv[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int qt = 0; qt * 16 < a.Tq; ++qt) {
+            f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, pacc = sacc;
+            const float *qs = Qs + (16 * qt + i) * kAttLd + g, *dos = dOs + (16 * qt + i) * kAttLd + g;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(qs[4 * e], kreg[e], sacc, 0, 0, 0);
+                pacc = __builtin_amdgcn_mfma_f32_16x16x4f32(dos[4 * e], vreg[e], pacc, 0, 0, 0);
+            }
+            f32x4 ds, pd;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int qi = 16 * qt + 4 * g + r;
+                const int ti = qi < a.Tq ? qi : a.Tq - 1;
+                float sc = sacc[r];
+                if (a.bias) sc = sc + bias_s[jc - ti + a.Tq - 1];
+                if (ma != 0.f || (a.causal && j > ti)) sc = sc + -FLT_MAX;
+                float p = expf(sc - mx_s[ti]) / sum_s[ti];
+                if (qi >= a.Tq || j >= a.Tk) p = 0.f;
+                float dp = pacc[r], pk = p;
+                if (a.thresh) {
+                    const bool keep = att_keep(seed, (idx0 + ti) * a.Tk + jc, a.thresh);
+                    dp = keep ? dp * a.inv_keep : 0.f;
+                    pk = keep ? p * a.inv_keep : 0.f;
+                }
+                ds[r] = p * (dp - dd_s[ti]);
+                pd[r] = pk;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float *q2 = Qs + (16 * qt + 4 * g + r) * kAttLd + i, *do2 = dOs + (16 * qt + 4 * g + r) * kAttLd + i;
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) {
+                    dk[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(q2[16 * dt], ds[r], dk[dt], 0, 0, 0);
+                    dv[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(do2[16 * dt], pd[r], dv[dt], 0, 0, 0);
+                }
+            }
+        }
+        if (j < a.Tk) {
+            const size_t off = krow * (size_t)a.H * kAttD + (size_t)h * kAttD + 4 * g;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                *reinterpret_cast<float4 *>(a.dk + off + 16 * dt) = make_float4(dk[dt][0], dk[dt][1], dk[dt][2], dk[dt][3]);
+                *reinterpret_cast<float4 *>(a.dv + off + 16 * dt) = make_float4(dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]);
+            }
+        }
+    }
+}
+
+// d_bias[row, h] = sum over the rows r, ascending, of part[(r, h)][row - base]; zero outside the call's delta range.
+__global__ __launch_bounds__(256) void t5_dbias_reduce_kernel(const float *part, long long R, int H, int nb, int base,
+                                                              int n_delta, float *out) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)n_delta * H) return;
+    const int row = (int)(idx / H), h = (int)(idx - (long long)row * H);
+    float acc = 0.f;
+    if (row >= base && row < base + nb)
+        for (long long r = 0; r < R; ++r) acc = acc + part[((size_t)r * H + h) * (size_t)nb + (row - base)];
+    out[idx] = acc;
+}
+
+template <int MT>
+int launch_att_bwd(const AttBwdArgs &a, long long R, int threads, size_t lds, hipStream_t s) {
+    if (lds > 64 * 1024) {
+        static LdsGrant grant;
+        const int t = MT * 16 < kAttMaxT ? MT * 16 : kAttMaxT;
+        RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_attention_bwd_kernel<MT>),
+                                      (int)(att_bwd_lds(kAttMaxT, t, true, 4).total * sizeof(float))));
+    }
+    hipLaunchKernelGGL(t5_attention_bwd_kernel<MT>, dim3((unsigned)(R * a.H)), dim3(threads), lds, s, a);
+    RQ_CHECK_LAUNCH("t5_attention_bwd_kernel");
+    return RQHIP_OK;
+}
+
+// The checks the training pair shares; `who` names the entry point in the message.
+int check_train_call(const char *who, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, bool strides_ok,
+                     const float *bias, int n_delta, int bias_offset, int causal, double p) {
+    if (R < 0 || Rk < 0 || H < 1 || d_kv < 1 || Tq < 1 || Tk < 1) {
+        set_error("%s: bad sizes (R=%lld, Rk=%lld, H=%d, d_kv=%d, Tq=%d, Tk=%d)", who, (long long)R, (long long)Rk, H,
+                  d_kv, Tq, Tk);
+        return RQHIP_EARG;
+    }
+    if (d_kv != kAttD) {
+        set_error("%s: d_kv=%d, only d_kv = %d is implemented", who, d_kv, kAttD);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (Tq > kAttMaxT || Tk > kAttMaxT) {
+        set_error("%s: Tq=%d / Tk=%d exceed Tq, Tk <= %d", who, Tq, Tk, kAttMaxT);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (Rk != R) {
+        set_error("%s: R=%lld query rows over Rk=%lld K/V rows: the training pair takes one K/V per row (Rk = R)", who,
+                  (long long)R, (long long)Rk);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (!strides_ok) {
+        set_error("%s: row strides must be multiples of 4 and >= H * 64 = %lld", who, (long long)H * kAttD);
+        return RQHIP_EARG;
+    }
+    if (Tq > Tk && (causal || bias)) {
+        set_error("%s: Tq = %d exceeds Tk = %d", who, Tq, Tk);
+        return RQHIP_EARG;
+    }
+    const int bias_base = bias_offset - (Tq - 1);
+    if (bias && (bias_base < 0 || (int64_t)bias_base + Tq + Tk - 1 > n_delta)) {
+        set_error("%s: the bias table (n_delta=%d, offset=%d) does not cover deltas %d .. %d", who, n_delta, bias_offset,
+                  -(Tq - 1), Tk - 1);
+        return RQHIP_EARG;
+    }
+    if (!(p >= 0.0 && p < 1.0)) {
+        set_error("%s: dropout probability p=%g outside 0 <= p < 1", who, p);
+        return RQHIP_EARG;
+    }
+    if (R * (int64_t)H >= (1ll << 31)) {
+        set_error("%s: R * H = %lld exceeds one workgroup per (row, head) (< 2^31)", who, (long long)(R * (int64_t)H));
+        return RQHIP_EUNSUPPORTED;
+    }
+    return RQHIP_OK;
+}
+
+unsigned dropout_threshold(double p) {
+    const double t = nearbyint(p * 4294967296.0);
+    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
 }
 
 }  // namespace
@@ -284,4 +730,101 @@ extern "C" int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, 
     if (ntiles == 1) return launch_att<1>(a, Rk, RQ_WAVE, lds, s);
     if (ntiles <= 6) return launch_att<6>(a, Rk, 4 * RQ_WAVE, lds, s);
     return launch_att<16>(a, Rk, 4 * RQ_WAVE, lds, s);
+}
+
+extern "C" int rqhip_t5_attention_bwd_supported(int d_kv, int H, int Tq, int Tk) {
+    return d_kv == kAttD && H >= 1 && Tq >= 1 && Tq <= kAttMaxT && Tk >= 1 && Tk <= kAttMaxT;
+}
+
+extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                            int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
+                                            const float *bias_by_delta, int n_delta, int bias_offset,
+                                            const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *out,
+                                            int64_t ld_out, float *lse, rqhip_stream_t stream) {
+    const int64_t inner = (int64_t)H * kAttD;
+    const bool strides = ld_q >= inner && ld_kv >= inner && ld_out >= inner && (ld_q | ld_kv | ld_out) % 4 == 0;
+    const int rc = check_train_call("t5_attention_fwd_train", R, Rk, H, d_kv, Tq, Tk, strides, bias_by_delta, n_delta,
+                                    bias_offset, causal, p);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0) return RQHIP_OK;
+    const unsigned thresh = dropout_threshold(p);
+    if (!q || !k || !v || !out || !lse || (thresh && !seed)) {
+        set_error("t5_attention_fwd_train: null pointer (q, k, v, out, lse; seed when p > 0)");
+        return RQHIP_EARG;
+    }
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) {
+        set_error("t5_attention_fwd_train: q, k, v and out must be 16-byte aligned");
+        return RQHIP_EARG;
+    }
+    AttArgs a;
+    a.q = q, a.k = k, a.v = v, a.out = out;
+    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
+    a.beams = 1, a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = 0, a.causal = causal != 0;
+    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
+    a.key_mask = key_mask;
+    a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
+    AttTrain t;
+    t.lse = lse, t.seed = reinterpret_cast<const long long *>(seed), t.thresh = thresh;
+    t.inv_keep = 1.0f / (1.0f - (float)p);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
+    const int ntiles = (Tk + 15) / 16;  // the inference entry point's plan
+    if (ntiles == 1) return launch_att_train<1>(a, t, R, RQ_WAVE, lds, s);
+    if (ntiles <= 6) return launch_att_train<6>(a, t, R, 4 * RQ_WAVE, lds, s);
+    return launch_att_train<16>(a, t, R, 4 * RQ_WAVE, lds, s);
+}
+
+extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                      const float *out, int64_t ld_out, const float *lse, const float *d_out,
+                                      int64_t ld_do, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
+                                      const float *bias_by_delta, int n_delta, int bias_offset, const uint8_t *key_mask,
+                                      int causal, double p, const int64_t *seed, float *d_q, float *d_k, float *d_v,
+                                      float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream) {
+    const int64_t inner = (int64_t)H * kAttD;
+    const bool strides = ld_q >= inner && ld_kv >= inner && ld_out >= inner && ld_do >= inner &&
+                         (ld_q | ld_kv | ld_out | ld_do) % 4 == 0;
+    const int rc = check_train_call("t5_attention_bwd", R, Rk, H, d_kv, Tq, Tk, strides, bias_by_delta, n_delta,
+                                    bias_offset, causal, p);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0 && !bias_by_delta) return RQHIP_OK;
+    const unsigned thresh = dropout_threshold(p);
+    if (!q || !k || !v || !out || !lse || !d_out || !d_q || !d_k || !d_v || (thresh && !seed) ||
+        (bias_by_delta && (!d_bias_by_delta || !d_bias_partial))) {
+        set_error("t5_attention_bwd: null pointer (q, k, v, out, lse, d_out, d_q, d_k, d_v; seed when p > 0; "
+                  "d_bias_by_delta and d_bias_partial with a bias table)");
+        return RQHIP_EARG;
+    }
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(d_out) || !aligned16(d_q) ||
+        !aligned16(d_k) || !aligned16(d_v)) {
+        set_error("t5_attention_bwd: q, k, v, out, d_out, d_q, d_k and d_v must be 16-byte aligned");
+        return RQHIP_EARG;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nb = Tq + Tk - 1;
+    if (R > 0) {
+        AttBwdArgs a;
+        a.q = q, a.k = k, a.v = v, a.d_out = d_out;
+        a.dq = d_q, a.dk = d_k, a.dv = d_v, a.dbias_part = d_bias_partial;
+        a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_do = ld_do;
+        a.H = H, a.Tq = Tq, a.Tk = Tk, a.causal = causal != 0;
+        a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
+        a.key_mask = key_mask;
+        a.seed = reinterpret_cast<const long long *>(seed), a.thresh = thresh;
+        a.inv_keep = 1.0f / (1.0f - (float)p);
+        const int ntiles = (Tk + 15) / 16;
+        const int threads = (Tq <= 16 && Tk <= 16) ? RQ_WAVE : 4 * RQ_WAVE;
+        const size_t lds = att_bwd_lds(Tq, Tk, bias_by_delta != nullptr, threads / RQ_WAVE).total * sizeof(float);
+        int lrc;
+        if (ntiles == 1) lrc = launch_att_bwd<1>(a, R, threads, lds, s);
+        else if (ntiles <= 6) lrc = launch_att_bwd<6>(a, R, threads, lds, s);
+        else lrc = launch_att_bwd<16>(a, R, threads, lds, s);
+        if (lrc != RQHIP_OK) return lrc;
+    }
+    if (bias_by_delta) {
+        const long long n = (long long)n_delta * H;
+        hipLaunchKernelGGL(t5_dbias_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_bias_partial, R, H,
+                           nb, bias_offset - (Tq - 1), n_delta, d_bias_by_delta);
+        RQ_CHECK_LAUNCH("t5_dbias_reduce_kernel");
+    }
+    return RQHIP_OK;
 }

@@ -4,7 +4,8 @@ next item's ids one hierarchy level at a time.  API and state dict of the refere
 
 The T5 body runs on torch operators (modules/t5.py), or, with `model.attention_impl = "hip"` (a plain attribute, default
 "torch"; inference only, see modules/t5.py), with every attention call as one HIP launch (ops.t5_attention) and the
-decoder's self-attention history of `generate` in per-position slabs that are never copied.
+decoder's self-attention history of `generate` in per-position slabs that are never copied.  "hip_train" is "hip" that
+also runs under grad: every attention of a training step is then one fused forward and one fused backward launch.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
@@ -87,7 +88,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
         self._prefix_index: Optional[SemIdPrefixIndex] = None
         self._prefix_key = None
-        self.attention_impl = "torch"  # or "hip"; handed to both T5 stacks whenever they are run
+        self.attention_impl = "torch"  # or "hip" / "hip_train"; handed to both T5 stacks whenever they are run
 
     @property
     def device(self) -> torch.device:

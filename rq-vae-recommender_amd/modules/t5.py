@@ -25,6 +25,14 @@ tensors with grad disabled, dropout inactive (eval mode), no operator-format cac
 supports; otherwise the operators run, silently.  The incremental decoder of the "hip" path keeps its self-attention
 K/V in per-position slabs (`T5DecodeCache`) that are written once and never copied: a beam search reorders an int32
 ancestor table instead of the cache.
+
+"hip_train" is "hip" under no_grad (the same launches, decode cache included) and, with grad enabled, makes every
+attention of a stack forward one autograd.T5AttentionFunction call: a forward launch that keeps the row log-sum-exp
+instead of the weights, and one backward launch that recomputes them.  In train mode with dropout_rate > 0 the
+attention-weight dropout happens in the kernel, from a seed drawn per call on the device with torch.randint (the
+default generator: torch.manual_seed reproduces a run); every other dropout stays torch's.  It needs fp32 device
+tensors, one K/V per query row (beams = 1), no operator-format cache and a shape the backward supports; otherwise the
+operators run, silently.  A decode_cache under grad raises.
 """
 import math
 from typing import List, Optional, Tuple
@@ -35,9 +43,10 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops
+from rqhip.autograd import T5AttentionFunction
 
 KV = Tuple[Tensor, Tensor]
-ATTENTION_IMPLS = ("torch", "hip")
+ATTENTION_IMPLS = ("torch", "hip", "hip_train")
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -122,7 +131,12 @@ def advance_ancestors(anc: Tensor, parent: Tensor, pos: int) -> Tensor:
 
 class _HipPlan:
     """What a stack forward on the "hip" path computes once for all its blocks."""
-    __slots__ = ("table", "offset", "key_mask", "causal", "past", "cross_mask", "cache")
+    __slots__ = ("table", "offset", "key_mask", "causal", "past", "cross_mask", "cache", "train", "p")
+
+
+def _draw_seed(p: float, device) -> Optional[Tensor]:
+    """The dropout seed of one fused attention call: one int64 drawn on the device, never read by the host."""
+    return torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=device) if p > 0 else None
 
 
 def _attend(module: nn.Module, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], mask: Optional[Tensor]) -> Tensor:
@@ -215,6 +229,11 @@ class T5Attention(nn.Module):
         """self_attention as one launch; with plan.cache the K/V projections go straight into their slabs."""
         R = x.shape[0]
         q = self.q(x)
+        if plan.train:
+            k, v = self.k(x), self.v(x)
+            out = T5AttentionFunction.apply(q, k, v, plan.table, self.n_heads, plan.offset, plan.key_mask, plan.causal,
+                                            plan.p, _draw_seed(plan.p, x.device))
+            return self.o(out), (self._heads(k), self._heads(v))
         if plan.cache is None:
             k, v = self.k(x), self.v(x)
             out = ops.t5_attention(q, k, v, self.n_heads, bias_by_delta=plan.table, bias_offset=plan.offset,
@@ -232,6 +251,9 @@ class T5Attention(nn.Module):
     def cross_attention_hip(self, x: Tensor, kv: KV, plan: _HipPlan) -> Tensor:
         """cross_attention as one launch: the beams of a user are the query rows of one K/V group."""
         k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in kv)  # a view of the Linear's output
+        if plan.train:
+            return self.o(T5AttentionFunction.apply(self.q(x), k, v, None, self.n_heads, 0, plan.cross_mask, False, plan.p,
+                                                    _draw_seed(plan.p, x.device)))
         return self.o(ops.t5_attention(self.q(x), k, v, self.n_heads, key_mask=plan.cross_mask))
 
 
@@ -307,7 +329,7 @@ class T5Stack(nn.Module):
                                     for i in range(config.num_layers)])
         self.final_layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
-        self.attention_impl = "torch"  # or "hip": see the module docstring
+        self.attention_impl = "torch"  # or "hip" / "hip_train": see the module docstring
         init_t5_weights(self, config)
 
     def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
@@ -319,7 +341,7 @@ class T5Stack(nn.Module):
         """Whether a forward of x with these lengths takes the "hip" path (module docstring)."""
         if self.attention_impl not in ATTENTION_IMPLS:
             raise ValueError(f"attention_impl must be one of {ATTENTION_IMPLS}, got {self.attention_impl!r}")
-        if self.attention_impl != "hip" or not x.is_cuda or torch.is_grad_enabled():
+        if self.attention_impl not in ("hip", "hip_train") or not x.is_cuda or torch.is_grad_enabled():
             return False
         if self.training and self.config.dropout_rate > 0:
             return False
@@ -329,13 +351,29 @@ class T5Stack(nn.Module):
             ok = ops.t5_attention_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, cross_length)
         return ok
 
+    def hip_train_active(self, x: Tensor, query_length: int, cross_kv: Optional[List[KV]]) -> bool:
+        """Whether a forward of x under grad takes the "hip_train" path (module docstring)."""
+        if self.attention_impl != "hip_train" or not x.is_cuda or not torch.is_grad_enabled():
+            return False
+        cfg = self.config
+        ok = ops.t5_attention_bwd_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, query_length)
+        if ok and self.is_decoder:
+            ck = cross_kv[0][0]
+            ok = ck.shape[0] == x.shape[0] and ck.dtype == x.dtype and ops.t5_attention_bwd_supported(
+                x.dtype, cfg.d_kv, cfg.num_heads, query_length, ck.shape[2])
+        return ok
+
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
-    def _forward_hip(self, inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache, decode_cache):
-        """forward on the "hip" path: the bias table and the byte masks are built once, every attention is one launch."""
+    def _forward_hip(self, inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache, decode_cache,
+                     train=False):
+        """forward on the "hip" path: the bias table and the byte masks are built once, every attention is one launch
+        (`train`: one T5AttentionFunction call, with the attention-weight dropout of train mode in the kernel)."""
         T = inputs_embeds.shape[1]
         plan = _HipPlan()
+        plan.train = train
+        plan.p = float(self.config.dropout_rate) if train and self.training else 0.0
         plan.cache = decode_cache
         plan.past = 0 if decode_cache is None else decode_cache.pos
         plan.table, plan.offset = self.block[0].layer[0].SelfAttention.delta_table(T, plan.past + T, plan.past)
@@ -367,6 +405,9 @@ class T5Stack(nn.Module):
             if self.is_decoder and cross_kv is None:
                 cross_kv = self.cross_kv(encoder_hidden_states)
             past = 0 if decode_cache is None else decode_cache.pos
+            if decode_cache is None and self.hip_train_active(inputs_embeds, T, cross_kv):
+                return self._forward_hip(inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache, None,
+                                         train=True)
             if self.hip_attention_active(inputs_embeds, T, past + T, cross_kv[0][0].shape[2] if self.is_decoder else None):
                 if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
                                                  or past >= decode_cache.steps or R > decode_cache.rows):

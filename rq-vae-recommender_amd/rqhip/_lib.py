@@ -101,6 +101,11 @@ SIGNATURES = {
     "rqhip_t5_attention_supported": (_int, [_int, _int, _int, _int]),
     "rqhip_t5_attention": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _int, _int, _vp, _int,
                                   _int, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "rqhip_t5_attention_bwd_supported": (_int, [_int, _int, _int, _int]),
+    "rqhip_t5_attention_fwd_train": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _int, _int,
+                                            _vp, _int, C.c_double, _vp, _vp, _i64, _vp, _vp]),
+    "rqhip_t5_attention_bwd": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int,
+                                      _int, _vp, _int, _int, _vp, _int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rqhip_recon_loss_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp]),
     "rqhip_recon_loss_backward": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
     "rqhip_recon_loss_forward_spec": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _f32, _vp, _vp, _vp]),

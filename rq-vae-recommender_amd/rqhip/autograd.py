@@ -270,3 +270,28 @@ class LossMeansFunction(torch.autograd.Function):
             rows, _ = ops.loss_means_backward(g_loss, None, None, ctx.n, True, False)
             return rows, rows       # the usual case (only `loss` is backpropagated): one vector serves both inputs
         return ops.loss_means_backward(g_loss, g_rmean, g_qmean, ctx.n, need_r, need_q)
+
+
+class T5AttentionFunction(torch.autograd.Function):
+    """One T5 attention call (modules/t5.py:_attend with its head transposes) as one launch forward and one attention
+    launch backward (ops.t5_attention_fwd_train / ops.t5_attention_bwd): q [R, Tq, heads * 64], k / v [R, Tk, heads * 64],
+    the relative-position bias as a table by j - i.  The weights are recomputed in the backward, the dropout decisions
+    (p > 0, `seed`: a one-element int64 device tensor) too; only q, k, v, out and the row log-sum-exp are saved.
+    Gradients: q, k, v and the table (whose own graph leads to relative_attention_bias.weight)."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, bias_by_delta: Optional[Tensor], n_heads: int, bias_offset: int,
+                key_mask: Optional[Tensor], causal: bool, p: float, seed: Optional[Tensor]):
+        out, lse = ops.t5_attention_fwd_train(q, k, v, n_heads, bias_by_delta=bias_by_delta, bias_offset=bias_offset,
+                                              key_mask=key_mask, causal=causal, p=p, seed=seed)
+        ctx.save_for_backward(q, k, v, out, lse, bias_by_delta, key_mask, seed)
+        ctx.call = (n_heads, bias_offset, causal, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        q, k, v, out, lse, table, mask, seed = ctx.saved_tensors
+        n_heads, bias_offset, causal, p = ctx.call
+        dq, dk, dv, dtable = ops.t5_attention_bwd(q, k, v, out, lse, d_out, n_heads, bias_by_delta=table,
+                                                  bias_offset=bias_offset, key_mask=mask, causal=causal, p=p, seed=seed)
+        return dq, dk, dv, dtable, None, None, None, None, None, None

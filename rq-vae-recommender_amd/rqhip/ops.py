@@ -610,6 +610,125 @@ def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta
     return out
 
 
+def t5_attention_bwd_supported(dtype: torch.dtype, d_kv: int, n_heads: int, Tq: int, Tk: int) -> bool:
+    """Whether t5_attention_fwd_train / t5_attention_bwd implement this shape (rqhip_t5_attention_bwd_supported): fp32,
+    d_kv = 64, Tq and Tk <= 256."""
+    return dtype == torch.float32 and bool(
+        _lib.lib().rqhip_t5_attention_bwd_supported(int(d_kv), int(n_heads), int(Tq), int(Tk)))
+
+
+_M32 = 0xFFFFFFFF
+
+
+def _fmix32(h: Tensor) -> Tensor:
+    """murmur3's 32-bit finaliser on int64 tensors holding values below 2^32 (products wrap; their low 32 bits hold)."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def t5_attention_dropout_keep(seed, R: int, H: int, Tq: int, Tk: int, p: float) -> Tensor:
+    """The kernels' dropout decision as a bool [R, H, Tq, Tk] (True = kept), in torch integer operations on the seed's
+    device (`seed`: an int or a one-element int64 tensor, host or device).  Element x = ((r * H + h) * Tq + i) * Tk + j is
+    kept iff fmix((fmix(lo(seed) ^ lo(x)) ^ hi(seed) ^ hi(x) * 0x85EBCA6B) + 0x9E3779B9) >= round(p * 2^32)
+    (include/rqhip.h)."""
+    if not 0.0 <= p < 1.0:
+        raise RqHipError(f"t5_attention_dropout_keep: p={p} outside 0 <= p < 1")
+    if not isinstance(seed, Tensor):
+        seed = torch.tensor(int(seed), dtype=torch.int64)
+    seed = seed.reshape(()).to(torch.int64)
+    x = torch.arange(R * H * Tq * Tk, dtype=torch.int64, device=seed.device)
+    h = _fmix32((seed & _M32) ^ (x & _M32))
+    h = _fmix32(((h ^ ((seed >> 32) & _M32) ^ ((((x >> 32) & _M32) * 0x85EBCA6B) & _M32)) + 0x9E3779B9) & _M32)
+    return (h >= min(int(round(p * 4294967296.0)), _M32)).view(R, H, Tq, Tk)
+
+
+def _train_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, bias_by_delta: Optional[Tensor],
+                key_mask: Optional[Tensor], p: float, seed: Optional[Tensor]):
+    """The checks and copies t5_attention_fwd_train and t5_attention_bwd share (t5_attention's, dense K/V)."""
+    q = _token_rows(q, "q")
+    R, Tq, inner = q.shape
+    if inner != n_heads * 64:
+        raise RqHipError(f"{who}: q has {inner} columns, not n_heads * 64 = {n_heads * 64}")
+    if k.shape != v.shape or k.shape[-1] != inner:
+        raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    k, v = _token_rows(k, "k"), _token_rows(v, "v")
+    if k.stride(1) != v.stride(1):
+        k, v = k.contiguous(), v.contiguous()
+    Rk, Tk = k.shape[0], k.shape[1]
+    if bias_by_delta is not None:
+        bias_by_delta = _f32c(bias_by_delta, "bias_by_delta")
+        if bias_by_delta.dim() != 2 or bias_by_delta.shape[1] != n_heads:
+            raise RqHipError(f"{who}: bias_by_delta must be [n_delta, {n_heads}], got {tuple(bias_by_delta.shape)}")
+    if key_mask is not None:
+        if key_mask.dtype not in (torch.bool, torch.uint8) or tuple(key_mask.shape) != (Rk, Tk):
+            raise RqHipError(f"{who}: key_mask must be bool / uint8 [{Rk}, {Tk}], got {key_mask.dtype} "
+                             f"{tuple(key_mask.shape)}")
+        key_mask = key_mask.contiguous()
+    if p > 0 and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
+        raise RqHipError(f"{who}: dropout (p={p}) needs `seed`, a one-element int64 device tensor")
+    return q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner
+
+
+def t5_attention_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
+                           bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False, p: float = 0.0,
+                           seed: Optional[Tensor] = None):
+    """t5_attention's dense form for training in one launch (rqhip_t5_attention_fwd_train) -> (out [R, Tq, n_heads * 64],
+    lse [R, n_heads, Tq]).  k, v [R, Tk, n_heads * 64]; with p > 0 the normalised weights are dropped by
+    t5_attention_dropout_keep(seed, ...) and scaled by 1 / (1 - p); `seed` is a one-element int64 device tensor the host
+    never reads.  At p = 0 `out` has the bits of t5_attention."""
+    _need_gpu(q, k, v, bias_by_delta, key_mask, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _train_args("t5_attention_fwd_train", q, k, v, n_heads,
+                                                                         bias_by_delta, key_mask, p, seed)
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
+        lse = torch.empty((R, int(n_heads), Tq), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_fwd_train(
+            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
+            _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
+            _ptr(key_mask), int(bool(causal)), float(p), _ptr(seed) if p > 0 else None, _ptr(out), inner, _ptr(lse),
+            _stream())
+        check(rc, "rqhip_t5_attention_fwd_train")
+    return out, lse
+
+
+def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, d_out: Tensor, n_heads: int, *,
+                     bias_by_delta: Optional[Tensor] = None, bias_offset: int = 0, key_mask: Optional[Tensor] = None,
+                     causal: bool = False, p: float = 0.0, seed: Optional[Tensor] = None):
+    """The gradients of t5_attention_fwd_train in one attention launch (rqhip_t5_attention_bwd) -> (dq [R, Tq, inner],
+    dk, dv [R, Tk, inner], dtable [n_delta, n_heads] or None without a bias table).  The arguments are the forward's, its
+    `out` and `lse`, and d_out [R, Tq, inner]; the weights are recomputed, the dropout decisions too."""
+    _need_gpu(q, k, v, out, lse, d_out, bias_by_delta, key_mask, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _train_args("t5_attention_bwd", q, k, v, n_heads,
+                                                                         bias_by_delta, key_mask, p, seed)
+    out, d_out = _token_rows(out, "out"), _token_rows(d_out, "d_out")
+    if out.shape != q.shape or d_out.shape != q.shape:
+        raise RqHipError(f"t5_attention_bwd: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q "
+                         f"{tuple(q.shape)}")
+    lse = _f32c(lse, "lse")
+    if tuple(lse.shape) != (R, int(n_heads), Tq):
+        raise RqHipError(f"t5_attention_bwd: lse must be [{R}, {n_heads}, {Tq}], got {tuple(lse.shape)}")
+    dev = q.device
+    with torch.cuda.device(dev):
+        dq = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
+        dk = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
+        dv = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
+        dtable = partial = None
+        if bias_by_delta is not None:
+            dtable = torch.empty_like(bias_by_delta)
+            partial = torch.empty((R * int(n_heads), Tq + Tk - 1), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_bwd(
+            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), _ptr(out), int(out.stride(1)), _ptr(lse),
+            _ptr(d_out), int(d_out.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk, _ptr(bias_by_delta),
+            0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset), _ptr(key_mask), int(bool(causal)),
+            float(p), _ptr(seed) if p > 0 else None, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dtable), _ptr(partial), _stream())
+        check(rc, "rqhip_t5_attention_bwd")
+    return dq, dk, dv, dtable
+
+
 def gumbel_matrix_path_min_rows(set_to: int = 0) -> int:
     """Query (set_to <= 0) or set the batch size from which the Gumbel level runs on the matrix instructions
     (rqhip_gumbel_matrix_path_min_rows); returns the previous value."""

@@ -1,0 +1,357 @@
+"""The trainable fused T5 attention on the GPU: ops.t5_attention_fwd_train / ops.t5_attention_bwd (csrc/t5_attention.hip)
+and autograd.T5AttentionFunction against `_attend`'s operator sequence in fp64 under torch autograd, and the retrieval
+model with attention_impl = "hip_train" against the reference's recorded values, "hip" and itself.
+
+Gate: e = max|x - x64| / max|x64| per tensor, for the kernel and for the same operator sequence in fp32 on the same
+inputs.  e_kernel <= 4 e_torch for `out` (the forward test's gate); e_kernel <= 8 e_torch for dq, dk, dv and the bias
+table's gradient (they pass through the recomputed P and through D: two more fp32 roundings than the operators' saved
+weights have).  A tensor whose fp64 reference is exactly zero must be exactly zero.  lse against fp64 logsumexp at 1e-6
+relative in the same measure (_lse_gate).  With dropout the reference multiplies the weights by keep / (1 - p), keep from
+ops.t5_attention_dropout_keep: the contract the kernels' three recomputations of the decision are held to.
+Measured ratios: profiles/retrieval_train_step.txt."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+from test_gpu_retrieval import _default_model_and_batch
+from test_gpu_t5_attention import _bias_module, _inputs, _padding
+from test_retrieval_model import CASES, build_model, check_forward, fixture_batch
+
+pytestmark = pytest.mark.gpu
+
+F32_MIN = torch.finfo(torch.float32).min   # what is ADDED to a masked score, in the fp64 reference too
+
+
+def _operators(q, k, v, H, table, offset, keep, drop, p, d_out, dtype):
+    """`_attend`'s sequence with its head transposes in `dtype` under autograd -> (out, lse, dq, dk, dv, dtable).
+    table [n_delta, H] or None (bias[h, i, j] = table[j - i + offset, h]); keep [R, 1, Tq or 1, Tk] bool or None;
+    drop [R, H, Tq, Tk] bool or None."""
+    Tq, Tk = q.shape[1], k.shape[1]
+    q, k, v = (x.detach().to(dtype).requires_grad_() for x in (q, k, v))
+    leaves = [q, k, v]
+
+    def heads(x):
+        return x.view(x.shape[0], x.shape[1], H, 64).transpose(1, 2)
+
+    scores = torch.matmul(heads(q), heads(k).transpose(-1, -2))
+    if table is not None:
+        table = table.detach().to(dtype).requires_grad_()
+        leaves.append(table)
+        i = torch.arange(Tq, device=q.device)[:, None]
+        j = torch.arange(Tk, device=q.device)[None, :]
+        scores = scores + table[(j - i) + offset].permute(2, 0, 1).unsqueeze(0)
+    if keep is not None:
+        scores = scores + (~keep).to(dtype) * F32_MIN
+    lse = torch.logsumexp(scores.detach(), dim=-1)
+    weights = torch.softmax(scores, dim=-1)
+    if drop is not None:
+        weights = weights * (drop.to(dtype) / (1 - p))
+    out = torch.matmul(weights, heads(v)).transpose(1, 2).reshape(q.shape[0], Tq, -1)
+    grads = torch.autograd.grad(out, leaves, d_out.to(dtype))
+    return (out.detach(), lse) + tuple(grads) + ((None,) if table is None else ())
+
+
+def _err(x, x64):
+    return float((x.double() - x64).abs().max() / x64.abs().max())
+
+
+def _lse_gate(name, lse, lse64):
+    """max|lse - lse64| / max|lse64| <= 1e-6, the error measure of the module docstring: a score is a 64-term fp32 dot
+    product whose error is relative to its terms, not to a sum that may cancel to nothing, so an element-wise relative
+    bound is not one fp32 can meet.  Rows with every key masked (|lse| = 3.4e38) are measured apart from the others, so
+    that their size does not hide the others' error."""
+    big = lse64.abs() > 1e30
+    for what, sel in (("masked rows", big), ("other rows", ~big)):
+        if bool(sel.any()):
+            e = float((lse.double()[sel] - lse64[sel]).abs().max() / lse64[sel].abs().max())
+            print(f"{name} lse, {what}: e_kernel {e:.3e}")
+            assert e <= 1e-6, name
+
+
+def _gate(name, got, ref32, ref64, factor):
+    if not bool(ref64.any()):
+        print(f"{name}: the fp64 reference is exactly zero")
+        assert not bool(got.any()), name
+        return
+    e_kernel, e_torch = _err(got, ref64), _err(ref32, ref64)
+    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
+    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
+    assert torch.isfinite(got).all(), name
+    assert e_kernel <= factor * e_torch, name
+
+
+def _case(name, q, k, v, H, *, table=None, offset=0, key_mask=None, causal=False, p=0.0, seed=None, seed_d_out=0,
+          masked_row=None):
+    """One shape through fwd_train and bwd: p = 0 bits of the inference kernel, every gate, the fully masked row on its
+    own, and a second run with identical bits.  Returns the kernel's tensors."""
+    from rqhip import ops
+    R, Tq, Tk = q.shape[0], q.shape[1], k.shape[1]
+    dev = q.device
+    d_out = torch.randn(R, Tq, H * 64, generator=torch.Generator().manual_seed(1000 + seed_d_out)).to(dev)
+    kw = dict(bias_by_delta=table, bias_offset=offset, key_mask=key_mask, causal=causal)
+
+    def run():
+        out, lse = ops.t5_attention_fwd_train(q, k, v, H, p=p, seed=seed, **kw)
+        return (out, lse) + tuple(ops.t5_attention_bwd(q, k, v, out, lse, d_out, H, p=p, seed=seed, **kw))
+
+    with torch.no_grad():
+        got = run()
+        if p == 0:
+            assert torch.equal(got[0].view(torch.int32), ops.t5_attention(q, k, v, H, **kw).view(torch.int32))
+    keep = None if key_mask is None else key_mask[:, None, None, :]
+    if causal:
+        tri = torch.ones(Tq, Tk, dtype=torch.bool, device=dev).tril()[None, None]
+        keep = tri if keep is None else keep & tri
+    drop = ops.t5_attention_dropout_keep(seed, R, H, Tq, Tk, p) if p > 0 else None
+    ref64 = _operators(q, k, v, H, table, offset, keep, drop, p, d_out, torch.float64)
+    ref32 = _operators(q, k, v, H, table, offset, keep, drop, p, d_out, torch.float32)
+    _lse_gate(name, got[1], ref64[1])
+    _gate(f"{name} out", got[0], ref32[0], ref64[0], 4)
+    for n, x, x32, x64 in zip(("dq", "dk", "dv", "dtable"), got[2:], ref32[2:], ref64[2:]):
+        assert (x is None) == (x64 is None)
+        if x is not None:
+            _gate(f"{name} {n}", x, x32, x64, 8)
+    if masked_row is not None and Tk > 1:     # every key masked: uniform P, dS != 0, no special case anywhere
+        assert not bool(key_mask[masked_row].any()) and bool(ref64[2][masked_row].any())
+        for n, x, x32, x64 in zip(("dq", "dk", "dv"), got[2:5], ref32[2:5], ref64[2:5]):
+            _gate(f"{name} {n} of the fully masked row", x[masked_row], x32[masked_row], x64[masked_row], 8)
+    with torch.no_grad():
+        again = run()
+    for x, y in zip(got, again):
+        assert (x is None and y is None) or torch.equal(x.view(torch.int32), y.view(torch.int32))
+    return got + (d_out,)
+
+
+def _encoder(T, H, p=0.0, seed=None):
+    R = 5
+    q, k, v, g = _inputs(R, T, R, T, H, 100 * T + H)
+    att = _bias_module(H, False, T + H)
+    keep = _padding(R, T, g)
+    with torch.no_grad():
+        table, offset = att.delta_table(T, T, 0)
+    return _case(f"encoder T={T} H={H} p={p}", q, k, v, H, table=table, offset=offset, key_mask=keep, p=p, seed=seed,
+                 seed_d_out=T + H, masked_row=1), v
+
+
+@pytest.mark.parametrize("H", [1, 6])
+@pytest.mark.parametrize("T", [1, 7, 17, 81])
+def test_encoder_backward_matches_operators(T, H):
+    (out, lse, dq, dk, dv, dtable, d_out), v = _encoder(T, H)
+    if T == 1:   # one key: P = 1 and dS = 0 exactly
+        assert torch.equal(dv.view(torch.int32), d_out.view(torch.int32))
+        assert not bool(dq.any()) and not bool(dk.any()) and not bool(dtable.any())
+
+
+def test_encoder_backward_at_the_stated_maximum():
+    from rqhip import ops
+    assert ops.t5_attention_bwd_supported(torch.float32, 64, 1, 256, 256)
+    assert not ops.t5_attention_bwd_supported(torch.float32, 64, 1, 257, 257)
+    _encoder(256, 1)
+
+
+@pytest.mark.parametrize("H", [1, 6])
+@pytest.mark.parametrize("T", [2, 4])
+def test_causal_backward_matches_operators(T, H):
+    R = 9
+    q, k, v, _ = _inputs(R, T, R, T, H, 7 * T + H)
+    att = _bias_module(H, True, T)
+    with torch.no_grad():
+        table, offset = att.delta_table(T, T, 0)
+    _case(f"causal T={T} H={H}", q, k, v, H, table=table, offset=offset, causal=True, seed_d_out=T)
+
+
+@pytest.mark.parametrize("H", [1, 6])
+@pytest.mark.parametrize("Tq,Tk", [(4, 81), (3, 33)])
+def test_cross_backward_matches_operators(Tq, Tk, H):
+    R = 6
+    q, k, v, g = _inputs(R, Tq, R, Tk, H, 31 + Tq + H)
+    _case(f"cross Tq={Tq} Tk={Tk} H={H}", q, k, v, H, key_mask=_padding(R, Tk, g), seed_d_out=Tk, masked_row=1)
+
+
+def _seed(value):
+    return torch.tensor([value], dtype=torch.int64, device="cuda")
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5])
+@pytest.mark.parametrize("T", [17, 81])
+def test_encoder_dropout_uses_the_contract_mask(T, p):
+    from rqhip import ops
+    H = 6
+    (out, *_), _ = _encoder(T, H, p=p, seed=_seed(77 + T))
+    R = 5
+    q, k, v, g = _inputs(R, T, R, T, H, 100 * T + H)          # the inputs of _encoder again
+    att = _bias_module(H, False, T + H)
+    keep = _padding(R, T, g)
+    with torch.no_grad():
+        table, offset = att.delta_table(T, T, 0)
+        other, _ = ops.t5_attention_fwd_train(q, k, v, H, bias_by_delta=table, bias_offset=offset, key_mask=keep, p=p,
+                                              seed=_seed(78 + T))
+    assert not torch.equal(other, out)
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5])
+def test_cross_dropout_uses_the_contract_mask(p):
+    from rqhip import ops
+    R, H, Tq, Tk = 6, 6, 4, 81
+    q, k, v, g = _inputs(R, Tq, R, Tk, H, 5)
+    keep = _padding(R, Tk, g)
+    out = _case(f"cross Tq={Tq} Tk={Tk} H={H} p={p}", q, k, v, H, key_mask=keep, p=p, seed=_seed(-3), masked_row=1)[0]
+    with torch.no_grad():
+        other, _ = ops.t5_attention_fwd_train(q, k, v, H, key_mask=keep, p=p, seed=_seed(4))
+    assert not torch.equal(other, out)
+
+
+def test_wrappers_reject_host_tensors_other_dtypes_and_beams():
+    from rqhip import ops
+    from rqhip._lib import RqHipError
+    dev = torch.device("cuda")
+    z = torch.zeros(2, 3, 64)
+    with pytest.raises(RqHipError):
+        ops.t5_attention_fwd_train(z, z, z, 1)
+    with pytest.raises(RqHipError, match="Rk = R"):
+        ops.t5_attention_fwd_train(torch.zeros(4, 1, 64, device=dev), torch.zeros(2, 8, 64, device=dev),
+                                   torch.zeros(2, 8, 64, device=dev), 1)
+    with pytest.raises(RqHipError, match="seed"):
+        ops.t5_attention_fwd_train(z.to(dev), z.to(dev), z.to(dev), 1, p=0.1)
+    with pytest.raises(RqHipError, match="float32"):
+        ops.t5_attention_fwd_train(z.to(dev).half(), z.to(dev).half(), z.to(dev).half(), 1)
+
+
+# ---- the autograd bridge
+
+
+def test_function_equals_the_direct_calls_and_reaches_the_embedding():
+    from rqhip import ops
+    from rqhip.autograd import T5AttentionFunction
+    R, T, H = 5, 17, 6
+    q, k, v, g = _inputs(R, T, R, T, H, 3)
+    att = _bias_module(H, False, 9)
+    keep = _padding(R, T, g)
+    w = torch.randn(R, T, H * 64, generator=g).to("cuda")
+    q, k, v = (x.requires_grad_() for x in (q, k, v))
+    table, offset = att.delta_table(T, T, 0)
+    out = T5AttentionFunction.apply(q, k, v, table, H, offset, keep, False, 0.0, None)
+    (out * w).sum().backward()
+    with torch.no_grad():
+        o2, lse = ops.t5_attention_fwd_train(q, k, v, H, bias_by_delta=table, bias_offset=offset, key_mask=keep)
+        dq, dk, dv, dtable = ops.t5_attention_bwd(q, k, v, o2, lse, w, H, bias_by_delta=table, bias_offset=offset,
+                                                  key_mask=keep)
+    assert torch.equal(out, o2) and torch.equal(q.grad, dq) and torch.equal(k.grad, dk) and torch.equal(v.grad, dv)
+    # the table's gradient went on through delta_table's gather to the embedding: the operators in fp64 agree
+    wgrad = att.relative_attention_bias.weight.grad
+    refs = []
+    for dtype in (torch.float32, torch.float64):
+        a2 = _bias_module(H, False, 9).to(dtype)
+        bias = a2.compute_bias(T, T)
+        hd = [x.detach().to(dtype).view(R, T, H, 64).transpose(1, 2) for x in (q, k, v)]
+        scores = torch.matmul(hd[0], hd[1].transpose(-1, -2)) + bias + (~keep[:, None, None, :]).to(dtype) * F32_MIN
+        o = torch.matmul(torch.softmax(scores, dim=-1), hd[2]).transpose(1, 2).reshape(R, T, -1)
+        (o * w.to(dtype)).sum().backward()
+        refs.append(a2.relative_attention_bias.weight.grad)
+    _gate("embedding weight gradient", wgrad, refs[0], refs[1], 8)
+    # a non-contiguous d_out (an expanded scalar, a transposed product) is accepted
+    for x in (q, k, v):
+        x.grad = None
+    out = T5AttentionFunction.apply(q, k, v, table.detach(), H, offset, keep, False, 0.0, None)
+    d_nc = w.transpose(0, 1).contiguous().transpose(0, 1)
+    assert not d_nc.is_contiguous()
+    out.backward(d_nc)
+    assert torch.equal(q.grad, dq) and torch.equal(k.grad, dk) and torch.equal(v.grad, dv)
+
+
+# ---- the model with attention_impl = "hip_train"
+
+
+def _count(monkeypatch):
+    import modules.t5 as t5
+    calls = {"fwd": 0, "bwd": 0, "hip": 0}
+    o_f, o_b, o_h = t5.ops.t5_attention_fwd_train, t5.ops.t5_attention_bwd, t5.ops.t5_attention
+
+    def fwd(*a, **kw):
+        calls["fwd"] += 1
+        return o_f(*a, **kw)
+
+    def bwd(*a, **kw):
+        calls["bwd"] += 1
+        return o_b(*a, **kw)
+
+    def hip(*a, **kw):
+        calls["hip"] += 1
+        return o_h(*a, **kw)
+
+    monkeypatch.setattr(t5.ops, "t5_attention_fwd_train", fwd)
+    monkeypatch.setattr(t5.ops, "t5_attention_bwd", bwd)
+    monkeypatch.setattr(t5.ops, "t5_attention", hip)
+    return calls
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_forward_and_gradients_match_reference_with_hip_train(case, monkeypatch):
+    fx = load_golden(f"retrieval_{case}.npz")
+    dev = torch.device("cuda")
+    model = build_model(fx, dev).eval()
+    batch = fixture_batch(fx, dev)
+    model.attention_impl = "hip_train"
+    calls = _count(monkeypatch)
+    check_forward(fx, model, batch)
+    layers = int(fx["config"][5])
+    assert calls == {"fwd": 3 * layers, "bwd": 3 * layers, "hip": 0}
+    with torch.no_grad():
+        got = model(batch)
+        assert calls == {"fwd": 3 * layers, "bwd": 3 * layers, "hip": 3 * layers}
+        model.attention_impl = "hip"
+        want = model(batch)
+    assert torch.equal(got.loss.view(torch.int32), want.loss.view(torch.int32))
+    assert torch.equal(got.loss_d.view(torch.int32), want.loss_d.view(torch.int32))
+
+
+def _three_steps(dev, impl):
+    from modules.model import EncoderDecoderRetrievalModel
+    model, batch = _default_model_and_batch(dev, B=64, N=12101, d=128, seed=5)
+    torch.manual_seed(5)
+    model = EncoderDecoderRetrievalModel(model.codebooks, 3, 256, t5_d_model=384, t5_num_heads=6, t5_d_ff=1024,
+                                         t5_num_layers=4).to(dev)
+    model.attention_impl = impl
+    opt = torch.optim.AdamW(model.parameters(), lr=1e-3)
+    model.train()
+    losses = []
+    for _ in range(3):
+        opt.zero_grad()
+        out = model(batch)
+        out.loss.backward()
+        opt.step()
+        losses.append(out.loss.item())
+    assert all(torch.isfinite(p).all() for p in model.parameters())
+    return losses
+
+
+def test_training_steps_amazon_shape_with_hip_train(monkeypatch):
+    """test_training_smoke_amazon_shape on the fused path: the kernels run under dropout, and a seeded run replays."""
+    dev = torch.device("cuda")
+    calls = _count(monkeypatch)
+    losses = _three_steps(dev, "hip_train")
+    print("losses", losses)
+    assert calls == {"fwd": 3 * 3 * 4, "bwd": 3 * 3 * 4, "hip": 0}
+    assert all(np.isfinite(losses)) and losses[-1] < losses[0], losses
+    assert _three_steps(dev, "hip_train") == losses
+
+
+def test_fallbacks_under_grad_make_no_fused_call(monkeypatch):
+    from modules.t5 import T5Config, T5Stack
+    dev = torch.device("cuda")
+    torch.manual_seed(2)
+    dec = T5Stack(T5Config(16, d_model=32, num_heads=2, d_ff=32, num_layers=1, is_decoder=True)).to(dev).eval()
+    enc = T5Stack(T5Config(16, d_model=32, num_heads=2, d_ff=32, num_layers=1)).to(dev).eval()
+    calls = _count(monkeypatch)
+    x = torch.randn(4, 3, 32, device=dev)
+    memory = torch.randn(2, 5, 32, device=dev)
+    long = torch.randn(1, 257, 32, device=dev)
+    want = dec(x, cross_kv=dec.cross_kv(memory)), enc(long)
+    dec.attention_impl = enc.attention_impl = "hip_train"
+    got = dec(x, cross_kv=dec.cross_kv(memory)), enc(long)     # two beams per K/V row; a length beyond the limit
+    assert calls == {"fwd": 0, "bwd": 0, "hip": 0}
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and got[0].requires_grad
+    # ... and with one K/V per row the fused path is taken
+    dec(x, cross_kv=dec.cross_kv(torch.randn(4, 5, 32, device=dev))).sum().backward()
+    assert calls == {"fwd": 2, "bwd": 2, "hip": 0}
