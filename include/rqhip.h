@@ -337,6 +337,38 @@ int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const f
                            const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *d_q, float *d_k,
                            float *d_v, float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream);
 
+/* "Add-norm": the glue between two T5 sub-layers in one launch (csrc/t5_add_norm.hip; modules/t5.py, norm_impl = "hip"):
+ * the dropout of a sub-layer's output y, the residual add, the NEXT RMS norm and, behind a stack's final norm, its
+ * dropout.  x (the residual stream, or NULL), y, x_new, n are dense [N, d] fp32, w [d], rstd [N]; all arithmetic is fp32
+ * without contraction.  With e = row * d + col and `hash`, `seed` as in rqhip_t5_attention_fwd_train above:
+ *   keep_in(e) = hash(seed, e) >= round(p_in * 2^32)     keep_out(e) = hash(seed, N * d + e) >= round(p_out * 2^32)
+ *   s_in = (float)(1 / (1 - p_in)), s_out = (float)(1 / (1 - p_out)), evaluated in double and rounded once
+ *   t     = y at p_in = 0, else keep_in ? y * s_in : +0          x_new = t without x, else x + t
+ *   rstd  = 1 / sqrt(sum_c x_new[c]^2 / d + eps)                 (IEEE divide and square root)
+ *   n     = w * (x_new * rstd), then at p_out > 0: keep_out ? n * s_out : +0
+ * (rqhip/ops.py:t5_attention_dropout_keep(seed, 2, 1, N, d, p) restates both masks: plane 0 keep_in, plane 1 keep_out.)
+ * A row sum adds each lane's elements (columns 4 l .. 4 l + 3, then + 256, + 512, + 768 of lane l) in ascending order and
+ * then the 64 lanes in an xor butterfly: the order is a function of d alone, so a row's bits depend neither on N nor on
+ * the row's position.
+ *   rqhip_t5_add_norm_bwd, from d_n and d_xnew (either may be NULL = zero):
+ *     g = d_n * (keep_out ? s_out : 0), gw = g * w, xh = x_new * rstd, c = (sum_c gw * xh) / d,
+ *     d_res = d_xnew + rstd * (gw - xh * c); d_x = d_res; d_y = d_res at p_in = 0, else keep_in ? d_res * s_in : 0;
+ *     d_w[c] = sum over the rows of g * xh.  d_x or d_y NULL: that gradient is not wanted.
+ *   d_w without float atomics: each workgroup owns a contiguous range of rows (64 up to N = 16384, then the smallest
+ *   64 * 2^k that needs at most 256 workgroups: a function of N alone), writes one partial [d] block into `workspace`
+ *   (rqhip_t5_add_norm_bwd_workspace_bytes(N, d) bytes), and a second kernel of the same call adds the blocks in
+ *   ascending order.  At N = 0 d_w (when not NULL) is set to zero.
+ * Limits (rqhip_t5_add_norm_supported): d a multiple of 4, 4 <= d <= 1024, else RQHIP_EUNSUPPORTED; x, y, w, x_new, n and
+ * the gradients 16-byte aligned; 0 <= p < 1; seed may be NULL when both probabilities are 0.  Same bits on every run and
+ * device; no allocation, copy or sync (graph-capturable). */
+int rqhip_t5_add_norm_supported(int d);
+size_t rqhip_t5_add_norm_bwd_workspace_bytes(int64_t N, int d);
+int rqhip_t5_add_norm_fwd(const float *x, const float *y, const float *w, int64_t N, int d, float eps, double p_in,
+                          double p_out, const int64_t *seed, float *x_new, float *n, float *rstd, rqhip_stream_t stream);
+int rqhip_t5_add_norm_bwd(const float *x_new, const float *rstd, const float *w, const float *d_n, const float *d_xnew,
+                          int64_t N, int d, double p_in, double p_out, const int64_t *seed, float *d_x, float *d_y,
+                          float *d_w, void *workspace, size_t workspace_bytes, rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include "rqhip_common.h"
+#include "t5_dropout_hash.h"
 
 namespace rqhip {
 
@@ -57,22 +58,7 @@ struct AttTrain {
     float inv_keep;           // 1 / (1 - p)
 };
 
-// The dropout decision of element idx = ((r * H + h) * Tq + i) * Tk + j: a pure function of the 64-bit seed and idx
-// (two rounds of the murmur3 finaliser).  rqhip/ops.py:t5_attention_dropout_keep restates it in torch integer operations.
-__device__ __forceinline__ unsigned att_fmix32(unsigned h) {
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ bool att_keep(unsigned long long seed, unsigned long long idx, unsigned thresh) {
-    unsigned h = att_fmix32((unsigned)seed ^ (unsigned)idx);
-    h = att_fmix32((h ^ (unsigned)(seed >> 32) ^ ((unsigned)(idx >> 32) * 0x85EBCA6Bu)) + 0x9E3779B9u);
-    return h >= thresh;
-}
+// The dropout decision of element idx = ((r * H + h) * Tq + i) * Tk + j is att_keep(seed, idx, thresh) of t5_dropout_hash.h.
 
 template <int MT, bool TRAIN>
 __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {

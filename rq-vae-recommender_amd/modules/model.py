@@ -6,6 +6,9 @@ The T5 body runs on torch operators (modules/t5.py), or, with `model.attention_i
 "torch"; inference only, see modules/t5.py), with every attention call as one HIP launch (ops.t5_attention) and the
 decoder's self-attention history of `generate` in per-position slabs that are never copied.  "hip_train" is "hip" that
 also runs under grad: every attention of a training step is then one fused forward and one fused backward launch.
+`model.norm_impl = "hip"` (default "torch") makes everything between two sub-layer bodies of both stacks -- dropout,
+residual add, the next RMS norm -- one launch forward and one backward (ops.t5_add_norm_fwd / _bwd), under either
+attention implementation, in inference and training.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
@@ -89,6 +92,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self._prefix_index: Optional[SemIdPrefixIndex] = None
         self._prefix_key = None
         self.attention_impl = "torch"  # or "hip" / "hip_train"; handed to both T5 stacks whenever they are run
+        self.norm_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
 
     @property
     def device(self) -> torch.device:
@@ -138,6 +142,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
     def _push_attention_impl(self) -> None:
         self.encoder.encoder.attention_impl = self.t5_decoder.attention_impl = self.attention_impl
+        self.encoder.encoder.norm_impl = self.t5_decoder.norm_impl = self.norm_impl
 
     def encoder_forward_pass(self, attention_mask, input_ids, user_id=None):
         self._push_attention_impl()

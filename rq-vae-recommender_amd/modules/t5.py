@@ -33,6 +33,15 @@ attention-weight dropout happens in the kernel, from a seed drawn per call on th
 default generator: torch.manual_seed reproduces a run); every other dropout stays torch's.  It needs fp32 device
 tensors, one K/V per query row (beams = 1), no operator-format cache and a shape the backward supports; otherwise the
 operators run, silently.  A decode_cache under grad raises.
+
+Norm implementation: a stack's `norm_impl` is "torch" (the default: T5LayerNorm, nn.Dropout and the residual add as
+operators) or "hip": the stack then drives the sub-layer bodies itself (the attention of either implementation, the
+feed-forward) on the normed input, and everything between two bodies -- the dropout of the sub-layer's output, the
+residual add, the next sub-layer's RMS norm -- is ONE autograd.T5AddNormFunction call (csrc/t5_add_norm.hip): 2 * layers
++ 1 calls per encoder forward, 3 * layers + 1 per decoder forward, the last one with the final norm's weight and the
+dropout behind it.  In train mode the dropout seeds of a stack forward are one torch.randint of that many int64s.  It is
+taken for fp32 device tensors with a d_model the kernel supports, in eval and train mode, with and without grad, under
+every attention_impl; otherwise the operators run, silently.  The module tree and the state dict are the same.
 """
 import math
 from typing import List, Optional, Tuple
@@ -43,10 +52,11 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops
-from rqhip.autograd import T5AttentionFunction
+from rqhip.autograd import T5AddNormFunction, T5AttentionFunction
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
+NORM_IMPLS = ("torch", "hip")
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -330,6 +340,7 @@ class T5Stack(nn.Module):
         self.final_layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
         self.attention_impl = "torch"  # or "hip" / "hip_train": see the module docstring
+        self.norm_impl = "torch"  # or "hip": see the module docstring
         init_t5_weights(self, config)
 
     def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
@@ -363,6 +374,40 @@ class T5Stack(nn.Module):
                 x.dtype, cfg.d_kv, cfg.num_heads, query_length, ck.shape[2])
         return ok
 
+    def hip_norm_active(self, x: Tensor) -> bool:
+        """Whether a forward of x takes the "hip" norm path (module docstring)."""
+        if self.norm_impl not in NORM_IMPLS:
+            raise ValueError(f"norm_impl must be one of {NORM_IMPLS}, got {self.norm_impl!r}")
+        return self.norm_impl == "hip" and x.is_cuda and ops.t5_add_norm_supported(x.dtype, self.config.d_model)
+
+    def _forward_add_norm(self, inputs_embeds, self_body, cross_body, use_cache):
+        """forward on the "hip" norm path.  self_body(i, attention, normed) -> (out, kv) and cross_body(i, attention,
+        normed) -> out are the attention bodies of the path `forward` chose; one add-norm call between two bodies."""
+        norms = [layer.layer_norm for blk in self.block for layer in blk.layer] + [self.final_layer_norm]
+        p = float(self.config.dropout_rate) if self.training else 0.0
+        seeds = None
+        if p > 0:  # one draw for the whole stack; a call gets a one-element view
+            seeds = torch.randint(0, 2 ** 62, (len(norms),), dtype=torch.int64, device=inputs_embeds.device)
+
+        def add_norm(x, y, k):
+            norm = norms[k]
+            return T5AddNormFunction.apply(x, y, norm.weight, norm.variance_epsilon, p,
+                                           p if k == len(norms) - 1 else 0.0, None if seeds is None else seeds[k:k + 1])
+
+        x, n = add_norm(None, inputs_embeds, 0)
+        k, new_kv = 0, []
+        for i, blk in enumerate(self.block):
+            out, kv = self_body(i, blk.layer[0].SelfAttention, n)
+            new_kv.append(kv)
+            k += 1
+            x, n = add_norm(x, out, k)
+            if self.is_decoder:
+                k += 1
+                x, n = add_norm(x, cross_body(i, blk.layer[1].EncDecAttention, n), k)
+            k += 1
+            x, n = add_norm(x, blk.layer[-1].DenseReluDense(n), k)
+        return (n, new_kv) if use_cache else n
+
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
@@ -380,6 +425,9 @@ class T5Stack(nn.Module):
         plan.key_mask = None if attention_mask is None else attention_mask.bool()
         plan.causal = self.is_decoder and T > 1
         plan.cross_mask = None if encoder_attention_mask is None else encoder_attention_mask.bool()
+        if self.hip_norm_active(inputs_embeds):
+            return self._forward_add_norm(inputs_embeds, lambda i, att, n: att.self_attention_hip(n, plan, i),
+                                          lambda i, att, n: att.cross_attention_hip(n, cross_kv[i], plan), use_cache)
         x = self.dropout(inputs_embeds)
         new_kv = []
         for i, blk in enumerate(self.block):
@@ -430,6 +478,11 @@ class T5Stack(nn.Module):
                 cross_kv = self.cross_kv(encoder_hidden_states)
             cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
 
+        if self.hip_norm_active(inputs_embeds):
+            return self._forward_add_norm(
+                inputs_embeds,
+                lambda i, att, n: att.self_attention(n, bias, mask, None if past_key_values is None else past_key_values[i]),
+                lambda i, att, n: att.cross_attention(n, cross_kv[i], cross_mask), use_cache)
         x = self.dropout(inputs_embeds)
         new_kv = []
         for i, blk in enumerate(self.block):

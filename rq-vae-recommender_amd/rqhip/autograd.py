@@ -295,3 +295,30 @@ class T5AttentionFunction(torch.autograd.Function):
         dq, dk, dv, dtable = ops.t5_attention_bwd(q, k, v, out, lse, d_out, n_heads, bias_by_delta=table,
                                                   bias_offset=bias_offset, key_mask=mask, causal=causal, p=p, seed=seed)
         return dq, dk, dv, dtable, None, None, None, None, None, None
+
+
+class T5AddNormFunction(torch.autograd.Function):
+    """The glue between two T5 sub-layers (modules/t5.py, norm_impl = "hip") as one launch forward and one backward
+    (ops.t5_add_norm_fwd / ops.t5_add_norm_bwd): apply(x or None, y, w, eps, p_in, p_out, seed) -> (x_new, n) with
+    x_new = x + dropout(y, p_in) and n = dropout(w * rms_norm(x_new), p_out).  Only x_new, the rows' rstd, w and the
+    seed are saved; the dropout decisions are recomputed.  Gradients: x, y and w; at p_in = 0 those of x and y are one
+    tensor."""
+
+    @staticmethod
+    def forward(ctx, x: Optional[Tensor], y: Tensor, w: Tensor, eps: float, p_in: float, p_out: float,
+                seed: Optional[Tensor]):
+        x_new, n, rstd = ops.t5_add_norm_fwd(x, y, w, eps, p_in, p_out, seed)
+        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None (= NULL at the C ABI)
+        ctx.save_for_backward(x_new, rstd, w, seed)
+        ctx.call = (p_in, p_out, x is not None)
+        return x_new, n
+
+    @staticmethod
+    def backward(ctx, d_xnew: Optional[Tensor], d_n: Optional[Tensor]):
+        x_new, rstd, w, seed = ctx.saved_tensors
+        p_in, p_out, has_x = ctx.call
+        if d_xnew is None and d_n is None:
+            return None, None, None, None, None, None, None
+        d_x, d_y, d_w = ops.t5_add_norm_bwd(x_new, rstd, w, _dense(d_n), _dense(d_xnew), p_in, p_out, seed,
+                                            need_x=has_x and ctx.needs_input_grad[0], need_y=ctx.needs_input_grad[1])
+        return d_x, d_y, d_w, None, None, None, None

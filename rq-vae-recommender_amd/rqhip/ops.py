@@ -729,6 +729,95 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
     return dq, dk, dv, dtable
 
 
+def t5_add_norm_supported(dtype: torch.dtype, d: int) -> bool:
+    """Whether t5_add_norm_fwd / t5_add_norm_bwd implement rows of this width (rqhip_t5_add_norm_supported): fp32, d a
+    multiple of 4 in 4 .. 1024."""
+    return dtype == torch.float32 and bool(_lib.lib().rqhip_t5_add_norm_supported(int(d)))
+
+
+def _norm_rows(t: Optional[Tensor], name: str, who: str, shape=None) -> Optional[Tensor]:
+    """A float32 [..., d] tensor as dense 16-byte-aligned rows, as the kernels' float4 accesses need them (copies when
+    it is not contiguous, or is a view that starts off a 16-byte boundary); `shape`: what it must match."""
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or t.dim() < 1:
+        raise RqHipError(f"{who}: {name} must be a float32 [..., d] tensor, got {t.dtype} {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RqHipError(f"{who}: {name} {tuple(t.shape)} does not match {tuple(shape)}")
+    return _aligned16(t.contiguous())
+
+
+def _aligned16(t: Tensor) -> Tensor:
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _norm_call(who: str, d: int, w: Tensor, p_in: float, p_out: float, seed: Optional[Tensor]) -> Tensor:
+    """The checks t5_add_norm_fwd and t5_add_norm_bwd share; returns w as the kernels read it."""
+    if w.dtype != torch.float32 or tuple(w.shape) != (d,):
+        raise RqHipError(f"{who}: w must be float32 [{d}], got {w.dtype} {tuple(w.shape)}")
+    if not (0.0 <= p_in < 1.0 and 0.0 <= p_out < 1.0):
+        raise RqHipError(f"{who}: p_in={p_in}, p_out={p_out} outside 0 <= p < 1")
+    if (p_in > 0 or p_out > 0) and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
+        raise RqHipError(f"{who}: dropout (p_in={p_in}, p_out={p_out}) needs `seed`, a one-element int64 device tensor")
+    return _aligned16(w.contiguous())
+
+
+def t5_add_norm_fwd(x: Optional[Tensor], y: Tensor, w: Tensor, eps: float, p_in: float = 0.0, p_out: float = 0.0,
+                    seed: Optional[Tensor] = None):
+    """The tail of one T5 sub-layer and the head of the next in one launch (rqhip_t5_add_norm_fwd) -> (x_new, n, rstd):
+    x_new = x + dropout(y, p_in) (x None: dropout(y, p_in)), rstd = rsqrt(mean(x_new^2) + eps) per row, n = w * (x_new *
+    rstd), dropped with p_out behind a final norm.  x, y [..., d] float32, w [d]; x_new and n have y's shape, rstd
+    y.shape[:-1].  The masks are t5_attention_dropout_keep(seed, 2, 1, N, d, p)[0 / 1] over the N = y.numel() / d rows;
+    `seed` is a one-element int64 device tensor the host never reads."""
+    _need_gpu(x, y, w, seed)
+    y = _norm_rows(y, "y", "t5_add_norm_fwd")
+    x = _norm_rows(x, "x", "t5_add_norm_fwd", y.shape)
+    d = y.shape[-1]
+    w = _norm_call("t5_add_norm_fwd", d, w, p_in, p_out, seed)
+    N = y.numel() // d if d else 0
+    dev = y.device
+    with torch.cuda.device(dev):
+        x_new, n = torch.empty_like(y), torch.empty_like(y)
+        rstd = torch.empty(y.shape[:-1], dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_add_norm_fwd(_ptr(x), _ptr(y), _ptr(w), N, d, float(eps), float(p_in), float(p_out),
+                                              _ptr(seed) if (p_in > 0 or p_out > 0) else None, _ptr(x_new), _ptr(n),
+                                              _ptr(rstd), _stream())
+        check(rc, "rqhip_t5_add_norm_fwd")
+    return x_new, n, rstd
+
+
+def t5_add_norm_bwd(x_new: Tensor, rstd: Tensor, w: Tensor, d_n: Optional[Tensor], d_xnew: Optional[Tensor],
+                    p_in: float = 0.0, p_out: float = 0.0, seed: Optional[Tensor] = None, *, need_x: bool = True,
+                    need_y: bool = True):
+    """The gradients of t5_add_norm_fwd in one call (rqhip_t5_add_norm_bwd: one launch and the small reduction of the
+    weight gradient) -> (d_x, d_y, d_w).  d_n and d_xnew are the gradients of n and x_new (None = zero); d_x / d_y are
+    None when not needed, and the SAME tensor at p_in = 0, where they are equal.  d_w [d] is summed without atomics in an
+    order that depends on the shape alone."""
+    _need_gpu(x_new, rstd, w, d_n, d_xnew, seed)
+    who = "t5_add_norm_bwd"
+    x_new = _norm_rows(x_new, "x_new", who)
+    d_n, d_xnew = _norm_rows(d_n, "d_n", who, x_new.shape), _norm_rows(d_xnew, "d_xnew", who, x_new.shape)
+    d = x_new.shape[-1]
+    w = _norm_call(who, d, w, p_in, p_out, seed)
+    rstd = _f32c(rstd, "rstd")
+    if tuple(rstd.shape) != tuple(x_new.shape[:-1]):
+        raise RqHipError(f"{who}: rstd must be {tuple(x_new.shape[:-1])}, got {tuple(rstd.shape)}")
+    N = x_new.numel() // d if d else 0
+    dev = x_new.device
+    with torch.cuda.device(dev):
+        shared = p_in == 0 and need_x and need_y
+        d_x = torch.empty_like(x_new) if need_x else None
+        d_y = torch.empty_like(x_new) if need_y and not shared else None
+        d_w = torch.empty_like(w)
+        nbytes = int(_lib.lib().rqhip_t5_add_norm_bwd_workspace_bytes(N, d))
+        work = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_add_norm_bwd(_ptr(x_new), _ptr(rstd), _ptr(w), _ptr(d_n), _ptr(d_xnew), N, d, float(p_in),
+                                              float(p_out), _ptr(seed) if (p_in > 0 or p_out > 0) else None, _ptr(d_x),
+                                              _ptr(d_y), _ptr(d_w), _ptr(work), nbytes, _stream())
+        check(rc, "rqhip_t5_add_norm_bwd")
+    return d_x, (d_x if shared else d_y), d_w
+
+
 def gumbel_matrix_path_min_rows(set_to: int = 0) -> int:
     """Query (set_to <= 0) or set the batch size from which the Gumbel level runs on the matrix instructions
     (rqhip_gumbel_matrix_path_min_rows); returns the previous value."""

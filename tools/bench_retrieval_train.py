@@ -1,18 +1,24 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) with either attention implementation:
+tails: encoder T = 81, decoder T = 4) in three arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
   hip_train  one ops.t5_attention_fwd_train launch per attention and one ops.t5_attention_bwd launch in the backward
+  hip_train+norm  hip_train with norm_impl = "hip": each dropout + residual add + RMS norm between two sub-layer bodies
+             as one ops.t5_add_norm_fwd launch and one ops.t5_add_norm_bwd call
 
-The two arms alternate --runs times in one process on one device (same weights at the start of every block, same
+The three arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
-median and the fastest step per arm over all blocks, and the peak torch.cuda.max_memory_allocated of a block, as one
-JSON line per arm plus a summary line; --out also writes them to a text file (profiles/retrieval_train_step.txt).
+median and the fastest step per arm over all blocks, the median of each block (their spread is what a difference
+between two arms has to exceed), and the peak torch.cuda.max_memory_allocated of a block, as one
+JSON line per arm plus a summary line; --out also writes them to a text file (profiles/retrieval_train_step_norm.txt
+holds a three-arm run; profiles/retrieval_train_step.txt is the older two-arm run and is not to be overwritten or
+compared against: two arms are compared within one run only).  --arms picks a subset, e.g. one arm under a kernel
+trace to count its launches per step.
 
-    python tools/bench_retrieval_train.py [--runs 5] [--warmup 3] [--iters 10] [--batch 64] [--out FILE]
+    python tools/bench_retrieval_train.py [--runs 5] [--warmup 3] [--iters 10] [--batch 64] [--arms A,B] [--out FILE]
 """
 import argparse
 import copy
@@ -29,7 +35,7 @@ import torch  # noqa: E402
 from data.schemas import TokenizedSeqBatch  # noqa: E402
 from modules.model import EncoderDecoderRetrievalModel  # noqa: E402
 
-ARMS = ("torch", "hip_train")
+ARMS = {"torch": ("torch", "torch"), "hip_train": ("hip_train", "torch"), "hip_train+norm": ("hip_train", "hip")}
 
 
 def make_batch(B, items, L, K, N, dev, seed):
@@ -49,10 +55,10 @@ def make_batch(B, items, L, K, N, dev, seed):
     return corpus, TokenizedSeqBatch(*[None if t is None else t.to(dev) for t in batch])
 
 
-def block(model, state, batch, impl, warmup, iters):
+def block(model, state, batch, arm, warmup, iters):
     """One block of one arm from the common starting weights -> (ms per step, peak bytes, last loss)."""
     model.load_state_dict(state)
-    model.attention_impl = impl
+    model.attention_impl, model.norm_impl = ARMS[arm]
     model.train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3)
     torch.manual_seed(0)
@@ -79,35 +85,44 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--arms", default=",".join(ARMS), help="comma-separated subset of: " + ", ".join(ARMS))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    arms = args.arms.split(",")
+    if not arms or any(a not in ARMS for a in arms):
+        ap.error(f"--arms takes names from {list(ARMS)}")
     dev = torch.device("cuda")
     corpus, batch = make_batch(args.batch, 20, 3, 256, 12101, dev, 5)
     torch.manual_seed(5)
     model = EncoderDecoderRetrievalModel(corpus, 3, 256, t5_d_model=384, t5_num_heads=6, t5_d_ff=1024,
                                          t5_num_layers=4).to(dev)
     state = copy.deepcopy(model.state_dict())
-    times = {a: [] for a in ARMS}
-    peak = {a: 0 for a in ARMS}
+    times = {a: [] for a in arms}
+    peak = {a: 0 for a in arms}
+    blocks = {a: [] for a in arms}
     loss = {}
     for _ in range(args.runs):
-        for arm in ARMS:
+        for arm in arms:
             ms, mem, loss[arm] = block(model, state, batch, arm, args.warmup, args.iters)
             times[arm] += ms
+            blocks[arm].append(round(statistics.median(ms), 3))
             peak[arm] = max(peak[arm], mem)
     lines = []
-    for arm in ARMS:
-        lines.append(json.dumps({"attention": arm, "batch": args.batch, "steps_timed": len(times[arm]),
+    for arm in arms:
+        lines.append(json.dumps({"arm": arm, "attention_impl": ARMS[arm][0], "norm_impl": ARMS[arm][1],
+                                 "batch": args.batch, "steps_timed": len(times[arm]),
                                  "ms_per_step_median": round(statistics.median(times[arm]), 3),
-                                 "ms_per_step_min": round(min(times[arm]), 3),
+                                 "ms_per_step_min": round(min(times[arm]), 3), "block_medians": blocks[arm],
                                  "peak_allocated_MiB": round(peak[arm] / 2 ** 20, 1),
                                  "last_loss": round(loss[arm], 4)}))
-    lines.append(json.dumps({"summary": "torch / hip_train",
-                             "median_ratio": round(statistics.median(times["torch"]) /
-                                                   statistics.median(times["hip_train"]), 3),
-                             "peak_ratio": round(peak["torch"] / peak["hip_train"], 3),
-                             "device": torch.cuda.get_device_name(0), "runs": args.runs, "warmup": args.warmup,
-                             "iters": args.iters}))
+    summary = {"summary": "median step, first arm / second arm"}
+    for a, b in (("torch", "hip_train"), ("hip_train", "hip_train+norm")):
+        if a in arms and b in arms:
+            summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
+            summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)
+    summary.update({"device": torch.cuda.get_device_name(0), "runs": args.runs, "warmup": args.warmup,
+                    "iters": args.iters})
+    lines.append(json.dumps(summary))
     print("\n".join(lines))
     if args.out:
         with open(args.out, "w") as f:
