@@ -369,6 +369,45 @@ int rqhip_t5_add_norm_bwd(const float *x_new, const float *rstd, const float *w,
                           int64_t N, int d, double p_in, double p_out, const int64_t *seed, float *d_x, float *d_y,
                           float *d_w, void *workspace, size_t workspace_bytes, rqhip_stream_t stream);
 
+/* Semantic-id heads and their cross-entropy losses in one call forward and one backward (csrc/sid_head_loss.hip;
+ * modules/model.py, head_impl = "hip").  B rows, T positions per row (T >= L), L levels, K codes, width d; all fp32.
+ *   x       the decoder's hidden states [B, T, d]: row stride ld_xb, position stride ld_xt (elements, multiples of 4);
+ *           positions t >= L are never read
+ *   w       a HOST array of L device pointers, w[h] a dense [K, d] matrix; the entry points copy the pointers into the
+ *           kernels' argument block, so the array may be a temporary
+ *   target  [B, >= L] int64 with row stride ld_t >= L; columns h >= L are never read
+ * rqhip_sid_head_loss_fwd:
+ *   z[b,h,k]  = sum_j x[b,h,j] * w[h][k,j]        one fmaf chain from 0 in ascending j
+ *   m = max_k z,  s = sum_k expf(z - m),  lse[b,h] = m + logf(s)
+ *   row_loss[h,b] = lse[b,h] - z[b,h,target[b,h]]
+ *   loss_d[h] = (sum_b row_loss[h,b]) / B          loss = ((0 + loss_d[0]) + loss_d[1]) + ...
+ *   Outputs: z [B, L, K], lse [B, L], row_loss [L, B] (all dense; the backward reads z and lse), loss_d [L], loss [1].
+ * rqhip_sid_head_loss_bwd, from d_loss (a DEVICE pointer to the upstream gradient of `loss`; the host never reads it):
+ *   q[b,h,k]    = (expf(z - lse) - [k == target[b,h]]) * (d_loss / B)
+ *   d_x[b,h,:]  = sum_k q[b,h,k] * w[h][k,:]       one fmaf chain from 0 in ascending k;  d_x[b,t,:] = 0 for t >= L
+ *   d_w[h][k,:] = sum_b q[b,h,k] * x[b,h,:]        blocks of 64 rows: a block is one fmaf chain from 0 in ascending b,
+ *                                                   the blocks are added in ascending order from 0
+ *   d_x is a dense [B, T, d] tensor, the zeros of t >= L written by the kernel; d_w a HOST array of L device pointers to
+ *   dense [K, d] matrices.  d_x NULL, d_w NULL or an entry d_w[h] NULL: that gradient is not wanted.
+ * Reductions: max and sum over K add per-lane partials (lane l holds k = l, l + 64, ... in ascending order) and then the
+ * 64 lanes in an xor butterfly (32, 16, 8, 4, 2, 1); the mean over B does the same over the rows.  Every order is a
+ * function of the sizes alone and there are no atomics, so the same inputs give the same bits on every run and device,
+ * a level's outputs depend on that level's targets only, and a row's lse on neither B nor the row's position.
+ * The softmax subtracts the row maximum: logits of several hundred give a finite loss.
+ * Targets: a target outside [0, K) is never used as an address; it makes row_loss of its row, loss_d[h] and loss NaN, and
+ * the row contributes no one-hot term to the backward.  torch's ignore_index (-100) is NOT reproduced: -100 is out of
+ * range like any other negative value.
+ * Limits (rqhip_sid_head_loss_supported): d a multiple of 4, 4 <= d <= 1024; 1 <= K <= 1024; 1 <= L <= 8, else
+ * RQHIP_EUNSUPPORTED; B >= 1; x and every w[h] 16-byte aligned.  No allocation, copy, memset or sync (graph-capturable);
+ * forward: two launches, backward: one. */
+int rqhip_sid_head_loss_supported(int d, int K, int L);
+int rqhip_sid_head_loss_fwd(const float *x, int64_t ld_xb, int64_t ld_xt, const float *const *w, const int64_t *target,
+                            int64_t ld_t, int64_t B, int T, int L, int K, int d, float *z, float *lse, float *row_loss,
+                            float *loss_d, float *loss, rqhip_stream_t stream);
+int rqhip_sid_head_loss_bwd(const float *x, int64_t ld_xb, int64_t ld_xt, const float *const *w, const int64_t *target,
+                            int64_t ld_t, const float *z, const float *lse, const float *d_loss, int64_t B, int T, int L,
+                            int K, int d, float *d_x, float *const *d_w, rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

@@ -9,6 +9,12 @@ also runs under grad: every attention of a training step is then one fused forwa
 `model.norm_impl = "hip"` (default "torch") makes everything between two sub-layer bodies of both stacks -- dropout,
 residual add, the next RMS norm -- one launch forward and one backward (ops.t5_add_norm_fwd / _bwd), under either
 attention implementation, in inference and training.
+`model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
+cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
+on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
+(the state dict is unchanged).  It is taken when the decoder output is an fp32 device tensor and the shape is supported
+(ops.sid_head_loss_supported), under grad and under no_grad and with every attention_impl / norm_impl; otherwise the
+operators run, silently.  `generate` has its own head and is not affected.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
@@ -30,6 +36,9 @@ from modules.sid_prefix import SemIdPrefixIndex
 from modules.t5 import T5Config, T5EncoderModel, T5Stack
 from rqhip import ops
 from rqhip._lib import RqHipError
+from rqhip.autograd import SidHeadLossFunction
+
+HEAD_IMPLS = ("torch", "hip")
 
 
 class ModelOutput(NamedTuple):
@@ -93,6 +102,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self._prefix_key = None
         self.attention_impl = "torch"  # or "hip" / "hip_train"; handed to both T5 stacks whenever they are run
         self.norm_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
+        self.head_impl = "torch"  # or "hip": the heads and their losses of `forward` as one fused call
 
     @property
     def device(self) -> torch.device:
@@ -188,6 +198,15 @@ class EncoderDecoderRetrievalModel(nn.Module):
                                encoder_attention_mask=attention_mask_for_encoder,
                                past_key_values=past_key_values or None, use_cache=use_cache)
 
+    def hip_head_active(self, decoder_output: Tensor) -> bool:
+        """Whether `forward` takes the "hip" head path for this decoder output (module docstring)."""
+        if self.head_impl not in HEAD_IMPLS:
+            raise ValueError(f"head_impl must be one of {HEAD_IMPLS}, got {self.head_impl!r}")
+        return (self.head_impl == "hip" and decoder_output.is_cuda
+                and all(m.weight.dtype == decoder_output.dtype for m in self.decoder_mlp)
+                and ops.sid_head_loss_supported(decoder_output.dtype, decoder_output.shape[-1],
+                                                self.num_embeddings_per_hierarchy, self.num_hierarchies))
+
     def forward(self, batch: TokenizedSeqBatch) -> ModelOutput:
         sem_ids_dim = self.num_hierarchies + 1
         input_ids = _strip_dedup_col(batch.sem_ids, sem_ids_dim, self.num_hierarchies)
@@ -197,7 +216,15 @@ class EncoderDecoderRetrievalModel(nn.Module):
             attention_mask=attention_mask, input_ids=input_ids, user_id=batch.user_ids)
         decoder_output = self.decoder_forward_pass(
             future_ids=fut_ids, encoder_output=encoder_output,
-            attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False)[:, :-1]
+            attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False)
+        if self.hip_head_active(decoder_output):
+            weights = [m.weight for m in self.decoder_mlp]
+            if torch.is_grad_enabled():
+                loss, loss_d = SidHeadLossFunction.apply(decoder_output, batch.sem_ids_fut, *weights)
+            else:
+                loss, loss_d = ops.sid_head_loss_fwd(decoder_output, weights, batch.sem_ids_fut, self.num_hierarchies)[:2]
+            return ModelOutput(loss=loss, logits=None, loss_d=loss_d)
+        decoder_output = decoder_output[:, :-1]
         total_loss = torch.tensor(0.0, device=decoder_output.device)
         loss_d = []
         for h in range(self.num_hierarchies):

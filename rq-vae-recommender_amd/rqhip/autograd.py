@@ -322,3 +322,30 @@ class T5AddNormFunction(torch.autograd.Function):
         d_x, d_y, d_w = ops.t5_add_norm_bwd(x_new, rstd, w, _dense(d_n), _dense(d_xnew), p_in, p_out, seed,
                                             need_x=has_x and ctx.needs_input_grad[0], need_y=ctx.needs_input_grad[1])
         return d_x, d_y, d_w, None, None, None, None
+
+
+class SidHeadLossFunction(torch.autograd.Function):
+    """The retrieval model's L semantic-id heads and their cross-entropy losses (modules/model.py, head_impl = "hip") as
+    one call forward and one backward (ops.sid_head_loss_fwd / ops.sid_head_loss_bwd): apply(x, target, *weights) ->
+    (loss, loss_d) with x the decoder's unsliced [B, T >= L, d] hidden states, target [B, >= L] and L = len(weights)
+    separate [K, d] matrices.  loss_d is not differentiable.  Saved: x, target, the weights, the logits z and the rows'
+    log-sum-exp.  Gradients: x (dense [B, T, d], zero at the positions no head reads) and each weight that needs one."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, target: Tensor, *weights: Tensor):
+        L = len(weights)
+        loss, loss_d, z, lse = ops.sid_head_loss_fwd(x, weights, target, L)
+        ctx.set_materialize_grads(False)   # without a gradient for `loss` there is nothing to do
+        ctx.mark_non_differentiable(loss_d)
+        ctx.save_for_backward(x, target, z, lse, *weights)
+        return loss, loss_d
+
+    @staticmethod
+    def backward(ctx, d_loss: Optional[Tensor], _d_loss_d):
+        x, target, z, lse, *weights = ctx.saved_tensors
+        L = len(weights)
+        if d_loss is None or not any(ctx.needs_input_grad):
+            return (None,) * (2 + L)
+        d_x, d_w = ops.sid_head_loss_bwd(x, weights, target, z, lse, _dense(d_loss), L,
+                                         need_x=ctx.needs_input_grad[0], need_w=ctx.needs_input_grad[2:])
+        return (d_x, None, *d_w)

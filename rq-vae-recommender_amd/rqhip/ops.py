@@ -818,6 +818,91 @@ def t5_add_norm_bwd(x_new: Tensor, rstd: Tensor, w: Tensor, d_n: Optional[Tensor
     return d_x, (d_x if shared else d_y), d_w
 
 
+def sid_head_loss_supported(dtype: torch.dtype, d: int, K: int, L: int) -> bool:
+    """Whether sid_head_loss_fwd / sid_head_loss_bwd implement this shape (rqhip_sid_head_loss_supported): fp32, d a
+    multiple of 4 in 4 .. 1024, K in 1 .. 1024 codes, L in 1 .. 8 levels."""
+    return dtype == torch.float32 and bool(_lib.lib().rqhip_sid_head_loss_supported(int(d), int(K), int(L)))
+
+
+def _sid_head_args(who: str, x: Tensor, weights, target: Tensor, L: int):
+    """The checks sid_head_loss_fwd and sid_head_loss_bwd share -> (x, its two strides, the weights' pointer array,
+    target, its row stride, B, T, K, d).  x and target go to the kernels as strided views; only a layout the kernels
+    cannot address (a last dimension that is not dense, strides off a float4 boundary) is copied."""
+    weights = list(weights)
+    _need_gpu(x, target, *weights)
+    L = int(L)
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise RqHipError(f"{who}: x must be a float32 [B, T, d] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, T, d = x.shape
+    if len(weights) != L or L < 1:
+        raise RqHipError(f"{who}: {len(weights)} weight matrices for L={L} levels")
+    K = weights[0].shape[0] if weights[0].dim() == 2 else -1
+    for h, w in enumerate(weights):
+        if w.dtype != torch.float32 or tuple(w.shape) != (K, d):
+            raise RqHipError(f"{who}: weights[{h}] must be float32 [K, {d}] like weights[0], got {w.dtype} {tuple(w.shape)}")
+    if target.dim() != 2 or target.shape[0] != B or target.shape[1] < L or target.is_floating_point():
+        raise RqHipError(f"{who}: target must be an integer [{B}, >= {L}] tensor, got {target.dtype} {tuple(target.shape)}")
+    if target.dtype != torch.int64:
+        target = target.long()
+    if target.stride(1) != 1 or target.stride(0) < L:
+        target = target.contiguous()
+    if x.stride(2) != 1 or x.stride(0) < 0 or x.stride(1) < 0 or x.stride(0) % 4 or x.stride(1) % 4 or x.data_ptr() % 16:
+        x = _aligned16(x.contiguous())
+    weights = [_aligned16(w.contiguous()) for w in weights]
+    w_ptrs = (C.c_void_p * L)(*[w.data_ptr() for w in weights])
+    return x, int(x.stride(0)), int(x.stride(1)), weights, w_ptrs, target, int(target.stride(0)), B, T, K, d
+
+
+def sid_head_loss_fwd(x: Tensor, weights, target: Tensor, L: int):
+    """All L semantic-id heads and their cross-entropy losses in one call (rqhip_sid_head_loss_fwd) ->
+    (loss, loss_d, z, lse): z[b, h] = weights[h] @ x[b, h], loss_d[h] = mean_b cross_entropy(z[:, h], target[:, h]),
+    loss = their sum in ascending order from 0.  x [B, T >= L, d] float32 (any row and position strides that are
+    multiples of 4; positions >= L are never read), weights: L separate [K, d] matrices, target [B, >= L] integers
+    (converted to int64 when they are not; columns >= L are never read).  loss is 0-dim, loss_d [L]; z [B, L, K] and
+    lse [B, L] are what sid_head_loss_bwd needs.  A target outside [0, K) makes its level's loss NaN; there is no
+    ignore_index."""
+    who = "sid_head_loss_fwd"
+    x, ld_xb, ld_xt, weights, w_ptrs, target, ld_t, B, T, K, d = _sid_head_args(who, x, weights, target, L)
+    dev = x.device
+    with torch.cuda.device(dev):
+        z = torch.empty((B, L, K), dtype=torch.float32, device=dev)
+        rows = torch.empty((2, B, L), dtype=torch.float32, device=dev)    # lse [B, L]; the rows' losses [L, B]
+        loss_d = torch.empty((L,), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_sid_head_loss_fwd(_ptr(x), ld_xb, ld_xt, w_ptrs, _ptr(target), ld_t, B, T, int(L), K, d,
+                                                _ptr(z), _ptr(rows[0]), _ptr(rows[1]), _ptr(loss_d), _ptr(loss), _stream())
+        check(rc, "rqhip_sid_head_loss_fwd")
+    return loss, loss_d, z, rows[0]
+
+
+def sid_head_loss_bwd(x: Tensor, weights, target: Tensor, z: Tensor, lse: Tensor, d_loss: Tensor, L: int, *,
+                      need_x: bool = True, need_w=None):
+    """The gradients of sid_head_loss_fwd's `loss` in one launch (rqhip_sid_head_loss_bwd) -> (d_x, [d_w[0], ...]).
+    z, lse: the forward's; d_loss: the upstream gradient, a one-element float32 device tensor the host never reads.
+    d_x is a dense [B, T, d] tensor whose positions >= L are zero (None without need_x); d_w[h] is None where need_w[h]
+    (default: every level) is false.  No atomics: the same bits on every run."""
+    who = "sid_head_loss_bwd"
+    x, ld_xb, ld_xt, weights, w_ptrs, target, ld_t, B, T, K, d = _sid_head_args(who, x, weights, target, L)
+    L = int(L)
+    need_w = [True] * L if need_w is None else [bool(n) for n in need_w]
+    _need_gpu(z, lse, d_loss)
+    z, lse = _f32c(z, "z"), _f32c(lse, "lse")
+    if tuple(z.shape) != (B, L, K) or tuple(lse.shape) != (B, L) or len(need_w) != L:
+        raise RqHipError(f"{who}: z {tuple(z.shape)}, lse {tuple(lse.shape)}, need_w {len(need_w)} do not match "
+                         f"B={B}, L={L}, K={K}")
+    if d_loss.dtype != torch.float32 or d_loss.numel() != 1:
+        raise RqHipError(f"{who}: d_loss must be one float32 element, got {d_loss.dtype} {tuple(d_loss.shape)}")
+    dev = x.device
+    with torch.cuda.device(dev):
+        d_x = torch.empty((B, T, d), dtype=torch.float32, device=dev) if need_x else None
+        d_w = [torch.empty((K, d), dtype=torch.float32, device=dev) if n else None for n in need_w]
+        g_ptrs = (C.c_void_p * L)(*[_ptr(g) for g in d_w])
+        rc = _lib.lib().rqhip_sid_head_loss_bwd(_ptr(x), ld_xb, ld_xt, w_ptrs, _ptr(target), ld_t, _ptr(z), _ptr(lse),
+                                                _ptr(d_loss), B, T, L, K, d, _ptr(d_x), g_ptrs, _stream())
+        check(rc, "rqhip_sid_head_loss_bwd")
+    return d_x, d_w
+
+
 def gumbel_matrix_path_min_rows(set_to: int = 0) -> int:
     """Query (set_to <= 0) or set the batch size from which the Gumbel level runs on the matrix instructions
     (rqhip_gumbel_matrix_path_min_rows); returns the previous value."""
