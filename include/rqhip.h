@@ -408,6 +408,45 @@ int rqhip_sid_head_loss_bwd(const float *x, int64_t ld_xb, int64_t ld_xt, const 
                             int64_t ld_t, const float *z, const float *lse, const float *d_loss, int64_t B, int T, int L,
                             int K, int d, float *d_x, float *const *d_w, rqhip_stream_t stream);
 
+/* The T5 feed-forward body in one launch forward and at most two backward (csrc/t5_ffn.hip; modules/t5.py, ffn_impl =
+ * "hip").  N rows, d = d_model, F = d_ff; x, y, d_y, d_x dense [N, d], h and the workspace's g dense [N, F], wi [F, d] and
+ * wo [d, F] the two nn.Linear weights as stored; all fp32.  With `hash`, `seed` as in rqhip_t5_attention_fwd_train above:
+ *   keep(n, f) = hash(seed, n * F + f) >= round(p * 2^32)        s = (float)(1 / (1 - p)), evaluated in double
+ *   h  = x . wi^T, then +0 wherever that is <= 0 (a NaN stays)   hd = h at p = 0, else keep ? h * s : +0
+ *   y  = hd . wo^T                                               (hd is never stored)
+ * (rqhip/ops.py:t5_attention_dropout_keep(seed, 1, 1, N, F, p)[0, 0] restates the mask.)  h NULL: it is not stored.
+ *   rqhip_t5_ffn_bwd, from d_y:
+ *     g    = (h > 0 and keep) ? (d_y . wo) * s : 0      (at p = 0: h > 0 ? d_y . wo : 0)
+ *     d_x  = g . wi        d_wi = g^T . x        d_wo = d_y^T . hd, hd recomputed from h and the seed
+ *   d_x, d_wi or d_wo NULL: that gradient is not wanted (all three: nothing is launched).  Launch 1 (skipped when only
+ *   d_wo is wanted) forms g tile by tile, writes it to `workspace` when d_wi is wanted (rqhip_t5_ffn_bwd_workspace_bytes
+ *   = 4 * N * F bytes; the workspace may be NULL otherwise) and produces d_x; launch 2 (skipped when neither weight
+ *   gradient is wanted) produces d_wi and d_wo.
+ * Arithmetic contract.  All products and sums are fp32 FMAs of v_mfma_f32_16x16x4_f32, every chain starts from +0, and
+ * the order of every chain is a function of the sizes alone:
+ *   - a GROUP of 32 consecutive reduction terms is consumed in the order 0 8 16 24 1 9 17 25 ... 7 15 23 31
+ *     (csrc/mlp_small.hip's order); 4 consecutive groups (128 terms) are ONE chain from +0, and a reduction's chains
+ *     are added in ascending order from +0: h and g over the chains of d, y and d_x over those of F.  The order
+ *     depends on (d, F) alone, so a row's h, y, g and d_x do not depend on N, on the row's position or on the other
+ *     rows of the batch (the row-tile height, 16 up to N = 16384 and 32 above, changes which workgroup computes a
+ *     row, not how);
+ *   - d_wi and d_wo reduce over the rows in blocks of 32 (rows 4 ks + kq of a block are the k-slots kq of instruction
+ *     ks = 0 .. 7; rows past N count as zero); with nb = ceil(N / 32), wave w = 0 .. 3 of the tile's owning workgroup
+ *     takes blocks [w nb / 4, (w + 1) nb / 4), starts a fresh chain every 8 blocks and adds its chains in ascending
+ *     order from +0; the result is ((s_0 + s_1) + s_2) + s_3 over the waves' sums.  The order depends on N alone.
+ * No atomics: the same bits on every run and device.  Rows past N read a valid row and store nothing.
+ * Limits (rqhip_t5_ffn_supported): d a multiple of 32 in 32 .. 512 and F a multiple of 32 in 32 .. 8192, else
+ * RQHIP_EUNSUPPORTED; any N >= 0 (N = 0 launches nothing); every pointer 16-byte aligned; 0 <= p < 1; `seed` is a
+ * one-element int64 DEVICE pointer the host never reads, required iff p > 0.  All argument checks come before any HIP
+ * call; no allocation, copy, memset or sync (graph-capturable). */
+int rqhip_t5_ffn_supported(int d, int F);
+size_t rqhip_t5_ffn_bwd_workspace_bytes(int64_t N, int d, int F);
+int rqhip_t5_ffn_fwd(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+                     const int64_t *seed, float *y, float *h, rqhip_stream_t stream);
+int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo, const float *h, const float *d_y, int64_t N, int d,
+                     int F, double p, const int64_t *seed, float *d_x, float *d_wi, float *d_wo, void *workspace,
+                     rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

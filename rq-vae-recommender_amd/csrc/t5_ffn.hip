@@ -1,0 +1,564 @@
+// t5_ffn.hip -- the T5 feed-forward body wo(dropout(relu(wi(x)))) as one launch forward and at most two backward
+// (gfx950; modules/t5.py, ffn_impl = "hip"; semantics and arithmetic contract in include/rqhip.h).  Exact fp32 on
+// v_mfma_f32_16x16x4_f32, operand layout as csrc/mlp_small.hip: lane (i, kq) = (lane & 15, lane >> 4) supplies k-slot kq
+// of row / column i, and of a GROUP of 32 reduction terms it holds the 8 terms 8 kq .. 8 kq + 7, so instruction e of a
+// group consumes term 8 kq + e of every slot (chain order 0 8 16 24 1 9 17 25 ... 7 15 23 31 within a group).
+//
+// Row kernel (forward, and backward kernel 1: the same structure with the weights in the other orientation).  A
+// workgroup of 4 waves owns T rows; their x (backward: d_y) stays in LDS.  It walks F in chunks of 128 columns:
+//   phase 1  wave w computes columns 32 w .. 32 w + 31 of the chunk (two 16-column tiles, T / 16 row tiles) over the
+//            whole of d, applies the epilogue (forward: ReLU, store of h, dropout and scale; backward: the mask
+//            h > 0 and keep * s, store of g) and writes the result into one of two LDS chunk buffers;
+//   phase 2  wave w adds chunk . W2 into the accumulators of its column pairs q = w, w + 4, ... (32 output columns
+//            each) -- they live in registers for the whole walk; y (d_x) is written once at the end.
+// No chain is longer than 128 terms: phase 1 starts a fresh chain every 4 groups of d, phase 2 one per chunk, and the
+// finished chains are added in ascending order.  (One chain over all of d = 384 or F = 1024 passed the test's gates,
+// but with three to four times the operators' error in the worst cases, next to a factor of 4; the library GEMMs sum
+// in such partial chains too.  With chains of 128 the error is the operators' or less: profiles/t5_ffn_error.txt.)
+// One barrier per chunk: chunk c + 1 goes into the other buffer, and nobody can still read that one (a wave passes
+// chunk c's barrier only after every wave has finished phase 2 of chunk c - 1).
+// The weights are read as stored.  Where the reduction runs along a weight's rows (forward: wi [F, d] and wo [d, F])
+// a lane loads its row's 8 terms as two float4; where it runs down the columns (backward: wo, then wi) it loads, for
+// each of its 8 terms, 2 consecutive columns (float2) and serves column 2 j + ct in column tile ct -- a permutation
+// the epilogues undo for free.
+// Row-tile height: T = 16 up to 16384 rows, 32 above.  A workgroup streams all of wi and wo through L2 whatever T
+// is, so T = 32 halves that traffic; but the model's shapes (5120 and 256 rows) are short of workgroups, not of L2
+// bandwidth: 16-row tiles give 320 and 16 workgroups instead of 160 and 8 on 256 CUs.  The registers of the
+// two-deep operand buffers leave one workgroup per CU at d = 384 (one wave per SIMD, which two independent
+// accumulators per wave keep at the matrix pipe's issue rate).  T follows N alone, and the chains do not depend on T.
+//
+// Weight-gradient kernel (backward kernel 2): every 32 x 32 tile of d_wi and of d_wo has one owning workgroup, which
+// reduces over all N rows: blocks of 32 rows, wave w of 4 takes the contiguous range of blocks [w nb / 4, (w + 1) nb
+// / 4); within its range a wave starts a fresh chain every 8 blocks (256 rows) and adds the finished chains in
+// ascending order (bounded chain length: the rounding error of a long row count grows with the number of chains,
+// not of rows); the four waves' sums meet in LDS and are added in wave order.  No partial blocks in memory, no
+// atomics, no reduction launch.  hd is recomputed from h and the seed as it is loaded.
+#include <math.h>
+
+#include "rqhip_common.h"
+#include "t5_dropout_hash.h"
+
+namespace rqhip {
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kFfnMaxD = 512, kFfnMaxF = 8192;
+constexpr int kFfnChunk = 128;            // columns of F per step of the walk: 32 per wave
+constexpr int kFfnLdh = kFfnChunk + 4;    // row stride of a chunk buffer in LDS
+constexpr int kFfnChainGroups = 4;        // groups of 32 terms per chain: 128 terms, as a chunk of F
+constexpr long long kFfnTallFrom = 16384; // rows above which the row tile is 32 high
+constexpr int kFfnWgBlock = 32;           // rows per block of the weight-gradient reduction
+constexpr int kFfnWgFlush = 8;            // blocks per chain
+
+bool ffn_supported(int d, int F) {
+    return d >= 32 && d <= kFfnMaxD && d % 32 == 0 && F >= 32 && F <= kFfnMaxF && F % 32 == 0;
+}
+
+struct FfnRows {
+    const float *x;            // forward: x [N, d]; backward: d_y [N, d]
+    const float *w1, *w2;      // forward: wi [F, d], wo [d, F]; backward: wo, wi
+    const float *h_in;         // backward: h [N, F]
+    float *mid;                // forward: h (or null); backward: g (or null)
+    float *out;                // forward: y; backward: d_x (null: phase 2 is skipped)
+    const long long *seed;     // one int64 on the device (read only when th != 0)
+    unsigned th;               // round(p * 2^32); 0 = no dropout
+    float s;                   // 1 / (1 - p)
+    long long N;
+    int d, F;
+};
+
+template <int RT>
+__device__ __forceinline__ void ffn_load_a(const float *base, int ld, int off, float (&a)[RT][8]) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(base + 16 * rt * ld + off);
+        const f32x4 hi = *reinterpret_cast<const f32x4 *>(base + 16 * rt * ld + off + 4);
+        a[rt][0] = lo.x; a[rt][1] = lo.y; a[rt][2] = lo.z; a[rt][3] = lo.w;
+        a[rt][4] = hi.x; a[rt][5] = hi.y; a[rt][6] = hi.z; a[rt][7] = hi.w;
+    }
+}
+
+// the weight operand of one group for two 16-column tiles.  KN = false: `at` points at term 0 of the group in the row
+// of tile 0's column, rows `ld` apart (tile 1: 16 rows on).  KN = true: `at` points at the lane's 2 columns in the row of
+// the group's term 0, terms `ld` apart.
+template <bool KN>
+__device__ __forceinline__ void ffn_load_b(const float *at, size_t ld, float (&b)[2][8]) {
+    if constexpr (KN) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const f32x2 v = *reinterpret_cast<const f32x2 *>(at + (size_t)e * ld);
+            b[0][e] = v.x; b[1][e] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const f32x4 lo = *reinterpret_cast<const f32x4 *>(at + (size_t)(16 * ct) * ld);
+            const f32x4 hi = *reinterpret_cast<const f32x4 *>(at + (size_t)(16 * ct) * ld + 4);
+            b[ct][0] = lo.x; b[ct][1] = lo.y; b[ct][2] = lo.z; b[ct][3] = lo.w;
+            b[ct][4] = hi.x; b[ct][5] = hi.y; b[ct][6] = hi.z; b[ct][7] = hi.w;
+        }
+    }
+}
+
+template <int RT>
+__device__ __forceinline__ void ffn_mma(const float (&a)[RT][8], const float (&b)[2][8], f32x4 (&acc)[RT][2]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+                acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], b[ct][e], acc[rt][ct], 0, 0, 0);
+}
+
+// a finished chain joins the sum of the chains before it; the next chain starts from +0
+template <int RT>
+__device__ __forceinline__ void ffn_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][2]) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sum[rt][ct][r] = sum[rt][ct][r] + run[rt][ct][r];
+            run[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+}
+
+// keeps a round's loads together and in front of the previous round's matrix instructions (csrc/mlp_small.hip)
+#define FFN_FENCE __builtin_amdgcn_sched_barrier(0)
+
+// RT: 16-row tiles per workgroup; NP: column pairs (32 output columns) per wave, >= ceil(d / 128)
+template <int RT, int NP, bool BWD>
+__global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
+    extern __shared__ __align__(16) float ffn_lds[];
+    constexpr int T = 16 * RT;
+    const int d = p.d, F = p.F, ldx = d + 4;
+    float *xs = ffn_lds;                 // [T][d + 4]
+    float *hs = ffn_lds + T * ldx;       // [2][T][kFfnLdh]
+    const int t = threadIdx.x, lane = t & 63, i = lane & 15, kq = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const long long m0 = (long long)blockIdx.x * T;
+
+    for (int f = t; f < T * (d >> 2); f += 256) {       // rows past the batch: a valid row is read, nothing is stored
+        const int r = f / (d >> 2), c4 = f % (d >> 2);
+        const long long row = m0 + r < p.N ? m0 + r : p.N - 1;
+        *reinterpret_cast<f32x4 *>(xs + r * ldx + 4 * c4) = *reinterpret_cast<const f32x4 *>(p.x + (size_t)row * d + 4 * c4);
+    }
+    __syncthreads();
+
+    const unsigned long long seed = p.th ? (unsigned long long)*p.seed : 0ull;
+    const int npairs = d >> 5, ngd = d >> 5;
+    f32x4 acc2[NP][RT][2];
+#pragma unroll
+    for (int q = 0; q < NP; ++q)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc2[q][rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // The weight operands come from L2 / HBM with about a microsecond of latency and one workgroup may have a CU to
+    // itself (256 rows are 16 workgroups), so each phase keeps two loads' worth of them in registers: while the
+    // matrix instructions of one round run, the next round's loads are in flight; a phase's first round is requested
+    // before the other phase ends (phase 2's over the epilogue and the barrier, the next chunk's phase 1 over phase 2).
+    constexpr int RG = 2;                          // groups per round of phase 1: two rounds are one chain
+    static_assert(kFfnChainGroups == 2 * RG, "a chain is closed after every second round");
+    const int nr1 = (ngd + RG - 1) / RG;
+    const size_t ld1 = BWD ? (size_t)F : (size_t)d, ld2 = BWD ? (size_t)d : (size_t)F;
+    float pb[2][RG][2][8];                         // phase 1: two rounds
+    float qb[2][NP][2][8];                         // phase 2: two groups
+    auto load1 = [&](float (&dst)[RG][2][8], int fw, int r) {
+#pragma unroll
+        for (int gg = 0; gg < RG; ++gg) {
+            const int g = min(RG * r + gg, ngd - 1);      // past d: a valid group is read and not used
+            const float *at = BWD ? p.w1 + (size_t)(32 * g + 8 * kq) * F + fw + 2 * i
+                                  : p.w1 + (size_t)(fw + i) * d + 32 * g + 8 * kq;
+            ffn_load_b<BWD>(at, ld1, dst[gg]);
+        }
+    };
+    auto comp1 = [&](const float (&src)[RG][2][8], int r, f32x4 (&run)[RT][2]) {
+#pragma unroll
+        for (int gg = 0; gg < RG; ++gg) {
+            const int g = RG * r + gg;
+            if (g < ngd) {
+                float a[RT][8];
+                ffn_load_a<RT>(xs + i * ldx + 8 * kq, ldx, 32 * g, a);
+                ffn_mma<RT>(a, src[gg], run);
+            }
+        }
+    };
+    auto load2 = [&](float (&dst)[NP][2][8], int f0, int g) {
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            const int pair = w + 4 * q;
+            if (pair < npairs) {
+                const float *at = BWD ? p.w2 + (size_t)(f0 + 32 * g + 8 * kq) * d + 32 * pair + 2 * i
+                                      : p.w2 + (size_t)(32 * pair + i) * F + f0 + 32 * g + 8 * kq;
+                ffn_load_b<BWD>(at, ld2, dst[q]);
+            }
+        }
+    };
+    auto comp2 = [&](const float (&src)[NP][2][8], const float *hb, int g, f32x4 (&run)[NP][RT][2]) {
+        float a[RT][8];
+        ffn_load_a<RT>(hb + i * kFfnLdh + 8 * kq, kFfnLdh, 32 * g, a);
+#pragma unroll
+        for (int q = 0; q < NP; ++q)
+            if (w + 4 * q < npairs) ffn_mma<RT>(a, src[q], run[q]);
+    };
+
+    if (32 * w < F) load1(pb[0], 32 * w, 0);
+    int buf = 0;
+    for (int f0 = 0; f0 < F; f0 += kFfnChunk, buf ^= 1) {
+        float *hb = hs + buf * T * kFfnLdh;
+        const int fw = f0 + 32 * w;     // this wave's 32 columns of the chunk
+        f32x4 acc1[RT][2], run1[RT][2];      // the sum of the finished chains; the running chain
+        float hv[RT][2][4];                  // backward: h at the lane's elements of the chunk
+        if (fw < F) {
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) acc1[rt][ct] = run1[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (BWD) {
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const long long grow = m0 + 16 * rt + 4 * kq + r;
+                        const f32x2 v = *reinterpret_cast<const f32x2 *>(p.h_in + (size_t)(grow < p.N ? grow : p.N - 1) * F + fw + 2 * i);
+                        hv[rt][0][r] = v.x; hv[rt][1][r] = v.y;
+                    }
+            }
+            for (int r = 0; r < nr1; r += 2) {
+                if (r + 1 < nr1) load1(pb[1], fw, r + 1);
+                FFN_FENCE; comp1(pb[0], r, run1); FFN_FENCE;
+                if (r + 1 < nr1) {
+                    if (r + 2 < nr1) load1(pb[0], fw, r + 2);
+                    FFN_FENCE; comp1(pb[1], r + 1, run1); FFN_FENCE;
+                }
+                ffn_close<RT>(acc1, run1);      // rounds r and r + 1: 4 groups
+            }
+        }
+        if (p.out) load2(qb[0], f0, 0);
+        FFN_FENCE;
+        if (fw < F) {
+            // acc1[rt][ct][r]: row 16 rt + 4 kq + r; column 16 ct + i (forward) or 2 i + ct (backward) of the wave's 32
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 16 * rt + 4 * kq + r, lc = 32 * w + (BWD ? 2 * i + ct : 16 * ct + i);
+                        const long long grow = m0 + row;
+                        const unsigned long long f = (unsigned long long)(f0 + lc);
+                        float v = acc1[rt][ct][r];
+                        if constexpr (!BWD) {
+                            v = v <= 0.f ? 0.f : v;      // +0 for every pre-activation <= 0; a NaN stays a NaN
+                            if (p.mid && grow < p.N) p.mid[(size_t)grow * F + f] = v;
+                            if (p.th) v = att_keep(seed, (unsigned long long)grow * F + f, p.th) ? v * p.s : 0.f;
+                        } else {
+                            bool on = hv[rt][ct][r] > 0.f;
+                            if (p.th) {
+                                on = on && att_keep(seed, (unsigned long long)(grow < p.N ? grow : p.N - 1) * F + f, p.th);
+                                v = v * p.s;
+                            }
+                            v = on ? v : 0.f;
+                            if (p.mid && grow < p.N) p.mid[(size_t)grow * F + f] = v;
+                        }
+                        hb[row * kFfnLdh + lc] = v;
+                    }
+        }
+        __syncthreads();
+        if (fw + kFfnChunk < F) load1(pb[0], fw + kFfnChunk, 0);
+        if (p.out) {
+            const int ng = (F - f0 < kFfnChunk ? F - f0 : kFfnChunk) >> 5;
+            f32x4 run2[NP][RT][2];               // this chunk's chains
+#pragma unroll
+            for (int q = 0; q < NP; ++q)
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) run2[q][rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int g = 0; g < ng; g += 2) {
+                if (g + 1 < ng) load2(qb[1], f0, g + 1);
+                FFN_FENCE; comp2(qb[0], hb, g, run2); FFN_FENCE;
+                if (g + 1 < ng) {
+                    if (g + 2 < ng) load2(qb[0], f0, g + 2);
+                    FFN_FENCE; comp2(qb[1], hb, g + 1, run2); FFN_FENCE;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NP; ++q) ffn_close<RT>(acc2[q], run2[q]);
+        }
+    }
+    if (!p.out) return;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int pair = w + 4 * q;
+        if (pair >= npairs) continue;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long grow = m0 + 16 * rt + 4 * kq + r;
+                if (grow >= p.N) continue;
+                float *o = p.out + (size_t)grow * d + 32 * pair;
+                if constexpr (BWD) {
+                    *reinterpret_cast<f32x2 *>(o + 2 * i) = f32x2{acc2[q][rt][0][r], acc2[q][rt][1][r]};
+                } else {
+                    o[i] = acc2[q][rt][0][r];
+                    o[16 + i] = acc2[q][rt][1][r];
+                }
+            }
+    }
+}
+
+struct FfnWgrad {
+    const float *g, *x;        // d_wi [F, d] = g^T . x
+    const float *dy, *h;       // d_wo [d, F] = d_y^T . hd, hd = keep ? h * s : 0
+    float *d_wi, *d_wo;        // either may be null
+    const long long *seed;
+    unsigned th;
+    float s;
+    long long N;
+    int d, F;
+    int tiles_wi;              // workgroups [0, tiles_wi) own d_wi's tiles, the rest d_wo's
+};
+
+__global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
+    __shared__ float red[4 * 32 * 33];
+    const int t = threadIdx.x, lane = t & 63, i = lane & 15, kq = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    int tile = blockIdx.x;
+    const bool is_wo = tile >= p.tiles_wi;
+    if (is_wo) tile -= p.tiles_wi;
+    // out [rows of P's columns, columns of Q's columns] = sum_n P[n][a0 + .] Q[n][b0 + .]
+    const float *P = is_wo ? p.dy : p.g, *Q = is_wo ? p.h : p.x;
+    const int lp = is_wo ? p.d : p.F, lq = is_wo ? p.F : p.d;
+    float *out = is_wo ? p.d_wo : p.d_wi;
+    const int a0 = 32 * (tile / (lq >> 5)), b0 = 32 * (tile % (lq >> 5));
+    const bool drop = is_wo && p.th != 0;
+    const unsigned long long seed = drop ? (unsigned long long)*p.seed : 0ull;
+
+    const long long nb = (p.N + kFfnWgBlock - 1) / kFfnWgBlock;
+    const long long lo = w * nb / 4, hi = (w + 1) * nb / 4;
+    f32x4 tot[2][2], acc[2][2];
+#pragma unroll
+    for (int at = 0; at < 2; ++at)
+#pragma unroll
+        for (int bt = 0; bt < 2; ++bt) tot[at][bt] = acc[at][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float *pp = P + a0 + 2 * i, *qp = Q + b0 + 2 * i;
+    // lane (i, kq): row 4 ks + kq of block b, columns 2 i and 2 i + 1; past the batch a valid row is read and counts as zero
+    auto load = [&](long long b, f32x2 (&pa)[8], f32x2 (&qb)[8]) {
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            const long long n = b * kFfnWgBlock + 4 * ks + kq;
+            const long long nn = n < p.N ? n : p.N - 1;
+            pa[ks] = *reinterpret_cast<const f32x2 *>(pp + (size_t)nn * lp);
+            qb[ks] = *reinterpret_cast<const f32x2 *>(qp + (size_t)nn * lq);
+        }
+    };
+    auto comp = [&](long long b, f32x2 (&pa)[8], f32x2 (&qb)[8]) {
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            const long long n = b * kFfnWgBlock + 4 * ks + kq;
+            if (drop) {
+                const unsigned long long e = (unsigned long long)n * p.F + (unsigned long long)(b0 + 2 * i);
+                qb[ks].x = att_keep(seed, e, p.th) ? qb[ks].x * p.s : 0.f;
+                qb[ks].y = att_keep(seed, e + 1, p.th) ? qb[ks].y * p.s : 0.f;
+            }
+            if (n >= p.N) pa[ks] = qb[ks] = f32x2{0.f, 0.f};
+        }
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+            for (int at = 0; at < 2; ++at)
+#pragma unroll
+                for (int bt = 0; bt < 2; ++bt)
+                    acc[at][bt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ks][at], qb[ks][bt], acc[at][bt], 0, 0, 0);
+        if (((b - lo) & (kFfnWgFlush - 1)) == kFfnWgFlush - 1) {
+#pragma unroll
+            for (int at = 0; at < 2; ++at)
+#pragma unroll
+                for (int bt = 0; bt < 2; ++bt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) tot[at][bt][r] = tot[at][bt][r] + acc[at][bt][r];
+                    acc[at][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
+    };
+    f32x2 pa0[8], qb0[8], pa1[8], qb1[8];      // two blocks: the next one's loads are in flight over this one's instructions
+    if (lo < hi) load(lo, pa0, qb0);
+    for (long long b = lo; b < hi; b += 2) {
+        if (b + 1 < hi) load(b + 1, pa1, qb1);
+        FFN_FENCE; comp(b, pa0, qb0); FFN_FENCE;
+        if (b + 1 < hi) {
+            if (b + 2 < hi) load(b + 2, pa0, qb0);
+            FFN_FENCE; comp(b + 1, pa1, qb1); FFN_FENCE;
+        }
+    }
+    // acc[at][bt][r]: row 2 (4 kq + r) + at, column 2 i + bt of the tile (the lanes' own column pairs on both sides)
+    float *mine = red + w * 32 * 33;
+#pragma unroll
+    for (int at = 0; at < 2; ++at)
+#pragma unroll
+        for (int bt = 0; bt < 2; ++bt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                mine[(2 * (4 * kq + r) + at) * 33 + 2 * i + bt] = tot[at][bt][r] + acc[at][bt][r];
+    __syncthreads();
+    for (int f = t; f < 32 * 32; f += 256) {
+        const int row = f >> 5, col = f & 31;
+        float v = red[row * 33 + col];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) v = v + red[k * 32 * 33 + row * 33 + col];
+        out[(size_t)(a0 + row) * lq + b0 + col] = v;
+    }
+}
+
+bool ffn_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+unsigned ffn_threshold(double p) {
+    const double t = nearbyint(p * 4294967296.0);
+    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+}
+
+int ffn_row_tiles(long long N) { return N > kFfnTallFrom ? 2 : 1; }
+
+// The checks the entry points share; `who` names the entry point in the message.
+int ffn_check(const char *who, int64_t N, int d, int F, double p) {
+    if (N < 0 || d < 1 || F < 1) {
+        set_error("%s: bad sizes (N=%lld, d=%d, F=%d)", who, (long long)N, d, F);
+        return RQHIP_EARG;
+    }
+    if (!(p >= 0.0 && p < 1.0)) {
+        set_error("%s: dropout probability p=%g outside 0 <= p < 1", who, p);
+        return RQHIP_EARG;
+    }
+    if (!ffn_supported(d, F)) {
+        set_error("%s: d=%d, F=%d: only multiples of 32 with 32 <= d <= %d and 32 <= F <= %d are implemented", who, d, F,
+                  kFfnMaxD, kFfnMaxF);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (N / 16 >= (1ll << 31) - 1) {
+        set_error("%s: N=%lld exceeds 16 rows per workgroup of a 2^31 grid", who, (long long)N);
+        return RQHIP_EUNSUPPORTED;
+    }
+    return RQHIP_OK;
+}
+
+template <int RT, int NP, bool BWD>
+int ffn_rows_launch(const FfnRows &p, hipStream_t s) {
+    static LdsGrant grant;
+    constexpr int T = 16 * RT;
+    const int bytes = (T * (p.d + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
+    // granted once per device: the most this instantiation can ask for (d <= 128 NP)
+    constexpr int most = (T * (128 * NP + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
+    RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_ffn_rows_kernel<RT, NP, BWD>), most));
+    hipLaunchKernelGGL((t5_ffn_rows_kernel<RT, NP, BWD>), dim3((unsigned)((p.N + T - 1) / T)), dim3(256), (size_t)bytes, s, p);
+    RQ_CHECK_LAUNCH("t5_ffn_rows_kernel");
+    return RQHIP_OK;
+}
+
+template <bool BWD>
+int ffn_rows(const FfnRows &p, hipStream_t s) {
+    const int np = (p.d / 32 + 3) / 4, rt = ffn_row_tiles(p.N);
+    if (rt == 1) {
+        if (np == 1) return ffn_rows_launch<1, 1, BWD>(p, s);
+        if (np == 2) return ffn_rows_launch<1, 2, BWD>(p, s);
+        if (np == 3) return ffn_rows_launch<1, 3, BWD>(p, s);
+        return ffn_rows_launch<1, 4, BWD>(p, s);
+    }
+    if (np == 1) return ffn_rows_launch<2, 1, BWD>(p, s);
+    if (np == 2) return ffn_rows_launch<2, 2, BWD>(p, s);
+    if (np == 3) return ffn_rows_launch<2, 3, BWD>(p, s);
+    return ffn_rows_launch<2, 4, BWD>(p, s);
+}
+
+}  // namespace
+
+}  // namespace rqhip
+
+using namespace rqhip;
+
+extern "C" int rqhip_t5_ffn_supported(int d, int F) { return ffn_supported(d, F) ? 1 : 0; }
+
+extern "C" size_t rqhip_t5_ffn_bwd_workspace_bytes(int64_t N, int d, int F) {
+    if (N < 0 || !ffn_supported(d, F)) return 0;
+    return (size_t)N * (size_t)F * sizeof(float);
+}
+
+extern "C" int rqhip_t5_ffn_fwd(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+                                const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
+    const int rc = ffn_check("t5_ffn_fwd", N, d, F, p);
+    if (rc != RQHIP_OK) return rc;
+    if (N == 0) return RQHIP_OK;
+    const unsigned th = ffn_threshold(p);
+    if (!x || !wi || !wo || !y) {
+        set_error("t5_ffn_fwd: null pointer (x, wi, wo, y)");
+        return RQHIP_EARG;
+    }
+    if (th && !seed) {
+        set_error("t5_ffn_fwd: dropout (p=%g) needs the seed, a one-element int64 device pointer", p);
+        return RQHIP_EARG;
+    }
+    if (!ffn_aligned16(x) || !ffn_aligned16(wi) || !ffn_aligned16(wo) || !ffn_aligned16(y) || !ffn_aligned16(h)) {
+        set_error("t5_ffn_fwd: x, wi, wo, y and h must be 16-byte aligned");
+        return RQHIP_EARG;
+    }
+    FfnRows a;
+    a.x = x, a.w1 = wi, a.w2 = wo, a.h_in = nullptr, a.mid = h, a.out = y;
+    a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = (float)(1.0 / (1.0 - p));
+    a.N = N, a.d = d, a.F = F;
+    return ffn_rows<false>(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo, const float *h, const float *d_y,
+                                int64_t N, int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi,
+                                float *d_wo, void *workspace, rqhip_stream_t stream) {
+    const int rc = ffn_check("t5_ffn_bwd", N, d, F, p);
+    if (rc != RQHIP_OK) return rc;
+    if (N == 0 || (!d_x && !d_wi && !d_wo)) return RQHIP_OK;
+    const unsigned th = ffn_threshold(p);
+    if (!x || !wi || !wo || !h || !d_y) {
+        set_error("t5_ffn_bwd: null pointer (x, wi, wo, h, d_y)");
+        return RQHIP_EARG;
+    }
+    if (th && !seed) {
+        set_error("t5_ffn_bwd: dropout (p=%g) needs the seed, a one-element int64 device pointer", p);
+        return RQHIP_EARG;
+    }
+    if (d_wi && !workspace) {
+        set_error("t5_ffn_bwd: d_wi needs a workspace of rqhip_t5_ffn_bwd_workspace_bytes(N, d, F) = %zu bytes",
+                  rqhip_t5_ffn_bwd_workspace_bytes(N, d, F));
+        return RQHIP_EWORKSPACE;
+    }
+    if (!ffn_aligned16(x) || !ffn_aligned16(wi) || !ffn_aligned16(wo) || !ffn_aligned16(h) || !ffn_aligned16(d_y) ||
+        !ffn_aligned16(d_x) || !ffn_aligned16(d_wi) || !ffn_aligned16(d_wo) || !ffn_aligned16(workspace)) {
+        set_error("t5_ffn_bwd: x, wi, wo, h, d_y, d_x, d_wi, d_wo and the workspace must be 16-byte aligned");
+        return RQHIP_EARG;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float *g = d_wi ? reinterpret_cast<float *>(workspace) : nullptr;
+    if (d_x || d_wi) {
+        FfnRows a;
+        a.x = d_y, a.w1 = wo, a.w2 = wi, a.h_in = h, a.mid = g, a.out = d_x;
+        a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = (float)(1.0 / (1.0 - p));
+        a.N = N, a.d = d, a.F = F;
+        const int rc1 = ffn_rows<true>(a, s);
+        if (rc1 != RQHIP_OK) return rc1;
+    }
+    if (d_wi || d_wo) {
+        FfnWgrad q;
+        q.g = g, q.x = x, q.dy = d_y, q.h = h, q.d_wi = d_wi, q.d_wo = d_wo;
+        q.seed = reinterpret_cast<const long long *>(seed), q.th = th, q.s = (float)(1.0 / (1.0 - p));
+        q.N = N, q.d = d, q.F = F;
+        const int tiles = (d / 32) * (F / 32);
+        q.tiles_wi = d_wi ? tiles : 0;
+        hipLaunchKernelGGL(t5_ffn_wgrad_kernel, dim3((unsigned)(q.tiles_wi + (d_wo ? tiles : 0))), dim3(256), 0, s, q);
+        RQ_CHECK_LAUNCH("t5_ffn_wgrad_kernel");
+    }
+    return RQHIP_OK;
+}

@@ -15,6 +15,11 @@ on the decoder's unsliced output and batch.sem_ids_fut as they are, with the dec
 (the state dict is unchanged).  It is taken when the decoder output is an fp32 device tensor and the shape is supported
 (ops.sid_head_loss_supported), under grad and under no_grad and with every attention_impl / norm_impl; otherwise the
 operators run, silently.  `generate` has its own head and is not affected.
+`model.ffn_impl = "hip"` (default "torch") makes the feed-forward body of every block of both stacks -- wi, ReLU,
+dropout, wo -- ONE autograd.T5FFNFunction call (csrc/t5_ffn.hip): one launch forward, at most two backward, one
+[rows, d_ff] tensor saved instead of three.  It is taken for fp32 device tensors with a supported (d_model, d_ff)
+(ops.t5_ffn_supported), in inference and training and with every attention_impl / norm_impl; otherwise the operators
+run, silently.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
@@ -103,6 +108,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.attention_impl = "torch"  # or "hip" / "hip_train"; handed to both T5 stacks whenever they are run
         self.norm_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.head_impl = "torch"  # or "hip": the heads and their losses of `forward` as one fused call
+        self.ffn_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
 
     @property
     def device(self) -> torch.device:
@@ -153,6 +159,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
     def _push_attention_impl(self) -> None:
         self.encoder.encoder.attention_impl = self.t5_decoder.attention_impl = self.attention_impl
         self.encoder.encoder.norm_impl = self.t5_decoder.norm_impl = self.norm_impl
+        self.encoder.encoder.ffn_impl = self.t5_decoder.ffn_impl = self.ffn_impl
 
     def encoder_forward_pass(self, attention_mask, input_ids, user_id=None):
         self._push_attention_impl()

@@ -42,6 +42,14 @@ residual add, the next sub-layer's RMS norm -- is ONE autograd.T5AddNormFunction
 dropout behind it.  In train mode the dropout seeds of a stack forward are one torch.randint of that many int64s.  It is
 taken for fp32 device tensors with a d_model the kernel supports, in eval and train mode, with and without grad, under
 every attention_impl; otherwise the operators run, silently.  The module tree and the state dict are the same.
+
+Feed-forward implementation: a stack's `ffn_impl` is "torch" (the default: wi, F.relu, nn.Dropout and wo as operators) or
+"hip": the feed-forward body of every block is then ONE autograd.T5FFNFunction call under grad (csrc/t5_ffn.hip: one
+launch forward, at most two backward, the ReLU output the only [rows, d_ff] tensor kept) or one ops.t5_ffn_fwd without
+that tensor under no_grad.  In train mode with dropout_rate > 0 the dropout inside the feed-forward happens in the
+kernel: on the "hip" norm path the stack's one torch.randint grows by num_layers seeds, on the other paths one seed is
+drawn per feed-forward.  It is taken for fp32 device tensors with a (d_model, d_ff) the kernel supports, in eval and
+train mode, with and without grad, under every attention_impl and norm_impl; otherwise the operators run, silently.
 """
 import math
 from typing import List, Optional, Tuple
@@ -52,11 +60,12 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops
-from rqhip.autograd import T5AddNormFunction, T5AttentionFunction
+from rqhip.autograd import T5AddNormFunction, T5AttentionFunction, T5FFNFunction
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
 NORM_IMPLS = ("torch", "hip")
+FFN_IMPLS = ("torch", "hip")
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -302,8 +311,14 @@ class T5DenseReluDense(nn.Module):
         self.wo = nn.Linear(config.d_ff, config.d_model, bias=False)
         self.dropout = nn.Dropout(config.dropout_rate)
 
-    def forward(self, x):
-        return self.wo(self.dropout(F.relu(self.wi(x))))
+    def forward(self, x, fused=None):
+        """fused: None (the operators) or (p, seed) of the "hip" feed-forward path: one fused call."""
+        if fused is None:
+            return self.wo(self.dropout(F.relu(self.wi(x))))
+        p, seed = fused
+        if torch.is_grad_enabled():
+            return T5FFNFunction.apply(x, self.wi.weight, self.wo.weight, p, seed)
+        return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False)[0]
 
 
 class T5LayerFF(nn.Module):
@@ -313,8 +328,8 @@ class T5LayerFF(nn.Module):
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
 
-    def forward(self, x):
-        return x + self.dropout(self.DenseReluDense(self.layer_norm(x)))
+    def forward(self, x, fused=None):
+        return x + self.dropout(self.DenseReluDense(self.layer_norm(x), fused))
 
 
 class T5Block(nn.Module):
@@ -341,6 +356,7 @@ class T5Stack(nn.Module):
         self.dropout = nn.Dropout(config.dropout_rate)
         self.attention_impl = "torch"  # or "hip" / "hip_train": see the module docstring
         self.norm_impl = "torch"  # or "hip": see the module docstring
+        self.ffn_impl = "torch"  # or "hip": see the module docstring
         init_t5_weights(self, config)
 
     def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
@@ -380,14 +396,30 @@ class T5Stack(nn.Module):
             raise ValueError(f"norm_impl must be one of {NORM_IMPLS}, got {self.norm_impl!r}")
         return self.norm_impl == "hip" and x.is_cuda and ops.t5_add_norm_supported(x.dtype, self.config.d_model)
 
+    def hip_ffn_active(self, x: Tensor) -> bool:
+        """Whether a forward of x takes the "hip" feed-forward path (module docstring)."""
+        if self.ffn_impl not in FFN_IMPLS:
+            raise ValueError(f"ffn_impl must be one of {FFN_IMPLS}, got {self.ffn_impl!r}")
+        return (self.ffn_impl == "hip" and x.is_cuda
+                and ops.t5_ffn_supported(x.dtype, self.config.d_model, self.config.d_ff))
+
+    def _ffn_plan(self, active: bool, device):
+        """What a T5LayerFF of the plain paths gets: None, or (p, one seed drawn for this feed-forward)."""
+        if not active:
+            return None
+        p = float(self.config.dropout_rate) if self.training else 0.0
+        return p, _draw_seed(p, device)
+
     def _forward_add_norm(self, inputs_embeds, self_body, cross_body, use_cache):
         """forward on the "hip" norm path.  self_body(i, attention, normed) -> (out, kv) and cross_body(i, attention,
         normed) -> out are the attention bodies of the path `forward` chose; one add-norm call between two bodies."""
         norms = [layer.layer_norm for blk in self.block for layer in blk.layer] + [self.final_layer_norm]
         p = float(self.config.dropout_rate) if self.training else 0.0
+        ffn = self.hip_ffn_active(inputs_embeds)
         seeds = None
-        if p > 0:  # one draw for the whole stack; a call gets a one-element view
-            seeds = torch.randint(0, 2 ** 62, (len(norms),), dtype=torch.int64, device=inputs_embeds.device)
+        if p > 0:  # one draw for the whole stack; a call gets a one-element view (the feed-forwards' behind the norms')
+            seeds = torch.randint(0, 2 ** 62, (len(norms) + (len(self.block) if ffn else 0),), dtype=torch.int64,
+                                  device=inputs_embeds.device)
 
         def add_norm(x, y, k):
             norm = norms[k]
@@ -405,7 +437,8 @@ class T5Stack(nn.Module):
                 k += 1
                 x, n = add_norm(x, cross_body(i, blk.layer[1].EncDecAttention, n), k)
             k += 1
-            x, n = add_norm(x, blk.layer[-1].DenseReluDense(n), k)
+            fused = (p, None if seeds is None else seeds[len(norms) + i:len(norms) + i + 1]) if ffn else None
+            x, n = add_norm(x, blk.layer[-1].DenseReluDense(n, fused), k)
         return (n, new_kv) if use_cache else n
 
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
@@ -428,6 +461,7 @@ class T5Stack(nn.Module):
         if self.hip_norm_active(inputs_embeds):
             return self._forward_add_norm(inputs_embeds, lambda i, att, n: att.self_attention_hip(n, plan, i),
                                           lambda i, att, n: att.cross_attention_hip(n, cross_kv[i], plan), use_cache)
+        ffn = self.hip_ffn_active(inputs_embeds)
         x = self.dropout(inputs_embeds)
         new_kv = []
         for i, blk in enumerate(self.block):
@@ -435,7 +469,7 @@ class T5Stack(nn.Module):
             new_kv.append(kv)
             if self.is_decoder:
                 x = blk.layer[1](x, cross_kv[i], None, hip=plan)
-            x = blk.layer[-1](x)
+            x = blk.layer[-1](x, self._ffn_plan(ffn, x.device))
         x = self.dropout(self.final_layer_norm(x))
         return (x, new_kv) if use_cache else x
 
@@ -483,6 +517,7 @@ class T5Stack(nn.Module):
                 inputs_embeds,
                 lambda i, att, n: att.self_attention(n, bias, mask, None if past_key_values is None else past_key_values[i]),
                 lambda i, att, n: att.cross_attention(n, cross_kv[i], cross_mask), use_cache)
+        ffn = self.hip_ffn_active(inputs_embeds)
         x = self.dropout(inputs_embeds)
         new_kv = []
         for i, blk in enumerate(self.block):
@@ -490,7 +525,7 @@ class T5Stack(nn.Module):
             new_kv.append(kv)
             if self.is_decoder:
                 x = blk.layer[1](x, cross_kv[i], cross_mask)
-            x = blk.layer[-1](x)
+            x = blk.layer[-1](x, self._ffn_plan(ffn, x.device))
         x = self.dropout(self.final_layer_norm(x))
         return (x, new_kv) if use_cache else x
 

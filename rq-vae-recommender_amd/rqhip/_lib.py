@@ -111,6 +111,10 @@ SIGNATURES = {
     "rqhip_t5_add_norm_fwd": (_int, [_vp, _vp, _vp, _i64, _int, _f32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "rqhip_t5_add_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp,
                                      _sz, _vp]),
+    "rqhip_t5_ffn_supported": (_int, [_int, _int]),
+    "rqhip_t5_ffn_bwd_workspace_bytes": (_sz, [_i64, _int, _int]),
+    "rqhip_t5_ffn_fwd": (_int, [_vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rqhip_sid_head_loss_supported": (_int, [_int, _int, _int]),
     "rqhip_sid_head_loss_fwd": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp,
                                        _vp, _vp]),

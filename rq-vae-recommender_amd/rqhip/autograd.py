@@ -324,6 +324,30 @@ class T5AddNormFunction(torch.autograd.Function):
         return d_x, d_y, d_w, None, None, None, None
 
 
+class T5FFNFunction(torch.autograd.Function):
+    """The T5 feed-forward body (modules/t5.py, ffn_impl = "hip") as one launch forward and at most two backward
+    (ops.t5_ffn_fwd / ops.t5_ffn_bwd): apply(x, wi, wo, p, seed) -> y = dropout(relu(x @ wi.T), p) @ wo.T.  Saved: x, the
+    ReLU output h, the two weights and the seed; the dropout decisions are recomputed.  Gradients: x, wi and wo, each
+    only when needed."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor]):
+        y, h = ops.t5_ffn_fwd(x, wi, wo, p, seed)
+        ctx.save_for_backward(x, h, wi, wo, seed)
+        ctx.p = p
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y: Tensor):
+        x, h, wi, wo, seed = ctx.saved_tensors
+        need_x, need_wi, need_wo = ctx.needs_input_grad[:3]
+        if not (need_x or need_wi or need_wo):
+            return None, None, None, None, None
+        d_x, d_wi, d_wo = ops.t5_ffn_bwd(x, wi, wo, h, _dense(d_y), ctx.p, seed, need_x=need_x, need_wi=need_wi,
+                                         need_wo=need_wo)
+        return d_x, d_wi, d_wo, None, None
+
+
 class SidHeadLossFunction(torch.autograd.Function):
     """The retrieval model's L semantic-id heads and their cross-entropy losses (modules/model.py, head_impl = "hip") as
     one call forward and one backward (ops.sid_head_loss_fwd / ops.sid_head_loss_bwd): apply(x, target, *weights) ->

@@ -818,6 +818,76 @@ def t5_add_norm_bwd(x_new: Tensor, rstd: Tensor, w: Tensor, d_n: Optional[Tensor
     return d_x, (d_x if shared else d_y), d_w
 
 
+def t5_ffn_supported(dtype: torch.dtype, d: int, F: int) -> bool:
+    """Whether t5_ffn_fwd / t5_ffn_bwd implement this (d_model, d_ff) (rqhip_t5_ffn_supported): fp32, d a multiple of 32
+    in 32 .. 512, F a multiple of 32 in 32 .. 8192."""
+    return dtype == torch.float32 and bool(_lib.lib().rqhip_t5_ffn_supported(int(d), int(F)))
+
+
+def _ffn_call(who: str, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor]):
+    """The checks and copies t5_ffn_fwd and t5_ffn_bwd share -> (x, wi, wo as the kernels read them, N, d, F)."""
+    x = _norm_rows(x, "x", who)
+    d = x.shape[-1]
+    if wi.dtype != torch.float32 or wi.dim() != 2 or wi.shape[1] != d:
+        raise RqHipError(f"{who}: wi must be float32 [F, {d}], got {wi.dtype} {tuple(wi.shape)}")
+    F = wi.shape[0]
+    if wo.dtype != torch.float32 or tuple(wo.shape) != (d, F):
+        raise RqHipError(f"{who}: wo must be float32 [{d}, {F}], got {wo.dtype} {tuple(wo.shape)}")
+    if not 0.0 <= p < 1.0:
+        raise RqHipError(f"{who}: p={p} outside 0 <= p < 1")
+    if p > 0 and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
+        raise RqHipError(f"{who}: dropout (p={p}) needs `seed`, a one-element int64 device tensor")
+    if not t5_ffn_supported(x.dtype, d, F):
+        raise RqHipError(f"{who}: (d, F) = ({d}, {F}) is not supported (multiples of 32, d <= 512, F <= 8192)")
+    return x, _aligned16(wi.contiguous()), _aligned16(wo.contiguous()), (x.numel() // d), d, F
+
+
+def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *, need_h: bool = True):
+    """The T5 feed-forward body in one launch (rqhip_t5_ffn_fwd) -> (y, h or None): h = relu(x @ wi.T), y = dropout(h, p)
+    @ wo.T.  x [..., d] float32, wi [F, d] and wo [d, F] the two Linear weights as stored; y has x's shape, h is
+    [..., F] (the one tensor t5_ffn_bwd needs; not stored without need_h).  The mask is t5_attention_dropout_keep(seed,
+    1, 1, N, F, p)[0, 0] over the N = x.numel() / d rows; `seed` is a one-element int64 device tensor the host never
+    reads."""
+    _need_gpu(x, wi, wo, seed)
+    x, wi, wo, N, d, F = _ffn_call("t5_ffn_fwd", x, wi, wo, p, seed)
+    dev = x.device
+    with torch.cuda.device(dev):
+        y = torch.empty_like(x)
+        h = torch.empty(x.shape[:-1] + (F,), dtype=torch.float32, device=dev) if need_h else None
+        rc = _lib.lib().rqhip_t5_ffn_fwd(_ptr(x), _ptr(wi), _ptr(wo), N, d, F, float(p), _ptr(seed) if p > 0 else None,
+                                         _ptr(y), _ptr(h), _stream())
+        check(rc, "rqhip_t5_ffn_fwd")
+    return y, h
+
+
+def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *,
+               need_x: bool = True, need_wi: bool = True, need_wo: bool = True):
+    """The gradients of t5_ffn_fwd in one call of at most two launches (rqhip_t5_ffn_bwd) -> (d_x, d_wi, d_wo), None
+    where not needed.  x, wi, wo, p, seed: the forward's; h: its second result; d_y: the gradient of y.  The dropout
+    decisions are recomputed from the seed; the weight gradients are summed without atomics in an order that depends on
+    the shape alone.  The [N, F] workspace comes from torch's allocator."""
+    _need_gpu(x, wi, wo, h, d_y, seed)
+    who = "t5_ffn_bwd"
+    x, wi, wo, N, d, F = _ffn_call(who, x, wi, wo, p, seed)
+    h = _norm_rows(h, "h", who, x.shape[:-1] + (F,))
+    d_y = _norm_rows(d_y, "d_y", who, x.shape)
+    dev = x.device
+    with torch.cuda.device(dev):
+        d_x = torch.empty_like(x) if need_x else None
+        make = torch.zeros if N == 0 else torch.empty      # without rows the sums are empty
+        d_wi = make((F, d), dtype=torch.float32, device=dev) if need_wi else None
+        d_wo = make((d, F), dtype=torch.float32, device=dev) if need_wo else None
+        work = None
+        if need_wi and N > 0:
+            nbytes = int(_lib.lib().rqhip_t5_ffn_bwd_workspace_bytes(N, d, F))
+            work = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_ffn_bwd(_ptr(x), _ptr(wi), _ptr(wo), _ptr(h), _ptr(d_y), N, d, F, float(p),
+                                         _ptr(seed) if p > 0 else None, _ptr(d_x), _ptr(d_wi), _ptr(d_wo), _ptr(work),
+                                         _stream())
+        check(rc, "rqhip_t5_ffn_bwd")
+    return d_x, d_wi, d_wo
+
+
 def sid_head_loss_supported(dtype: torch.dtype, d: int, K: int, L: int) -> bool:
     """Whether sid_head_loss_fwd / sid_head_loss_bwd implement this shape (rqhip_sid_head_loss_supported): fp32, d a
     multiple of 4 in 4 .. 1024, K in 1 .. 1024 codes, L in 1 .. 8 levels."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) in four arms:
+tails: encoder T = 81, decoder T = 4) in five arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
@@ -10,14 +10,17 @@ tails: encoder T = 81, decoder T = 4) in four arms:
              as one ops.t5_add_norm_fwd launch and one ops.t5_add_norm_bwd call
   hip_train+norm+head  hip_train+norm with head_impl = "hip": the three heads and their cross-entropy losses as one
              ops.sid_head_loss_fwd call and one ops.sid_head_loss_bwd launch
+  hip_train+norm+head+ffn  hip_train+norm+head with ffn_impl = "hip": each feed-forward body (wi, ReLU, dropout, wo) as
+             one ops.t5_ffn_fwd launch and one ops.t5_ffn_bwd call of two launches
 
 The arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
 median and the fastest step per arm over all blocks, the median of each block (their spread is what a difference
 between two arms has to exceed), and the peak torch.cuda.max_memory_allocated of a block, as one
 JSON line per arm plus a summary line; --out also writes them to a text file (profiles/retrieval_train_step_norm.txt
-holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run; profiles/retrieval_train_step.txt is the
-older two-arm run; none of them is to be overwritten or compared against: two arms are compared within one run only).
+holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run, profiles/retrieval_train_step_ffn.txt a
+five-arm run; profiles/retrieval_train_step.txt is the older two-arm run; none of them is to be overwritten or compared
+against: two arms are compared within one run only).
 --arms picks a subset, e.g. one arm under a kernel trace to count its launches per step.
 
     python tools/bench_retrieval_train.py [--runs 5] [--warmup 3] [--iters 10] [--batch 64] [--arms A,B] [--out FILE]
@@ -37,9 +40,10 @@ import torch  # noqa: E402
 from data.schemas import TokenizedSeqBatch  # noqa: E402
 from modules.model import EncoderDecoderRetrievalModel  # noqa: E402
 
-# arm -> (attention_impl, norm_impl, head_impl)
-ARMS = {"torch": ("torch", "torch", "torch"), "hip_train": ("hip_train", "torch", "torch"),
-        "hip_train+norm": ("hip_train", "hip", "torch"), "hip_train+norm+head": ("hip_train", "hip", "hip")}
+# arm -> (attention_impl, norm_impl, head_impl, ffn_impl)
+ARMS = {"torch": ("torch", "torch", "torch", "torch"), "hip_train": ("hip_train", "torch", "torch", "torch"),
+        "hip_train+norm": ("hip_train", "hip", "torch", "torch"), "hip_train+norm+head": ("hip_train", "hip", "hip", "torch"),
+        "hip_train+norm+head+ffn": ("hip_train", "hip", "hip", "hip")}
 
 
 def make_batch(B, items, L, K, N, dev, seed):
@@ -62,7 +66,7 @@ def make_batch(B, items, L, K, N, dev, seed):
 def block(model, state, batch, arm, warmup, iters):
     """One block of one arm from the common starting weights -> (ms per step, peak bytes, last loss)."""
     model.load_state_dict(state)
-    model.attention_impl, model.norm_impl, model.head_impl = ARMS[arm]
+    model.attention_impl, model.norm_impl, model.head_impl, model.ffn_impl = ARMS[arm]
     model.train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3)
     torch.manual_seed(0)
@@ -114,13 +118,15 @@ def main():
     lines = []
     for arm in arms:
         lines.append(json.dumps({"arm": arm, "attention_impl": ARMS[arm][0], "norm_impl": ARMS[arm][1],
-                                 "head_impl": ARMS[arm][2], "batch": args.batch, "steps_timed": len(times[arm]),
+                                 "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3], "batch": args.batch,
+                                 "steps_timed": len(times[arm]),
                                  "ms_per_step_median": round(statistics.median(times[arm]), 3),
                                  "ms_per_step_min": round(min(times[arm]), 3), "block_medians": blocks[arm],
                                  "peak_allocated_MiB": round(peak[arm] / 2 ** 20, 1),
                                  "last_loss": round(loss[arm], 4)}))
     summary = {"summary": "median step, first arm / second arm"}
-    for a, b in (("torch", "hip_train"), ("hip_train", "hip_train+norm"), ("hip_train+norm", "hip_train+norm+head")):
+    for a, b in (("torch", "hip_train"), ("hip_train", "hip_train+norm"), ("hip_train+norm", "hip_train+norm+head"),
+                 ("hip_train+norm+head", "hip_train+norm+head+ffn")):
         if a in arms and b in arms:
             summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
             summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)
