@@ -713,6 +713,26 @@ int rqhip_adamw_step(float *const *p, const float *const *g, float *const *m, fl
                      float *step, unsigned *scratch, float lr, float beta1, float beta2, float eps, float weight_decay,
                      rqhip_stream_t stream);
 
+/* The optimizer tail of the retrieval model's training loop (reference train_decoder.py:147-151, 202-205: clip_grad_norm_, AdamW,
+ * InverseSquareRootScheduler) with every scalar formed on the device, so that a captured hipGraph replays this step's clip coefficient
+ * and learning rate rather than the capture's.  Tensors, `step` and the AdamW hyper-parameters as for the adamw_step call above.  In order:
+ *   max_norm > 0: norm = 2-norm of all gradients (one fp32 partial per 1024 elements in `workspace`, stored and summed in a fixed order:
+ *     the same bits on every run), coef = min(1, max_norm / (norm + 1e-6)) as torch.nn.utils.clip_grad_norm_; max_norm <= 0: coef = 1,
+ *     norm = NaN (not computed), workspace unused;
+ *   warmup >= 0: lr = base_lr if *lr_step <= warmup else base_lr sqrt(warmup) / sqrt(*lr_step) (in double, rounded once), then
+ *     *lr_step += 1 (device int64); warmup < 0: lr = the argument `lr`, lr_step unused (may be null);
+ *   the update of the adamw_step call above with g coef in place of g (gradients are not written back).
+ * `scalars`: RQHIP_ADAMW_TAIL_SCALARS device floats, 16-byte aligned, written by the call: [0] lr / (1 - beta1^t), [1] sqrt(1 - beta2^t),
+ * [2] lr, [3] coef, [4] norm.  With max_norm <= 0 and warmup < 0, [0] and [1] and the updated tensors are adamw_step's bits.
+ * rqhip_adamw_tail_workspace_bytes needs no GPU; -1 (and an error message) for a negative count, a null list or a negative numel.
+ * All arguments are checked before the first launch. */
+#define RQHIP_ADAMW_TAIL_SCALARS 8
+int64_t rqhip_adamw_tail_workspace_bytes(const int64_t *numel, int n);
+int rqhip_adamw_tail_step(float *const *p, const float *const *g, float *const *m, float *const *v, const int64_t *numel, int n,
+                          float *step, int64_t *lr_step, float *scalars, float *workspace, size_t workspace_bytes, float max_norm,
+                          float lr, double base_lr, int64_t warmup, float beta1, float beta2, float eps, float weight_decay,
+                          rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Kernel timing for bench.py's roofline objects (no reference counterpart).  While enabled, the calls below bracket
  * their MAIN kernel(s) with a hipEvent pair recorded on the call's stream and note what the launch was: a tag, its

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) in five arms:
+tails: encoder T = 81, decoder T = 4) in six arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
@@ -12,6 +12,8 @@ tails: encoder T = 81, decoder T = 4) in five arms:
              ops.sid_head_loss_fwd call and one ops.sid_head_loss_bwd launch
   hip_train+norm+head+ffn  hip_train+norm+head with ffn_impl = "hip": each feed-forward body (wi, ReLU, dropout, wo) as
              one ops.t5_ffn_fwd launch and one ops.t5_ffn_bwd call of two launches
+  hip_train+norm+head+ffn+optim  hip_train+norm+head+ffn stepped by rqhip.optim.FlatAdamW (csrc/adamw.hip: one bump launch and
+             one update launch per 24 tensors) instead of torch.optim.AdamW; no clipping and no schedule, as in the other arms
 
 The arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
@@ -19,7 +21,8 @@ median and the fastest step per arm over all blocks, the median of each block (t
 between two arms has to exceed), and the peak torch.cuda.max_memory_allocated of a block, as one
 JSON line per arm plus a summary line; --out also writes them to a text file (profiles/retrieval_train_step_norm.txt
 holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run, profiles/retrieval_train_step_ffn.txt a
-five-arm run; profiles/retrieval_train_step.txt is the older two-arm run; none of them is to be overwritten or compared
+five-arm run, profiles/retrieval_optim_tail.txt a six-arm run; profiles/retrieval_train_step.txt is the older two-arm run; none
+of them is to be overwritten or compared
 against: two arms are compared within one run only).
 --arms picks a subset, e.g. one arm under a kernel trace to count its launches per step.
 
@@ -43,7 +46,9 @@ from modules.model import EncoderDecoderRetrievalModel  # noqa: E402
 # arm -> (attention_impl, norm_impl, head_impl, ffn_impl)
 ARMS = {"torch": ("torch", "torch", "torch", "torch"), "hip_train": ("hip_train", "torch", "torch", "torch"),
         "hip_train+norm": ("hip_train", "hip", "torch", "torch"), "hip_train+norm+head": ("hip_train", "hip", "hip", "torch"),
-        "hip_train+norm+head+ffn": ("hip_train", "hip", "hip", "hip")}
+        "hip_train+norm+head+ffn": ("hip_train", "hip", "hip", "hip"),
+        "hip_train+norm+head+ffn+optim": ("hip_train", "hip", "hip", "hip")}
+FLAT_ADAMW = ("hip_train+norm+head+ffn+optim",)      # arms stepped by rqhip.optim.FlatAdamW; the others by torch.optim.AdamW
 
 
 def make_batch(B, items, L, K, N, dev, seed):
@@ -68,7 +73,11 @@ def block(model, state, batch, arm, warmup, iters):
     model.load_state_dict(state)
     model.attention_impl, model.norm_impl, model.head_impl, model.ffn_impl = ARMS[arm]
     model.train()
-    opt = torch.optim.AdamW(model.parameters(), lr=1e-3)
+    if arm in FLAT_ADAMW:
+        from rqhip.optim import FlatAdamW
+        opt = FlatAdamW(model.parameters(), lr=1e-3)
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=1e-3)
     torch.manual_seed(0)
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -118,7 +127,8 @@ def main():
     lines = []
     for arm in arms:
         lines.append(json.dumps({"arm": arm, "attention_impl": ARMS[arm][0], "norm_impl": ARMS[arm][1],
-                                 "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3], "batch": args.batch,
+                                 "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3],
+                                 "optimizer": "FlatAdamW" if arm in FLAT_ADAMW else "torch.optim.AdamW", "batch": args.batch,
                                  "steps_timed": len(times[arm]),
                                  "ms_per_step_median": round(statistics.median(times[arm]), 3),
                                  "ms_per_step_min": round(min(times[arm]), 3), "block_medians": blocks[arm],
@@ -126,7 +136,8 @@ def main():
                                  "last_loss": round(loss[arm], 4)}))
     summary = {"summary": "median step, first arm / second arm"}
     for a, b in (("torch", "hip_train"), ("hip_train", "hip_train+norm"), ("hip_train+norm", "hip_train+norm+head"),
-                 ("hip_train+norm+head", "hip_train+norm+head+ffn")):
+                 ("hip_train+norm+head", "hip_train+norm+head+ffn"),
+                 ("hip_train+norm+head+ffn", "hip_train+norm+head+ffn+optim")):
         if a in arms and b in arms:
             summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
             summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)

@@ -16,7 +16,11 @@ replacement returns what torch.multinomial returns under the same seed, for the 
 
 retrieval_state_dict.npz holds the names and shapes of the default config's state_dict() and its parameter count.
 
-    python tools/gen_retrieval_golden.py
+inv_sqrt_sched.npz is recorded from the reference's modules/scheduler/inv_sqrt.py:InverseSquareRootScheduler on a CPU
+torch.optim.AdamW (base lr 1e-3, 8 optimizer steps, warm-up 3 and warm-up 1): per case the lr each optimizer step ran at,
+get_last_lr() after each scheduler step, and last_epoch / _step_count after the fourth; plus the key names of its state dict.
+
+    python tools/gen_retrieval_golden.py [--sched-only]
 """
 from __future__ import annotations
 
@@ -169,9 +173,44 @@ def gen_state_dict(m) -> None:
     print(f"{path}: {len(names)} entries, {n_params} parameters")
 
 
+SCHED_CASES = {"w3": dict(base_lr=1e-3, warmup=3, steps=8), "w1": dict(base_lr=1e-3, warmup=1, steps=8)}
+
+
+def gen_inv_sqrt_sched() -> None:
+    """The reference's train_decoder.py loop around its scheduler: optimizer.step(), then lr_scheduler.step()."""
+    from modules.scheduler.inv_sqrt import InverseSquareRootScheduler  # (the reference's: REF is first on sys.path)
+    assert os.path.abspath(sys.modules[InverseSquareRootScheduler.__module__].__file__).startswith(os.path.abspath(REF))
+    rec = {}
+    for name, c in SCHED_CASES.items():
+        p = torch.nn.Parameter(torch.ones(3))
+        opt = torch.optim.AdamW([p], lr=c["base_lr"])
+        sched = InverseSquareRootScheduler(optimizer=opt, warmup_steps=c["warmup"])
+        used, last = [], []
+        for t in range(c["steps"]):
+            p.grad = torch.ones(3)
+            used.append(opt.param_groups[0]["lr"])
+            opt.step()
+            sched.step()
+            last.append(sched.get_last_lr()[0])
+            if t == 3:
+                sd = sched.state_dict()
+                rec[f"{name}.after4"] = np.array([sd["last_epoch"], sd["_step_count"]], dtype=np.int64)
+        rec[f"{name}.lr_used"] = np.array(used, dtype=np.float64)
+        rec[f"{name}.last_lr"] = np.array(last, dtype=np.float64)
+        rec[f"{name}.config"] = np.array([c["base_lr"], c["warmup"], c["steps"]], dtype=np.float64)
+    rec["state_dict_keys"] = np.array(sorted(sched.state_dict().keys()))
+    path = os.path.join(OUT, "inv_sqrt_sched.npz")
+    np.savez_compressed(path, **rec)
+    assert os.path.getsize(path) < MAX_BYTES
+    print(f"{path}: {os.path.getsize(path)} bytes, keys {list(rec['state_dict_keys'])}, w3 lrs {rec['w3.lr_used']}")
+
+
 def main() -> None:
     m, sch = import_reference()
     torch.set_num_threads(4)
+    gen_inv_sqrt_sched()
+    if sys.argv[1:] == ["--sched-only"]:
+        return
     gen_state_dict(m)
     for name, c in CASES.items():
         gen_case(m, sch, name, c)
