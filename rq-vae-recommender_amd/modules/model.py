@@ -2,24 +2,15 @@
 next item's ids one hierarchy level at a time.  API and state dict of the reference's modules/model.py
 (EncoderDecoderRetrievalModel), so a checkpoint trained there loads here with strict=True.
 
-The T5 body runs on torch operators (modules/t5.py), or, with `model.attention_impl = "hip"` (a plain attribute, default
-"torch"; inference only, see modules/t5.py), with every attention call as one HIP launch (ops.t5_attention) and the
-decoder's self-attention history of `generate` in per-position slabs that are never copied.  "hip_train" is "hip" that
-also runs under grad: every attention of a training step is then one fused forward and one fused backward launch.
-`model.norm_impl = "hip"` (default "torch") makes everything between two sub-layer bodies of both stacks -- dropout,
-residual add, the next RMS norm -- one launch forward and one backward (ops.t5_add_norm_fwd / _bwd), under either
-attention implementation, in inference and training.
+The T5 body runs on torch operators, or on fused HIP calls chosen by three plain attributes that are handed to both
+stacks whenever they are run: `model.attention_impl` ("torch", the default, "hip" or "hip_train"), `model.norm_impl` and
+`model.ffn_impl` ("torch", the default, or "hip").  What each replaces and when it is taken: modules/t5.py.
 `model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
 cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
 on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
 (the state dict is unchanged).  It is taken when the decoder output is an fp32 device tensor and the shape is supported
 (ops.sid_head_loss_supported), under grad and under no_grad and with every attention_impl / norm_impl; otherwise the
 operators run, silently.  `generate` has its own head and is not affected.
-`model.ffn_impl = "hip"` (default "torch") makes the feed-forward body of every block of both stacks -- wi, ReLU,
-dropout, wo -- ONE autograd.T5FFNFunction call (csrc/t5_ffn.hip): one launch forward, at most two backward, one
-[rows, d_ff] tensor saved instead of three.  It is taken for fp32 device tensors with a supported (d_model, d_ff)
-(ops.t5_ffn_supported), in inference and training and with every attention_impl / norm_impl; otherwise the operators
-run, silently.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
@@ -157,9 +148,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return self._prefix_index_for_codebooks().check_valid_prefix(prefix, batch_size)
 
     def _push_attention_impl(self) -> None:
-        self.encoder.encoder.attention_impl = self.t5_decoder.attention_impl = self.attention_impl
-        self.encoder.encoder.norm_impl = self.t5_decoder.norm_impl = self.norm_impl
-        self.encoder.encoder.ffn_impl = self.t5_decoder.ffn_impl = self.ffn_impl
+        for name in ("attention_impl", "norm_impl", "ffn_impl"):
+            for stack in (self.encoder.encoder, self.t5_decoder):
+                setattr(stack, name, getattr(self, name))
 
     def encoder_forward_pass(self, attention_mask, input_ids, user_id=None):
         self._push_attention_impl()

@@ -18,38 +18,34 @@ The decoder can run incrementally: `T5Stack.forward` takes and returns a self-at
 block, [rows, heads, t, 64]) and accepts precomputed cross-attention K/V (`cross_kv`) on fewer rows than the queries:
 rows r = b * beams + beam all read user b's encoder output, as the beams of a beam search do.
 
-Attention implementation: a stack's `attention_impl` is "torch" (the default: the operators above) or "hip": every
-attention call is then ONE launch of ops.t5_attention (csrc/t5_attention.hip), fed the q / k / v Linears' outputs as
-they are and a [n_delta, heads] table of the relative-position bias by j - i.  "hip" is taken only for fp32 device
-tensors with grad disabled, dropout inactive (eval mode), no operator-format cache passed in and a shape the kernel
-supports; otherwise the operators run, silently.  The incremental decoder of the "hip" path keeps its self-attention
-K/V in per-position slabs (`T5DecodeCache`) that are written once and never copied: a beam search reorders an int32
-ancestor table instead of the cache.
+A stack forward chooses an attention body, a glue and a feed-forward body, then runs ONE loop over its blocks:
+self-attention, cross-attention (decoder), feed-forward, with a glue call between every two bodies.  Each of the three
+attributes below is "torch" (the default: the operators above) or names a fused form.  That form is taken for fp32
+device tensors and a shape its kernel supports, under every setting of the other two attributes; otherwise the
+operators run, silently.  The module tree and the state dict are the same on every path.
 
-"hip_train" is "hip" under no_grad (the same launches, decode cache included) and, with grad enabled, makes every
-attention of a stack forward one autograd.T5AttentionFunction call: a forward launch that keeps the row log-sum-exp
-instead of the weights, and one backward launch that recomputes them.  In train mode with dropout_rate > 0 the
-attention-weight dropout happens in the kernel, from a seed drawn per call on the device with torch.randint (the
-default generator: torch.manual_seed reproduces a run); every other dropout stays torch's.  It needs fp32 device
-tensors, one K/V per query row (beams = 1), no operator-format cache and a shape the backward supports; otherwise the
-operators run, silently.  A decode_cache under grad raises.
+- `attention_impl` = "hip": every attention call is ONE launch of ops.t5_attention (csrc/t5_attention.hip), fed the
+  q / k / v Linears' outputs as they are and a [n_delta, heads] table of the relative-position bias by j - i.  Taken
+  only with grad disabled, dropout inactive (eval mode) and no operator-format cache passed in.  Its incremental
+  decoder keeps the self-attention K/V in per-position slabs (`T5DecodeCache`) that are written once and never copied:
+  a beam search reorders an int32 ancestor table instead of the cache.
+  "hip_train" is "hip" under no_grad (the same launches, decode cache included) and, with grad enabled, makes every
+  attention one autograd.T5AttentionFunction call: a forward launch that keeps the row log-sum-exp instead of the
+  weights, and one backward launch that recomputes them.  In train mode with dropout_rate > 0 the attention-weight
+  dropout happens in the kernel; every other dropout stays torch's.  It needs one K/V per query row (beams = 1), no
+  operator-format cache and a shape the backward supports.  A decode_cache under grad raises.
+- `norm_impl` = "hip": the glue -- the dropout of a sub-layer's output, the residual add and the next sub-layer's RMS
+  norm -- is ONE autograd.T5AddNormFunction call (csrc/t5_add_norm.hip), in eval and train mode, with and without grad:
+  2 * layers + 1 calls per encoder forward, 3 * layers + 1 per decoder forward, the first on the input embeddings
+  alone, the last with the final norm's weight and the dropout behind it.
+- `ffn_impl` = "hip": every feed-forward body is ONE autograd.T5FFNFunction call under grad (csrc/t5_ffn.hip: one
+  launch forward, at most two backward, the ReLU output the only [rows, d_ff] tensor kept) or one ops.t5_ffn_fwd
+  without that tensor under no_grad, in eval and train mode; in train mode its inner dropout happens in the kernel.
 
-Norm implementation: a stack's `norm_impl` is "torch" (the default: T5LayerNorm, nn.Dropout and the residual add as
-operators) or "hip": the stack then drives the sub-layer bodies itself (the attention of either implementation, the
-feed-forward) on the normed input, and everything between two bodies -- the dropout of the sub-layer's output, the
-residual add, the next sub-layer's RMS norm -- is ONE autograd.T5AddNormFunction call (csrc/t5_add_norm.hip): 2 * layers
-+ 1 calls per encoder forward, 3 * layers + 1 per decoder forward, the last one with the final norm's weight and the
-dropout behind it.  In train mode the dropout seeds of a stack forward are one torch.randint of that many int64s.  It is
-taken for fp32 device tensors with a d_model the kernel supports, in eval and train mode, with and without grad, under
-every attention_impl; otherwise the operators run, silently.  The module tree and the state dict are the same.
-
-Feed-forward implementation: a stack's `ffn_impl` is "torch" (the default: wi, F.relu, nn.Dropout and wo as operators) or
-"hip": the feed-forward body of every block is then ONE autograd.T5FFNFunction call under grad (csrc/t5_ffn.hip: one
-launch forward, at most two backward, the ReLU output the only [rows, d_ff] tensor kept) or one ops.t5_ffn_fwd without
-that tensor under no_grad.  In train mode with dropout_rate > 0 the dropout inside the feed-forward happens in the
-kernel: on the "hip" norm path the stack's one torch.randint grows by num_layers seeds, on the other paths one seed is
-drawn per feed-forward.  It is taken for fp32 device tensors with a (d_model, d_ff) the kernel supports, in eval and
-train mode, with and without grad, under every attention_impl and norm_impl; otherwise the operators run, silently.
+The fused forms take their dropout seeds as int64s drawn on the device with torch.randint (the default generator:
+torch.manual_seed reproduces a run), none in eval mode or at dropout_rate 0.  The fused attention draws one per call.
+With the "hip" glue a stack forward draws once before its first body, one seed per glue call and behind them one per
+fused feed-forward; with the operator glue each fused feed-forward draws its own, immediately before its sub-layer.
 """
 import math
 from typing import List, Optional, Tuple
@@ -148,14 +144,24 @@ def advance_ancestors(anc: Tensor, parent: Tensor, pos: int) -> Tensor:
     return out
 
 
-class _HipPlan:
-    """What a stack forward on the "hip" path computes once for all its blocks."""
-    __slots__ = ("table", "offset", "key_mask", "causal", "past", "cross_mask", "cache", "train", "p")
+def _draw_seed(p: float, device, n: int = 1) -> Optional[Tensor]:
+    """Dropout seeds of fused calls: n int64s from one draw on the device, never read by the host."""
+    return torch.randint(0, 2 ** 62, (n,), dtype=torch.int64, device=device) if p > 0 else None
 
 
-def _draw_seed(p: float, device) -> Optional[Tensor]:
-    """The dropout seed of one fused attention call: one int64 drawn on the device, never read by the host."""
-    return torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=device) if p > 0 else None
+class _Seeds:
+    """Where the seeds of a stack forward's glue and feed-forward calls come from (module docstring).  n_glue > 0 (the
+    "hip" glue): one draw now of n_glue + n_ffn seeds, a call gets a one-element view; else every feed-forward draws."""
+
+    def __init__(self, p: float, device, n_glue: int, n_ffn: int) -> None:
+        self.p, self.device, self.n_glue = p, device, n_glue
+        self.drawn = _draw_seed(p, device, n_glue + n_ffn) if n_glue else None
+
+    def glue(self, k: int) -> Optional[Tensor]:
+        return None if self.drawn is None else self.drawn[k:k + 1]
+
+    def ffn(self, i: int) -> Optional[Tensor]:
+        return self.glue(self.n_glue + i) if self.n_glue else _draw_seed(self.p, self.device)
 
 
 def _attend(module: nn.Module, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], mask: Optional[Tensor]) -> Tensor:
@@ -244,51 +250,92 @@ class T5Attention(nn.Module):
             out = out.view(B, self.n_heads, beams, T, self.d_kv).transpose(1, 2).reshape(R, self.n_heads, T, self.d_kv)
         return self.o(out.transpose(1, 2).reshape(R, T, -1))
 
-    def self_attention_hip(self, x: Tensor, plan: _HipPlan, block: int) -> Tuple[Tensor, KV]:
-        """self_attention as one launch; with plan.cache the K/V projections go straight into their slabs."""
-        R = x.shape[0]
-        q = self.q(x)
-        if plan.train:
-            k, v = self.k(x), self.v(x)
-            out = T5AttentionFunction.apply(q, k, v, plan.table, self.n_heads, plan.offset, plan.key_mask, plan.causal,
-                                            plan.p, _draw_seed(plan.p, x.device))
-            return self.o(out), (self._heads(k), self._heads(v))
-        if plan.cache is None:
-            k, v = self.k(x), self.v(x)
-            out = ops.t5_attention(q, k, v, self.n_heads, bias_by_delta=plan.table, bias_offset=plan.offset,
-                                   key_mask=plan.key_mask, causal=plan.causal)
-            return self.o(out), (self._heads(k), self._heads(v))
-        ks, vs = plan.cache.slabs[block]
-        pos = plan.cache.pos
-        x2 = x.reshape(R, -1)
-        torch.mm(x2, self.k.weight.t(), out=ks[pos, :R])
-        torch.mm(x2, self.v.weight.t(), out=vs[pos, :R])
-        out = ops.t5_attention(q, ks, vs, self.n_heads, bias_by_delta=plan.table, bias_offset=plan.offset, past=pos,
-                               anc=plan.cache.anc[:R])
-        return self.o(out), (ks, vs)
 
-    def cross_attention_hip(self, x: Tensor, kv: KV, plan: _HipPlan) -> Tensor:
-        """cross_attention as one launch: the beams of a user are the query rows of one K/V group."""
-        k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in kv)  # a view of the Linear's output
-        if plan.train:
-            return self.o(T5AttentionFunction.apply(self.q(x), k, v, None, self.n_heads, 0, plan.cross_mask, False, plan.p,
-                                                    _draw_seed(plan.p, x.device)))
-        return self.o(ops.t5_attention(self.q(x), k, v, self.n_heads, key_mask=plan.cross_mask))
+class _OperatorAttention:
+    """The attention bodies of a stack forward as torch operators: the bias and the additive masks are built once."""
+
+    def __init__(self, stack: "T5Stack", inputs_embeds: Tensor, attention_mask: Optional[Tensor],
+                 encoder_hidden_states: Optional[Tensor], encoder_attention_mask: Optional[Tensor],
+                 past_key_values: Optional[List[KV]], cross_kv: Optional[List[KV]]) -> None:
+        T, dtype = inputs_embeds.shape[1], inputs_embeds.dtype
+        past = 0 if past_key_values is None else past_key_values[0][0].shape[2]
+        keys = past + T
+        keep = None if attention_mask is None else attention_mask[:, None, None, :].bool()
+        if stack.is_decoder and T > 1:
+            causal = torch.ones(T, keys, dtype=torch.bool, device=inputs_embeds.device).tril(diagonal=past)[None, None]
+            keep = causal if keep is None else keep & causal
+        self.mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
+        self.bias = stack.block[0].layer[0].SelfAttention.compute_bias(T, keys, past)
+        self.past_key_values = past_key_values
+        if stack.is_decoder:
+            self.cross_kv = stack.cross_kv(encoder_hidden_states) if cross_kv is None else cross_kv
+            self.cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
+
+    def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
+        return module.self_attention(normed, self.bias, self.mask,
+                                     None if self.past_key_values is None else self.past_key_values[i])
+
+    def cross_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tensor:
+        return module.cross_attention(normed, self.cross_kv[i], self.cross_mask)
+
+
+class _HipAttention:
+    """The attention bodies of a stack forward on the "hip" path: the bias table and the byte masks are built once,
+    every attention is one launch (`train`: one T5AttentionFunction call, with the attention-weight dropout of train
+    mode in the kernel, from a seed drawn per call)."""
+
+    def __init__(self, stack: "T5Stack", T: int, attention_mask: Optional[Tensor],
+                 encoder_attention_mask: Optional[Tensor], cross_kv: Optional[List[KV]],
+                 cache: Optional[T5DecodeCache], train: bool) -> None:
+        self.train = train
+        self.p = float(stack.config.dropout_rate) if train and stack.training else 0.0
+        self.cache = cache
+        self.past = 0 if cache is None else cache.pos
+        self.table, self.offset = stack.block[0].layer[0].SelfAttention.delta_table(T, self.past + T, self.past)
+        self.key_mask = None if attention_mask is None else attention_mask.bool()
+        self.causal = stack.is_decoder and T > 1
+        self.cross_kv = cross_kv
+        self.cross_mask = None if encoder_attention_mask is None else encoder_attention_mask.bool()
+
+    def _launch(self, module: T5Attention, q: Tensor, k: Tensor, v: Tensor, table: Optional[Tensor], offset: int,
+                key_mask: Optional[Tensor], causal: bool) -> Tensor:
+        if self.train:
+            return T5AttentionFunction.apply(q, k, v, table, module.n_heads, offset, key_mask, causal, self.p,
+                                             _draw_seed(self.p, q.device))
+        return ops.t5_attention(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset, key_mask=key_mask,
+                                causal=causal)
+
+    def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
+        """One launch; with a decode cache the K/V projections go straight into block i's slabs."""
+        q = module.q(normed)
+        if self.cache is None:
+            k, v = module.k(normed), module.v(normed)
+            out = self._launch(module, q, k, v, self.table, self.offset, self.key_mask, self.causal)
+            return module.o(out), (module._heads(k), module._heads(v))
+        R = normed.shape[0]
+        ks, vs = self.cache.slabs[i]
+        x2 = normed.reshape(R, -1)
+        torch.mm(x2, module.k.weight.t(), out=ks[self.past, :R])
+        torch.mm(x2, module.v.weight.t(), out=vs[self.past, :R])
+        out = ops.t5_attention(q, ks, vs, module.n_heads, bias_by_delta=self.table, bias_offset=self.offset,
+                               past=self.past, anc=self.cache.anc[:R])
+        return module.o(out), (ks, vs)
+
+    def cross_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tensor:
+        """One launch: the beams of a user are the query rows of one K/V group."""
+        # a view of the Linear's output
+        k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in self.cross_kv[i])
+        return module.o(self._launch(module, module.q(normed), k, v, None, 0, self.cross_mask, False))
 
 
 class T5LayerSelfAttention(nn.Module):
+    """A sub-layer's body, norm and dropout, as T5LayerCrossAttention and T5LayerFF are; T5Stack.forward drives them."""
+
     def __init__(self, config: T5Config, has_relative_attention_bias: bool = False) -> None:
         super().__init__()
         self.SelfAttention = T5Attention(config, has_relative_attention_bias)
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
-
-    def forward(self, x, bias, mask, past, hip=None, block=0):
-        if hip is not None:
-            out, kv = self.SelfAttention.self_attention_hip(self.layer_norm(x), hip, block)
-        else:
-            out, kv = self.SelfAttention.self_attention(self.layer_norm(x), bias, mask, past)
-        return x + self.dropout(out), kv
 
 
 class T5LayerCrossAttention(nn.Module):
@@ -298,11 +345,6 @@ class T5LayerCrossAttention(nn.Module):
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
 
-    def forward(self, x, kv, mask, hip=None):
-        if hip is not None:
-            return x + self.dropout(self.EncDecAttention.cross_attention_hip(self.layer_norm(x), kv, hip))
-        return x + self.dropout(self.EncDecAttention.cross_attention(self.layer_norm(x), kv, mask))
-
 
 class T5DenseReluDense(nn.Module):
     def __init__(self, config: T5Config) -> None:
@@ -311,11 +353,11 @@ class T5DenseReluDense(nn.Module):
         self.wo = nn.Linear(config.d_ff, config.d_model, bias=False)
         self.dropout = nn.Dropout(config.dropout_rate)
 
-    def forward(self, x, fused=None):
-        """fused: None (the operators) or (p, seed) of the "hip" feed-forward path: one fused call."""
-        if fused is None:
-            return self.wo(self.dropout(F.relu(self.wi(x))))
-        p, seed = fused
+    def forward(self, x: Tensor) -> Tensor:
+        return self.wo(self.dropout(F.relu(self.wi(x))))
+
+    def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor]) -> Tensor:
+        """forward as one fused call (the "hip" feed-forward body), its dropout at rate p from `seed`."""
         if torch.is_grad_enabled():
             return T5FFNFunction.apply(x, self.wi.weight, self.wo.weight, p, seed)
         return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False)[0]
@@ -327,9 +369,6 @@ class T5LayerFF(nn.Module):
         self.DenseReluDense = T5DenseReluDense(config)
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
-
-    def forward(self, x, fused=None):
-        return x + self.dropout(self.DenseReluDense(self.layer_norm(x), fused))
 
 
 class T5Block(nn.Module):
@@ -403,75 +442,50 @@ class T5Stack(nn.Module):
         return (self.ffn_impl == "hip" and x.is_cuda
                 and ops.t5_ffn_supported(x.dtype, self.config.d_model, self.config.d_ff))
 
-    def _ffn_plan(self, active: bool, device):
-        """What a T5LayerFF of the plain paths gets: None, or (p, one seed drawn for this feed-forward)."""
-        if not active:
-            return None
-        p = float(self.config.dropout_rate) if self.training else 0.0
-        return p, _draw_seed(p, device)
-
-    def _forward_add_norm(self, inputs_embeds, self_body, cross_body, use_cache):
-        """forward on the "hip" norm path.  self_body(i, attention, normed) -> (out, kv) and cross_body(i, attention,
-        normed) -> out are the attention bodies of the path `forward` chose; one add-norm call between two bodies."""
-        norms = [layer.layer_norm for blk in self.block for layer in blk.layer] + [self.final_layer_norm]
-        p = float(self.config.dropout_rate) if self.training else 0.0
-        ffn = self.hip_ffn_active(inputs_embeds)
-        seeds = None
-        if p > 0:  # one draw for the whole stack; a call gets a one-element view (the feed-forwards' behind the norms')
-            seeds = torch.randint(0, 2 ** 62, (len(norms) + (len(self.block) if ffn else 0),), dtype=torch.int64,
-                                  device=inputs_embeds.device)
-
-        def add_norm(x, y, k):
-            norm = norms[k]
-            return T5AddNormFunction.apply(x, y, norm.weight, norm.variance_epsilon, p,
-                                           p if k == len(norms) - 1 else 0.0, None if seeds is None else seeds[k:k + 1])
-
-        x, n = add_norm(None, inputs_embeds, 0)
-        k, new_kv = 0, []
-        for i, blk in enumerate(self.block):
-            out, kv = self_body(i, blk.layer[0].SelfAttention, n)
-            new_kv.append(kv)
-            k += 1
-            x, n = add_norm(x, out, k)
-            if self.is_decoder:
-                k += 1
-                x, n = add_norm(x, cross_body(i, blk.layer[1].EncDecAttention, n), k)
-            k += 1
-            fused = (p, None if seeds is None else seeds[len(norms) + i:len(norms) + i + 1]) if ffn else None
-            x, n = add_norm(x, blk.layer[-1].DenseReluDense(n, fused), k)
-        return (n, new_kv) if use_cache else n
-
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
-    def _forward_hip(self, inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache, decode_cache,
-                     train=False):
-        """forward on the "hip" path: the bias table and the byte masks are built once, every attention is one launch
-        (`train`: one T5AttentionFunction call, with the attention-weight dropout of train mode in the kernel)."""
-        T = inputs_embeds.shape[1]
-        plan = _HipPlan()
-        plan.train = train
-        plan.p = float(self.config.dropout_rate) if train and self.training else 0.0
-        plan.cache = decode_cache
-        plan.past = 0 if decode_cache is None else decode_cache.pos
-        plan.table, plan.offset = self.block[0].layer[0].SelfAttention.delta_table(T, plan.past + T, plan.past)
-        plan.key_mask = None if attention_mask is None else attention_mask.bool()
-        plan.causal = self.is_decoder and T > 1
-        plan.cross_mask = None if encoder_attention_mask is None else encoder_attention_mask.bool()
-        if self.hip_norm_active(inputs_embeds):
-            return self._forward_add_norm(inputs_embeds, lambda i, att, n: att.self_attention_hip(n, plan, i),
-                                          lambda i, att, n: att.cross_attention_hip(n, cross_kv[i], plan), use_cache)
-        ffn = self.hip_ffn_active(inputs_embeds)
-        x = self.dropout(inputs_embeds)
-        new_kv = []
-        for i, blk in enumerate(self.block):
-            x, kv = blk.layer[0](x, None, None, None, hip=plan, block=i)
-            new_kv.append(kv)
-            if self.is_decoder:
-                x = blk.layer[1](x, cross_kv[i], None, hip=plan)
-            x = blk.layer[-1](x, self._ffn_plan(ffn, x.device))
-        x = self.dropout(self.final_layer_norm(x))
-        return (x, new_kv) if use_cache else x
+    def _attention_body(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
+                        past_key_values, cross_kv, decode_cache):
+        """The attention body of this forward (module docstring): _HipAttention where it applies, else the operators."""
+        R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
+        if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
+            if self.is_decoder and cross_kv is None:
+                cross_kv = self.cross_kv(encoder_hidden_states)
+            past = 0 if decode_cache is None else decode_cache.pos
+            if decode_cache is None and self.hip_train_active(inputs_embeds, T, cross_kv):
+                return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, None, train=True)
+            cross_length = cross_kv[0][0].shape[2] if self.is_decoder else None
+            if self.hip_attention_active(inputs_embeds, T, past + T, cross_length):
+                if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
+                                                 or past >= decode_cache.steps or R > decode_cache.rows):
+                    raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
+                                     "past_key_values or attention_mask")
+                return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, decode_cache,
+                                     train=False)
+            if decode_cache is not None:
+                raise ValueError('decode_cache belongs to the "hip" attention path, which is not active here')
+        return _OperatorAttention(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
+                                  past_key_values, cross_kv)
+
+    def _glue(self, layers, fused: bool, p: float, seeds: _Seeds):
+        """glue(k, x, y) -> (x + dropout_k(y), norm_k of that sum): what lies between body k - 1 and body k of a
+        forward.  k = 0 takes x = None and the input embeddings as y; the last k is the final norm with the stack's
+        dropout behind it."""
+        norms = [layer.layer_norm for layer in layers] + [self.final_layer_norm]
+        last = len(layers)
+        if fused:
+            def glue(k, x, y):
+                return T5AddNormFunction.apply(x, y, norms[k].weight, norms[k].variance_epsilon, p,
+                                               p if k == last else 0.0, seeds.glue(k))
+        else:
+            dropouts = [self.dropout] + [layer.dropout for layer in layers]
+
+            def glue(k, x, y):
+                x = dropouts[k](y) if x is None else x + dropouts[k](y)
+                normed = norms[k](x)
+                return x, self.dropout(normed) if k == last else normed
+        return glue
 
     def forward(self, inputs_embeds: Tensor, attention_mask: Optional[Tensor] = None,
                 encoder_hidden_states: Optional[Tensor] = None, encoder_attention_mask: Optional[Tensor] = None,
@@ -481,53 +495,31 @@ class T5Stack(nn.Module):
         [B, S] keep-mask of the encoder output (B rows, R = B * beams).  Returns the hidden states, and with use_cache
         the per-block self-attention (K, V) including these T positions.  decode_cache ("hip" path, T = 1) holds the
         self-attention history instead of past_key_values: this position's K/V are written into it."""
-        R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        dtype = inputs_embeds.dtype
-        if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
-            if self.is_decoder and cross_kv is None:
-                cross_kv = self.cross_kv(encoder_hidden_states)
-            past = 0 if decode_cache is None else decode_cache.pos
-            if decode_cache is None and self.hip_train_active(inputs_embeds, T, cross_kv):
-                return self._forward_hip(inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache, None,
-                                         train=True)
-            if self.hip_attention_active(inputs_embeds, T, past + T, cross_kv[0][0].shape[2] if self.is_decoder else None):
-                if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
-                                                 or past >= decode_cache.steps or R > decode_cache.rows):
-                    raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
-                                     "past_key_values or attention_mask")
-                return self._forward_hip(inputs_embeds, attention_mask, encoder_attention_mask, cross_kv, use_cache,
-                                         decode_cache)
-            if decode_cache is not None:
-                raise ValueError('decode_cache belongs to the "hip" attention path, which is not active here')
-        past = 0 if past_key_values is None else past_key_values[0][0].shape[2]
-        keys = past + T
-        keep = None if attention_mask is None else attention_mask[:, None, None, :].bool()
-        if self.is_decoder and T > 1:
-            causal = torch.ones(T, keys, dtype=torch.bool, device=inputs_embeds.device).tril(diagonal=past)[None, None]
-            keep = causal if keep is None else keep & causal
-        mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
-        bias = self.block[0].layer[0].SelfAttention.compute_bias(T, keys, past)
-        if self.is_decoder:
-            if cross_kv is None:
-                cross_kv = self.cross_kv(encoder_hidden_states)
-            cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
+        attention = self._attention_body(inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
+                                         past_key_values, cross_kv, decode_cache)
+        fused_glue = self.hip_norm_active(inputs_embeds)
+        fused_ffn = self.hip_ffn_active(inputs_embeds)
+        p = float(self.config.dropout_rate) if self.training else 0.0
+        layers = [layer for blk in self.block for layer in blk.layer]
+        seeds = _Seeds(p, inputs_embeds.device, len(layers) + 1 if fused_glue else 0,
+                       len(self.block) if fused_ffn else 0)
+        glue = self._glue(layers, fused_glue, p, seeds)
 
-        if self.hip_norm_active(inputs_embeds):
-            return self._forward_add_norm(
-                inputs_embeds,
-                lambda i, att, n: att.self_attention(n, bias, mask, None if past_key_values is None else past_key_values[i]),
-                lambda i, att, n: att.cross_attention(n, cross_kv[i], cross_mask), use_cache)
-        ffn = self.hip_ffn_active(inputs_embeds)
-        x = self.dropout(inputs_embeds)
-        new_kv = []
+        x, normed = glue(0, None, inputs_embeds)
+        k, new_kv = 0, []
         for i, blk in enumerate(self.block):
-            x, kv = blk.layer[0](x, bias, mask, None if past_key_values is None else past_key_values[i])
+            out, kv = attention.self_attention(i, blk.layer[0].SelfAttention, normed)
             new_kv.append(kv)
+            k += 1
+            x, normed = glue(k, x, out)
+            del out  # not kept alive through the bodies that follow
             if self.is_decoder:
-                x = blk.layer[1](x, cross_kv[i], cross_mask)
-            x = blk.layer[-1](x, self._ffn_plan(ffn, x.device))
-        x = self.dropout(self.final_layer_norm(x))
-        return (x, new_kv) if use_cache else x
+                k += 1
+                x, normed = glue(k, x, attention.cross_attention(i, blk.layer[1].EncDecAttention, normed))
+            dense = blk.layer[-1].DenseReluDense
+            k += 1
+            x, normed = glue(k, x, dense.forward_hip(normed, p, seeds.ffn(i)) if fused_ffn else dense(normed))
+        return (normed, new_kv) if use_cache else normed
 
 
 class T5EncoderModel(nn.Module):

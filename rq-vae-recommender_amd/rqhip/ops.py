@@ -559,6 +559,43 @@ def _token_rows(t: Tensor, name: str, copy: bool = True) -> Tensor:
     return t
 
 
+def _attention_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, bias_by_delta: Optional[Tensor],
+                    key_mask: Optional[Tensor], p: float = 0.0, seed: Optional[Tensor] = None, past: int = 0,
+                    anc: Optional[Tensor] = None):
+    """The checks and copies t5_attention, t5_attention_fwd_train and t5_attention_bwd share.  With `anc` k and v are
+    the position slabs, which are never copied, and the keys are the positions 0 .. past of each of the R rows."""
+    q = _token_rows(q, "q")
+    R, Tq, inner = q.shape
+    if inner != n_heads * 64:
+        raise RqHipError(f"{who}: q has {inner} columns, not n_heads * 64 = {n_heads * 64}")
+    if k.shape != v.shape or k.shape[-1] != inner:
+        raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    k, v = _token_rows(k, "k", copy=anc is None), _token_rows(v, "v", copy=anc is None)
+    if k.stride(1) != v.stride(1):
+        if anc is not None:
+            raise RqHipError(f"{who}: the k and v slabs must share one row stride")
+        k, v = k.contiguous(), v.contiguous()
+    Rk, Tk = k.shape[0], k.shape[1]
+    if anc is not None:
+        if (anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < past or anc.stride(1) != 1
+                or k.shape[0] <= past or k.shape[1] < R):
+            raise RqHipError(f"{who}: anc must be an int32 [R, >= past] table with unit column stride, and the "
+                             "slabs must hold position `past` and at least R rows")
+        Rk, Tk = R, past + 1
+    if bias_by_delta is not None:
+        bias_by_delta = _f32c(bias_by_delta, "bias_by_delta")
+        if bias_by_delta.dim() != 2 or bias_by_delta.shape[1] != n_heads:
+            raise RqHipError(f"{who}: bias_by_delta must be [n_delta, {n_heads}], got {tuple(bias_by_delta.shape)}")
+    if key_mask is not None:
+        if key_mask.dtype not in (torch.bool, torch.uint8) or tuple(key_mask.shape) != (Rk, Tk):
+            raise RqHipError(f"{who}: key_mask must be bool / uint8 [{Rk}, {Tk}], got {key_mask.dtype} "
+                             f"{tuple(key_mask.shape)}")
+        key_mask = key_mask.contiguous()
+    if p > 0 and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
+        raise RqHipError(f"{who}: dropout (p={p}) needs `seed`, a one-element int64 device tensor")
+    return q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner
+
+
 def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
                  bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False, past: int = 0,
                  anc: Optional[Tensor] = None) -> Tensor:
@@ -571,34 +608,9 @@ def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta
     bias_by_delta [n_delta, n_heads]: table[(j - i - past) + bias_offset] is added.  key_mask [Rk, Tk] bool / uint8
     (0 = masked), causal keeps j <= i + past; masked scores get finfo(float32).min added."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, anc)
-    q = _token_rows(q, "q")
-    R, Tq, inner = q.shape
-    if inner != n_heads * 64:
-        raise RqHipError(f"t5_attention: q has {inner} columns, not n_heads * 64 = {n_heads * 64}")
-    if k.shape != v.shape or k.shape[-1] != inner:
-        raise RqHipError(f"t5_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
-    k, v = _token_rows(k, "k", copy=anc is None), _token_rows(v, "v", copy=anc is None)
-    if k.stride(1) != v.stride(1):
-        if anc is not None:
-            raise RqHipError("t5_attention: the k and v slabs must share one row stride")
-        k, v = k.contiguous(), v.contiguous()
-    if anc is not None:
-        if (anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < past or anc.stride(1) != 1
-                or k.shape[0] <= past or k.shape[1] < R):
-            raise RqHipError("t5_attention: anc must be an int32 [R, >= past] table with unit column stride, and the "
-                             "slabs must hold position `past` and at least R rows")
-        Rk, Tk, slab_rows, ld_anc = R, past + 1, k.shape[1], int(anc.stride(0))
-    else:
-        Rk, Tk, slab_rows, ld_anc = k.shape[0], k.shape[1], 0, 0
-    if bias_by_delta is not None:
-        bias_by_delta = _f32c(bias_by_delta, "bias_by_delta")
-        if bias_by_delta.dim() != 2 or bias_by_delta.shape[1] != n_heads:
-            raise RqHipError(f"t5_attention: bias_by_delta must be [n_delta, {n_heads}], got {tuple(bias_by_delta.shape)}")
-    if key_mask is not None:
-        if key_mask.dtype not in (torch.bool, torch.uint8) or tuple(key_mask.shape) != (Rk, Tk):
-            raise RqHipError(f"t5_attention: key_mask must be bool / uint8 [{Rk}, {Tk}], got {key_mask.dtype} "
-                             f"{tuple(key_mask.shape)}")
-        key_mask = key_mask.contiguous()
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _attention_args("t5_attention", q, k, v, n_heads,
+                                                                             bias_by_delta, key_mask, past=past, anc=anc)
+    slab_rows, ld_anc = (0, 0) if anc is None else (k.shape[1], int(anc.stride(0)))
     dev = q.device
     with torch.cuda.device(dev):
         out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
@@ -645,33 +657,6 @@ def t5_attention_dropout_keep(seed, R: int, H: int, Tq: int, Tk: int, p: float) 
     return (h >= min(int(round(p * 4294967296.0)), _M32)).view(R, H, Tq, Tk)
 
 
-def _train_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, bias_by_delta: Optional[Tensor],
-                key_mask: Optional[Tensor], p: float, seed: Optional[Tensor]):
-    """The checks and copies t5_attention_fwd_train and t5_attention_bwd share (t5_attention's, dense K/V)."""
-    q = _token_rows(q, "q")
-    R, Tq, inner = q.shape
-    if inner != n_heads * 64:
-        raise RqHipError(f"{who}: q has {inner} columns, not n_heads * 64 = {n_heads * 64}")
-    if k.shape != v.shape or k.shape[-1] != inner:
-        raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
-    k, v = _token_rows(k, "k"), _token_rows(v, "v")
-    if k.stride(1) != v.stride(1):
-        k, v = k.contiguous(), v.contiguous()
-    Rk, Tk = k.shape[0], k.shape[1]
-    if bias_by_delta is not None:
-        bias_by_delta = _f32c(bias_by_delta, "bias_by_delta")
-        if bias_by_delta.dim() != 2 or bias_by_delta.shape[1] != n_heads:
-            raise RqHipError(f"{who}: bias_by_delta must be [n_delta, {n_heads}], got {tuple(bias_by_delta.shape)}")
-    if key_mask is not None:
-        if key_mask.dtype not in (torch.bool, torch.uint8) or tuple(key_mask.shape) != (Rk, Tk):
-            raise RqHipError(f"{who}: key_mask must be bool / uint8 [{Rk}, {Tk}], got {key_mask.dtype} "
-                             f"{tuple(key_mask.shape)}")
-        key_mask = key_mask.contiguous()
-    if p > 0 and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
-        raise RqHipError(f"{who}: dropout (p={p}) needs `seed`, a one-element int64 device tensor")
-    return q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner
-
-
 def t5_attention_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
                            bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False, p: float = 0.0,
                            seed: Optional[Tensor] = None):
@@ -680,8 +665,8 @@ def t5_attention_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bia
     t5_attention_dropout_keep(seed, ...) and scaled by 1 / (1 - p); `seed` is a one-element int64 device tensor the host
     never reads.  At p = 0 `out` has the bits of t5_attention."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _train_args("t5_attention_fwd_train", q, k, v, n_heads,
-                                                                         bias_by_delta, key_mask, p, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _attention_args("t5_attention_fwd_train", q, k, v,
+                                                                             n_heads, bias_by_delta, key_mask, p, seed)
     dev = q.device
     with torch.cuda.device(dev):
         out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
@@ -702,8 +687,8 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
     dk, dv [R, Tk, inner], dtable [n_delta, n_heads] or None without a bias table).  The arguments are the forward's, its
     `out` and `lse`, and d_out [R, Tq, inner]; the weights are recomputed, the dropout decisions too."""
     _need_gpu(q, k, v, out, lse, d_out, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _train_args("t5_attention_bwd", q, k, v, n_heads,
-                                                                         bias_by_delta, key_mask, p, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _attention_args("t5_attention_bwd", q, k, v, n_heads,
+                                                                             bias_by_delta, key_mask, p, seed)
     out, d_out = _token_rows(out, "out"), _token_rows(d_out, "d_out")
     if out.shape != q.shape or d_out.shape != q.shape:
         raise RqHipError(f"t5_attention_bwd: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q "
