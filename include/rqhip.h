@@ -305,8 +305,11 @@ int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, const float
  * attention-weight dropout, and the backward.  Dense K/V with one K/V per query row only (Rk = R, else
  * RQHIP_EUNSUPPORTED), no `past`; q, k, v, bias_by_delta, bias_offset, key_mask and causal as above.
  *   Dropout (0 <= p < 1): weight (r, h, i, j) is kept iff hash(seed, ((r * H + h) * Tq + i) * Tk + j) >= round(p * 2^32)
- *     and kept weights are scaled by 1 / (1 - p), AFTER the softmax's normalisation.  With x = the index, s = *seed and
- *     fmix = murmur3's 32-bit finaliser:  hash = fmix((fmix(lo(s) ^ lo(x)) ^ hi(s) ^ hi(x) * 0x85EBCA6B) + 0x9E3779B9).
+ *     and kept weights are scaled by 1 / (1 - p), AFTER the softmax's normalisation.  The scale is computed in fp32, as
+ *     1.0f / (1.0f - (float)p), in the forward and in the backward: at some p (0.15, 0.6, 0.8, 0.9; not 0.1 or 0.5) its
+ *     last bits differ from the (float)(1 / (1 - p)) evaluated in double of rqhip_t5_add_norm_* and rqhip_t5_ffn_* below.
+ *     With x = the index, s = *seed and fmix = murmur3's 32-bit finaliser:
+ *     hash = fmix((fmix(lo(s) ^ lo(x)) ^ hi(s) ^ hi(x) * 0x85EBCA6B) + 0x9E3779B9).
  *     `seed` points to ONE int64 on the device (NULL allowed at p = 0); the host never reads it.  The forward and both
  *     passes of the backward recompute the decision; no mask is stored (rqhip/ops.py:t5_attention_dropout_keep restates
  *     it in torch).

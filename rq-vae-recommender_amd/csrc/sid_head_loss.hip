@@ -18,12 +18,11 @@
 #include <math.h>
 
 #include "rqhip_common.h"
+#include "t5_common.h"
 
 namespace rqhip {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kShMaxD = 1024, kShMaxK = 1024, kShMaxL = 8;
 constexpr int kShThreads = 256;
@@ -40,18 +39,6 @@ struct ShWeightGrads {
 
 bool sh_supported(int d, int K, int L) {
     return d >= 4 && d <= kShMaxD && d % 4 == 0 && K >= 1 && K <= kShMaxK && L >= 1 && L <= kShMaxL;
-}
-
-__device__ __forceinline__ float sh_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, RQ_WAVE);
-    return v;
-}
-
-__device__ __forceinline__ float sh_wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, RQ_WAVE));
-    return v;
 }
 
 __global__ __launch_bounds__(kShThreads) void sid_head_loss_fwd_kernel(const float *x, long long ld_xb, long long ld_xt,
@@ -96,10 +83,10 @@ __global__ __launch_bounds__(kShThreads) void sid_head_loss_fwd_kernel(const flo
         const float *zr = z + ((size_t)b * L + h) * K;
         float m = -INFINITY;
         for (int k = lane; k < K; k += RQ_WAVE) m = fmaxf(m, zr[k]);
-        m = sh_wave_max(m);
+        m = wave_max(m);
         float s = 0.f;
         for (int k = lane; k < K; k += RQ_WAVE) s = s + expf(zr[k] - m);
-        s = sh_wave_sum(s);
+        s = wave_sum(s);
         const float l = m + logf(s);
         if (lane == 0) {
             const long long t = target[(size_t)b * ld_t + h];
@@ -117,7 +104,7 @@ __global__ __launch_bounds__(kShMaxL * RQ_WAVE) void sid_head_loss_mean_kernel(c
     const int lane = threadIdx.x & (RQ_WAVE - 1), h = threadIdx.x / RQ_WAVE;
     float s = 0.f;
     for (long long b = lane; b < B; b += RQ_WAVE) s = s + row_loss[(size_t)h * B + b];
-    s = sh_wave_sum(s) / (float)B;
+    s = wave_sum(s) / (float)B;
     if (lane == 0) {
         ld[h] = s;
         loss_d[h] = s;
@@ -219,8 +206,6 @@ __global__ __launch_bounds__(kShThreads) void sid_head_loss_bwd_kernel(const flo
     }
 }
 
-bool sh_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // The checks both entry points share; `who` names the entry point in the message.
 int sh_check(const char *who, int64_t B, int T, int L, int K, int d, int64_t ld_xb, int64_t ld_xt, int64_t ld_t) {
     if (B < 1 || T < 0 || L < 0 || K < 0 || d < 0) {
@@ -267,15 +252,15 @@ extern "C" int rqhip_sid_head_loss_fwd(const float *x, int64_t ld_xb, int64_t ld
     const char *who = "sid_head_loss_fwd";
     const int rc = sh_check(who, B, T, L, K, d, ld_xb, ld_xt, ld_t);
     if (rc != RQHIP_OK) return rc;
-    bool null = !x || !w || !target || !z || !lse || !row_loss || !loss_d || !loss;
+    bool null = any_null(x, w, target, z, lse, row_loss, loss_d, loss);
     ShWeights ws = {};
     for (int h = 0; h < L && !null; ++h) null = !(ws.p[h] = w[h]);
     if (null) {
         set_error("%s: null pointer (x, w and its L entries, target, z, lse, row_loss, loss_d, loss)", who);
         return RQHIP_EARG;
     }
-    bool aligned = sh_aligned16(x);
-    for (int h = 0; h < L; ++h) aligned = aligned && sh_aligned16(ws.p[h]);
+    bool aligned = aligned16(x);
+    for (int h = 0; h < L; ++h) aligned = aligned && aligned16(ws.p[h]);
     if (!aligned) {
         set_error("%s: x and every w[h] must be 16-byte aligned", who);
         return RQHIP_EARG;
@@ -299,14 +284,14 @@ extern "C" int rqhip_sid_head_loss_bwd(const float *x, int64_t ld_xb, int64_t ld
     const char *who = "sid_head_loss_bwd";
     const int rc = sh_check(who, B, T, L, K, d, ld_xb, ld_xt, ld_t);
     if (rc != RQHIP_OK) return rc;
-    bool null = !x || !w || !target || !z || !lse || !d_loss;
+    bool null = any_null(x, w, target, z, lse, d_loss);
     ShWeights ws = {};
     for (int h = 0; h < L && !null; ++h) null = !(ws.p[h] = w[h]);
     if (null) {
         set_error("%s: null pointer (x, w and its L entries, target, z, lse, d_loss)", who);
         return RQHIP_EARG;
     }
-    if (!sh_aligned16(x)) {
+    if (!aligned16(x)) {
         set_error("%s: x must be 16-byte aligned", who);
         return RQHIP_EARG;
     }

@@ -11,13 +11,11 @@
 #include <math.h>
 
 #include "rqhip_common.h"
-#include "t5_dropout_hash.h"
+#include "t5_common.h"
 
 namespace rqhip {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAnMaxD = 1024;
 constexpr int kAnWaves = 4;       // waves (forward: rows) per workgroup
@@ -43,12 +41,6 @@ struct AnDrop {
     float s_in, s_out;        // 1 / (1 - p)
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, RQ_WAVE);
-    return v;
-}
-
 __global__ __launch_bounds__(kAnWaves * RQ_WAVE) void t5_add_norm_fwd_kernel(const float *x, const float *y, const float *w,
                                                                              long long N, int d, float eps, AnDrop dr,
                                                                              float *x_new, float *n, float *rstd) {
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(kAnWaves * RQ_WAVE) void t5_add_norm_fwd_kernel(con
             f32x4 t = *reinterpret_cast<const f32x4 *>(y + base + c);
             if (dr.th_in) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = att_keep(seed, e0 + c + j, dr.th_in) ? t[j] * dr.s_in : 0.f;
+                for (int j = 0; j < 4; ++j) t[j] = dropout_keep(seed, e0 + c + j, dr.th_in) ? t[j] * dr.s_in : 0.f;
             }
             if (x) {
                 const f32x4 xx = *reinterpret_cast<const f32x4 *>(x + base + c);
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(kAnWaves * RQ_WAVE) void t5_add_norm_fwd_kernel(con
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 o[j] = ww[j] * (v[k][j] * r);
-                if (dr.th_out) o[j] = att_keep(seed, plane + e0 + c + j, dr.th_out) ? o[j] * dr.s_out : 0.f;
+                if (dr.th_out) o[j] = dropout_keep(seed, plane + e0 + c + j, dr.th_out) ? o[j] * dr.s_out : 0.f;
             }
             *reinterpret_cast<f32x4 *>(n + base + c) = o;
         }
@@ -137,7 +129,7 @@ __global__ __launch_bounds__(kAnWaves * RQ_WAVE) void t5_add_norm_bwd_kernel(con
                 if (d_n) g = *reinterpret_cast<const f32x4 *>(d_n + base + c);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (dr.th_out) g[j] = g[j] * (att_keep(seed, plane + e0 + c + j, dr.th_out) ? dr.s_out : 0.f);
+                    if (dr.th_out) g[j] = g[j] * (dropout_keep(seed, plane + e0 + c + j, dr.th_out) ? dr.s_out : 0.f);
                     xh[k][j] = xn[j] * r;
                     gw[k][j] = g[j] * ww[k][j];
                     acc[k][j] = acc[k][j] + g[j] * xh[k][j];
@@ -162,7 +154,7 @@ __global__ __launch_bounds__(kAnWaves * RQ_WAVE) void t5_add_norm_bwd_kernel(con
                 if (d_y) {
                     if (dr.th_in) {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) o[j] = att_keep(seed, e0 + c + j, dr.th_in) ? o[j] * dr.s_in : 0.f;
+                        for (int j = 0; j < 4; ++j) o[j] = dropout_keep(seed, e0 + c + j, dr.th_in) ? o[j] * dr.s_in : 0.f;
                     }
                     *reinterpret_cast<f32x4 *>(d_y + base + c) = o;
                 }
@@ -194,20 +186,13 @@ __global__ __launch_bounds__(256) void t5_add_norm_dw_kernel(const float *part, 
     d_w[c] = s;
 }
 
-bool an_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-unsigned an_threshold(double p) {
-    const double t = nearbyint(p * 4294967296.0);
-    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-}
-
 // The checks both entry points share; `who` names the entry point in the message.
 int an_check(const char *who, int64_t N, int d, double p_in, double p_out) {
     if (N < 0 || d < 1) {
         set_error("%s: bad sizes (N=%lld, d=%d)", who, (long long)N, d);
         return RQHIP_EARG;
     }
-    if (!(p_in >= 0.0 && p_in < 1.0) || !(p_out >= 0.0 && p_out < 1.0)) {
+    if (!dropout_p_valid(p_in) || !dropout_p_valid(p_out)) {
         set_error("%s: dropout probabilities p_in=%g, p_out=%g outside 0 <= p < 1", who, p_in, p_out);
         return RQHIP_EARG;
     }
@@ -225,8 +210,8 @@ int an_check(const char *who, int64_t N, int d, double p_in, double p_out) {
 AnDrop an_drop(double p_in, double p_out, const int64_t *seed) {
     AnDrop dr;
     dr.seed = reinterpret_cast<const long long *>(seed);
-    dr.th_in = an_threshold(p_in), dr.th_out = an_threshold(p_out);
-    dr.s_in = (float)(1.0 / (1.0 - p_in)), dr.s_out = (float)(1.0 / (1.0 - p_out));
+    dr.th_in = dropout_threshold(p_in), dr.th_out = dropout_threshold(p_out);
+    dr.s_in = dropout_scale_f64(p_in), dr.s_out = dropout_scale_f64(p_out);
     return dr;
 }
 
@@ -250,11 +235,11 @@ extern "C" int rqhip_t5_add_norm_fwd(const float *x, const float *y, const float
     if (rc != RQHIP_OK) return rc;
     if (N == 0) return RQHIP_OK;
     const AnDrop dr = an_drop(p_in, p_out, seed);
-    if (!y || !w || !x_new || !n || !rstd || ((dr.th_in | dr.th_out) && !seed)) {
+    if (any_null(y, w, x_new, n, rstd) || ((dr.th_in | dr.th_out) && !seed)) {
         set_error("t5_add_norm_fwd: null pointer (y, w, x_new, n, rstd; seed when p_in > 0 or p_out > 0)");
         return RQHIP_EARG;
     }
-    if (!an_aligned16(x) || !an_aligned16(y) || !an_aligned16(w) || !an_aligned16(x_new) || !an_aligned16(n)) {
+    if (!all_aligned16(x, y, w, x_new, n)) {
         set_error("t5_add_norm_fwd: x, y, w, x_new and n must be 16-byte aligned");
         return RQHIP_EARG;
     }
@@ -272,12 +257,11 @@ extern "C" int rqhip_t5_add_norm_bwd(const float *x_new, const float *rstd, cons
     if (rc != RQHIP_OK) return rc;
     if (N == 0 && !d_w) return RQHIP_OK;
     const AnDrop dr = an_drop(p_in, p_out, seed);
-    if (!d_w || (N > 0 && (!x_new || !rstd || !w || ((dr.th_in | dr.th_out) && !seed)))) {
+    if (!d_w || (N > 0 && (any_null(x_new, rstd, w) || ((dr.th_in | dr.th_out) && !seed)))) {
         set_error("t5_add_norm_bwd: null pointer (x_new, rstd, w, d_w; seed when p_in > 0 or p_out > 0)");
         return RQHIP_EARG;
     }
-    if (!an_aligned16(x_new) || !an_aligned16(w) || !an_aligned16(d_n) || !an_aligned16(d_xnew) || !an_aligned16(d_x) ||
-        !an_aligned16(d_y)) {
+    if (!all_aligned16(x_new, w, d_n, d_xnew, d_x, d_y)) {
         set_error("t5_add_norm_bwd: x_new, w, d_n, d_xnew, d_x and d_y must be 16-byte aligned");
         return RQHIP_EARG;
     }

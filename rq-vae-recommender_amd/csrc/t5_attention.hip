@@ -25,14 +25,15 @@
 #include <float.h>
 #include <math.h>
 
+#include <initializer_list>
+#include <type_traits>
+
 #include "rqhip_common.h"
-#include "t5_dropout_hash.h"
+#include "t5_common.h"
 
 namespace rqhip {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAttD = 64;       // d_kv
 constexpr int kAttLd = 68;      // LDS row stride of K and V (floats)
@@ -55,10 +56,10 @@ struct AttTrain {
     float *lse;               // [R, H, Tq]
     const long long *seed;    // one int64 on the device (read only when thresh != 0)
     unsigned thresh;          // round(p * 2^32): element kept when its hash >= thresh; 0 = no dropout
-    float inv_keep;           // 1 / (1 - p)
+    float inv_keep;           // dropout_scale_f32(p)
 };
 
-// The dropout decision of element idx = ((r * H + h) * Tq + i) * Tk + j is att_keep(seed, idx, thresh) of t5_dropout_hash.h.
+// The dropout decision of element idx = ((r * H + h) * Tq + i) * Tk + j is dropout_keep(seed, idx, thresh) of t5_common.h.
 
 template <int MT, bool TRAIN>
 __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
@@ -170,7 +171,7 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
                     if (mt < ntiles) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            if (!att_keep(seed, (unsigned long long)qh * a.Tk + (16 * mt + 4 * g + r), t.thresh))
+                            if (!dropout_keep(seed, (unsigned long long)qh * a.Tk + (16 * mt + 4 * g + r), t.thresh))
                                 s[mt][r] = 0.f;
                     }
                 }
@@ -224,32 +225,29 @@ size_t att_lds_bytes(int Tq, int Tk, bool bias) {
     return (2 * Tkp * kAttLd + Tkp + (bias ? (size_t)(Tq + Tk - 1) : 0)) * sizeof(float);
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The most keys an instantiation can meet: the LDS grant is made once per device and never raised again.
+constexpr int att_most_tk(int MT) { return MT * 16 < kAttMaxT ? MT * 16 : kAttMaxT; }
 
-template <int MT>
-int launch_att(const AttArgs &a, long long groups, int threads, size_t lds, hipStream_t s) {
+// One launch of any of the three attention kernels.  `most`: the dynamic LDS the grant asks for; the grant is one static
+// per instantiation of this template, that is per kernel instantiation.
+template <auto Kernel, class... Args>
+int launch_att(const char *name, size_t most, long long blocks, int threads, size_t lds, hipStream_t s, const Args &...args) {
     if (lds > 64 * 1024) {
-        // the grant is made once per device and never raised again: ask for the most this instantiation can need
         static LdsGrant grant;
-        RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_attention_kernel<MT>),
-                                      (int)att_lds_bytes(kAttMaxT, MT * 16 < kAttMaxT ? MT * 16 : kAttMaxT, true)));
+        RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(Kernel), (int)most));
     }
-    hipLaunchKernelGGL(t5_attention_kernel<MT>, dim3((unsigned)(groups * a.H)), dim3(threads), lds, s, a);
-    RQ_CHECK_LAUNCH("t5_attention_kernel");
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3(threads), lds, s, args...);
+    RQ_CHECK_LAUNCH(name);
     return RQHIP_OK;
 }
 
-
-template <int MT>
-int launch_att_train(const AttArgs &a, const AttTrain &t, long long groups, int threads, size_t lds, hipStream_t s) {
-    if (lds > 64 * 1024) {
-        static LdsGrant grant;
-        RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_attention_train_kernel<MT>),
-                                      (int)att_lds_bytes(kAttMaxT, MT * 16 < kAttMaxT ? MT * 16 : kAttMaxT, true)));
-    }
-    hipLaunchKernelGGL(t5_attention_train_kernel<MT>, dim3((unsigned)(groups * a.H)), dim3(threads), lds, s, a, t);
-    RQ_CHECK_LAUNCH("t5_attention_train_kernel");
-    return RQHIP_OK;
+// The kernels' MT (key tiles a lane holds in registers) for Tk keys: f(std::integral_constant<int, MT>).
+template <class F>
+int att_with_mt(int Tk, F f) {
+    const int ntiles = (Tk + 15) / 16;
+    if (ntiles == 1) return f(std::integral_constant<int, 1>{});
+    if (ntiles <= 6) return f(std::integral_constant<int, 6>{});
+    return f(std::integral_constant<int, 16>{});
 }
 
 // ---- backward
@@ -412,7 +410,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
                 for (int r = 0; r < 4; ++r) {
                     float d = acc[r];
                     if (a.thresh)
-                        d = att_keep(seed, (idx0 + ti) * a.Tk + (16 * mt + 4 * g + r), a.thresh) ? d * a.inv_keep : 0.f;
+                        d = dropout_keep(seed, (idx0 + ti) * a.Tk + (16 * mt + 4 * g + r), a.thresh) ? d * a.inv_keep : 0.f;
                     const float p = s[mt][r] / sum;
                     s[mt][r] = p;
                     dp[mt][r] = d;
@@ -523,7 +521,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
                 if (qi >= a.Tq || j >= a.Tk) p = 0.f;
                 float dp = pacc[r], pk = p;
                 if (a.thresh) {
-                    const bool keep = att_keep(seed, (idx0 + ti) * a.Tk + jc, a.thresh);
+                    const bool keep = dropout_keep(seed, (idx0 + ti) * a.Tk + jc, a.thresh);
                     dp = keep ? dp * a.inv_keep : 0.f;
                     pk = keep ? p * a.inv_keep : 0.f;
                 }
@@ -563,25 +561,19 @@ __global__ __launch_bounds__(256) void t5_dbias_reduce_kernel(const float *part,
     out[idx] = acc;
 }
 
-template <int MT>
-int launch_att_bwd(const AttBwdArgs &a, long long R, int threads, size_t lds, hipStream_t s) {
-    if (lds > 64 * 1024) {
-        static LdsGrant grant;
-        const int t = MT * 16 < kAttMaxT ? MT * 16 : kAttMaxT;
-        RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_attention_bwd_kernel<MT>),
-                                      (int)(att_bwd_lds(kAttMaxT, t, true, 4).total * sizeof(float))));
-    }
-    hipLaunchKernelGGL(t5_attention_bwd_kernel<MT>, dim3((unsigned)(R * a.H)), dim3(threads), lds, s, a);
-    RQ_CHECK_LAUNCH("t5_attention_bwd_kernel");
-    return RQHIP_OK;
+bool att_supported(int d_kv, int H, int Tq, int Tk) {
+    return d_kv == kAttD && H >= 1 && Tq >= 1 && Tq <= kAttMaxT && Tk >= 1 && Tk <= kAttMaxT;
 }
 
-// The checks the training pair shares; `who` names the entry point in the message.
-int check_train_call(const char *who, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, bool strides_ok,
-                     const float *bias, int n_delta, int bias_offset, int causal, double p) {
-    if (R < 0 || Rk < 0 || H < 1 || d_kv < 1 || Tq < 1 || Tk < 1) {
-        set_error("%s: bad sizes (R=%lld, Rk=%lld, H=%d, d_kv=%d, Tq=%d, Tk=%d)", who, (long long)R, (long long)Rk, H,
-                  d_kv, Tq, Tk);
+// The checks the three entry points share, in their one order; `who` names the entry point in the message.  The
+// inference call passes its `past` and ancestor table (and p = 0); the training pair (`train`) passes 0 / null, takes
+// one K/V per row and has no group of beams.  `strides`: the call's row strides, q, k/v and out first.
+int check_att_call(const char *who, bool train, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, int past,
+                   const int32_t *anc, int64_t ld_anc, int64_t slab_rows, std::initializer_list<int64_t> strides,
+                   const float *bias, int n_delta, int bias_offset, int causal, double p) {
+    if (R < 0 || Rk < 0 || H < 1 || d_kv < 1 || Tq < 1 || Tk < 1 || past < 0) {
+        set_error("%s: bad sizes (R=%lld, Rk=%lld, H=%d, d_kv=%d, Tq=%d, Tk=%d, past=%d)", who, (long long)R,
+                  (long long)Rk, H, d_kv, Tq, Tk, past);
         return RQHIP_EARG;
     }
     if (d_kv != kAttD) {
@@ -592,39 +584,60 @@ int check_train_call(const char *who, int64_t R, int64_t Rk, int H, int d_kv, in
         set_error("%s: Tq=%d / Tk=%d exceed Tq, Tk <= %d", who, Tq, Tk, kAttMaxT);
         return RQHIP_EUNSUPPORTED;
     }
-    if (Rk != R) {
+    if (train && Rk != R) {
         set_error("%s: R=%lld query rows over Rk=%lld K/V rows: the training pair takes one K/V per row (Rk = R)", who,
                   (long long)R, (long long)Rk);
         return RQHIP_EUNSUPPORTED;
     }
+    if (!train && ((R > 0 && Rk == 0) || (Rk > 0 && R % Rk != 0))) {
+        set_error("%s: R=%lld query rows are not a multiple of the Rk=%lld K/V groups", who, (long long)R, (long long)Rk);
+        return RQHIP_EARG;
+    }
+    const int64_t inner = (int64_t)H * kAttD;
+    bool strides_ok = true;
+    for (const int64_t ld : strides) strides_ok = strides_ok && ld >= inner && ld % 4 == 0;
     if (!strides_ok) {
-        set_error("%s: row strides must be multiples of 4 and >= H * 64 = %lld", who, (long long)H * kAttD);
+        if (train)
+            set_error("%s: row strides must be multiples of 4 and >= H * 64 = %lld", who, (long long)inner);
+        else
+            set_error("%s: row strides (q %lld, k/v %lld, out %lld) must be multiples of 4 and >= H * 64 = %lld", who,
+                      (long long)strides.begin()[0], (long long)strides.begin()[1], (long long)strides.begin()[2],
+                      (long long)inner);
         return RQHIP_EARG;
     }
-    if (Tq > Tk && (causal || bias)) {
-        set_error("%s: Tq = %d exceeds Tk = %d", who, Tq, Tk);
+    if (anc) {
+        if (Tq != 1 || Rk != R || Tk != past + 1 || ld_anc < past || slab_rows < R) {
+            set_error("%s: the ancestor table takes Tq = 1, Rk = R, Tk = past + 1, ld_anc >= past and "
+                      "slab_rows >= R (Tq=%d, R=%lld, Rk=%lld, Tk=%d, past=%d, ld_anc=%lld, slab_rows=%lld)",
+                      who, Tq, (long long)R, (long long)Rk, Tk, past, (long long)ld_anc, (long long)slab_rows);
+            return RQHIP_EARG;
+        }
+    } else if (past + Tq > Tk && (causal || bias)) {
+        if (train)
+            set_error("%s: Tq = %d exceeds Tk = %d", who, Tq, Tk);
+        else
+            set_error("%s: past + Tq = %d exceeds Tk = %d", who, past + Tq, Tk);
         return RQHIP_EARG;
     }
-    const int bias_base = bias_offset - (Tq - 1);
+    const int bias_base = bias_offset - (Tq - 1) - past;
     if (bias && (bias_base < 0 || (int64_t)bias_base + Tq + Tk - 1 > n_delta)) {
         set_error("%s: the bias table (n_delta=%d, offset=%d) does not cover deltas %d .. %d", who, n_delta, bias_offset,
-                  -(Tq - 1), Tk - 1);
+                  -(Tq - 1) - past, Tk - 1 - past);
         return RQHIP_EARG;
     }
-    if (!(p >= 0.0 && p < 1.0)) {
+    if (!dropout_p_valid(p)) {
         set_error("%s: dropout probability p=%g outside 0 <= p < 1", who, p);
         return RQHIP_EARG;
     }
-    if (R * (int64_t)H >= (1ll << 31)) {
-        set_error("%s: R * H = %lld exceeds one workgroup per (row, head) (< 2^31)", who, (long long)(R * (int64_t)H));
+    if (Rk * (int64_t)H >= (1ll << 31)) {
+        if (train)
+            set_error("%s: R * H = %lld exceeds one workgroup per (row, head) (< 2^31)", who, (long long)(Rk * (int64_t)H));
+        else
+            set_error("%s: Rk * H = %lld exceeds one workgroup per (group, head) (< 2^31)", who,
+                      (long long)(Rk * (int64_t)H));
         return RQHIP_EUNSUPPORTED;
     }
     return RQHIP_OK;
-}
-
-unsigned dropout_threshold(double p) {
-    const double t = nearbyint(p * 4294967296.0);
-    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
 }
 
 }  // namespace
@@ -633,76 +646,30 @@ unsigned dropout_threshold(double p) {
 
 using namespace rqhip;
 
-extern "C" int rqhip_t5_attention_supported(int d_kv, int H, int Tq, int Tk) {
-    return d_kv == kAttD && H >= 1 && Tq >= 1 && Tq <= kAttMaxT && Tk >= 1 && Tk <= kAttMaxT;
-}
+extern "C" int rqhip_t5_attention_supported(int d_kv, int H, int Tq, int Tk) { return att_supported(d_kv, H, Tq, Tk); }
 
 extern "C" int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, int64_t R,
                                   int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta,
                                   int bias_offset, const uint8_t *key_mask, int causal, int past, const int32_t *anc,
                                   int64_t ld_anc, int64_t slab_rows, float *out, int64_t ld_out,
                                   rqhip_stream_t stream) {
-    if (R < 0 || Rk < 0 || H < 1 || d_kv < 1 || Tq < 1 || Tk < 1 || past < 0) {
-        set_error("t5_attention: bad sizes (R=%lld, Rk=%lld, H=%d, d_kv=%d, Tq=%d, Tk=%d, past=%d)", (long long)R,
-                  (long long)Rk, H, d_kv, Tq, Tk, past);
-        return RQHIP_EARG;
-    }
-    if (d_kv != kAttD) {
-        set_error("t5_attention: d_kv=%d, only d_kv = %d is implemented", d_kv, kAttD);
-        return RQHIP_EUNSUPPORTED;
-    }
-    if (Tq > kAttMaxT || Tk > kAttMaxT) {
-        set_error("t5_attention: Tq=%d / Tk=%d exceed Tq, Tk <= %d", Tq, Tk, kAttMaxT);
-        return RQHIP_EUNSUPPORTED;
-    }
-    if ((R > 0 && Rk == 0) || (Rk > 0 && R % Rk != 0)) {
-        set_error("t5_attention: R=%lld query rows are not a multiple of the Rk=%lld K/V groups", (long long)R,
-                  (long long)Rk);
-        return RQHIP_EARG;
-    }
-    const int64_t inner = (int64_t)H * kAttD;
-    if (ld_q < inner || ld_kv < inner || ld_out < inner || (ld_q | ld_kv | ld_out) % 4 != 0) {
-        set_error("t5_attention: row strides (q %lld, k/v %lld, out %lld) must be multiples of 4 and >= H * 64 = %lld",
-                  (long long)ld_q, (long long)ld_kv, (long long)ld_out, (long long)inner);
-        return RQHIP_EARG;
-    }
-    if (anc) {
-        if (Tq != 1 || Rk != R || Tk != past + 1 || ld_anc < past || slab_rows < R) {
-            set_error("t5_attention: the ancestor table takes Tq = 1, Rk = R, Tk = past + 1, ld_anc >= past and "
-                      "slab_rows >= R (Tq=%d, R=%lld, Rk=%lld, Tk=%d, past=%d, ld_anc=%lld, slab_rows=%lld)",
-                      Tq, (long long)R, (long long)Rk, Tk, past, (long long)ld_anc, (long long)slab_rows);
-            return RQHIP_EARG;
-        }
-    } else if (past + Tq > Tk && (causal || bias_by_delta)) {
-        set_error("t5_attention: past + Tq = %d exceeds Tk = %d", past + Tq, Tk);
-        return RQHIP_EARG;
-    }
-    const int bias_base = bias_offset - (Tq - 1) - past;  // table row of the smallest delta j - i - past
-    if (bias_by_delta && (bias_base < 0 || (int64_t)bias_base + Tq + Tk - 1 > n_delta)) {
-        set_error("t5_attention: the bias table (n_delta=%d, offset=%d) does not cover deltas %d .. %d", n_delta,
-                  bias_offset, -(Tq - 1) - past, Tk - 1 - past);
-        return RQHIP_EARG;
-    }
-    if (Rk * (int64_t)H >= (1ll << 31)) {
-        set_error("t5_attention: Rk * H = %lld exceeds one workgroup per (group, head) (< 2^31)",
-                  (long long)(Rk * (int64_t)H));
-        return RQHIP_EUNSUPPORTED;
-    }
+    const int rc = check_att_call("t5_attention", false, R, Rk, H, d_kv, Tq, Tk, past, anc, ld_anc, slab_rows,
+                                  {ld_q, ld_kv, ld_out}, bias_by_delta, n_delta, bias_offset, causal, 0.0);
+    if (rc != RQHIP_OK) return rc;
     if (R == 0) return RQHIP_OK;
-    if (!q || !k || !v || !out) {
+    if (any_null(q, k, v, out)) {
         set_error("t5_attention: null pointer (q, k, v, out)");
         return RQHIP_EARG;
     }
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) {
+    if (!all_aligned16(q, k, v, out)) {
         set_error("t5_attention: q, k, v and out must be 16-byte aligned");
         return RQHIP_EARG;
     }
-
     AttArgs a;
     a.q = q, a.k = k, a.v = v, a.out = out;
     a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
     a.beams = (int)(R / Rk), a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = past, a.causal = causal != 0;
-    a.bias = bias_by_delta, a.bias_base = bias_base;
+    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1) - past;  // table row of the smallest delta j - i - past
     a.key_mask = key_mask;
     a.anc = past > 0 ? anc : nullptr;  // at past = 0 the only key is the row's own: the dense form of slab 0
     a.ld_anc = ld_anc, a.slab_rows = slab_rows;
@@ -712,14 +679,15 @@ extern "C" int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, 
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
-    const int ntiles = (Tk + 15) / 16;
-    if (ntiles == 1) return launch_att<1>(a, Rk, RQ_WAVE, lds, s);
-    if (ntiles <= 6) return launch_att<6>(a, Rk, 4 * RQ_WAVE, lds, s);
-    return launch_att<16>(a, Rk, 4 * RQ_WAVE, lds, s);
+    return att_with_mt(Tk, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        return launch_att<t5_attention_kernel<MT>>("t5_attention_kernel", att_lds_bytes(kAttMaxT, att_most_tk(MT), true),
+                                                   Rk * H, MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a);
+    });
 }
 
 extern "C" int rqhip_t5_attention_bwd_supported(int d_kv, int H, int Tq, int Tk) {
-    return d_kv == kAttD && H >= 1 && Tq >= 1 && Tq <= kAttMaxT && Tk >= 1 && Tk <= kAttMaxT;
+    return att_supported(d_kv, H, Tq, Tk);
 }
 
 extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
@@ -727,18 +695,16 @@ extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const 
                                             const float *bias_by_delta, int n_delta, int bias_offset,
                                             const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *out,
                                             int64_t ld_out, float *lse, rqhip_stream_t stream) {
-    const int64_t inner = (int64_t)H * kAttD;
-    const bool strides = ld_q >= inner && ld_kv >= inner && ld_out >= inner && (ld_q | ld_kv | ld_out) % 4 == 0;
-    const int rc = check_train_call("t5_attention_fwd_train", R, Rk, H, d_kv, Tq, Tk, strides, bias_by_delta, n_delta,
-                                    bias_offset, causal, p);
+    const int rc = check_att_call("t5_attention_fwd_train", true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
+                                  {ld_q, ld_kv, ld_out}, bias_by_delta, n_delta, bias_offset, causal, p);
     if (rc != RQHIP_OK) return rc;
     if (R == 0) return RQHIP_OK;
     const unsigned thresh = dropout_threshold(p);
-    if (!q || !k || !v || !out || !lse || (thresh && !seed)) {
+    if (any_null(q, k, v, out, lse) || (thresh && !seed)) {
         set_error("t5_attention_fwd_train: null pointer (q, k, v, out, lse; seed when p > 0)");
         return RQHIP_EARG;
     }
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) {
+    if (!all_aligned16(q, k, v, out)) {
         set_error("t5_attention_fwd_train: q, k, v and out must be 16-byte aligned");
         return RQHIP_EARG;
     }
@@ -751,13 +717,15 @@ extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const 
     a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
     AttTrain t;
     t.lse = lse, t.seed = reinterpret_cast<const long long *>(seed), t.thresh = thresh;
-    t.inv_keep = 1.0f / (1.0f - (float)p);
+    t.inv_keep = dropout_scale_f32(p);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
-    const int ntiles = (Tk + 15) / 16;  // the inference entry point's plan
-    if (ntiles == 1) return launch_att_train<1>(a, t, R, RQ_WAVE, lds, s);
-    if (ntiles <= 6) return launch_att_train<6>(a, t, R, 4 * RQ_WAVE, lds, s);
-    return launch_att_train<16>(a, t, R, 4 * RQ_WAVE, lds, s);
+    return att_with_mt(Tk, [&](auto mt) {  // the inference entry point's plan
+        constexpr int MT = decltype(mt)::value;
+        return launch_att<t5_attention_train_kernel<MT>>("t5_attention_train_kernel",
+                                                         att_lds_bytes(kAttMaxT, att_most_tk(MT), true), R * H,
+                                                         MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a, t);
+    });
 }
 
 extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
@@ -766,22 +734,18 @@ extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float 
                                       const float *bias_by_delta, int n_delta, int bias_offset, const uint8_t *key_mask,
                                       int causal, double p, const int64_t *seed, float *d_q, float *d_k, float *d_v,
                                       float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream) {
-    const int64_t inner = (int64_t)H * kAttD;
-    const bool strides = ld_q >= inner && ld_kv >= inner && ld_out >= inner && ld_do >= inner &&
-                         (ld_q | ld_kv | ld_out | ld_do) % 4 == 0;
-    const int rc = check_train_call("t5_attention_bwd", R, Rk, H, d_kv, Tq, Tk, strides, bias_by_delta, n_delta,
-                                    bias_offset, causal, p);
+    const int rc = check_att_call("t5_attention_bwd", true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
+                                  {ld_q, ld_kv, ld_out, ld_do}, bias_by_delta, n_delta, bias_offset, causal, p);
     if (rc != RQHIP_OK) return rc;
     if (R == 0 && !bias_by_delta) return RQHIP_OK;
     const unsigned thresh = dropout_threshold(p);
-    if (!q || !k || !v || !out || !lse || !d_out || !d_q || !d_k || !d_v || (thresh && !seed) ||
-        (bias_by_delta && (!d_bias_by_delta || !d_bias_partial))) {
+    if (any_null(q, k, v, out, lse, d_out, d_q, d_k, d_v) || (thresh && !seed) ||
+        (bias_by_delta && any_null(d_bias_by_delta, d_bias_partial))) {
         set_error("t5_attention_bwd: null pointer (q, k, v, out, lse, d_out, d_q, d_k, d_v; seed when p > 0; "
                   "d_bias_by_delta and d_bias_partial with a bias table)");
         return RQHIP_EARG;
     }
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(d_out) || !aligned16(d_q) ||
-        !aligned16(d_k) || !aligned16(d_v)) {
+    if (!all_aligned16(q, k, v, out, d_out, d_q, d_k, d_v)) {
         set_error("t5_attention_bwd: q, k, v, out, d_out, d_q, d_k and d_v must be 16-byte aligned");
         return RQHIP_EARG;
     }
@@ -796,14 +760,15 @@ extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float 
         a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
         a.key_mask = key_mask;
         a.seed = reinterpret_cast<const long long *>(seed), a.thresh = thresh;
-        a.inv_keep = 1.0f / (1.0f - (float)p);
-        const int ntiles = (Tk + 15) / 16;
+        a.inv_keep = dropout_scale_f32(p);
         const int threads = (Tq <= 16 && Tk <= 16) ? RQ_WAVE : 4 * RQ_WAVE;
         const size_t lds = att_bwd_lds(Tq, Tk, bias_by_delta != nullptr, threads / RQ_WAVE).total * sizeof(float);
-        int lrc;
-        if (ntiles == 1) lrc = launch_att_bwd<1>(a, R, threads, lds, s);
-        else if (ntiles <= 6) lrc = launch_att_bwd<6>(a, R, threads, lds, s);
-        else lrc = launch_att_bwd<16>(a, R, threads, lds, s);
+        const int lrc = att_with_mt(Tk, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            return launch_att<t5_attention_bwd_kernel<MT>>(
+                "t5_attention_bwd_kernel", att_bwd_lds(kAttMaxT, att_most_tk(MT), true, 4).total * sizeof(float), R * H,
+                threads, lds, s, a);
+        });
         if (lrc != RQHIP_OK) return lrc;
     }
     if (bias_by_delta) {

@@ -36,13 +36,12 @@
 #include <math.h>
 
 #include "rqhip_common.h"
-#include "t5_dropout_hash.h"
+#include "t5_common.h"
 
 namespace rqhip {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kFfnMaxD = 512, kFfnMaxF = 8192;
@@ -257,11 +256,11 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
                         if constexpr (!BWD) {
                             v = v <= 0.f ? 0.f : v;      // +0 for every pre-activation <= 0; a NaN stays a NaN
                             if (p.mid && grow < p.N) p.mid[(size_t)grow * F + f] = v;
-                            if (p.th) v = att_keep(seed, (unsigned long long)grow * F + f, p.th) ? v * p.s : 0.f;
+                            if (p.th) v = dropout_keep(seed, (unsigned long long)grow * F + f, p.th) ? v * p.s : 0.f;
                         } else {
                             bool on = hv[rt][ct][r] > 0.f;
                             if (p.th) {
-                                on = on && att_keep(seed, (unsigned long long)(grow < p.N ? grow : p.N - 1) * F + f, p.th);
+                                on = on && dropout_keep(seed, (unsigned long long)(grow < p.N ? grow : p.N - 1) * F + f, p.th);
                                 v = v * p.s;
                             }
                             v = on ? v : 0.f;
@@ -366,8 +365,8 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
             const long long n = b * kFfnWgBlock + 4 * ks + kq;
             if (drop) {
                 const unsigned long long e = (unsigned long long)n * p.F + (unsigned long long)(b0 + 2 * i);
-                qb[ks].x = att_keep(seed, e, p.th) ? qb[ks].x * p.s : 0.f;
-                qb[ks].y = att_keep(seed, e + 1, p.th) ? qb[ks].y * p.s : 0.f;
+                qb[ks].x = dropout_keep(seed, e, p.th) ? qb[ks].x * p.s : 0.f;
+                qb[ks].y = dropout_keep(seed, e + 1, p.th) ? qb[ks].y * p.s : 0.f;
             }
             if (n >= p.N) pa[ks] = qb[ks] = f32x2{0.f, 0.f};
         }
@@ -418,13 +417,6 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
     }
 }
 
-bool ffn_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-unsigned ffn_threshold(double p) {
-    const double t = nearbyint(p * 4294967296.0);
-    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-}
-
 int ffn_row_tiles(long long N) { return N > kFfnTallFrom ? 2 : 1; }
 
 // The checks the entry points share; `who` names the entry point in the message.
@@ -433,7 +425,7 @@ int ffn_check(const char *who, int64_t N, int d, int F, double p) {
         set_error("%s: bad sizes (N=%lld, d=%d, F=%d)", who, (long long)N, d, F);
         return RQHIP_EARG;
     }
-    if (!(p >= 0.0 && p < 1.0)) {
+    if (!dropout_p_valid(p)) {
         set_error("%s: dropout probability p=%g outside 0 <= p < 1", who, p);
         return RQHIP_EARG;
     }
@@ -495,8 +487,8 @@ extern "C" int rqhip_t5_ffn_fwd(const float *x, const float *wi, const float *wo
     const int rc = ffn_check("t5_ffn_fwd", N, d, F, p);
     if (rc != RQHIP_OK) return rc;
     if (N == 0) return RQHIP_OK;
-    const unsigned th = ffn_threshold(p);
-    if (!x || !wi || !wo || !y) {
+    const unsigned th = dropout_threshold(p);
+    if (any_null(x, wi, wo, y)) {
         set_error("t5_ffn_fwd: null pointer (x, wi, wo, y)");
         return RQHIP_EARG;
     }
@@ -504,13 +496,13 @@ extern "C" int rqhip_t5_ffn_fwd(const float *x, const float *wi, const float *wo
         set_error("t5_ffn_fwd: dropout (p=%g) needs the seed, a one-element int64 device pointer", p);
         return RQHIP_EARG;
     }
-    if (!ffn_aligned16(x) || !ffn_aligned16(wi) || !ffn_aligned16(wo) || !ffn_aligned16(y) || !ffn_aligned16(h)) {
+    if (!all_aligned16(x, wi, wo, y, h)) {
         set_error("t5_ffn_fwd: x, wi, wo, y and h must be 16-byte aligned");
         return RQHIP_EARG;
     }
     FfnRows a;
     a.x = x, a.w1 = wi, a.w2 = wo, a.h_in = nullptr, a.mid = h, a.out = y;
-    a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = (float)(1.0 / (1.0 - p));
+    a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
     a.N = N, a.d = d, a.F = F;
     return ffn_rows<false>(a, reinterpret_cast<hipStream_t>(stream));
 }
@@ -521,8 +513,8 @@ extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo
     const int rc = ffn_check("t5_ffn_bwd", N, d, F, p);
     if (rc != RQHIP_OK) return rc;
     if (N == 0 || (!d_x && !d_wi && !d_wo)) return RQHIP_OK;
-    const unsigned th = ffn_threshold(p);
-    if (!x || !wi || !wo || !h || !d_y) {
+    const unsigned th = dropout_threshold(p);
+    if (any_null(x, wi, wo, h, d_y)) {
         set_error("t5_ffn_bwd: null pointer (x, wi, wo, h, d_y)");
         return RQHIP_EARG;
     }
@@ -535,8 +527,7 @@ extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo
                   rqhip_t5_ffn_bwd_workspace_bytes(N, d, F));
         return RQHIP_EWORKSPACE;
     }
-    if (!ffn_aligned16(x) || !ffn_aligned16(wi) || !ffn_aligned16(wo) || !ffn_aligned16(h) || !ffn_aligned16(d_y) ||
-        !ffn_aligned16(d_x) || !ffn_aligned16(d_wi) || !ffn_aligned16(d_wo) || !ffn_aligned16(workspace)) {
+    if (!all_aligned16(x, wi, wo, h, d_y, d_x, d_wi, d_wo, workspace)) {
         set_error("t5_ffn_bwd: x, wi, wo, h, d_y, d_x, d_wi, d_wo and the workspace must be 16-byte aligned");
         return RQHIP_EARG;
     }
@@ -545,7 +536,7 @@ extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo
     if (d_x || d_wi) {
         FfnRows a;
         a.x = d_y, a.w1 = wo, a.w2 = wi, a.h_in = h, a.mid = g, a.out = d_x;
-        a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = (float)(1.0 / (1.0 - p));
+        a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
         a.N = N, a.d = d, a.F = F;
         const int rc1 = ffn_rows<true>(a, s);
         if (rc1 != RQHIP_OK) return rc1;
@@ -553,7 +544,7 @@ extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo
     if (d_wi || d_wo) {
         FfnWgrad q;
         q.g = g, q.x = x, q.dy = d_y, q.h = h, q.d_wi = d_wi, q.d_wo = d_wo;
-        q.seed = reinterpret_cast<const long long *>(seed), q.th = th, q.s = (float)(1.0 / (1.0 - p));
+        q.seed = reinterpret_cast<const long long *>(seed), q.th = th, q.s = dropout_scale_f64(p);
         q.N = N, q.d = d, q.F = F;
         const int tiles = (d / 32) * (F / 32);
         q.tiles_wi = d_wi ? tiles : 0;

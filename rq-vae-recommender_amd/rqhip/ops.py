@@ -559,11 +559,24 @@ def _token_rows(t: Tensor, name: str, copy: bool = True) -> Tensor:
     return t
 
 
+def _dropout_seed(who: str, seed: Optional[Tensor], **ps: float) -> Optional[int]:
+    """Checks a call's one or two dropout probabilities (by the caller's names) and their seed -> the seed pointer, or None."""
+    named = lambda: ", ".join(f"{name}={p}" for name, p in ps.items())  # only when raised: this runs once per launch
+    live = False
+    for p in ps.values():
+        if not 0.0 <= p < 1.0:
+            raise RqHipError(f"{who}: {named()} outside 0 <= p < 1")
+        live = live or p > 0
+    if live and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
+        raise RqHipError(f"{who}: dropout ({named()}) needs `seed`, a one-element int64 device tensor")
+    return seed.data_ptr() if live else None
+
+
 def _attention_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, bias_by_delta: Optional[Tensor],
                     key_mask: Optional[Tensor], p: float = 0.0, seed: Optional[Tensor] = None, past: int = 0,
                     anc: Optional[Tensor] = None):
-    """The checks and copies t5_attention, t5_attention_fwd_train and t5_attention_bwd share.  With `anc` k and v are
-    the position slabs, which are never copied, and the keys are the positions 0 .. past of each of the R rows."""
+    """The checks and copies t5_attention, t5_attention_fwd_train and t5_attention_bwd share (last result: the seed pointer).
+    With `anc` k and v are the position slabs, which are never copied, and the keys are the positions 0 .. past of each row."""
     q = _token_rows(q, "q")
     R, Tq, inner = q.shape
     if inner != n_heads * 64:
@@ -591,9 +604,7 @@ def _attention_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, bia
             raise RqHipError(f"{who}: key_mask must be bool / uint8 [{Rk}, {Tk}], got {key_mask.dtype} "
                              f"{tuple(key_mask.shape)}")
         key_mask = key_mask.contiguous()
-    if p > 0 and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
-        raise RqHipError(f"{who}: dropout (p={p}) needs `seed`, a one-element int64 device tensor")
-    return q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner
+    return q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _dropout_seed(who, seed, p=p)
 
 
 def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
@@ -608,8 +619,8 @@ def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta
     bias_by_delta [n_delta, n_heads]: table[(j - i - past) + bias_offset] is added.  key_mask [Rk, Tk] bool / uint8
     (0 = masked), causal keeps j <= i + past; masked scores get finfo(float32).min added."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, anc)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _attention_args("t5_attention", q, k, v, n_heads,
-                                                                             bias_by_delta, key_mask, past=past, anc=anc)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _ = _attention_args("t5_attention", q, k, v, n_heads,
+                                                                                bias_by_delta, key_mask, past=past, anc=anc)
     slab_rows, ld_anc = (0, 0) if anc is None else (k.shape[1], int(anc.stride(0)))
     dev = q.device
     with torch.cuda.device(dev):
@@ -665,8 +676,8 @@ def t5_attention_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bia
     t5_attention_dropout_keep(seed, ...) and scaled by 1 / (1 - p); `seed` is a one-element int64 device tensor the host
     never reads.  At p = 0 `out` has the bits of t5_attention."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _attention_args("t5_attention_fwd_train", q, k, v,
-                                                                             n_heads, bias_by_delta, key_mask, p, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+        "t5_attention_fwd_train", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
     dev = q.device
     with torch.cuda.device(dev):
         out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
@@ -674,8 +685,7 @@ def t5_attention_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bia
         rc = _lib.lib().rqhip_t5_attention_fwd_train(
             _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
             _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
-            _ptr(key_mask), int(bool(causal)), float(p), _ptr(seed) if p > 0 else None, _ptr(out), inner, _ptr(lse),
-            _stream())
+            _ptr(key_mask), int(bool(causal)), float(p), seed_ptr, _ptr(out), inner, _ptr(lse), _stream())
         check(rc, "rqhip_t5_attention_fwd_train")
     return out, lse
 
@@ -687,8 +697,8 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
     dk, dv [R, Tk, inner], dtable [n_delta, n_heads] or None without a bias table).  The arguments are the forward's, its
     `out` and `lse`, and d_out [R, Tq, inner]; the weights are recomputed, the dropout decisions too."""
     _need_gpu(q, k, v, out, lse, d_out, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner = _attention_args("t5_attention_bwd", q, k, v, n_heads,
-                                                                             bias_by_delta, key_mask, p, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+        "t5_attention_bwd", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
     out, d_out = _token_rows(out, "out"), _token_rows(d_out, "d_out")
     if out.shape != q.shape or d_out.shape != q.shape:
         raise RqHipError(f"t5_attention_bwd: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q "
@@ -709,7 +719,7 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
             _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), _ptr(out), int(out.stride(1)), _ptr(lse),
             _ptr(d_out), int(d_out.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk, _ptr(bias_by_delta),
             0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset), _ptr(key_mask), int(bool(causal)),
-            float(p), _ptr(seed) if p > 0 else None, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dtable), _ptr(partial), _stream())
+            float(p), seed_ptr, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dtable), _ptr(partial), _stream())
         check(rc, "rqhip_t5_attention_bwd")
     return dq, dk, dv, dtable
 
@@ -736,15 +746,11 @@ def _aligned16(t: Tensor) -> Tensor:
     return t.clone() if t.data_ptr() % 16 else t
 
 
-def _norm_call(who: str, d: int, w: Tensor, p_in: float, p_out: float, seed: Optional[Tensor]) -> Tensor:
-    """The checks t5_add_norm_fwd and t5_add_norm_bwd share; returns w as the kernels read it."""
+def _norm_call(who: str, d: int, w: Tensor, p_in: float, p_out: float, seed: Optional[Tensor]):
+    """The checks t5_add_norm_fwd and t5_add_norm_bwd share -> (w as the kernels read it, the seed pointer)."""
     if w.dtype != torch.float32 or tuple(w.shape) != (d,):
         raise RqHipError(f"{who}: w must be float32 [{d}], got {w.dtype} {tuple(w.shape)}")
-    if not (0.0 <= p_in < 1.0 and 0.0 <= p_out < 1.0):
-        raise RqHipError(f"{who}: p_in={p_in}, p_out={p_out} outside 0 <= p < 1")
-    if (p_in > 0 or p_out > 0) and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
-        raise RqHipError(f"{who}: dropout (p_in={p_in}, p_out={p_out}) needs `seed`, a one-element int64 device tensor")
-    return _aligned16(w.contiguous())
+    return _aligned16(w.contiguous()), _dropout_seed(who, seed, p_in=p_in, p_out=p_out)
 
 
 def t5_add_norm_fwd(x: Optional[Tensor], y: Tensor, w: Tensor, eps: float, p_in: float = 0.0, p_out: float = 0.0,
@@ -758,15 +764,14 @@ def t5_add_norm_fwd(x: Optional[Tensor], y: Tensor, w: Tensor, eps: float, p_in:
     y = _norm_rows(y, "y", "t5_add_norm_fwd")
     x = _norm_rows(x, "x", "t5_add_norm_fwd", y.shape)
     d = y.shape[-1]
-    w = _norm_call("t5_add_norm_fwd", d, w, p_in, p_out, seed)
+    w, seed_ptr = _norm_call("t5_add_norm_fwd", d, w, p_in, p_out, seed)
     N = y.numel() // d if d else 0
     dev = y.device
     with torch.cuda.device(dev):
         x_new, n = torch.empty_like(y), torch.empty_like(y)
         rstd = torch.empty(y.shape[:-1], dtype=torch.float32, device=dev)
         rc = _lib.lib().rqhip_t5_add_norm_fwd(_ptr(x), _ptr(y), _ptr(w), N, d, float(eps), float(p_in), float(p_out),
-                                              _ptr(seed) if (p_in > 0 or p_out > 0) else None, _ptr(x_new), _ptr(n),
-                                              _ptr(rstd), _stream())
+                                              seed_ptr, _ptr(x_new), _ptr(n), _ptr(rstd), _stream())
         check(rc, "rqhip_t5_add_norm_fwd")
     return x_new, n, rstd
 
@@ -783,7 +788,7 @@ def t5_add_norm_bwd(x_new: Tensor, rstd: Tensor, w: Tensor, d_n: Optional[Tensor
     x_new = _norm_rows(x_new, "x_new", who)
     d_n, d_xnew = _norm_rows(d_n, "d_n", who, x_new.shape), _norm_rows(d_xnew, "d_xnew", who, x_new.shape)
     d = x_new.shape[-1]
-    w = _norm_call(who, d, w, p_in, p_out, seed)
+    w, seed_ptr = _norm_call(who, d, w, p_in, p_out, seed)
     rstd = _f32c(rstd, "rstd")
     if tuple(rstd.shape) != tuple(x_new.shape[:-1]):
         raise RqHipError(f"{who}: rstd must be {tuple(x_new.shape[:-1])}, got {tuple(rstd.shape)}")
@@ -797,8 +802,8 @@ def t5_add_norm_bwd(x_new: Tensor, rstd: Tensor, w: Tensor, d_n: Optional[Tensor
         nbytes = int(_lib.lib().rqhip_t5_add_norm_bwd_workspace_bytes(N, d))
         work = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=dev)
         rc = _lib.lib().rqhip_t5_add_norm_bwd(_ptr(x_new), _ptr(rstd), _ptr(w), _ptr(d_n), _ptr(d_xnew), N, d, float(p_in),
-                                              float(p_out), _ptr(seed) if (p_in > 0 or p_out > 0) else None, _ptr(d_x),
-                                              _ptr(d_y), _ptr(d_w), _ptr(work), nbytes, _stream())
+                                              float(p_out), seed_ptr, _ptr(d_x), _ptr(d_y), _ptr(d_w), _ptr(work), nbytes,
+                                              _stream())
         check(rc, "rqhip_t5_add_norm_bwd")
     return d_x, (d_x if shared else d_y), d_w
 
@@ -810,7 +815,7 @@ def t5_ffn_supported(dtype: torch.dtype, d: int, F: int) -> bool:
 
 
 def _ffn_call(who: str, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor]):
-    """The checks and copies t5_ffn_fwd and t5_ffn_bwd share -> (x, wi, wo as the kernels read them, N, d, F)."""
+    """The checks and copies t5_ffn_fwd and t5_ffn_bwd share -> (x, wi, wo as the kernels read them, N, d, F, seed pointer)."""
     x = _norm_rows(x, "x", who)
     d = x.shape[-1]
     if wi.dtype != torch.float32 or wi.dim() != 2 or wi.shape[1] != d:
@@ -818,13 +823,10 @@ def _ffn_call(who: str, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optio
     F = wi.shape[0]
     if wo.dtype != torch.float32 or tuple(wo.shape) != (d, F):
         raise RqHipError(f"{who}: wo must be float32 [{d}, {F}], got {wo.dtype} {tuple(wo.shape)}")
-    if not 0.0 <= p < 1.0:
-        raise RqHipError(f"{who}: p={p} outside 0 <= p < 1")
-    if p > 0 and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1):
-        raise RqHipError(f"{who}: dropout (p={p}) needs `seed`, a one-element int64 device tensor")
+    seed_ptr = _dropout_seed(who, seed, p=p)
     if not t5_ffn_supported(x.dtype, d, F):
         raise RqHipError(f"{who}: (d, F) = ({d}, {F}) is not supported (multiples of 32, d <= 512, F <= 8192)")
-    return x, _aligned16(wi.contiguous()), _aligned16(wo.contiguous()), (x.numel() // d), d, F
+    return x, _aligned16(wi.contiguous()), _aligned16(wo.contiguous()), (x.numel() // d), d, F, seed_ptr
 
 
 def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *, need_h: bool = True):
@@ -834,13 +836,12 @@ def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional
     1, 1, N, F, p)[0, 0] over the N = x.numel() / d rows; `seed` is a one-element int64 device tensor the host never
     reads."""
     _need_gpu(x, wi, wo, seed)
-    x, wi, wo, N, d, F = _ffn_call("t5_ffn_fwd", x, wi, wo, p, seed)
+    x, wi, wo, N, d, F, seed_ptr = _ffn_call("t5_ffn_fwd", x, wi, wo, p, seed)
     dev = x.device
     with torch.cuda.device(dev):
         y = torch.empty_like(x)
         h = torch.empty(x.shape[:-1] + (F,), dtype=torch.float32, device=dev) if need_h else None
-        rc = _lib.lib().rqhip_t5_ffn_fwd(_ptr(x), _ptr(wi), _ptr(wo), N, d, F, float(p), _ptr(seed) if p > 0 else None,
-                                         _ptr(y), _ptr(h), _stream())
+        rc = _lib.lib().rqhip_t5_ffn_fwd(_ptr(x), _ptr(wi), _ptr(wo), N, d, F, float(p), seed_ptr, _ptr(y), _ptr(h), _stream())
         check(rc, "rqhip_t5_ffn_fwd")
     return y, h
 
@@ -853,7 +854,7 @@ def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: flo
     the shape alone.  The [N, F] workspace comes from torch's allocator."""
     _need_gpu(x, wi, wo, h, d_y, seed)
     who = "t5_ffn_bwd"
-    x, wi, wo, N, d, F = _ffn_call(who, x, wi, wo, p, seed)
+    x, wi, wo, N, d, F, seed_ptr = _ffn_call(who, x, wi, wo, p, seed)
     h = _norm_rows(h, "h", who, x.shape[:-1] + (F,))
     d_y = _norm_rows(d_y, "d_y", who, x.shape)
     dev = x.device
@@ -866,9 +867,8 @@ def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: flo
         if need_wi and N > 0:
             nbytes = int(_lib.lib().rqhip_t5_ffn_bwd_workspace_bytes(N, d, F))
             work = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        rc = _lib.lib().rqhip_t5_ffn_bwd(_ptr(x), _ptr(wi), _ptr(wo), _ptr(h), _ptr(d_y), N, d, F, float(p),
-                                         _ptr(seed) if p > 0 else None, _ptr(d_x), _ptr(d_wi), _ptr(d_wo), _ptr(work),
-                                         _stream())
+        rc = _lib.lib().rqhip_t5_ffn_bwd(_ptr(x), _ptr(wi), _ptr(wo), _ptr(h), _ptr(d_y), N, d, F, float(p), seed_ptr,
+                                         _ptr(d_x), _ptr(d_wi), _ptr(d_wo), _ptr(work), _stream())
         check(rc, "rqhip_t5_ffn_bwd")
     return d_x, d_wi, d_wo
 
