@@ -1,0 +1,350 @@
+"""What the retrieval-model tests share: the accuracy gate, the bit comparisons, the synthetic batch, the small, tiny,
+default and fixture models, the switch between kernel implementations and the operator restatements of the beam step
+and of the attention inputs.
+
+Test infrastructure like tests/parity_gate.py: imported by the tests and by tools/bench_retrieval_train.py and
+tools/bench_generate.py (which put tests/ on sys.path); the product package never imports it, and it imports the product
+only inside its functions."""
+import contextlib
+import copy
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+# ---- the gate: e = max|a - a64| / max|a64| per tensor, e_kernel <= max(factor * e_torch, floor)
+
+FLOOR = 2.0 ** -22      # two fp32 ulps of the largest element, for the cases in which the operators happen to be exact
+
+
+def err(a, a64):
+    return float((a.to(a64.device).double() - a64).abs().max() / a64.abs().max())
+
+
+def gate(name, got, ref32, ref64, factor, floor=FLOOR):
+    """Prints and asserts the gate of `got` (the kernel) and `ref32` (the operators in fp32 on the same inputs) against
+    `ref64`.  A tensor whose fp64 reference is exactly zero must be exactly zero."""
+    assert torch.isfinite(got).all(), name
+    if not bool(ref64.any()):
+        print(f"{name}: the fp64 reference is exactly zero")
+        assert not bool(got.any()), name
+        return
+    e_kernel, e_torch = err(got, ref64), err(ref32, ref64)
+    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
+    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
+    assert e_kernel <= max(factor * e_torch, floor), name
+
+
+# ---- small helpers
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+
+
+def seed(value):
+    return torch.tensor([value], dtype=torch.int64, device="cuda")
+
+
+def loss_and_grads(model, batch, seed=None):
+    model.zero_grad(set_to_none=True)
+    if seed is not None:
+        torch.manual_seed(seed)
+    loss = model(batch).loss
+    loss.backward()
+    return loss.detach(), {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
+
+
+@contextlib.contextmanager
+def impls(model, *, attention="torch", norm="torch", ffn="torch", head="torch"):
+    """The four implementation choices on `model` and both of its stacks inside the block; after it, also when it
+    raised, all four are "torch" again, the model is in the mode (train / eval) it came in and has no gradients."""
+    def put(*choice):
+        model.attention_impl, model.norm_impl, model.ffn_impl, model.head_impl = choice
+        model._push_attention_impl()
+
+    training = model.training
+    put(attention, norm, ffn, head)
+    try:
+        yield model
+    finally:
+        put("torch", "torch", "torch", "torch")
+        model.train(training)
+        model.zero_grad(set_to_none=True)
+
+
+# ---- the batch: histories with the dedup column, padded tails, future ids, user ids, drawn in that order
+
+
+def synthetic_batch(corpus, B, items, generator, *, pad="none", user_ids=True):
+    """A host TokenizedSeqBatch of B users with `items` corpus rows each.  pad: "none", "row1" (the last item of user 1)
+    or "b_mod_items" (the last b % items items of user b); a padded id is -1 and its mask False.  user_ids False: zeros,
+    and no draw."""
+    from data.schemas import TokenizedSeqBatch
+    N, L = corpus.shape
+    hist = torch.cat([corpus[torch.randint(0, N, (B, items), generator=generator)],
+                      torch.zeros(B, items, 1, dtype=torch.long)], dim=-1)
+    mask = torch.ones(B, items, L + 1, dtype=torch.bool)
+    tails = {"none": {}, "row1": {1: 1}, "b_mod_items": {b: b % items for b in range(B) if b % items}}[pad]
+    for b, n in tails.items():
+        hist[b, items - n:] = -1
+        mask[b, items - n:] = False
+    fut = torch.cat([corpus[torch.randint(0, N, (B,), generator=generator)], torch.zeros(B, 1, dtype=torch.long)], dim=-1)
+    users = torch.randint(0, 100, (B, 1), generator=generator) if user_ids else torch.zeros(B, 1, dtype=torch.long)
+    return TokenizedSeqBatch(users, hist.reshape(B, -1), fut, mask.reshape(B, -1), None, None)
+
+
+def to_device(batch, dev):
+    return type(batch)(*[None if t is None else t.to(dev) for t in batch])
+
+
+# ---- models
+
+LAYERS = 2
+
+
+@functools.lru_cache(maxsize=None)
+def small_model(seed, d_ff, perturb_norms, device="cuda"):
+    """(fp32 model on the device, its fp64 copy on the host, the batch on both) -- built once: d_model 64, 2 heads, 2
+    layers, K = 16, L = 3, batch 3 with one padded row; encoder T = 9, decoder T = 4."""
+    from modules.model import EncoderDecoderRetrievalModel
+    B, items, L, K, N = 3, 2, 3, 16, 200
+    g = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    corpus = torch.randint(0, K, (N, L), generator=g)
+    model = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=64, t5_num_heads=2, t5_d_ff=d_ff, t5_num_layers=LAYERS)
+    if perturb_norms:                              # norm weights away from 1, some negative: their gradients matter
+        with torch.no_grad():
+            for name, p in model.named_parameters():
+                if name.endswith("layer_norm.weight"):
+                    p.copy_(1 + 0.5 * torch.randn(p.shape, generator=g))
+    batch = synthetic_batch(corpus, B, items, g, pad="row1")
+    model64 = copy.deepcopy(model).double().eval()
+    return model.to(device).eval(), model64, to_device(batch, device), batch
+
+
+@functools.lru_cache(maxsize=None)
+def reference(seed, d_ff, perturb_norms):
+    """loss_and_grads of small_model's fp64 copy."""
+    _, model64, _, batch = small_model(seed, d_ff, perturb_norms)
+    return loss_and_grads(model64, batch)
+
+
+def tiny_model(d_model=8, d_ff=8):
+    from modules.model import EncoderDecoderRetrievalModel
+    torch.manual_seed(0)
+    return EncoderDecoderRetrievalModel(torch.zeros(4, 3, dtype=torch.long), 3, 16, t5_d_model=d_model, t5_num_heads=2,
+                                        t5_d_ff=d_ff, t5_num_layers=1)
+
+
+def tiny_batch():
+    from data.schemas import TokenizedSeqBatch
+    g = torch.Generator().manual_seed(1)
+    return TokenizedSeqBatch(torch.zeros(2, 1, dtype=torch.long), torch.randint(0, 16, (2, 8), generator=g),
+                             torch.randint(0, 16, (2, 4), generator=g), torch.ones(2, 8, dtype=torch.bool), None, None)
+
+
+def _corpus(K, L, N, g, dev):
+    base = torch.randint(0, K, (N, L), generator=g)
+    # shared prefixes: a third of the rows copy another row's first L - 1 ids
+    m = N // 3
+    base[:m, : L - 1] = base[torch.randint(m, N, (m,), generator=g), : L - 1]
+    return base.to(dev)
+
+
+def default_model_and_batch(dev, B=64, N=20000, items=20, d=128, L=3, K=256, seed=0):
+    from modules.model import EncoderDecoderRetrievalModel
+    g = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    corpus = _corpus(K, L, N, g, "cpu")
+    model = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=d).to(dev).eval()
+    with torch.no_grad():
+        for lin in model.decoder_mlp:
+            lin.weight.mul_(8.0)
+    return model, to_device(synthetic_batch(corpus, B, items, g, pad="b_mod_items"), dev)
+
+
+# ---- the reference's recorded runs (tests/golden/retrieval_*.npz, tools/gen_retrieval_golden.py)
+
+CASES = ("a", "b", "c")
+
+
+def build_model(fx, device="cpu"):
+    """The fixture's model with its recorded weights (the unused shared / embed_tokens tables filled with zeros)."""
+    from modules.model import EncoderDecoderRetrievalModel
+    L, K, d, heads, d_ff, layers, sep, bins, k = (int(v) for v in fx["config"])
+    corpus = torch.from_numpy(fx["corpus"])
+    model = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=d, t5_num_heads=heads, t5_d_ff=d_ff,
+                                         t5_num_layers=layers, top_k_for_generation=k, should_add_sep_token=bool(sep),
+                                         num_user_bins=bins or None)
+    sd = {name: torch.zeros_like(v) for name, v in model.state_dict().items()}
+    for name in list(sd):
+        if "w." + name in fx:
+            sd[name] = torch.from_numpy(fx["w." + name])
+    model.load_state_dict(sd, strict=True)
+    return model.to(device)
+
+
+def fixture_batch(fx, device="cpu"):
+    from data.schemas import TokenizedSeqBatch
+    return TokenizedSeqBatch(*[torch.from_numpy(fx["batch." + f]).to(device) for f in TokenizedSeqBatch._fields])
+
+
+def check_forward(fx, model, batch):
+    model.eval()
+    model.zero_grad()
+    out = model(batch)
+    out.loss.backward()
+    assert out.logits is None
+    np.testing.assert_allclose(out.loss.item(), float(fx["loss"]), rtol=1e-5)
+    np.testing.assert_allclose(out.loss_d.cpu().numpy(), fx["loss_d"], rtol=1e-5)
+    seen = 0
+    for name, p in model.named_parameters():
+        if "g." + name in fx:
+            want = fx["g." + name]
+            scale = max(float(np.abs(want).max()), 1e-6)
+            got = p.grad.detach().cpu().numpy()
+            np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-4 * scale, err_msg=name)
+            seen += 1
+        else:  # no gradient in the reference: the unused tables
+            assert p.grad is None or not p.grad.any(), name
+    assert seen > 10
+
+
+# ---- the beam step as the reference's operators, and what compares two sets of beams
+
+GAP = 1e-5
+
+
+def _close(a, b):
+    """|a - b| within GAP relative (two equal values, -inf included, are close)."""
+    both_inf = torch.isinf(a) & torch.isinf(b) & (a == b)
+    finite = torch.isfinite(a) & torch.isfinite(b)
+    return both_inf | (finite & ((a - b).abs() <= GAP * torch.maximum(a.abs(), b.abs())))
+
+
+def ref_beam_step(logits, noise, parent_scores, parent_ids, index, corpus, n, k):
+    """The reference's step as torch operators: softmax, topk(p / q) (multinomial without replacement), gather, log,
+    prefix lookup, masked_fill, stable descending sort, gathers.  Also returns, per user, whether an order the kernel
+    may legitimately resolve differently decides the outcome (a gap within 1e-5 relative)."""
+    from rqhip import ops
+    rows, K = logits.shape
+    beams_in = 1 if parent_ids is None else parent_ids.shape[1]
+    h = 0 if parent_ids is None else parent_ids.shape[2]
+    B = rows // beams_in
+    p = F.softmax(logits, dim=-1)
+    keys = p / noise
+    kv, order = torch.sort(keys, dim=-1, descending=True, stable=True)
+    samples = order[:, :n]
+    lp = torch.log(torch.gather(p, 1, samples))
+    if h:
+        prev = parent_ids.repeat_interleave(n, dim=1)                       # [B, beams_in * n, h]
+        prefix = torch.cat([prev, samples.reshape(B, beams_in * n, 1)], dim=-1)
+        scores = lp.reshape(B, beams_in * n) + parent_scores.repeat_interleave(n, dim=1)
+    else:
+        prefix = samples.reshape(B, n, 1)
+        scores = lp.reshape(B, n)
+    valid = ops.prefix_lookup(index, corpus, prefix.reshape(-1, h + 1)).reshape(B, -1)
+    scores = scores.masked_fill(~valid, float("-inf"))
+    sv, idx = torch.sort(scores, dim=-1, descending=True, stable=True)
+    top = idx[:, :k]
+    ids = torch.gather(prefix, 1, top.unsqueeze(-1).expand(-1, -1, h + 1))
+    parent = top // n + torch.arange(B, device=logits.device).unsqueeze(1) * beams_in
+    # ambiguity: the n-th vs the (n+1)-th nonzero key of a row (which codes are sampled; the order inside the n only
+    # numbers the candidates, which matters between equal scores alone), neighbouring finite scores among the first
+    # k + 1 of a user (which candidates are kept, and their order)
+    if n < K:
+        key_tie = (_close(kv[:, n - 1], kv[:, n]) & (kv[:, n - 1] > 0)).reshape(B, beams_in).any(dim=1)
+    else:
+        key_tie = torch.zeros(B, dtype=torch.bool, device=logits.device)
+    ss = sv[:, : min(k + 1, sv.shape[1])]
+    score_tie = (_close(ss[:, :-1], ss[:, 1:]) & torch.isfinite(ss[:, :-1])).any(dim=1)
+    return ids, sv[:, :k], parent, key_tie | score_tie
+
+
+def compare_beams(ids, scores, parent, r_ids, r_scores, r_parent, ambiguous, score_atol, score_rtol=0.0):
+    """Equal ids / parents at every kept beam with a finite reference score, of every user whose outcome no
+    near-tie decides; scores within score_atol or both -inf everywhere.  Returns the number of ambiguous users."""
+    fin = torch.isfinite(r_scores)
+    assert torch.equal(torch.isfinite(scores), fin), "-inf beams differ"
+    np.testing.assert_allclose(scores[fin].cpu().numpy(), r_scores[fin].cpu().numpy(), rtol=score_rtol,
+                               atol=score_atol)
+    ok = (~ambiguous).unsqueeze(1) & fin
+    assert torch.equal(ids[ok], r_ids[ok]), "ids differ"
+    if parent is not None:
+        assert torch.equal(parent[ok], r_parent[ok]), "parents differ"
+    return int(ambiguous.sum())
+
+
+class _Replay:
+    """Stands in for modules.model._exponential_like: hands out given noise tensors in order."""
+
+    def __init__(self, noise):
+        self.noise = list(noise)
+        self.i = 0
+
+    def __call__(self, probas):
+        q = self.noise[self.i]
+        self.i += 1
+        assert q.shape == probas.shape
+        return q
+
+
+def _cache_free_generate(model, batch, noise):
+    """generate() with every step decoded in full (BOS + all ids so far, no cache) and the reference's operators."""
+    from modules.model import _strip_dedup_col
+    L, K, k = model.num_hierarchies, model.num_embeddings_per_hierarchy, model.top_k_for_generation
+    n = min(64, K)
+    ids_in = _strip_dedup_col(batch.sem_ids, L + 1, L)
+    mask = _strip_dedup_col(batch.seq_mask.long(), L + 1, L)
+    idx = model._prefix_index_for_codebooks()
+    with torch.no_grad():
+        enc, enc_mask = model.encoder_forward_pass(mask, ids_in, batch.user_ids)
+        B = enc.shape[0]
+        ids = scores = None
+        amb_any = torch.zeros(B, dtype=torch.bool, device=enc.device)
+        for h in range(L):
+            if h == 0:
+                hid = model.decoder_forward_pass(encoder_output=enc, attention_mask_for_encoder=enc_mask)
+            else:
+                hid = model.decoder_forward_pass(future_ids=ids.reshape(-1, h),
+                                                 encoder_output=enc.repeat_interleave(k, dim=0),
+                                                 attention_mask_for_encoder=enc_mask.repeat_interleave(k, dim=0))
+            logits = model.decoder_mlp[h](hid[:, -1])
+            ids, scores, _, amb = ref_beam_step(logits, noise[h], scores, ids, idx._index, idx._corpus, n, k)
+            amb_any |= amb
+    return ids, scores, amb_any
+
+
+# ---- inputs of the fused attention's tests
+
+
+def _inputs(R, Tq, Rk, Tk, H, seed):
+    g = torch.Generator().manual_seed(seed)
+    dev = torch.device("cuda")
+    q = (torch.randn(R, Tq, H * 64, generator=g) * 1.5).to(dev)   # no 1/sqrt(d): scores reach 30 and beyond
+    k = torch.randn(Rk, Tk, H * 64, generator=g).to(dev)
+    v = torch.randn(Rk, Tk, H * 64, generator=g).to(dev)
+    return q, k, v, g
+
+
+def _bias_module(H, is_decoder, seed):
+    from modules.t5 import T5Attention, T5Config
+    torch.manual_seed(seed)
+    att = T5Attention(T5Config(64, d_model=32, num_heads=H, is_decoder=is_decoder), has_relative_attention_bias=True)
+    torch.nn.init.normal_(att.relative_attention_bias.weight)
+    return att.to("cuda")
+
+
+def _padding(R, T, g):
+    """Keep-mask [R, T] with padded tails of every length; row 1 (if any) is fully masked."""
+    keep = torch.arange(T)[None, :] < torch.randint(1, T + 1, (R, 1), generator=g)
+    keep[0] = True
+    if R > 1:
+        keep[1] = False
+    return keep.to("cuda")

@@ -12,6 +12,8 @@ import math
 import pytest
 import torch
 
+from retrieval_cases import synthetic_batch, to_device
+
 pytestmark = pytest.mark.gpu
 
 LR, WD, B1, B2, EPS = 1e-2, 1e-2, 0.9, 0.999, 1e-8
@@ -286,7 +288,6 @@ def test_tail_continues_from_a_torch_adamw_checkpoint():
 def test_tail_on_the_retrieval_model_s_parameter_list():
     """Against clip_grad_norm_ + torch.optim.AdamW(foreach) + the scheduler on a deep copy fed the same gradients: the tied shared /
     embed_tokens table, the decoder's never-used embed_tokens (.grad None), bos_token and sep_token."""
-    from data.schemas import TokenizedSeqBatch
     from modules.model import EncoderDecoderRetrievalModel
     from modules.scheduler.inv_sqrt import InverseSquareRootScheduler
     from rqhip.optim import FlatAdamW
@@ -294,11 +295,7 @@ def test_tail_on_the_retrieval_model_s_parameter_list():
     g = torch.Generator().manual_seed(11)
     B, items, L, K, N = 4, 3, 3, 8, 20
     corpus = torch.randint(0, K, (N, L), generator=g)
-    hist = torch.cat([corpus[torch.randint(0, N, (B, items), generator=g)], torch.zeros(B, items, 1, dtype=torch.long)], dim=-1)
-    mask = torch.ones(B, items, L + 1, dtype=torch.bool)
-    fut = torch.cat([corpus[torch.randint(0, N, (B,), generator=g)], torch.zeros(B, 1, dtype=torch.long)], dim=-1)
-    batch = TokenizedSeqBatch(torch.randint(0, 100, (B, 1), generator=g).to(dev), hist.reshape(B, -1).to(dev), fut.to(dev),
-                              mask.reshape(B, -1).to(dev), None, None)
+    batch = to_device(synthetic_batch(corpus, B, items, g), dev)
     torch.manual_seed(11)
     a = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=64, t5_num_heads=2, t5_d_ff=128, t5_num_layers=1).to(dev)
     a.attention_impl = a.norm_impl = a.head_impl = a.ffn_impl = "torch"

@@ -7,80 +7,10 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden
-from test_retrieval_model import CASES, build_model, check_forward, fixture_batch
+from retrieval_cases import (CASES, GAP, _cache_free_generate, _close, _corpus, _Replay, build_model, check_forward, compare_beams,
+                             default_model_and_batch, fixture_batch, ref_beam_step, same_bits)
 
 pytestmark = pytest.mark.gpu
-
-GAP = 1e-5
-
-
-def _close(a, b):
-    """|a - b| within GAP relative (two equal values, -inf included, are close)."""
-    both_inf = torch.isinf(a) & torch.isinf(b) & (a == b)
-    finite = torch.isfinite(a) & torch.isfinite(b)
-    return both_inf | (finite & ((a - b).abs() <= GAP * torch.maximum(a.abs(), b.abs())))
-
-
-def ref_beam_step(logits, noise, parent_scores, parent_ids, index, corpus, n, k):
-    """The reference's step as torch operators: softmax, topk(p / q) (multinomial without replacement), gather, log,
-    prefix lookup, masked_fill, stable descending sort, gathers.  Also returns, per user, whether an order the kernel
-    may legitimately resolve differently decides the outcome (a gap within 1e-5 relative)."""
-    from rqhip import ops
-    rows, K = logits.shape
-    beams_in = 1 if parent_ids is None else parent_ids.shape[1]
-    h = 0 if parent_ids is None else parent_ids.shape[2]
-    B = rows // beams_in
-    p = F.softmax(logits, dim=-1)
-    keys = p / noise
-    kv, order = torch.sort(keys, dim=-1, descending=True, stable=True)
-    samples = order[:, :n]
-    lp = torch.log(torch.gather(p, 1, samples))
-    if h:
-        prev = parent_ids.repeat_interleave(n, dim=1)                       # [B, beams_in * n, h]
-        prefix = torch.cat([prev, samples.reshape(B, beams_in * n, 1)], dim=-1)
-        scores = lp.reshape(B, beams_in * n) + parent_scores.repeat_interleave(n, dim=1)
-    else:
-        prefix = samples.reshape(B, n, 1)
-        scores = lp.reshape(B, n)
-    valid = ops.prefix_lookup(index, corpus, prefix.reshape(-1, h + 1)).reshape(B, -1)
-    scores = scores.masked_fill(~valid, float("-inf"))
-    sv, idx = torch.sort(scores, dim=-1, descending=True, stable=True)
-    top = idx[:, :k]
-    ids = torch.gather(prefix, 1, top.unsqueeze(-1).expand(-1, -1, h + 1))
-    parent = top // n + torch.arange(B, device=logits.device).unsqueeze(1) * beams_in
-    # ambiguity: the n-th vs the (n+1)-th nonzero key of a row (which codes are sampled; the order inside the n only
-    # numbers the candidates, which matters between equal scores alone), neighbouring finite scores among the first
-    # k + 1 of a user (which candidates are kept, and their order)
-    if n < K:
-        key_tie = (_close(kv[:, n - 1], kv[:, n]) & (kv[:, n - 1] > 0)).reshape(B, beams_in).any(dim=1)
-    else:
-        key_tie = torch.zeros(B, dtype=torch.bool, device=logits.device)
-    ss = sv[:, : min(k + 1, sv.shape[1])]
-    score_tie = (_close(ss[:, :-1], ss[:, 1:]) & torch.isfinite(ss[:, :-1])).any(dim=1)
-    return ids, sv[:, :k], parent, key_tie | score_tie
-
-
-def compare_beams(ids, scores, parent, r_ids, r_scores, r_parent, ambiguous, score_atol, score_rtol=0.0):
-    """Equal ids / parents at every kept beam with a finite reference score, of every user whose outcome no
-    near-tie decides; scores within score_atol or both -inf everywhere.  Returns the number of ambiguous users."""
-    fin = torch.isfinite(r_scores)
-    assert torch.equal(torch.isfinite(scores), fin), "-inf beams differ"
-    np.testing.assert_allclose(scores[fin].cpu().numpy(), r_scores[fin].cpu().numpy(), rtol=score_rtol,
-                               atol=score_atol)
-    ok = (~ambiguous).unsqueeze(1) & fin
-    assert torch.equal(ids[ok], r_ids[ok]), "ids differ"
-    if parent is not None:
-        assert torch.equal(parent[ok], r_parent[ok]), "parents differ"
-    return int(ambiguous.sum())
-
-
-def _corpus(K, L, N, g, dev):
-    base = torch.randint(0, K, (N, L), generator=g)
-    # shared prefixes: a third of the rows copy another row's first L - 1 ids
-    m = N // 3
-    base[:m, : L - 1] = base[torch.randint(m, N, (m,), generator=g), : L - 1]
-    return base.to(dev)
-
 
 # the step's domain: n <= K, and k <= n at the first step (one row per user)
 STEP_SHAPES = [(K, n, k, h) for K in (8, 256, 4096) for n in (8, 64) for k in (1, 10, 64) for h in (0, 1, 2)
@@ -119,7 +49,7 @@ def test_beam_step_matches_reference_ops(K, n, k, h):
     assert n_amb <= B // 4
     # deterministic
     again = ops.beam_step(logits, noise, parent_scores, parent_ids, index, corpus, n, k)
-    assert torch.equal(again[0], ids) and torch.equal(again[1].view(torch.int32), scores.view(torch.int32))
+    assert torch.equal(again[0], ids) and same_bits(again[1], scores)
 
 
 @pytest.mark.parametrize("K,n", [(16, 16), (256, 64), (4096, 64)])
@@ -141,20 +71,6 @@ def test_forward_and_gradients_match_reference_gpu(case):
     check_forward(fx, build_model(fx, dev), fixture_batch(fx, dev))
 
 
-class _Replay:
-    """Stands in for modules.model._exponential_like: hands out given noise tensors in order."""
-
-    def __init__(self, noise):
-        self.noise = list(noise)
-        self.i = 0
-
-    def __call__(self, probas):
-        q = self.noise[self.i]
-        self.i += 1
-        assert q.shape == probas.shape
-        return q
-
-
 @pytest.mark.parametrize("case", CASES)
 def test_generate_matches_reference_with_recorded_noise(case, monkeypatch):
     import modules.model as mm
@@ -173,62 +89,12 @@ def test_generate_matches_reference_with_recorded_noise(case, monkeypatch):
     assert n_amb == 0
 
 
-def _default_model_and_batch(dev, B=64, N=20000, items=20, d=128, L=3, K=256, seed=0):
-    from data.schemas import TokenizedSeqBatch
-    from modules.model import EncoderDecoderRetrievalModel
-    g = torch.Generator().manual_seed(seed)
-    torch.manual_seed(seed)
-    corpus = _corpus(K, L, N, g, "cpu")
-    model = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=d).to(dev).eval()
-    with torch.no_grad():
-        for lin in model.decoder_mlp:
-            lin.weight.mul_(8.0)
-    hist = torch.cat([corpus[torch.randint(0, N, (B, items), generator=g)], torch.zeros(B, items, 1, dtype=torch.long)],
-                     dim=-1)
-    mask = torch.ones(B, items, L + 1, dtype=torch.bool)
-    for b in range(B):
-        pad = b % items
-        if pad:
-            hist[b, items - pad:] = -1
-            mask[b, items - pad:] = False
-    fut = torch.cat([corpus[torch.randint(0, N, (B,), generator=g)], torch.zeros(B, 1, dtype=torch.long)], dim=-1)
-    batch = TokenizedSeqBatch(torch.randint(0, 100, (B, 1), generator=g), hist.reshape(B, -1), fut,
-                              mask.reshape(B, -1), None, None)
-    return model, TokenizedSeqBatch(*[None if t is None else t.to(dev) for t in batch])
-
-
-def _cache_free_generate(model, batch, noise):
-    """generate() with every step decoded in full (BOS + all ids so far, no cache) and the reference's operators."""
-    from modules.model import _strip_dedup_col
-    L, K, k = model.num_hierarchies, model.num_embeddings_per_hierarchy, model.top_k_for_generation
-    n = min(64, K)
-    ids_in = _strip_dedup_col(batch.sem_ids, L + 1, L)
-    mask = _strip_dedup_col(batch.seq_mask.long(), L + 1, L)
-    idx = model._prefix_index_for_codebooks()
-    with torch.no_grad():
-        enc, enc_mask = model.encoder_forward_pass(mask, ids_in, batch.user_ids)
-        B = enc.shape[0]
-        ids = scores = None
-        amb_any = torch.zeros(B, dtype=torch.bool, device=enc.device)
-        for h in range(L):
-            if h == 0:
-                hid = model.decoder_forward_pass(encoder_output=enc, attention_mask_for_encoder=enc_mask)
-            else:
-                hid = model.decoder_forward_pass(future_ids=ids.reshape(-1, h),
-                                                 encoder_output=enc.repeat_interleave(k, dim=0),
-                                                 attention_mask_for_encoder=enc_mask.repeat_interleave(k, dim=0))
-            logits = model.decoder_mlp[h](hid[:, -1])
-            ids, scores, _, amb = ref_beam_step(logits, noise[h], scores, ids, idx._index, idx._corpus, n, k)
-            amb_any |= amb
-    return ids, scores, amb_any
-
-
 def test_generate_self_consistency_default_config(monkeypatch):
     import modules.model as mm
     from evaluate.metrics import TopKAccumulator
     from rqhip import ops
     dev = torch.device("cuda")
-    model, batch = _default_model_and_batch(dev)
+    model, batch = default_model_and_batch(dev)
     L, k = model.num_hierarchies, model.top_k_for_generation
     B = batch.sem_ids.shape[0]
     # record the noise the model draws
@@ -263,13 +129,13 @@ def test_generate_self_consistency_default_config(monkeypatch):
     torch.manual_seed(7)
     again = model.generate_next_sem_id(batch)
     assert torch.equal(again.sem_ids, out.sem_ids)
-    assert torch.equal(again.log_probas.view(torch.int32), out.log_probas.view(torch.int32))
+    assert same_bits(again.log_probas, out.log_probas)
 
 
 def test_generate_under_graph_capture_equals_eager(monkeypatch):
     import modules.model as mm
     dev = torch.device("cuda")
-    model, batch = _default_model_and_batch(dev, B=32, N=5000, seed=3)
+    model, batch = default_model_and_batch(dev, B=32, N=5000, seed=3)
     L, K, k = model.num_hierarchies, model.num_embeddings_per_hierarchy, model.top_k_for_generation
     B = batch.sem_ids.shape[0]
     torch.manual_seed(11)
@@ -298,13 +164,13 @@ def test_generate_under_graph_capture_equals_eager(monkeypatch):
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(captured.sem_ids, eager.sem_ids)
-    assert torch.equal(captured.log_probas.view(torch.int32), eager.log_probas.view(torch.int32))
+    assert same_bits(captured.log_probas, eager.log_probas)
 
 
 def test_training_smoke_amazon_shape():
     dev = torch.device("cuda")
     from modules.model import EncoderDecoderRetrievalModel
-    model, batch = _default_model_and_batch(dev, B=64, N=12101, d=128, seed=5)
+    model, batch = default_model_and_batch(dev, B=64, N=12101, d=128, seed=5)
     torch.manual_seed(5)
     model = EncoderDecoderRetrievalModel(model.codebooks, 3, 256, t5_d_model=384, t5_num_heads=6, t5_d_ff=1024,
                                          t5_num_layers=4).to(dev)

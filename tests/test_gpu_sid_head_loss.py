@@ -1,7 +1,7 @@
 """The fused semantic-id heads + cross-entropy on the GPU: ops.sid_head_loss_fwd / _bwd and autograd.SidHeadLossFunction
 (csrc/sid_head_loss.hip) against torch's own F.linear / F.cross_entropy in fp64.
 
-Gates as in tests/test_gpu_t5_add_norm.py: e = max|a - a64| / max|a64| per tensor, e_hip <= max(4 e_torch, 2^-22) for
+Gates: retrieval_cases.gate, e = max|a - a64| / max|a64| per tensor, e_kernel <= max(4 e_torch, 2^-22) for
 loss_d and max(8 e_torch, 2^-22) for d_x and each d_w[h]; e_torch from the same operators in fp32 on the same device with
 the same inputs.  Every gated value is printed: profiles/sid_head_loss_error.txt is that output.  Everything the header
 promises about bits (run-to-run, strides, unread positions and columns, independence of the levels, out-of-range
@@ -12,9 +12,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from retrieval_cases import bits, gate
+
 pytestmark = pytest.mark.gpu
 
-FLOOR = 2.0 ** -22
 # (B, K, d, L, T): the smallest sizes at which row blocks of 8, code blocks of 8, 64-row blocks of d_w, 256 codes or
 # columns per pass and their tails can go wrong, and the workload's own (64, 256, 384, 3, 4)
 CASES = [(1, 1, 4, 1, 1), (1, 2, 4, 1, 2), (2, 3, 8, 2, 3), (4, 16, 16, 8, 9), (3, 32, 64, 3, 4), (16, 32, 128, 3, 4),
@@ -24,12 +25,8 @@ SCALED = [((64, 256, 384, 3, 4), 8.0), ((64, 256, 384, 3, 4), 0.05)]
 BITS = [(2, 3, 8, 2, 3), (17, 100, 260, 3, 6), (65, 257, 64, 3, 4)]     # the cases of the exact checks
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
 def _same(a, b):
-    return (a is None and b is None) or torch.equal(_bits(a), _bits(b))
+    return (a is None and b is None) or torch.equal(bits(a), bits(b))
 
 
 @functools.lru_cache(maxsize=None)
@@ -76,22 +73,6 @@ def _fused(x, ws, target, d_loss=None, x_grad=True, frozen=()):
     return loss.detach(), loss_d, x.grad, [w.grad for w in ws]
 
 
-def _err(a, a64):
-    return float((a.double().cpu() - a64).abs().max() / a64.abs().max())
-
-
-def _gate(name, got, ref32, ref64, factor):
-    assert torch.isfinite(got).all(), name
-    if not bool(ref64.any()):
-        print(f"{name}: reference is zero")
-        assert not bool(got.any()), name
-        return
-    e_hip, e_torch = _err(got, ref64), _err(ref32, ref64)
-    ratio = e_hip / e_torch if e_torch > 0 else (0.0 if e_hip == 0 else float("inf"))
-    print(f"{name}: e_hip {e_hip:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
-    assert e_hip <= max(factor * e_torch, FLOOR), name
-
-
 def _on_device(case, scale=1.0):
     dev = torch.device("cuda")
     x, ws, target = _inputs(case, scale)
@@ -118,10 +99,10 @@ def test_against_fp64(case, scale, d_loss):
         assert float(F.linear(x[:, 0], ws[0]).abs().max()) > 100      # logits that need the stable softmax
     if scale == 0.05:
         assert abs(float(loss_d64[0]) - 5.545) < 0.01                 # ln 256
-    _gate(f"{name} loss_d", loss_d, loss_d32, loss_d64, 4)
-    _gate(f"{name} d_x", d_x, dx32, dx64, 8)
+    gate(f"{name} loss_d", loss_d, loss_d32, loss_d64, 4)
+    gate(f"{name} d_x", d_x, dx32, dx64, 8)
     for h in range(L):
-        _gate(f"{name} d_w[{h}]", d_w[h], dw32[h], dw64[h], 8)
+        gate(f"{name} d_w[{h}]", d_w[h], dw32[h], dw64[h], 8)
     # bits: the loss is the levels in torch's order, unread positions get exact zeros, a second run repeats every bit
     assert _same(loss, _ordered_sum(loss_d))
     assert d_x.shape == (B, T, d) and d_x.is_contiguous() and not bool(d_x[:, L:].any())

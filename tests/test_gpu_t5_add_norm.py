@@ -2,7 +2,7 @@
 against the operators of modules/t5.py (dropout, residual add, T5LayerNorm, dropout) with the kernel's masks inserted.
 
 x_new is one rounded multiply and one rounded add: bit-exact against the same two torch operators.  n, rstd and the
-gradients are gated as everywhere in this project: e = max|a - a64| / max|a64| per tensor, for the kernel and for the
+gradients are gated by retrieval_cases.gate: e = max|a - a64| / max|a64| per tensor, for the kernel and for the
 operator chain in fp32 on the same inputs, both against the chain in fp64 (under autograd for the gradients);
 e_kernel <= max(4 e_torch, 2^-22) for n and rstd, e_kernel <= max(8 e_torch, 2^-22) for d_x, d_y and d_w.  The floor is
 two fp32 ulps of the largest element, for the cases in which the operators happen to be exact.  A tensor whose fp64
@@ -17,17 +17,14 @@ test_ordinary_rows_alone repeats the gates on normal rows only, where every row 
 import pytest
 import torch
 
+from retrieval_cases import gate, same_bits, seed as _seed
+
 pytestmark = pytest.mark.gpu
 
 DS = (4, 64, 128, 260, 384, 1024)
 NS = (1, 3, 4, 5, 63, 64, 65, 200)
 PS = ((0.0, 0.0), (0.1, 0.0), (0.0, 0.1), (0.5, 0.5))
 EPS = 1e-6
-FLOOR = 2.0 ** -22
-
-
-def _seed(value):
-    return torch.tensor([value], dtype=torch.int64, device="cuda")
 
 
 def _data(N, d, has_x=True, ordinary=False):
@@ -77,26 +74,6 @@ def _chain(x, y, w, keep_in, keep_out, p_in, p_out, dtype, d_xnew=None, d_n=None
     return x_new.detach(), n.detach(), rstd.detach().squeeze(-1), grads
 
 
-def _err(a, a64):
-    return float((a.double() - a64).abs().max() / a64.abs().max())
-
-
-def _gate(name, got, ref32, ref64, factor):
-    assert torch.isfinite(got).all(), name
-    if not bool(ref64.any()):
-        print(f"{name}: the fp64 reference is exactly zero")
-        assert not bool(got.any()), name
-        return
-    e_kernel, e_torch = _err(got, ref64), _err(ref32, ref64)
-    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
-    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
-    assert e_kernel <= max(factor * e_torch, FLOOR), name
-
-
-def _bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 @pytest.mark.parametrize("has_x", [True, False])
 @pytest.mark.parametrize("d", DS)
 def test_forward(d, has_x):
@@ -113,19 +90,19 @@ def test_forward(d, has_x):
                 x_new, n, rstd = ops.t5_add_norm_fwd(x, y, w, EPS, p_in, p_out, seed)
                 # x_new: one rounded multiply, one rounded add
                 t = y if keep_in is None else torch.where(keep_in, y * (1.0 / (1.0 - p_in)), torch.zeros_like(y))
-                assert _bits(x_new, t if x is None else x + t), name
+                assert same_bits(x_new, t if x is None else x + t), name
                 assert x_new.shape == y.shape and n.shape == y.shape and rstd.shape == (N,)
                 if p_out > 0:   # exactly +0 where dropped, elsewhere the undropped n of the same x_new times s_out
                     base = ops.t5_add_norm_fwd(x, y, w, EPS, p_in, 0.0, seed)
-                    assert _bits(base[0], x_new) and _bits(base[2], rstd), name
-                    assert _bits(n, torch.where(keep_out, base[1] * (1.0 / (1.0 - p_out)), torch.zeros_like(n))), name
+                    assert same_bits(base[0], x_new) and same_bits(base[2], rstd), name
+                    assert same_bits(n, torch.where(keep_out, base[1] * (1.0 / (1.0 - p_out)), torch.zeros_like(n))), name
                     assert not bool(n.view(torch.int32)[~keep_out].any()), name
                 if p_in == 0 and p_out == 0:
-                    assert all(_bits(a, b) for a, b in zip(plain, (x_new, n, rstd))), name
+                    assert all(same_bits(a, b) for a, b in zip(plain, (x_new, n, rstd))), name
             ref64 = _chain(x, y, w, keep_in, keep_out, p_in, p_out, torch.float64)
             ref32 = _chain(x, y, w, keep_in, keep_out, p_in, p_out, torch.float32)
-            _gate(f"{name} n", n, ref32[1], ref64[1], 4)
-            _gate(f"{name} rstd", rstd, ref32[2], ref64[2], 4)
+            gate(f"{name} n", n, ref32[1], ref64[1], 4)
+            gate(f"{name} rstd", rstd, ref32[2], ref64[2], 4)
             if N >= 4:           # the all-zero row: rstd = 1 / sqrt(eps), n = 0
                 assert not bool(x_new[3].any()) and not bool(n[3].any()), name
                 assert abs(float(rstd[3]) - 1000.0) <= 1e-3, name
@@ -153,16 +130,16 @@ def test_backward(d):
                 assert (d_x is None) == (x is None)
                 if p_in == 0:
                     assert both[0] is both[1], name
-                    assert _bits(both[0], d_y), name
+                    assert same_bits(both[0], d_y), name
                 else:
-                    assert _bits(both[1], torch.where(keep_in, both[0] * (1.0 / (1.0 - p_in)), torch.zeros_like(d_y))), name
-                    assert _bits(both[1], d_y), name
-                assert _bits(both[2], d_w) and (d_x is None or _bits(both[0], d_x)), name
+                    assert same_bits(both[1], torch.where(keep_in, both[0] * (1.0 / (1.0 - p_in)), torch.zeros_like(d_y))), name
+                    assert same_bits(both[1], d_y), name
+                assert same_bits(both[2], d_w) and (d_x is None or same_bits(both[0], d_x)), name
                 ref64 = _chain(x, y, w, keep_in, keep_out, p_in, p_out, torch.float64, d_xnew, d_n)[3]
                 ref32 = _chain(x, y, w, keep_in, keep_out, p_in, p_out, torch.float32, d_xnew, d_n)[3]
                 for nm, a, a32, a64 in zip(("d_x", "d_y", "d_w"), (d_x, d_y, d_w), ref32, ref64):
                     if a is not None:
-                        _gate(f"{name} {nm}", a, a32, a64, 8)
+                        gate(f"{name} {nm}", a, a32, a64, 8)
 
 
 @pytest.mark.parametrize("d", DS)
@@ -182,12 +159,12 @@ def test_ordinary_rows_alone(d):
                     grads = ops.t5_add_norm_bwd(x_new, rstd, w, d_n, d_xnew, p_in, p_out, seed, need_x=has_x)
                 ref64 = _chain(x, y, w, keep_in, keep_out, p_in, p_out, torch.float64, d_xnew, d_n)
                 ref32 = _chain(x, y, w, keep_in, keep_out, p_in, p_out, torch.float32, d_xnew, d_n)
-                assert _bits(x_new, ref32[0]), name
-                _gate(f"{name} n", n, ref32[1], ref64[1], 4)
-                _gate(f"{name} rstd", rstd, ref32[2], ref64[2], 4)
+                assert same_bits(x_new, ref32[0]), name
+                gate(f"{name} n", n, ref32[1], ref64[1], 4)
+                gate(f"{name} rstd", rstd, ref32[2], ref64[2], 4)
                 for nm, a, a32, a64 in zip(("d_x", "d_y", "d_w"), grads, ref32[3], ref64[3]):
                     if a is not None:
-                        _gate(f"{name} {nm}", a, a32, a64, 8)
+                        gate(f"{name} {nm}", a, a32, a64, 8)
 
 
 @pytest.mark.parametrize("d", DS)
@@ -204,17 +181,17 @@ def test_same_bits_twice_and_rows_do_not_depend_on_the_batch(d):
 
     for p_in, p_out in PS:
         a, b = run(p_in, p_out, _seed(3)), run(p_in, p_out, _seed(3))
-        assert all(_bits(u, v) for u, v in zip(a, b)), (p_in, p_out)
+        assert all(same_bits(u, v) for u, v in zip(a, b)), (p_in, p_out)
     whole = run(0.0, 0.0, None)
     for r in (0, 1, 2, 3, 62, 63, 64, 67, 199):
         one = run(0.0, 0.0, None, slice(r, r + 1))
         for k in (0, 1, 2, 3):       # x_new, n, rstd, d_x
-            assert _bits(whole[k][r:r + 1], one[k]), (r, k)
+            assert same_bits(whole[k][r:r + 1], one[k]), (r, k)
     # another seed, other masks: x_new carries keep_in, n keep_out
     a, b = run(0.5, 0.0, _seed(3)), run(0.5, 0.0, _seed(4))
-    assert not _bits(a[0], b[0])
+    assert not same_bits(a[0], b[0])
     a, b = run(0.0, 0.5, _seed(3)), run(0.0, 0.5, _seed(4))
-    assert _bits(a[0], b[0]) and not _bits(a[1], b[1])
+    assert same_bits(a[0], b[0]) and not same_bits(a[1], b[1])
     keep = ops.t5_attention_dropout_keep(_seed(3), 2, 1, N, d, 0.5)
     assert not torch.equal(keep[0], keep[1])          # the two planes of one seed differ too
 
@@ -232,8 +209,8 @@ def test_function_matches_the_direct_calls():
         with torch.no_grad():
             f = ops.t5_add_norm_fwd(x, y, w, EPS, p_in, 0.1, seed)
             g = ops.t5_add_norm_bwd(f[0], f[2], w, d_n, d_xnew, p_in, 0.1, seed)
-        assert _bits(x_new, f[0]) and _bits(n, f[1])
-        assert _bits(xs.grad, g[0]) and _bits(ys.grad, g[1]) and _bits(ws.grad, g[2])
+        assert same_bits(x_new, f[0]) and same_bits(n, f[1])
+        assert same_bits(xs.grad, g[0]) and same_bits(ys.grad, g[1]) and same_bits(ws.grad, g[2])
         # only n used, x absent, a non-contiguous upstream gradient
         ys.grad = ws.grad = None
         _, n = T5AddNormFunction.apply(None, ys, ws, EPS, p_in, 0.1, seed)
@@ -243,7 +220,7 @@ def test_function_matches_the_direct_calls():
         with torch.no_grad():
             f = ops.t5_add_norm_fwd(None, y, w, EPS, p_in, 0.1, seed)
             g = ops.t5_add_norm_bwd(f[0], f[2], w, d_n, None, p_in, 0.1, seed, need_x=False)
-        assert g[0] is None and _bits(ys.grad, g[1]) and _bits(ws.grad, g[2])
+        assert g[0] is None and same_bits(ys.grad, g[1]) and same_bits(ws.grad, g[2])
 
 
 def test_views_off_a_16_byte_boundary_are_realigned():
@@ -263,10 +240,10 @@ def test_views_off_a_16_byte_boundary_are_realigned():
     with torch.no_grad():
         want = ops.t5_add_norm_fwd(x, y, w, EPS, 0.1, 0.1, seed)
         got = ops.t5_add_norm_fwd(off(x), off(y), off(w), EPS, 0.1, 0.1, seed)
-        assert all(_bits(a, b) for a, b in zip(want, got))
+        assert all(same_bits(a, b) for a, b in zip(want, got))
         want_g = ops.t5_add_norm_bwd(want[0], want[2], w, d_n, d_xnew, 0.1, 0.1, seed)
         got_g = ops.t5_add_norm_bwd(off(want[0]), off(want[2]), off(w), off(d_n), off(d_xnew), 0.1, 0.1, seed)
-        assert all(_bits(a, b) for a, b in zip(want_g, got_g))
+        assert all(same_bits(a, b) for a, b in zip(want_g, got_g))
 
 
 def test_wrappers_reject_what_the_kernel_does_not_take():

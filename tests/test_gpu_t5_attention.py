@@ -12,8 +12,8 @@ import pytest
 import torch
 
 from conftest import load_golden
-from test_gpu_retrieval import (GAP, _cache_free_generate, _close, _default_model_and_batch, _Replay, compare_beams)
-from test_retrieval_model import CASES, build_model, fixture_batch
+from retrieval_cases import (CASES, GAP, _bias_module, _cache_free_generate, _close, _inputs, _padding, _Replay, build_model,
+                             compare_beams, default_model_and_batch, err, fixture_batch, same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,9 +46,7 @@ def _gate(name, out, q, k, v, H, bias, keep):
     """Prints and asserts the gate of the module docstring; k / v already expanded to one K/V per query row."""
     out64 = _operators(q, k, v, H, bias, keep, torch.float64)
     out32 = _operators(q, k, v, H, bias, keep, torch.float32)
-    scale = out64.abs().max()
-    e_kernel = float((out.double() - out64).abs().max() / scale)
-    e_torch = float((out32.double() - out64).abs().max() / scale)
+    e_kernel, e_torch = err(out, out64), err(out32, out64)
     smax = float(torch.einsum("rihd,rjhd->rhij", q.double().view(*q.shape[:2], H, 64),
                               k.double().view(*k.shape[:2], H, 64)).abs().max())
     ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
@@ -59,32 +57,6 @@ def _gate(name, out, q, k, v, H, bias, keep):
     else:
         assert e_kernel <= 4 * e_torch
     return smax
-
-
-def _inputs(R, Tq, Rk, Tk, H, seed):
-    g = torch.Generator().manual_seed(seed)
-    dev = torch.device("cuda")
-    q = (torch.randn(R, Tq, H * 64, generator=g) * 1.5).to(dev)   # no 1/sqrt(d): scores reach 30 and beyond
-    k = torch.randn(Rk, Tk, H * 64, generator=g).to(dev)
-    v = torch.randn(Rk, Tk, H * 64, generator=g).to(dev)
-    return q, k, v, g
-
-
-def _bias_module(H, is_decoder, seed):
-    from modules.t5 import T5Attention, T5Config
-    torch.manual_seed(seed)
-    att = T5Attention(T5Config(64, d_model=32, num_heads=H, is_decoder=is_decoder), has_relative_attention_bias=True)
-    torch.nn.init.normal_(att.relative_attention_bias.weight)
-    return att.to("cuda")
-
-
-def _padding(R, T, g):
-    """Keep-mask [R, T] with padded tails of every length; row 1 (if any) is fully masked."""
-    keep = torch.arange(T)[None, :] < torch.randint(1, T + 1, (R, 1), generator=g)
-    keep[0] = True
-    if R > 1:
-        keep[1] = False
-    return keep.to("cuda")
 
 
 @pytest.mark.parametrize("H", [1, 6, 8])
@@ -106,7 +78,7 @@ def test_encoder_attention_matches_operators(T, H):
             np.testing.assert_allclose(out[1].cpu().numpy(), v[1].mean(dim=0, keepdim=True).expand(T, -1).cpu().numpy(),
                                        rtol=0, atol=1e-5)
         again = ops.t5_attention(q, k, v, H, bias_by_delta=table, bias_offset=offset, key_mask=keep)
-    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+    assert same_bits(again, out)
 
 
 @pytest.mark.parametrize("H", [1, 6, 8])
@@ -124,7 +96,7 @@ def test_causal_attention_matches_operators(T, H):
         # the first query sees one key: exact
         assert torch.equal(out[:, 0], v[:, 0])
         again = ops.t5_attention(q, k, v, H, bias_by_delta=table, bias_offset=offset, causal=True)
-    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+    assert same_bits(again, out)
 
 
 @pytest.mark.parametrize("H", [1, 6, 8])
@@ -142,7 +114,7 @@ def test_cross_attention_matches_operators(beams, Tq, H):
         _gate(f"cross beams={beams} Tq={Tq} H={H} no mask", unmasked, q, k.repeat_interleave(beams, 0),
               v.repeat_interleave(beams, 0), H, None, None)
         again = ops.t5_attention(q, k, v, H, key_mask=keep)
-    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+    assert same_bits(again, out)
 
 
 @pytest.mark.parametrize("H", [1, 6, 8])
@@ -168,7 +140,7 @@ def test_cached_step_through_ancestors_matches_cat_and_index_select(past, H):
         again = ops.t5_attention(q, ks, vs, H, bias_by_delta=table, bias_offset=offset, past=past, anc=anc)
         # the gathered cache through the dense form (the matrix kernel) meets the same gate
         _gate(f"cached past={past} H={H} dense form", dense, q, k, v, H, att.compute_bias(1, past + 1, past), None)
-    assert torch.equal(again.view(torch.int32), out.view(torch.int32))
+    assert same_bits(again, out)
 
 
 def test_wrapper_rejects_host_tensors_and_unsupported_shapes():
@@ -284,7 +256,7 @@ def test_generate_matches_reference_with_recorded_noise_hip_attention(case, monk
 def test_generate_hip_attention_default_config(monkeypatch):
     import modules.model as mm
     dev = torch.device("cuda")
-    model, batch = _default_model_and_batch(dev)
+    model, batch = default_model_and_batch(dev)
     L, k = model.num_hierarchies, model.top_k_for_generation
     B = batch.sem_ids.shape[0]
     drawn = []
@@ -315,7 +287,7 @@ def test_generate_hip_attention_default_config(monkeypatch):
     torch.manual_seed(7)
     again = model.generate_next_sem_id(batch)
     assert torch.equal(again.sem_ids, out.sem_ids)
-    assert torch.equal(again.log_probas.view(torch.int32), out.log_probas.view(torch.int32))
+    assert same_bits(again.log_probas, out.log_probas)
 
 
 def test_generate_hip_attention_makes_no_cache_copies(monkeypatch):
@@ -323,7 +295,7 @@ def test_generate_hip_attention_makes_no_cache_copies(monkeypatch):
     the cross-attention Linears' outputs themselves, and the only index_select of a generate is the ancestor table's."""
     import modules.t5 as t5
     dev = torch.device("cuda")
-    model, batch = _default_model_and_batch(dev, B=16, N=3000, seed=2)
+    model, batch = default_model_and_batch(dev, B=16, N=3000, seed=2)
     model.attention_impl = "hip"
     model.generate_next_sem_id(batch)
     selected, cats, copies, kv_ptrs, caches, cross = [], [], [], [], [], []
@@ -436,7 +408,7 @@ def test_lds_limit_does_not_depend_on_the_order_of_lengths():
 def test_generate_hip_attention_under_graph_capture_equals_eager(monkeypatch):
     import modules.model as mm
     dev = torch.device("cuda")
-    model, batch = _default_model_and_batch(dev, B=32, N=5000, seed=3)
+    model, batch = default_model_and_batch(dev, B=32, N=5000, seed=3)
     model.attention_impl = "hip"
     L, K, k = model.num_hierarchies, model.num_embeddings_per_hierarchy, model.top_k_for_generation
     B = batch.sem_ids.shape[0]
@@ -466,4 +438,4 @@ def test_generate_hip_attention_under_graph_capture_equals_eager(monkeypatch):
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(captured.sem_ids, eager.sem_ids)
-    assert torch.equal(captured.log_probas.view(torch.int32), eager.log_probas.view(torch.int32))
+    assert same_bits(captured.log_probas, eager.log_probas)

@@ -8,15 +8,14 @@ table's gradient (they pass through the recomputed P and through D: two more fp3
 weights have).  A tensor whose fp64 reference is exactly zero must be exactly zero.  lse against fp64 logsumexp at 1e-6
 relative in the same measure (_lse_gate).  With dropout the reference multiplies the weights by keep / (1 - p), keep from
 ops.t5_attention_dropout_keep: the contract the kernels' three recomputations of the decision are held to.
-Measured ratios: profiles/retrieval_train_step.txt."""
+The gate itself is retrieval_cases.gate with floor 0.  Measured ratios: profiles/retrieval_train_step.txt."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_golden
-from test_gpu_retrieval import _default_model_and_batch
-from test_gpu_t5_attention import _bias_module, _inputs, _padding
-from test_retrieval_model import CASES, build_model, check_forward, fixture_batch
+from retrieval_cases import (CASES, _bias_module, _inputs, _padding, build_model, check_forward, default_model_and_batch, err,
+                             fixture_batch, gate, same_bits, seed as _seed)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,10 +51,6 @@ def _operators(q, k, v, H, table, offset, keep, drop, p, d_out, dtype):
     return (out.detach(), lse) + tuple(grads) + ((None,) if table is None else ())
 
 
-def _err(x, x64):
-    return float((x.double() - x64).abs().max() / x64.abs().max())
-
-
 def _lse_gate(name, lse, lse64):
     """max|lse - lse64| / max|lse64| <= 1e-6, the error measure of the module docstring: a score is a 64-term fp32 dot
     product whose error is relative to its terms, not to a sum that may cancel to nothing, so an element-wise relative
@@ -64,21 +59,13 @@ def _lse_gate(name, lse, lse64):
     big = lse64.abs() > 1e30
     for what, sel in (("masked rows", big), ("other rows", ~big)):
         if bool(sel.any()):
-            e = float((lse.double()[sel] - lse64[sel]).abs().max() / lse64[sel].abs().max())
+            e = err(lse[sel], lse64[sel])
             print(f"{name} lse, {what}: e_kernel {e:.3e}")
             assert e <= 1e-6, name
 
 
 def _gate(name, got, ref32, ref64, factor):
-    if not bool(ref64.any()):
-        print(f"{name}: the fp64 reference is exactly zero")
-        assert not bool(got.any()), name
-        return
-    e_kernel, e_torch = _err(got, ref64), _err(ref32, ref64)
-    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
-    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
-    assert torch.isfinite(got).all(), name
-    assert e_kernel <= factor * e_torch, name
+    gate(name, got, ref32, ref64, factor, floor=0.0)       # no floor here: the docstring's rule
 
 
 def _case(name, q, k, v, H, *, table=None, offset=0, key_mask=None, causal=False, p=0.0, seed=None, seed_d_out=0,
@@ -98,7 +85,7 @@ def _case(name, q, k, v, H, *, table=None, offset=0, key_mask=None, causal=False
     with torch.no_grad():
         got = run()
         if p == 0:
-            assert torch.equal(got[0].view(torch.int32), ops.t5_attention(q, k, v, H, **kw).view(torch.int32))
+            assert same_bits(got[0], ops.t5_attention(q, k, v, H, **kw))
     keep = None if key_mask is None else key_mask[:, None, None, :]
     if causal:
         tri = torch.ones(Tq, Tk, dtype=torch.bool, device=dev).tril()[None, None]
@@ -119,7 +106,7 @@ def _case(name, q, k, v, H, *, table=None, offset=0, key_mask=None, causal=False
     with torch.no_grad():
         again = run()
     for x, y in zip(got, again):
-        assert (x is None and y is None) or torch.equal(x.view(torch.int32), y.view(torch.int32))
+        assert (x is None and y is None) or same_bits(x, y)
     return got + (d_out,)
 
 
@@ -139,7 +126,7 @@ def _encoder(T, H, p=0.0, seed=None):
 def test_encoder_backward_matches_operators(T, H):
     (out, lse, dq, dk, dv, dtable, d_out), v = _encoder(T, H)
     if T == 1:   # one key: P = 1 and dS = 0 exactly
-        assert torch.equal(dv.view(torch.int32), d_out.view(torch.int32))
+        assert same_bits(dv, d_out)
         assert not bool(dq.any()) and not bool(dk.any()) and not bool(dtable.any())
 
 
@@ -167,10 +154,6 @@ def test_cross_backward_matches_operators(Tq, Tk, H):
     R = 6
     q, k, v, g = _inputs(R, Tq, R, Tk, H, 31 + Tq + H)
     _case(f"cross Tq={Tq} Tk={Tk} H={H}", q, k, v, H, key_mask=_padding(R, Tk, g), seed_d_out=Tk, masked_row=1)
-
-
-def _seed(value):
-    return torch.tensor([value], dtype=torch.int64, device="cuda")
 
 
 @pytest.mark.parametrize("p", [0.1, 0.5])
@@ -302,13 +285,12 @@ def test_forward_and_gradients_match_reference_with_hip_train(case, monkeypatch)
         assert calls == {"fwd": 3 * layers, "bwd": 3 * layers, "hip": 3 * layers}
         model.attention_impl = "hip"
         want = model(batch)
-    assert torch.equal(got.loss.view(torch.int32), want.loss.view(torch.int32))
-    assert torch.equal(got.loss_d.view(torch.int32), want.loss_d.view(torch.int32))
+    assert same_bits(got.loss, want.loss) and same_bits(got.loss_d, want.loss_d)
 
 
 def _three_steps(dev, impl):
     from modules.model import EncoderDecoderRetrievalModel
-    model, batch = _default_model_and_batch(dev, B=64, N=12101, d=128, seed=5)
+    model, batch = default_model_and_batch(dev, B=64, N=12101, d=128, seed=5)
     torch.manual_seed(5)
     model = EncoderDecoderRetrievalModel(model.codebooks, 3, 256, t5_d_model=384, t5_num_heads=6, t5_d_ff=1024,
                                          t5_num_layers=4).to(dev)

@@ -1,7 +1,7 @@
 """The fused T5 feed-forward on the GPU: ops.t5_ffn_fwd / ops.t5_ffn_bwd (csrc/t5_ffn.hip) against the operators of
 modules/t5.py:T5DenseReluDense (wi, relu, dropout, wo) with the kernel's dropout mask inserted.
 
-Gates, as everywhere in this project: e = max|a - a64| / max|a64| per tensor, for the kernel and for the operator chain in
+Gates (retrieval_cases.gate): e = max|a - a64| / max|a64| per tensor, for the kernel and for the operator chain in
 fp32 on the same inputs, both against the chain in fp64 (under autograd for the gradients); e_kernel <= max(4 e_torch,
 2^-22) for h and y, e_kernel <= max(8 e_torch, 2^-22) for d_x, d_wi and d_wo.  A tensor whose fp64 reference is exactly
 zero must be exactly zero.  Measured ratios: profiles/t5_ffn_error.txt.
@@ -22,17 +22,14 @@ max|a64| of every tensor, so test_ordinary_rows_alone repeats the gates on norma
 import pytest
 import torch
 
+from retrieval_cases import gate, same_bits, seed as _seed
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = ((32, 32), (64, 96), (128, 256), (384, 1024))
 NS = (1, 15, 16, 17, 31, 32, 33, 200)
 PS = (0.0, 0.1, 0.5)
 T = 16          # the row tile of every N <= 16384
-FLOOR = 2.0 ** -22
-
-
-def _seed(value):
-    return torch.tensor([value], dtype=torch.int64, device="cuda")
 
 
 def _data(N, d, F, ordinary=False):
@@ -70,26 +67,6 @@ def _chain(x, wi, wo, keep, p, dtype, act=None, d_y=None):
     return pre.detach(), h.detach(), y.detach(), grads
 
 
-def _err(a, a64):
-    return float((a.double() - a64).abs().max() / a64.abs().max())
-
-
-def _gate(name, got, ref32, ref64, factor):
-    assert torch.isfinite(got).all(), name
-    if not bool(ref64.any()):
-        print(f"{name}: the fp64 reference is exactly zero")
-        assert not bool(got.any()), name
-        return
-    e_kernel, e_torch = _err(got, ref64), _err(ref32, ref64)
-    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
-    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
-    assert e_kernel <= max(factor * e_torch, FLOOR), name
-
-
-def _bits(a, b):
-    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 def _case(N, d, F, p, ordinary=False, tag=""):
     """Forward and backward of one shape: every gate, and what must hold bit for bit within one case."""
     from rqhip import ops
@@ -103,8 +80,8 @@ def _case(N, d, F, p, ordinary=False, tag=""):
     assert y.shape == (N, d) and h.shape == (N, F) and d_x.shape == (N, d) and d_wi.shape == (F, d) and d_wo.shape == (d, F)
     pre64, h64, y64, _ = _chain(x, wi, wo, keep, p, torch.float64)
     _, h32, y32, _ = _chain(x, wi, wo, keep, p, torch.float32)
-    _gate(f"{name} h", h, h32, h64, 4)
-    _gate(f"{name} y", y, y32, y64, 4)
+    gate(f"{name} h", h, h32, h64, 4)
+    gate(f"{name} y", y, y32, y64, 4)
     # +0 wherever the pre-activation is <= 0, active wherever it is > 0 (rows apart in scale: compare within a row)
     clear = pre64.abs() > 1e-5 * pre64.abs().amax(dim=1, keepdim=True)
     act = h > 0
@@ -114,7 +91,7 @@ def _case(N, d, F, p, ordinary=False, tag=""):
     ref64 = _chain(x, wi, wo, keep, p, torch.float64, act, d_y)[3]
     ref32 = _chain(x, wi, wo, keep, p, torch.float32, act, d_y)[3]
     for nm, a, a32, a64 in zip(("d_x", "d_wi", "d_wo"), (d_x, d_wi, d_wo), ref32, ref64):
-        _gate(f"{name} {nm}", a, a32, a64, 8)
+        gate(f"{name} {nm}", a, a32, a64, 8)
     assert not bool(d_wi[2].any()), name                            # g is 0 in that column
     if N >= 4 and not ordinary:                                     # the all-zero row of x
         assert not bool(h[3].any()) and not bool(y[3].any()) and not bool(d_x[3].any()), name
@@ -130,9 +107,9 @@ def test_forward_and_backward(d, F):
             plain = ops.t5_ffn_fwd(x, wi, wo)
         for p in PS:
             y, h, *_ = _case(N, d, F, p)
-            assert _bits(h, plain[1]), (N, p)             # h does not know about the dropout
+            assert same_bits(h, plain[1]), (N, p)             # h does not know about the dropout
             if p == 0:
-                assert _bits(y, plain[0]), N              # p = 0 with and without a seed
+                assert same_bits(y, plain[0]), N              # p = 0 with and without a seed
 
 
 @pytest.mark.parametrize("d,F", SHAPES)
@@ -163,15 +140,15 @@ def test_same_bits_twice_rows_alone_and_seeds(d, F):
 
     for p in PS:
         a, b = run(p, _seed(3)), run(p, _seed(3))
-        assert all(_bits(u, v) for u, v in zip(a, b)), p
+        assert all(same_bits(u, v) for u, v in zip(a, b)), p
     whole = run(0.0, None)
     for r in (0, 1, T - 1, T, N - 1):
         one = run(0.0, None, slice(r, r + 1))
         for k in (0, 1, 2):          # y, h, d_x
-            assert _bits(whole[k][r:r + 1], one[k]), (r, k)
+            assert same_bits(whole[k][r:r + 1], one[k]), (r, k)
     a, b = run(0.5, _seed(3)), run(0.5, _seed(4))
-    assert not _bits(a[0], b[0]) and _bits(a[1], b[1])
-    assert not _bits(a[2], b[2]) and not _bits(a[4], b[4])
+    assert not same_bits(a[0], b[0]) and same_bits(a[1], b[1])
+    assert not same_bits(a[2], b[2]) and not same_bits(a[4], b[4])
 
 
 def test_rows_of_the_tall_tile_do_not_depend_on_the_batch():
@@ -185,7 +162,7 @@ def test_rows_of_the_tall_tile_do_not_depend_on_the_batch():
         for r in (0, 1, 31, 32, 16383, 16384, N - 1):
             y1, h1 = ops.t5_ffn_fwd(x[r:r + 1], wi, wo)
             d_x1 = ops.t5_ffn_bwd(x[r:r + 1], wi, wo, h1, d_y[r:r + 1], need_wi=False, need_wo=False)[0]
-            assert _bits(y[r:r + 1], y1) and _bits(h[r:r + 1], h1) and _bits(d_x[r:r + 1], d_x1), r
+            assert same_bits(y[r:r + 1], y1) and same_bits(h[r:r + 1], h1) and same_bits(d_x[r:r + 1], d_x1), r
 
 
 def test_unwanted_outputs_leave_the_others_unchanged():
@@ -196,13 +173,13 @@ def test_unwanted_outputs_leave_the_others_unchanged():
     with torch.no_grad():
         y, h = ops.t5_ffn_fwd(x, wi, wo, 0.1, seed)
         y2, none = ops.t5_ffn_fwd(x, wi, wo, 0.1, seed, need_h=False)
-        assert none is None and _bits(y, y2)
+        assert none is None and same_bits(y, y2)
         full = ops.t5_ffn_bwd(x, wi, wo, h, d_y, 0.1, seed)
         for need in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (0, 0, 0)):
             got = ops.t5_ffn_bwd(x, wi, wo, h, d_y, 0.1, seed, need_x=bool(need[0]), need_wi=bool(need[1]),
                                  need_wo=bool(need[2]))
             for n, a, b in zip(need, got, full):
-                assert (a is None and not n) or (n and _bits(a, b)), need
+                assert (a is None and not n) or (n and same_bits(a, b)), need
 
 
 def test_function_matches_the_direct_calls():
@@ -217,19 +194,19 @@ def test_function_matches_the_direct_calls():
             g = ops.t5_ffn_bwd(x, wi, wo, h, d_y, p, seed)
         xs, wis, wos = (t.clone().requires_grad_() for t in (x.view(R, L, d), wi, wo))
         out = T5FFNFunction.apply(xs, wis, wos, p, seed)
-        assert out.shape == (R, L, d) and _bits(out.view(-1, d), y)
+        assert out.shape == (R, L, d) and same_bits(out.view(-1, d), y)
         d_nc = d_y.view(R, L, d).transpose(0, 1).contiguous().transpose(0, 1)       # non-contiguous upstream gradient
         assert not d_nc.is_contiguous()
         out.backward(d_nc)
-        assert _bits(xs.grad.view(-1, d), g[0]) and _bits(wis.grad, g[1]) and _bits(wos.grad, g[2])
+        assert same_bits(xs.grad.view(-1, d), g[0]) and same_bits(wis.grad, g[1]) and same_bits(wos.grad, g[2])
         # only the input needs a gradient: frozen weights
         xs = x.clone().requires_grad_()
         T5FFNFunction.apply(xs, wi, wo, p, seed).backward(d_y)
-        assert _bits(xs.grad, g[0])
+        assert same_bits(xs.grad, g[0])
         # only the weights do
         wis, wos = wi.clone().requires_grad_(), wo.clone().requires_grad_()
         T5FFNFunction.apply(x, wis, wos, p, seed).backward(d_y)
-        assert _bits(wis.grad, g[1]) and _bits(wos.grad, g[2])
+        assert same_bits(wis.grad, g[1]) and same_bits(wos.grad, g[2])
 
 
 def test_views_off_a_16_byte_boundary_are_realigned():
@@ -249,13 +226,13 @@ def test_views_off_a_16_byte_boundary_are_realigned():
     with torch.no_grad():
         want = ops.t5_ffn_fwd(x, wi, wo, 0.1, seed)
         got = ops.t5_ffn_fwd(off(x), off(wi), off(wo), 0.1, seed)
-        assert all(_bits(a, b) for a, b in zip(want, got))
+        assert all(same_bits(a, b) for a, b in zip(want, got))
         want_g = ops.t5_ffn_bwd(x, wi, wo, want[1], d_y, 0.1, seed)
         got_g = ops.t5_ffn_bwd(off(x), off(wi), off(wo), off(want[1]), off(d_y), 0.1, seed)
-        assert all(_bits(a, b) for a, b in zip(want_g, got_g))
+        assert all(same_bits(a, b) for a, b in zip(want_g, got_g))
         # a transposed weight (not contiguous) is copied too
         got = ops.t5_ffn_fwd(x, wi.t().contiguous().t(), wo, 0.1, seed)
-        assert all(_bits(a, b) for a, b in zip(want, got))
+        assert all(same_bits(a, b) for a, b in zip(want, got))
 
 
 def test_wrappers_reject_what_the_kernel_does_not_take():

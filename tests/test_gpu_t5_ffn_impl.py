@@ -2,109 +2,46 @@
 every block as one autograd.T5FFNFunction call (csrc/t5_ffn.hip), under every attention_impl / norm_impl.
 
 A small model (d_model 64, 2 heads, d_ff 96, 2 layers, K = 16, L = 3, batch 3; encoder T = 9 with one padded row,
-decoder T = 4) against the same module in fp64 on the CPU.  Gates as in tests/test_gpu_t5_ffn.py: e = max|a - a64| /
-max|a64| per tensor, e_hip <= max(4 e_torch, 2^-22) for the loss, max(8 e_torch, 2^-22) for parameter gradients, e_torch
+decoder T = 4) against the same module in fp64 on the CPU.  Gates: retrieval_cases.gate, e = max|a - a64| /
+max|a64| per tensor, e_kernel <= max(4 e_torch, 2^-22) for the loss, max(8 e_torch, 2^-22) for parameter gradients, e_torch
 from ffn_impl = "torch" with the same attention and norm implementation on the same device."""
-import copy
-import functools
-
 import pytest
 import torch
 
+from retrieval_cases import LAYERS, gate, impls, loss_and_grads, reference, same_bits, small_model
+
 pytestmark = pytest.mark.gpu
 
-LAYERS = 2
-FLOOR = 2.0 ** -22
-
-
-@functools.lru_cache(maxsize=None)
-def _setup():
-    """(fp32 model on the device, its fp64 copy on the CPU, the batch on both) -- built once."""
-    from data.schemas import TokenizedSeqBatch
-    from modules.model import EncoderDecoderRetrievalModel
-    B, items, L, K, N = 3, 2, 3, 16, 200
-    g = torch.Generator().manual_seed(12)
-    torch.manual_seed(12)
-    corpus = torch.randint(0, K, (N, L), generator=g)
-    model = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=64, t5_num_heads=2, t5_d_ff=96, t5_num_layers=LAYERS)
-    hist = torch.cat([corpus[torch.randint(0, N, (B, items), generator=g)], torch.zeros(B, items, 1, dtype=torch.long)],
-                     dim=-1)
-    mask = torch.ones(B, items, L + 1, dtype=torch.bool)
-    hist[1, items - 1:] = -1                   # one padded row
-    mask[1, items - 1:] = False
-    fut = torch.cat([corpus[torch.randint(0, N, (B,), generator=g)], torch.zeros(B, 1, dtype=torch.long)], dim=-1)
-    batch = TokenizedSeqBatch(torch.randint(0, 100, (B, 1), generator=g), hist.reshape(B, -1), fut, mask.reshape(B, -1),
-                              None, None)
-    model64 = copy.deepcopy(model).double().eval()
-    dev = torch.device("cuda")
-    return (model.to(dev).eval(), model64, TokenizedSeqBatch(*[None if t is None else t.to(dev) for t in batch]), batch)
-
-
-def _err(a, a64):
-    return float((a.double().cpu() - a64).abs().max() / a64.abs().max())
-
-
-def _gate(name, got, ref32, ref64, factor):
-    assert torch.isfinite(got).all(), name
-    if not bool(ref64.any()):
-        assert not bool(got.any()), name
-        return
-    e_hip, e_torch = _err(got, ref64), _err(ref32, ref64)
-    ratio = e_hip / e_torch if e_torch > 0 else (0.0 if e_hip == 0 else float("inf"))
-    print(f"{name}: e_hip {e_hip:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
-    assert e_hip <= max(factor * e_torch, FLOOR), name
-
-
-def _loss_and_grads(model, batch, seed=None):
-    model.zero_grad(set_to_none=True)
-    if seed is not None:
-        torch.manual_seed(seed)
-    loss = model(batch).loss
-    loss.backward()
-    return loss.detach(), {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
-
-
-@functools.lru_cache(maxsize=None)
-def _reference():
-    _, model64, _, batch = _setup()
-    return _loss_and_grads(model64, batch)
-
-
-def _set(model, attention, norm, ffn):
-    model.attention_impl, model.norm_impl, model.ffn_impl = attention, norm, ffn
-    model._push_attention_impl()
+SMALL = (12, 96, False)         # retrieval_cases.small_model: seed, d_ff, norm weights as initialised
 
 
 @pytest.mark.parametrize("norm", ["torch", "hip"])
 @pytest.mark.parametrize("attention", ["torch", "hip_train"])
 def test_eval_loss_and_gradients_against_fp64(attention, norm):
-    model, _, batch, _ = _setup()
-    loss64, grads64 = _reference()
-    _set(model.eval(), attention, norm, "torch")
-    loss32, grads32 = _loss_and_grads(model, batch)
-    _set(model, attention, norm, "hip")
-    loss, grads = _loss_and_grads(model, batch)
-    _set(model, "torch", "torch", "torch")
+    model, _, batch, _ = small_model(*SMALL)
+    loss64, grads64 = reference(*SMALL)
+    with impls(model.eval(), attention=attention, norm=norm):
+        loss32, grads32 = loss_and_grads(model, batch)
+    with impls(model, attention=attention, norm=norm, ffn="hip"):
+        loss, grads = loss_and_grads(model, batch)
     assert sorted(grads) == sorted(grads64) == sorted(grads32) and len(grads) > 40
-    _gate(f"{attention}/{norm} loss", loss.reshape(1), loss32.reshape(1), loss64.reshape(1), 4)
+    gate(f"{attention}/{norm} loss", loss.reshape(1), loss32.reshape(1), loss64.reshape(1), 4)
     for n in sorted(grads):
-        _gate(f"{attention}/{norm} grad {n}", grads[n], grads32[n], grads64[n], 8)
+        gate(f"{attention}/{norm} grad {n}", grads[n], grads32[n], grads64[n], 8)
 
 
 @pytest.mark.parametrize("attention,norm", [("torch", "torch"), ("hip_train", "torch"), ("torch", "hip"), ("hip_train", "hip")])
 def test_train_mode_replays_under_a_seed(attention, norm):
-    model, _, batch, _ = _setup()
-    _set(model.train(), attention, norm, "hip")
-    try:
-        loss_a, grads_a = _loss_and_grads(model, batch, seed=5)
-        loss_b, grads_b = _loss_and_grads(model, batch, seed=5)
-        loss_c, _ = _loss_and_grads(model, batch, seed=6)
-    finally:
-        _set(model.eval(), "torch", "torch", "torch")
-    assert torch.isfinite(loss_a) and torch.equal(loss_a.view(torch.int32), loss_b.view(torch.int32))
+    model, _, batch, _ = small_model(*SMALL)
+    with impls(model.eval(), attention=attention, norm=norm, ffn="hip"):
+        model.train()
+        loss_a, grads_a = loss_and_grads(model, batch, seed=5)
+        loss_b, grads_b = loss_and_grads(model, batch, seed=5)
+        loss_c, _ = loss_and_grads(model, batch, seed=6)
+    assert torch.isfinite(loss_a) and same_bits(loss_a, loss_b)
     assert sorted(grads_a) == sorted(grads_b) and len(grads_a) > 40
     for n in grads_a:
-        assert torch.equal(grads_a[n].view(torch.int32), grads_b[n].view(torch.int32)), n
+        assert same_bits(grads_a[n], grads_b[n]), n
     assert not torch.equal(loss_a, loss_c)
 
 
@@ -139,7 +76,7 @@ def _counts(calls):
 
 def test_call_counts(monkeypatch):
     import modules.t5 as t5
-    model = _setup()[0]
+    model = small_model(*SMALL)[0]
     enc, dec = model.encoder.encoder, model.t5_decoder
     dev = torch.device("cuda")
     x = torch.randn(3, 9, 64, device=dev)
@@ -150,22 +87,17 @@ def test_call_counts(monkeypatch):
     def reset():
         calls.update(fwd=0, bwd=0, randint=0, need_h=[])
 
-    try:
-        for norm in ("torch", "hip"):
-            for stack in (enc, dec):
-                stack.attention_impl, stack.norm_impl, stack.ffn_impl = "torch", norm, "torch"
-            model.eval()
+    for norm in ("torch", "hip"):
+        with impls(model.eval(), norm=norm):
             enc(x), dec(y, encoder_hidden_states=memory)
             model.train()
             enc(x).sum().backward()
             assert calls["fwd"] == 0 and calls["bwd"] == 0     # "torch": the fused op is never called
             assert calls["randint"] == (1 if norm == "hip" else 0)
             reset()
-        for norm in ("torch", "hip"):
-            for stack in (enc, dec):
-                stack.attention_impl, stack.norm_impl, stack.ffn_impl = "torch", norm, "hip"
+    for norm in ("torch", "hip"):
+        with impls(model, norm=norm, ffn="hip"):
             # eval mode under grad: one Function call per block, no seeds
-            model.eval()
             enc(x).sum().backward()
             assert _counts(calls) == {"fwd": LAYERS, "bwd": LAYERS, "randint": 0} and all(calls["need_h"])
             reset()
@@ -190,20 +122,14 @@ def test_call_counts(monkeypatch):
                 enc(x)
             assert _counts(calls) == {"fwd": LAYERS, "bwd": 0, "randint": draws} and not any(calls["need_h"])
             reset()
-    finally:
-        model.eval()
-        model.zero_grad(set_to_none=True)
-        for stack in (enc, dec):
-            stack.attention_impl, stack.norm_impl, stack.ffn_impl = "torch", "torch", "torch"
 
 
 @pytest.mark.parametrize("attention", ["torch", "hip"])
 def test_generate_runs_with_hip_ffn(attention):
-    model, _, batch, _ = _setup()
-    _set(model.eval(), attention, "torch", "hip")
-    torch.manual_seed(1)
-    out = model.generate_next_sem_id(batch)
-    _set(model, "torch", "torch", "torch")
+    model, _, batch, _ = small_model(*SMALL)
+    with impls(model.eval(), attention=attention, ffn="hip"):
+        torch.manual_seed(1)
+        out = model.generate_next_sem_id(batch)
     ids, scores = out.sem_ids, out.log_probas
     assert ids.shape == (3, 10, 3) and scores.shape == (3, 10) and not bool(torch.isnan(scores).any())
     valid = scores != float("-inf")

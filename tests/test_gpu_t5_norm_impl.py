@@ -2,100 +2,35 @@
 add and RMS norm between two sub-layer bodies as one autograd.T5AddNormFunction call (csrc/t5_add_norm.hip).
 
 A small model (d_model 64, 2 heads, d_ff 128, 2 layers, K = 16, L = 3, batch 3; encoder T = 9 with one padded row,
-decoder T = 4) against the same module in fp64 on the CPU.  Gates as in tests/test_gpu_t5_add_norm.py: e = max|a - a64| /
-max|a64| per tensor, e_hip <= max(4 e_torch, 2^-22) for the loss and hidden states, max(8 e_torch, 2^-22) for parameter
+decoder T = 4) against the same module in fp64 on the CPU.  Gates: retrieval_cases.gate, e = max|a - a64| /
+max|a64| per tensor, e_kernel <= max(4 e_torch, 2^-22) for the loss and hidden states, max(8 e_torch, 2^-22) for parameter
 gradients, e_torch from norm_impl = "torch" with the same attention implementation on the same device."""
-import copy
-import functools
-
 import pytest
 import torch
 
+from retrieval_cases import LAYERS, gate, impls, loss_and_grads, reference, same_bits, small_model
+
 pytestmark = pytest.mark.gpu
 
-LAYERS = 2
-FLOOR = 2.0 ** -22
-
-
-@functools.lru_cache(maxsize=None)
-def _setup():
-    """(fp32 model on the device, its fp64 copy on the CPU, the batch on both) -- built once."""
-    from data.schemas import TokenizedSeqBatch
-    from modules.model import EncoderDecoderRetrievalModel
-    B, items, L, K, N = 3, 2, 3, 16, 200
-    g = torch.Generator().manual_seed(11)
-    torch.manual_seed(11)
-    corpus = torch.randint(0, K, (N, L), generator=g)
-    model = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=64, t5_num_heads=2, t5_d_ff=128, t5_num_layers=LAYERS)
-    with torch.no_grad():                      # norm weights away from 1, some negative: their gradients matter
-        for name, p in model.named_parameters():
-            if name.endswith("layer_norm.weight"):
-                p.copy_(1 + 0.5 * torch.randn(p.shape, generator=g))
-    hist = torch.cat([corpus[torch.randint(0, N, (B, items), generator=g)], torch.zeros(B, items, 1, dtype=torch.long)],
-                     dim=-1)
-    mask = torch.ones(B, items, L + 1, dtype=torch.bool)
-    hist[1, items - 1:] = -1                   # one padded row
-    mask[1, items - 1:] = False
-    fut = torch.cat([corpus[torch.randint(0, N, (B,), generator=g)], torch.zeros(B, 1, dtype=torch.long)], dim=-1)
-    batch = TokenizedSeqBatch(torch.randint(0, 100, (B, 1), generator=g), hist.reshape(B, -1), fut, mask.reshape(B, -1),
-                              None, None)
-    model64 = copy.deepcopy(model).double().eval()
-    dev = torch.device("cuda")
-    return (model.to(dev).eval(), model64, TokenizedSeqBatch(*[None if t is None else t.to(dev) for t in batch]), batch)
-
-
-def _err(a, a64):
-    return float((a.double().cpu() - a64).abs().max() / a64.abs().max())
-
-
-def _gate(name, got, ref32, ref64, factor):
-    assert torch.isfinite(got).all(), name
-    if not bool(ref64.any()):
-        assert not bool(got.any()), name
-        return
-    e_hip, e_torch = _err(got, ref64), _err(ref32, ref64)
-    ratio = e_hip / e_torch if e_torch > 0 else (0.0 if e_hip == 0 else float("inf"))
-    print(f"{name}: e_hip {e_hip:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f}")
-    assert e_hip <= max(factor * e_torch, FLOOR), name
-
-
-def _loss_and_grads(model, batch, seed=None):
-    model.zero_grad(set_to_none=True)
-    if seed is not None:
-        torch.manual_seed(seed)
-    loss = model(batch).loss
-    loss.backward()
-    return loss.detach(), {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
-
-
-@functools.lru_cache(maxsize=None)
-def _reference():
-    _, model64, _, batch = _setup()
-    return _loss_and_grads(model64, batch)
-
-
-def _set(model, attention, norm):
-    model.attention_impl, model.norm_impl = attention, norm
-    model._push_attention_impl()
+SMALL = (11, 128, True)         # retrieval_cases.small_model: seed, d_ff, norm weights perturbed
 
 
 @pytest.mark.parametrize("attention", ["torch", "hip_train"])
 def test_eval_loss_and_gradients_against_fp64(attention):
-    model, _, batch, _ = _setup()
-    loss64, grads64 = _reference()
-    _set(model.eval(), attention, "torch")
-    loss32, grads32 = _loss_and_grads(model, batch)
-    _set(model, attention, "hip")
-    loss, grads = _loss_and_grads(model, batch)
-    _set(model, "torch", "torch")
+    model, _, batch, _ = small_model(*SMALL)
+    loss64, grads64 = reference(*SMALL)
+    with impls(model.eval(), attention=attention):
+        loss32, grads32 = loss_and_grads(model, batch)
+    with impls(model, attention=attention, norm="hip"):
+        loss, grads = loss_and_grads(model, batch)
     assert sorted(grads) == sorted(grads64) == sorted(grads32) and len(grads) > 40
-    _gate(f"{attention} loss", loss.reshape(1), loss32.reshape(1), loss64.reshape(1), 4)
+    gate(f"{attention} loss", loss.reshape(1), loss32.reshape(1), loss64.reshape(1), 4)
     for n in sorted(grads):
-        _gate(f"{attention} grad {n}", grads[n], grads32[n], grads64[n], 8)
+        gate(f"{attention} grad {n}", grads[n], grads32[n], grads64[n], 8)
 
 
 def _decoder_inputs():
-    model, model64, batch, batch_cpu = _setup()
+    model, model64, batch, batch_cpu = small_model(*SMALL)
     from modules.model import _strip_dedup_col
     L = model.num_hierarchies
     with torch.no_grad():
@@ -133,28 +68,26 @@ def _decode(dec, path, x, enc, mask):
 @pytest.mark.parametrize("path", ["operators, past_key_values", "hip, no cache", "hip, decode_cache"])
 def test_decoder_hidden_states_without_grad(path, monkeypatch):
     import modules.t5 as t5
-    model = _setup()[0].eval()
+    model = small_model(*SMALL)[0].eval()
     dec = model.t5_decoder
     x, enc, mask, hidden64 = _decoder_inputs()
     calls = _count(monkeypatch, t5)
-    dec.norm_impl = "torch"
-    ref32 = _decode(dec, path, x, enc, mask)
-    assert calls["fwd"] == 0
-    dec.norm_impl = "hip"
-    got = _decode(dec, path, x, enc, mask)
-    dec.norm_impl = dec.attention_impl = "torch"
+    with impls(model):                     # the decoder stack is set directly; the exit resets it
+        ref32 = _decode(dec, path, x, enc, mask)
+        assert calls["fwd"] == 0
+        dec.norm_impl = "hip"
+        got = _decode(dec, path, x, enc, mask)
     steps = 1 if path == "hip, no cache" else x.shape[1]
     assert calls["fwd"] == steps * (3 * LAYERS + 1)
-    _gate(f"decoder hidden states, {path}", got, ref32, hidden64, 4)
+    gate(f"decoder hidden states, {path}", got, ref32, hidden64, 4)
 
 
 @pytest.mark.parametrize("attention", ["torch", "hip"])
 def test_generate_runs_with_hip_norm(attention):
-    model, _, batch, _ = _setup()
-    _set(model.eval(), attention, "hip")
-    torch.manual_seed(1)
-    out = model.generate_next_sem_id(batch)
-    _set(model, "torch", "torch")
+    model, _, batch, _ = small_model(*SMALL)
+    with impls(model.eval(), attention=attention, norm="hip"):
+        torch.manual_seed(1)
+        out = model.generate_next_sem_id(batch)
     ids, scores = out.sem_ids, out.log_probas
     assert ids.shape == (3, 10, 3) and scores.shape == (3, 10) and not bool(torch.isnan(scores).any())
     valid = scores != float("-inf")
@@ -165,18 +98,16 @@ def test_generate_runs_with_hip_norm(attention):
 
 @pytest.mark.parametrize("attention", ["torch", "hip_train"])
 def test_train_mode_replays_under_a_seed(attention):
-    model, _, batch, _ = _setup()
-    _set(model.train(), attention, "hip")
-    try:
-        loss_a, grads_a = _loss_and_grads(model, batch, seed=5)
-        loss_b, grads_b = _loss_and_grads(model, batch, seed=5)
-        loss_c, _ = _loss_and_grads(model, batch, seed=6)
-    finally:
-        _set(model.eval(), "torch", "torch")
-    assert torch.isfinite(loss_a) and torch.equal(loss_a.view(torch.int32), loss_b.view(torch.int32))
+    model, _, batch, _ = small_model(*SMALL)
+    with impls(model.eval(), attention=attention, norm="hip"):
+        model.train()
+        loss_a, grads_a = loss_and_grads(model, batch, seed=5)
+        loss_b, grads_b = loss_and_grads(model, batch, seed=5)
+        loss_c, _ = loss_and_grads(model, batch, seed=6)
+    assert torch.isfinite(loss_a) and same_bits(loss_a, loss_b)
     assert sorted(grads_a) == sorted(grads_b) and len(grads_a) > 40
     for n in grads_a:
-        assert torch.equal(grads_a[n].view(torch.int32), grads_b[n].view(torch.int32)), n
+        assert same_bits(grads_a[n], grads_b[n]), n
     assert not torch.equal(loss_a, loss_c)
 
 
@@ -204,23 +135,19 @@ def _count(monkeypatch, t5):
 
 def test_call_counts(monkeypatch):
     import modules.t5 as t5
-    model = _setup()[0]
+    model = small_model(*SMALL)[0]
     enc, dec = model.encoder.encoder, model.t5_decoder
     dev = torch.device("cuda")
     x = torch.randn(3, 9, 64, device=dev)
     memory = torch.randn(3, 9, 64, device=dev)
     y = torch.randn(3, 4, 64, device=dev)
     calls = _count(monkeypatch, t5)
-    try:
-        for stack in (enc, dec):
-            stack.attention_impl, stack.norm_impl = "torch", "torch"
-        model.eval()
+    with impls(model.eval()):
         enc(x), dec(y, encoder_hidden_states=memory)
         model.train()
         enc(x).sum().backward()
         assert calls == {"fwd": 0, "bwd": 0, "randint": 0}      # "torch": the fused op is never called
-        enc.norm_impl = dec.norm_impl = "hip"
-        model.eval()
+    with impls(model, norm="hip"):
         enc(x)
         assert calls == {"fwd": 2 * LAYERS + 1, "bwd": 0, "randint": 0}
         dec(y, encoder_hidden_states=memory)
@@ -238,11 +165,6 @@ def test_call_counts(monkeypatch):
         calls.update(fwd=0, bwd=0, randint=0)
         enc(x).sum().backward()
         assert calls == {"fwd": 2 * LAYERS + 1, "bwd": 2 * LAYERS + 1, "randint": LAYERS + 1}
-    finally:
-        model.eval()
-        model.zero_grad(set_to_none=True)
-        for stack in (enc, dec):
-            stack.attention_impl, stack.norm_impl = "torch", "torch"
 
 
 def test_unsupported_width_runs_the_operators(monkeypatch):

@@ -8,9 +8,11 @@ import itertools
 import pytest
 import torch
 
-from test_gpu_t5_ffn_impl import LAYERS, _gate, _set, _setup
+from retrieval_cases import LAYERS, gate, impls, small_model
 
 pytestmark = pytest.mark.gpu
+
+SMALL = (12, 96, False)         # the set-up of tests/test_gpu_t5_ffn_impl.py
 
 
 def _hidden_states(model, batch, launches=()):
@@ -30,16 +32,16 @@ def _hidden_states(model, batch, launches=()):
 @functools.lru_cache(maxsize=None)
 def _references():
     """The hidden states of the fp64 model on the CPU and of the all-operator fp32 model on the device."""
-    model, model64, batch, batch64 = _setup()
-    _set(model.eval(), "torch", "torch", "torch")
-    return _hidden_states(model64, batch64)[:2], _hidden_states(model, batch)[:2]
+    model, model64, batch, batch64 = small_model(*SMALL)
+    with impls(model.eval()):
+        return _hidden_states(model64, batch64)[:2], _hidden_states(model, batch)[:2]
 
 
 @pytest.mark.parametrize("attention,norm,ffn", list(itertools.product(("torch", "hip", "hip_train"), ("torch", "hip"),
                                                                       ("torch", "hip"))))
 def test_hidden_states_and_attention_launches(attention, norm, ffn, monkeypatch):
     import modules.t5 as t5
-    model, _, batch, _ = _setup()
+    model, _, batch, _ = small_model(*SMALL)
     (enc64, dec64), (enc32, dec32) = _references()
     calls = []
     orig = t5.ops.t5_attention
@@ -49,13 +51,10 @@ def test_hidden_states_and_attention_launches(attention, norm, ffn, monkeypatch)
         return orig(*a, **kw)
 
     monkeypatch.setattr(t5.ops, "t5_attention", counted)
-    _set(model.eval(), attention, norm, ffn)
-    try:
+    with impls(model.eval(), attention=attention, norm=norm, ffn=ffn):
         enc, dec, n_enc = _hidden_states(model, batch, calls)
-    finally:
-        _set(model, "torch", "torch", "torch")
     assert enc.shape == enc32.shape and dec.shape == dec32.shape == (3, 4, 64)
     fused = attention != "torch"
     assert (n_enc, len(calls) - n_enc) == ((LAYERS, 2 * LAYERS) if fused else (0, 0))
-    _gate(f"{attention}/{norm}/{ffn} encoder", enc, enc32, enc64, 4)
-    _gate(f"{attention}/{norm}/{ffn} decoder", dec, dec32, dec64, 4)
+    gate(f"{attention}/{norm}/{ffn} encoder", enc, enc32, enc64, 4)
+    gate(f"{attention}/{norm}/{ffn} decoder", dec, dec32, dec64, 4)

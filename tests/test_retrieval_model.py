@@ -1,55 +1,11 @@
 """The retrieval model (modules/model.py) on the host: state-dict layout, forward / gradients against the reference's
 recorded values (tests/golden/retrieval_*.npz, tools/gen_retrieval_golden.py), the beam step's argument checks and the
 k > n_cands error.  No GPU needed."""
-import numpy as np
 import pytest
 import torch
 
 from conftest import load_golden
-
-CASES = ("a", "b", "c")
-
-
-def build_model(fx, device="cpu"):
-    """The fixture's model with its recorded weights (the unused shared / embed_tokens tables filled with zeros)."""
-    from modules.model import EncoderDecoderRetrievalModel
-    L, K, d, heads, d_ff, layers, sep, bins, k = (int(v) for v in fx["config"])
-    corpus = torch.from_numpy(fx["corpus"])
-    model = EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=d, t5_num_heads=heads, t5_d_ff=d_ff,
-                                         t5_num_layers=layers, top_k_for_generation=k, should_add_sep_token=bool(sep),
-                                         num_user_bins=bins or None)
-    sd = {name: torch.zeros_like(v) for name, v in model.state_dict().items()}
-    for name in list(sd):
-        if "w." + name in fx:
-            sd[name] = torch.from_numpy(fx["w." + name])
-    model.load_state_dict(sd, strict=True)
-    return model.to(device)
-
-
-def fixture_batch(fx, device="cpu"):
-    from data.schemas import TokenizedSeqBatch
-    return TokenizedSeqBatch(*[torch.from_numpy(fx["batch." + f]).to(device) for f in TokenizedSeqBatch._fields])
-
-
-def check_forward(fx, model, batch):
-    model.eval()
-    model.zero_grad()
-    out = model(batch)
-    out.loss.backward()
-    assert out.logits is None
-    np.testing.assert_allclose(out.loss.item(), float(fx["loss"]), rtol=1e-5)
-    np.testing.assert_allclose(out.loss_d.cpu().numpy(), fx["loss_d"], rtol=1e-5)
-    seen = 0
-    for name, p in model.named_parameters():
-        if "g." + name in fx:
-            want = fx["g." + name]
-            scale = max(float(np.abs(want).max()), 1e-6)
-            got = p.grad.detach().cpu().numpy()
-            np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-4 * scale, err_msg=name)
-            seen += 1
-        else:  # no gradient in the reference: the unused tables
-            assert p.grad is None or not p.grad.any(), name
-    assert seen > 10
+from retrieval_cases import CASES, build_model, check_forward, fixture_batch
 
 
 def test_state_dict_names_shapes_and_strict_load():

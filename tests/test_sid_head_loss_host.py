@@ -6,6 +6,8 @@ import ctypes as C
 import pytest
 import torch
 
+from retrieval_cases import tiny_batch, tiny_model
+
 
 def _fwd(l, *, B=8, T=4, L=3, K=16, d=64, ld_xb=None, ld_xt=None, ld_t=None, x=None, w=None, rest=None):
     # by default every data pointer stays null: they are checked last, so a call that passes every other check launches
@@ -93,33 +95,19 @@ def test_wrappers_reject_host_tensors():
         ops.sid_head_loss_bwd(x, w, t, torch.zeros(2, 2, 4), torch.zeros(2, 2), torch.ones(()), 2)
 
 
-def _tiny_model():
-    from modules.model import EncoderDecoderRetrievalModel
-    torch.manual_seed(0)
-    return EncoderDecoderRetrievalModel(torch.zeros(4, 3, dtype=torch.long), 3, 16, t5_d_model=8, t5_num_heads=2,
-                                        t5_d_ff=8, t5_num_layers=1)
-
-
-def _batch():
-    from data.schemas import TokenizedSeqBatch
-    g = torch.Generator().manual_seed(1)
-    return TokenizedSeqBatch(torch.zeros(2, 1, dtype=torch.long), torch.randint(0, 16, (2, 8), generator=g),
-                             torch.randint(0, 16, (2, 4), generator=g), torch.ones(2, 8, dtype=torch.bool), None, None)
-
-
 def test_option_values_and_state_dict():
     from modules.model import HEAD_IMPLS
     assert HEAD_IMPLS == ("torch", "hip")
-    keys = sorted(_tiny_model().state_dict())
-    m = _tiny_model().eval()
+    keys = sorted(tiny_model().state_dict())
+    m = tiny_model().eval()
     assert m.head_impl == "torch"
     m.head_impl = "hip"
     with torch.no_grad():
-        m(_batch())
+        m(tiny_batch())
     assert sorted(m.state_dict()) == keys
     m.head_impl = "nope"
     with pytest.raises(ValueError, match="head_impl"):
-        m(_batch())
+        m(tiny_batch())
 
     class OnDevice:                # hip_head_active reads only these
         is_cuda, dtype, shape = True, torch.float32, (2, 4, 8)
@@ -148,8 +136,8 @@ def test_hip_head_on_host_tensors_is_the_operators(grad, monkeypatch):
 
     monkeypatch.setattr(model_module.ops, "sid_head_loss_fwd", counted("fwd"))
     monkeypatch.setattr(model_module.ops, "sid_head_loss_bwd", counted("bwd"))
-    m = _tiny_model().eval()
-    batch = _batch()
+    m = tiny_model().eval()
+    batch = tiny_batch()
 
     def run():
         m.zero_grad(set_to_none=True)

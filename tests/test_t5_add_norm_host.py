@@ -5,6 +5,8 @@ No GPU needed."""
 import pytest
 import torch
 
+from retrieval_cases import tiny_batch, tiny_model
+
 
 def _fwd(l, *, N=8, d=64, p_in=0.0, p_out=0.0, eps=1e-6):
     # every data pointer stays null: they are checked last, so a call that passes every other check launches nothing
@@ -88,34 +90,20 @@ def test_wrappers_reject_host_tensors():
         ops.t5_add_norm_bwd(y, torch.zeros(3), w, y, None)
 
 
-def _tiny_model():
-    from modules.model import EncoderDecoderRetrievalModel
-    torch.manual_seed(0)
-    return EncoderDecoderRetrievalModel(torch.zeros(4, 3, dtype=torch.long), 3, 16, t5_d_model=8, t5_num_heads=2,
-                                        t5_d_ff=8, t5_num_layers=1)
-
-
-def _batch():
-    from data.schemas import TokenizedSeqBatch
-    g = torch.Generator().manual_seed(1)
-    return TokenizedSeqBatch(torch.zeros(2, 1, dtype=torch.long), torch.randint(0, 16, (2, 8), generator=g),
-                             torch.randint(0, 16, (2, 4), generator=g), torch.ones(2, 8, dtype=torch.bool), None, None)
-
-
 def test_option_values_and_state_dict():
     from modules.t5 import NORM_IMPLS, T5Config, T5Stack
     assert NORM_IMPLS == ("torch", "hip")
-    keys = sorted(_tiny_model().state_dict())
-    m = _tiny_model().eval()
+    keys = sorted(tiny_model().state_dict())
+    m = tiny_model().eval()
     assert m.norm_impl == "torch" and m.encoder.encoder.norm_impl == "torch" and m.t5_decoder.norm_impl == "torch"
     m.norm_impl = "hip"
     with torch.no_grad():
-        m(_batch())
+        m(tiny_batch())
     assert m.encoder.encoder.norm_impl == "hip" and m.t5_decoder.norm_impl == "hip"
     assert sorted(m.state_dict()) == keys
     m.norm_impl = "bogus"
     with pytest.raises(ValueError, match="norm_impl"):
-        m(_batch())
+        m(tiny_batch())
     stack = T5Stack(T5Config(16, d_model=8, num_heads=2, d_ff=8, num_layers=1)).eval()
     assert stack.norm_impl == "torch"
     stack.norm_impl = "bogus"
@@ -136,9 +124,9 @@ def test_option_values_and_state_dict():
 
 @pytest.mark.parametrize("attention", ["torch", "hip", "hip_train"])
 def test_hip_norm_on_host_tensors_is_the_operators(attention):
-    m = _tiny_model().eval()
+    m = tiny_model().eval()
     m.attention_impl = attention
-    batch = _batch()
+    batch = tiny_batch()
 
     def run():
         m.zero_grad(set_to_none=True)

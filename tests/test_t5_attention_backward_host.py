@@ -7,6 +7,8 @@ import math
 import pytest
 import torch
 
+from retrieval_cases import loss_and_grads, tiny_batch, tiny_model
+
 
 def _fwd(l, *, R=4, Rk=4, H=6, d_kv=64, Tq=8, Tk=8, ld=None, bias=None, n_delta=0, offset=0, causal=0, p=0.0):
     ld = H * 64 if ld is None else ld
@@ -112,33 +114,16 @@ def test_dropout_keep_uses_the_low_index_bits():
         assert bool(((frac > 0) & (frac < 1)).all())
 
 
-def _tiny_model():
-    from modules.model import EncoderDecoderRetrievalModel
-    torch.manual_seed(0)
-    return EncoderDecoderRetrievalModel(torch.zeros(4, 3, dtype=torch.long), 3, 16, t5_d_model=8, t5_num_heads=2,
-                                        t5_d_ff=8, t5_num_layers=1)
-
-
-def _loss_and_grads(m, batch, seed):
-    m.zero_grad(set_to_none=True)
-    torch.manual_seed(seed)
-    loss = m(batch).loss
-    loss.backward()
-    return loss.detach(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
-
-
 @pytest.mark.parametrize("train", [False, True])
 def test_hip_train_on_host_tensors_is_the_operators(train):
-    from data.schemas import TokenizedSeqBatch
     from modules.t5 import ATTENTION_IMPLS
     assert ATTENTION_IMPLS == ("torch", "hip", "hip_train")
-    m = _tiny_model()
+    m = tiny_model()
     m.train(train)
-    batch = TokenizedSeqBatch(torch.zeros(2, 1, dtype=torch.long), torch.randint(0, 16, (2, 8)),
-                              torch.randint(0, 16, (2, 4)), torch.ones(2, 8, dtype=torch.bool), None, None)
-    want, want_g = _loss_and_grads(m, batch, 3)
+    batch = tiny_batch()
+    want, want_g = loss_and_grads(m, batch, 3)
     m.attention_impl = "hip_train"
-    got, got_g = _loss_and_grads(m, batch, 3)
+    got, got_g = loss_and_grads(m, batch, 3)
     assert m.encoder.encoder.attention_impl == "hip_train" and m.t5_decoder.attention_impl == "hip_train"
     assert torch.equal(got, want) and sorted(got_g) == sorted(want_g) and len(got_g) > 10
     for n in want_g:

@@ -4,6 +4,8 @@ the incremental decoder against an index_select + cat cache, and the switch's de
 import pytest
 import torch
 
+from retrieval_cases import tiny_batch, tiny_model
+
 
 def _att(l, *, q=0, R=4, Rk=4, H=6, d_kv=64, Tq=8, Tk=8, ld=None, anc=None, past=0, bias=None, n_delta=0, offset=0):
     ld = H * 64 if ld is None else ld
@@ -125,21 +127,12 @@ def test_ancestor_table_reproduces_the_index_select_and_cat_cache():
     assert cache.anc.dtype == torch.int32
 
 
-def _tiny_model():
-    from modules.model import EncoderDecoderRetrievalModel
-    torch.manual_seed(0)
-    return EncoderDecoderRetrievalModel(torch.zeros(4, 3, dtype=torch.long), 3, 16, t5_d_model=8, t5_num_heads=2,
-                                        t5_d_ff=8, t5_num_layers=1)
-
-
 def test_attention_impl_defaults_to_torch_and_is_pushed_to_both_stacks():
-    from data.schemas import TokenizedSeqBatch
-    m = _tiny_model()
+    m = tiny_model()
     assert m.attention_impl == "torch"
     assert m.encoder.encoder.attention_impl == "torch" and m.t5_decoder.attention_impl == "torch"
     assert "attention_impl" not in m.state_dict() and not any("delta" in n for n in m.state_dict())
-    batch = TokenizedSeqBatch(torch.zeros(2, 1, dtype=torch.long), torch.randint(0, 16, (2, 8)),
-                              torch.randint(0, 16, (2, 4)), torch.ones(2, 8, dtype=torch.bool), None, None)
+    batch = tiny_batch()
     m.eval()
     want = m(batch).loss
     m.attention_impl = "hip"

@@ -4,6 +4,8 @@ on the stack and on the model, and the fall-back to the operators on host tensor
 import pytest
 import torch
 
+from retrieval_cases import tiny_batch, tiny_model
+
 
 def _fwd(l, *, N=8, d=64, F=96, p=0.0):
     # every data pointer stays null: they are checked last, so a call that passes every other check launches nothing
@@ -115,35 +117,21 @@ def test_wrappers_reject_host_tensors_and_other_dtypes():
         ops.t5_ffn_bwd(x, wi, wo, torch.zeros(3, 64), x)
 
 
-def _tiny_model(d_ff=32):
-    from modules.model import EncoderDecoderRetrievalModel
-    torch.manual_seed(0)
-    return EncoderDecoderRetrievalModel(torch.zeros(4, 3, dtype=torch.long), 3, 16, t5_d_model=32, t5_num_heads=2,
-                                        t5_d_ff=d_ff, t5_num_layers=1)
-
-
-def _batch():
-    from data.schemas import TokenizedSeqBatch
-    g = torch.Generator().manual_seed(1)
-    return TokenizedSeqBatch(torch.zeros(2, 1, dtype=torch.long), torch.randint(0, 16, (2, 8), generator=g),
-                             torch.randint(0, 16, (2, 4), generator=g), torch.ones(2, 8, dtype=torch.bool), None, None)
-
-
 def test_option_values_and_state_dict():
     from modules.t5 import FFN_IMPLS, T5Config, T5Stack
     assert FFN_IMPLS == ("torch", "hip")
-    keys = sorted(_tiny_model().state_dict())
-    m = _tiny_model().eval()
+    keys = sorted(tiny_model(32, 32).state_dict())
+    m = tiny_model(32, 32).eval()
     assert m.ffn_impl == "torch" and m.encoder.encoder.ffn_impl == "torch" and m.t5_decoder.ffn_impl == "torch"
     m.ffn_impl = "hip"
     with torch.no_grad():
-        m(_batch())
+        m(tiny_batch())
     assert m.encoder.encoder.ffn_impl == "hip" and m.t5_decoder.ffn_impl == "hip"
     assert sorted(m.state_dict()) == keys
     for norm in ("torch", "hip"):
         m.ffn_impl, m.norm_impl = "bogus", norm
         with pytest.raises(ValueError, match="ffn_impl"):
-            m(_batch())
+            m(tiny_batch())
     stack = T5Stack(T5Config(16, d_model=32, num_heads=2, d_ff=64, num_layers=1)).eval()
     assert stack.ffn_impl == "torch"
     stack.ffn_impl = "bogus"
@@ -178,9 +166,9 @@ def test_hip_ffn_on_host_tensors_is_the_operators(attention, norm, monkeypatch):
     monkeypatch.setattr(t5_module.ops, "t5_ffn_fwd", refuse)
     monkeypatch.setattr(t5_module.ops, "t5_ffn_bwd", refuse)
     monkeypatch.setattr(t5_module.T5FFNFunction, "apply", refuse)
-    m = _tiny_model().eval()
+    m = tiny_model(32, 32).eval()
     m.attention_impl, m.norm_impl = attention, norm
-    batch = _batch()
+    batch = tiny_batch()
 
     def run():
         m.zero_grad(set_to_none=True)

@@ -24,13 +24,13 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "rq-vae-recommender_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "rq-vae-recommender_amd"), os.path.join(ROOT, "tests")]
 
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 import modules.model as mm  # noqa: E402
-from data.schemas import TokenizedSeqBatch  # noqa: E402
+from retrieval_cases import synthetic_batch, to_device  # noqa: E402  (tests/retrieval_cases.py)
 
 
 def reference_beam_step(corpus):
@@ -78,12 +78,7 @@ def build(dev, B=640, items=20, N=12101, L=3, K=256, seed=0):
     corpus = torch.randint(0, K, (N, L), generator=g)
     model = mm.EncoderDecoderRetrievalModel(corpus, L, K, t5_d_model=384, t5_num_heads=6, t5_d_ff=1024,
                                             t5_num_layers=4, top_k_for_generation=10).to(dev).eval()
-    hist = torch.cat([corpus[torch.randint(0, N, (B, items), generator=g)], torch.zeros(B, items, 1, dtype=torch.long)],
-                     dim=-1).reshape(B, -1)
-    mask = torch.ones_like(hist, dtype=torch.bool)
-    fut = torch.cat([corpus[torch.randint(0, N, (B,), generator=g)], torch.zeros(B, 1, dtype=torch.long)], dim=-1)
-    batch = TokenizedSeqBatch(torch.zeros(B, 1, dtype=torch.long), hist, fut, mask, None, None)
-    return model, TokenizedSeqBatch(*[None if t is None else t.to(dev) for t in batch])
+    return model, to_device(synthetic_batch(corpus, B, items, g, user_ids=False), dev)
 
 
 def time_path(model, batch, warmup, iters):
