@@ -450,6 +450,45 @@ int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo, const flo
                      int F, double p, const int64_t *seed, float *d_x, float *d_wi, float *d_wo, void *workspace,
                      rqhip_stream_t stream);
 
+/* The retrieval model's input embedding in one launch forward and one backward (csrc/sid_embed.hip; modules/model.py,
+ * embed_impl = "hip"): semantic ids -> a T5 stack's inputs_embeds, for the encoder and the decoder front alike.
+ * B rows, `items` items per row, L levels, K codes per level, width d; table [V = L * K, d], x dense [B, T, d], fp32.
+ * has_sep = (sep != NULL), has_prefix = (prefix_table != NULL), T = has_prefix + items * (L + has_sep).  Row b of x:
+ *   prefix (t = 0, optional)     row floor_mod(prefix_idx[b * prefix_idx_ld], prefix_rows) of prefix_table
+ *                                [prefix_rows, d] (torch.remainder: never negative); prefix_idx NULL: row 0 for every b
+ *   id position (item i, level h)   m = mask ? (mask[b, i * ld_item + h] != 0) : 1
+ *                                row (ids[b, i * ld_item + h] + h * K) * m of table
+ *   separator after each item (optional)   sep [d]
+ *   ids   [B, items * ld_item] int64, dense rows; ld_item >= L columns per item, columns h >= L of an item never read
+ *   mask  the same layout, elements of mask_elt_size bytes: 1 (bool) or 8 (int64); NULL = all ones
+ *   mask_out [B, T] bytes (optional): 1 at the prefix, m at an id position, at a separator the m of level L - 1
+ * A padded id (-1 with mask 0) reads row 0.  An index outside [0, V) after the offset and the mask is never used as an
+ * address: the forward clamps it into the table (it reads row 0 or row V - 1), the backward drops that token.
+ * rqhip_sid_embed_bwd, from d_x dense [B, T, d] and the same plan (has_sep, has_prefix given as flags):
+ *   d_table  [V, d]: row r = the sum of d_x over the id positions whose index is r, zero where there is none
+ *   d_sep    [d]: the sum over every separator position            d_prefix [prefix_rows, d]: per prefix row, the sum
+ *   over the rows b that read it (prefix_idx NULL: row 0 is the sum over b).  Each is written whole; NULL: not wanted.
+ *   One workgroup per destination row scans the tokens in chunks of 1024, keeps a chunk's matches in ascending token
+ *   order, and with G = max(1, 256 / (d / 4)) adds per column the entries g, g + G, g + 2G, ... of a chunk from +0 for
+ *   g = 0 .. G - 1, then those G sums in ascending g, then the chunks in ascending order from +0.  No atomics, no host
+ *   read: the order is a function of the shape and the ids alone, so the same inputs give the same bits on every run.
+ *   rqhip_sid_embed_bwd_workspace_bytes is the size of `workspace` (a function of the shape alone; this version keeps
+ *   every partial sum on chip and returns 0, and `workspace` may then be NULL).
+ * Limits (rqhip_sid_embed_supported): d a multiple of 4 in 4 .. 1024, 1 <= L <= 8, else RQHIP_EARG; any K >= 1, items >= 1,
+ * B >= 0 (B = 0 returns RQHIP_OK without a launch); B * T and L * K + prefix_rows below 2^31; table, sep,
+ * prefix_table, x and the gradients 16-byte aligned.  All argument checks come before any HIP call; no allocation, copy,
+ * memset or sync (graph-capturable). */
+int rqhip_sid_embed_supported(int d, int L);
+size_t rqhip_sid_embed_bwd_workspace_bytes(int64_t B, int items, int L, int K, int d);
+int rqhip_sid_embed_fwd(const int64_t *ids, const void *mask, int mask_elt_size, int64_t B, int items, int L, int ld_item,
+                        int K, int d, const float *table, const float *sep, const float *prefix_table,
+                        const int64_t *prefix_idx, int64_t prefix_idx_ld, int64_t prefix_rows, float *x, uint8_t *mask_out,
+                        rqhip_stream_t stream);
+int rqhip_sid_embed_bwd(const float *d_x, const int64_t *ids, const void *mask, int mask_elt_size, int64_t B, int items,
+                        int L, int ld_item, int K, int d, int has_sep, int has_prefix, const int64_t *prefix_idx,
+                        int64_t prefix_idx_ld, int64_t prefix_rows, float *d_table, float *d_sep, float *d_prefix,
+                        void *workspace, size_t workspace_bytes, rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

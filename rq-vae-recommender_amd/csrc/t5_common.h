@@ -1,5 +1,6 @@
-// t5_common.h -- what the T5 kernel files share (t5_attention.hip, t5_add_norm.hip, t5_ffn.hip, sid_head_loss.hip): the
-// dropout decision, its threshold and its two scales, the wave reductions and the entry points' pointer checks.
+// t5_common.h -- what the T5 kernel files share (t5_attention.hip, t5_add_norm.hip, t5_ffn.hip, sid_head_loss.hip,
+// sid_embed.hip): the dropout decision, its threshold and its two scales, the wave reductions and the entry points'
+// pointer checks.
 #pragma once
 
 #include <math.h>

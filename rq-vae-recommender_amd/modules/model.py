@@ -11,6 +11,16 @@ on the decoder's unsliced output and batch.sem_ids_fut as they are, with the dec
 (the state dict is unchanged).  It is taken when the decoder output is an fp32 device tensor and the shape is supported
 (ops.sid_head_loss_supported), under grad and under no_grad and with every attention_impl / norm_impl; otherwise the
 operators run, silently.  `generate` has its own head and is not affected.
+`model.embed_impl = "hip"` (default "torch") makes the front that turns semantic ids into a stack's inputs_embeds -- the
+level offsets, the mask product, the table gather, the separator, the user / BOS row and the mask that goes with them --
+ONE autograd.SidEmbedFunction call per stack (csrc/sid_embed.hip): one launch forward, one backward, in
+`encoder_forward_pass` and in `decoder_forward_pass` (without a cache).  `forward` hands both the batch's tensors as
+they are, dedup column included, with that column skipped by the kernel's column stride.  It is taken when the ids and
+the fp32 parameters are on the device and the shape is supported (`hip_embed_active`), under grad and under no_grad,
+and by the encoder pass of `generate`; otherwise the operators run, silently.  inputs_embeds has the operators' bits;
+the encoder's returned attention mask is then a bool tensor with the operators' truth values.  An id outside the table,
+a device assert of the operators, reads a clamped row and gets no gradient.  The per-step lookup of `generate` is not
+affected.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
@@ -32,9 +42,10 @@ from modules.sid_prefix import SemIdPrefixIndex
 from modules.t5 import T5Config, T5EncoderModel, T5Stack
 from rqhip import ops
 from rqhip._lib import RqHipError
-from rqhip.autograd import SidHeadLossFunction
+from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
 
 HEAD_IMPLS = ("torch", "hip")
+EMBED_IMPLS = ("torch", "hip")
 
 
 class ModelOutput(NamedTuple):
@@ -100,6 +111,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.norm_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.head_impl = "torch"  # or "hip": the heads and their losses of `forward` as one fused call
         self.ffn_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
+        self.embed_impl = "torch"  # or "hip": each stack's input embedding as one fused call
 
     @property
     def device(self) -> torch.device:
@@ -152,8 +164,42 @@ class EncoderDecoderRetrievalModel(nn.Module):
             for stack in (self.encoder.encoder, self.t5_decoder):
                 setattr(stack, name, getattr(self, name))
 
-    def encoder_forward_pass(self, attention_mask, input_ids, user_id=None):
+    def hip_embed_active(self, input_ids: Tensor, attention_mask: Optional[Tensor] = None) -> bool:
+        """Whether the "hip" input embedding is taken for these ids and this mask (module docstring)."""
+        if self.embed_impl not in EMBED_IMPLS:
+            raise ValueError(f"embed_impl must be one of {EMBED_IMPLS}, got {self.embed_impl!r}")
+        params = [self.item_sid_embedding_table.weight, self.bos_token, self.sep_token,
+                  None if self.user_embedding is None else self.user_embedding.weight]
+        return (self.embed_impl == "hip" and input_ids.is_cuda and input_ids.dtype == torch.int64
+                and (attention_mask is None or (attention_mask.is_cuda
+                                                and attention_mask.dtype in (torch.bool, torch.int64)))
+                and all(p is None or (p.is_cuda and p.dtype == torch.float32) for p in params)
+                and ops.sid_embed_supported(torch.float32, self.item_sid_embedding_table.embedding_dim,
+                                            self.num_hierarchies))
+
+    def _hip_embed(self, ids, mask, ld_item, sep, prefix_table, prefix_idx, need_mask):
+        """One fused call -> (inputs_embeds, its bool keep-mask or None)."""
+        table = self.item_sid_embedding_table.weight
+        if torch.is_grad_enabled():
+            return SidEmbedFunction.apply(ids, mask, table, sep, prefix_table, prefix_idx, self.num_hierarchies, ld_item,
+                                          need_mask)
+        return ops.sid_embed_fwd(ids, mask, table, self.num_hierarchies, ld_item, sep, prefix_table, prefix_idx,
+                                 need_mask=need_mask)
+
+    def encoder_forward_pass(self, attention_mask, input_ids, user_id=None, *, ld_item=None):
+        """ld_item: columns per item in input_ids and attention_mask, num_hierarchies (the default) or more; columns
+        past num_hierarchies of an item (the tokenizer's dedup column) are not read."""
         self._push_attention_impl()
+        ld_item = self.num_hierarchies if ld_item is None else ld_item
+        with_user = user_id is not None and self.user_embedding is not None
+        if attention_mask is not None and self.hip_embed_active(input_ids, attention_mask):
+            inputs_embeds, attention_mask = self._hip_embed(
+                input_ids, attention_mask, ld_item, self.sep_token,
+                self.user_embedding.weight if with_user else None, user_id if with_user else None, True)
+            return self.encoder(inputs_embeds=inputs_embeds, attention_mask=attention_mask), attention_mask
+        if ld_item != self.num_hierarchies:
+            input_ids = _strip_dedup_col(input_ids, ld_item, self.num_hierarchies)
+            attention_mask = _strip_dedup_col(attention_mask.long(), ld_item, self.num_hierarchies)
         shifted = self._add_repeating_offset_to_rows(input_sids=input_ids,
                                                      codebook_size=self.num_embeddings_per_hierarchy,
                                                      num_hierarchies=self.num_hierarchies,
@@ -163,7 +209,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
             inputs_embeds, attention_mask = self._inject_sep_token_between_sids(
                 id_embeddings=inputs_embeds, attention_mask=attention_mask, sep_token=self.sep_token,
                 num_hierarchies=self.num_hierarchies)
-        if user_id is not None and self.user_embedding is not None:
+        if with_user:
             user_embeds = self.user_embedding(torch.remainder(user_id[:, 0], self.user_embedding.num_embeddings))
             inputs_embeds = torch.cat([user_embeds.unsqueeze(1), inputs_embeds], dim=1)
             attention_mask = torch.cat(
@@ -172,11 +218,22 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return encoder_output, attention_mask
 
     def decoder_forward_pass(self, attention_mask=None, future_ids=None, encoder_output=None,
-                             attention_mask_for_encoder=None, use_cache=False, past_key_values=None):
+                             attention_mask_for_encoder=None, use_cache=False, past_key_values=None, *, ld_item=None):
         """BOS followed by the embedded future ids (or BOS alone); with a cache (the list this returns when use_cache)
-        only the last future id is run.  Returns the hidden states, and the self-attention cache when use_cache."""
+        only the last future id is run.  Returns the hidden states, and the self-attention cache when use_cache.
+        ld_item: as in encoder_forward_pass, for future_ids and attention_mask."""
         self._push_attention_impl()
-        if future_ids is not None:
+        ld_item = self.num_hierarchies if ld_item is None else ld_item
+        if (future_ids is not None and not past_key_values and future_ids.dim() == 2
+                and future_ids.shape[1] >= ld_item and future_ids.shape[1] % ld_item == 0
+                and self.hip_embed_active(future_ids, attention_mask)):
+            inputs_embeds, attention_mask = self._hip_embed(future_ids, attention_mask, ld_item, None, self.bos_token,
+                                                            None, attention_mask is not None)
+        elif future_ids is not None:
+            if ld_item != self.num_hierarchies:
+                future_ids = _strip_dedup_col(future_ids, ld_item, self.num_hierarchies)
+                if attention_mask is not None:
+                    attention_mask = _strip_dedup_col(attention_mask, ld_item, self.num_hierarchies)
             shifted = self._add_repeating_offset_to_rows(
                 input_sids=future_ids, codebook_size=self.num_embeddings_per_hierarchy,
                 num_hierarchies=self.num_hierarchies,
@@ -207,14 +264,21 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
     def forward(self, batch: TokenizedSeqBatch) -> ModelOutput:
         sem_ids_dim = self.num_hierarchies + 1
-        input_ids = _strip_dedup_col(batch.sem_ids, sem_ids_dim, self.num_hierarchies)
-        attention_mask = _strip_dedup_col(batch.seq_mask.long(), sem_ids_dim, self.num_hierarchies)
         fut_ids = batch.sem_ids_fut[:, : self.num_hierarchies]
-        encoder_output, attention_mask_for_encoder = self.encoder_forward_pass(
-            attention_mask=attention_mask, input_ids=input_ids, user_id=batch.user_ids)
-        decoder_output = self.decoder_forward_pass(
-            future_ids=fut_ids, encoder_output=encoder_output,
-            attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False)
+        if self.hip_embed_active(batch.sem_ids, batch.seq_mask):      # the batch's tensors as they are
+            encoder_output, attention_mask_for_encoder = self.encoder_forward_pass(
+                attention_mask=batch.seq_mask, input_ids=batch.sem_ids, user_id=batch.user_ids, ld_item=sem_ids_dim)
+            decoder_output = self.decoder_forward_pass(
+                future_ids=batch.sem_ids_fut, encoder_output=encoder_output,
+                attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False, ld_item=sem_ids_dim)
+        else:
+            input_ids = _strip_dedup_col(batch.sem_ids, sem_ids_dim, self.num_hierarchies)
+            attention_mask = _strip_dedup_col(batch.seq_mask.long(), sem_ids_dim, self.num_hierarchies)
+            encoder_output, attention_mask_for_encoder = self.encoder_forward_pass(
+                attention_mask=attention_mask, input_ids=input_ids, user_id=batch.user_ids)
+            decoder_output = self.decoder_forward_pass(
+                future_ids=fut_ids, encoder_output=encoder_output,
+                attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False)
         if self.hip_head_active(decoder_output):
             weights = [m.weight for m in self.decoder_mlp]
             if torch.is_grad_enabled():

@@ -122,6 +122,12 @@ SIGNATURES = {
                                        _vp, _vp]),
     "rqhip_sid_head_loss_bwd": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp,
                                        _vp, _vp]),
+    "rqhip_sid_embed_supported": (_int, [_int, _int]),
+    "rqhip_sid_embed_bwd_workspace_bytes": (_sz, [_i64, _int, _int, _int, _int]),
+    "rqhip_sid_embed_fwd": (_int, [_vp, _vp, _int, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _i64, _i64, _vp,
+                                   _vp, _vp]),
+    "rqhip_sid_embed_bwd": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _i64,
+                                   _vp, _vp, _vp, _vp, _sz, _vp]),
     "rqhip_recon_loss_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp]),
     "rqhip_recon_loss_backward": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
     "rqhip_recon_loss_forward_spec": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _f32, _vp, _vp, _vp]),

@@ -373,3 +373,39 @@ class SidHeadLossFunction(torch.autograd.Function):
         d_x, d_w = ops.sid_head_loss_bwd(x, weights, target, z, lse, _dense(d_loss), L,
                                          need_x=ctx.needs_input_grad[0], need_w=ctx.needs_input_grad[2:])
         return (d_x, None, *d_w)
+
+
+class SidEmbedFunction(torch.autograd.Function):
+    """The retrieval model's input embedding (modules/model.py, embed_impl = "hip") as one launch forward and one
+    backward (ops.sid_embed_fwd / ops.sid_embed_bwd): apply(ids, mask or None, table, sep or None, prefix_table or None,
+    prefix_idx or None, L, ld_item, need_mask) -> (x, mask_out).  mask_out is not differentiable (None without
+    need_mask).  Saved: the ids, the mask and the prefix indices, no activation.  Gradients: table, sep (in its own
+    shape) and prefix_table, each only when needed."""
+
+    @staticmethod
+    def forward(ctx, ids: Tensor, mask: Optional[Tensor], table: Tensor, sep: Optional[Tensor],
+                prefix_table: Optional[Tensor], prefix_idx: Optional[Tensor], L: int, ld_item: int, need_mask: bool):
+        x, mask_out = ops.sid_embed_fwd(ids, mask, table, L, ld_item, sep, prefix_table, prefix_idx, need_mask=need_mask)
+        if prefix_table is None:
+            prefix_idx = None
+        ctx.set_materialize_grads(False)   # no zero-filled gradient for mask_out; x unused: its gradient arrives as None
+        ctx.save_for_backward(ids, mask, prefix_idx)
+        ctx.plan = (L, ld_item, table.shape[0] // L, None if sep is None else sep.shape,
+                    0 if prefix_table is None else prefix_table.shape[0])
+        if mask_out is not None:
+            ctx.mark_non_differentiable(mask_out)
+        return x, mask_out
+
+    @staticmethod
+    def backward(ctx, d_x: Optional[Tensor], _d_mask_out):
+        ids, mask, prefix_idx = ctx.saved_tensors
+        L, ld_item, K, sep_shape, prefix_rows = ctx.plan
+        need_table, need_sep, need_prefix = ctx.needs_input_grad[2:5]
+        if d_x is None or not (need_table or need_sep or need_prefix):
+            return (None,) * 9
+        d_table, d_sep, d_prefix = ops.sid_embed_bwd(_dense(d_x), ids, mask, L, ld_item, K, has_sep=sep_shape is not None,
+                                                     prefix_rows=prefix_rows, prefix_idx=prefix_idx,
+                                                     need_table=need_table, need_sep=need_sep, need_prefix=need_prefix)
+        if d_sep is not None:
+            d_sep = d_sep.view(sep_shape)
+        return None, None, d_table, d_sep, d_prefix, None, None, None, None

@@ -958,6 +958,127 @@ def sid_head_loss_bwd(x: Tensor, weights, target: Tensor, z: Tensor, lse: Tensor
     return d_x, d_w
 
 
+def sid_embed_supported(dtype: torch.dtype, d: int, L: int) -> bool:
+    """Whether sid_embed_fwd / sid_embed_bwd implement this shape (rqhip_sid_embed_supported): fp32, d a multiple of 4
+    in 4 .. 1024, L in 1 .. 8 levels."""
+    return dtype == torch.float32 and bool(_lib.lib().rqhip_sid_embed_supported(int(d), int(L)))
+
+
+def _sid_embed_plan(who: str, ids: Tensor, mask: Optional[Tensor], L: int, ld_item: int, d: int,
+                    prefix_idx: Optional[Tensor]):
+    """The checks of the row plan sid_embed_fwd and sid_embed_bwd share (shapes and dtypes first, so that they are
+    reported on any device) -> (ids, mask, its element size, B, items, prefix_idx, its row stride)."""
+    L, ld_item = int(L), int(ld_item)
+    if ids.dim() != 2 or ids.dtype != torch.int64:
+        raise RqHipError(f"{who}: ids must be an int64 [B, items * ld_item] tensor, got {ids.dtype} {tuple(ids.shape)}")
+    if L < 1 or ld_item < L or ids.shape[1] < ld_item or ids.shape[1] % ld_item:
+        raise RqHipError(f"{who}: ids of width {ids.shape[1]} are not items * ld_item columns (ld_item={ld_item}, L={L})")
+    if mask is not None and (mask.dtype not in (torch.bool, torch.int64) or mask.shape != ids.shape):
+        raise RqHipError(f"{who}: mask must be a bool or int64 tensor of ids' shape {tuple(ids.shape)}, got {mask.dtype} "
+                         f"{tuple(mask.shape)}")
+    if prefix_idx is not None and (prefix_idx.dtype != torch.int64 or prefix_idx.dim() not in (1, 2)
+                                   or prefix_idx.shape[0] != ids.shape[0]):
+        raise RqHipError(f"{who}: prefix_idx must be an int64 [{ids.shape[0]}] or [{ids.shape[0]}, n] tensor (column 0 "
+                         f"is read), got {prefix_idx.dtype} {tuple(prefix_idx.shape)}")
+    if not sid_embed_supported(torch.float32, d, L):
+        raise RqHipError(f"{who}: (d, L) = ({d}, {L}) is not supported (d a multiple of 4 in 4 .. 1024, L in 1 .. 8)")
+    _need_gpu(ids, mask, prefix_idx)
+    ids = ids.contiguous()
+    if mask is not None:
+        mask = mask.contiguous()
+    ld_p = 0
+    if prefix_idx is not None:
+        if prefix_idx.shape[0] > 1 and prefix_idx.stride(0) < 1:
+            prefix_idx = prefix_idx.contiguous()
+        ld_p = int(prefix_idx.stride(0))
+    return (ids, mask, 0 if mask is None else mask.element_size(), ids.shape[0], ids.shape[1] // ld_item, prefix_idx,
+            ld_p)
+
+
+def sid_embed_fwd(ids: Tensor, mask: Optional[Tensor], table: Tensor, L: int, ld_item: int, sep: Optional[Tensor] = None,
+                  prefix_table: Optional[Tensor] = None, prefix_idx: Optional[Tensor] = None, *, need_mask: bool = True):
+    """Semantic ids -> a T5 stack's inputs_embeds in one launch (rqhip_sid_embed_fwd) -> (x, mask_out).  Row b of x
+    [B, T, d] is an optional prefix, then per item its L id positions and an optional separator, T = has_prefix + items
+    * (L + has_sep):
+      ids [B, items * ld_item] int64, ld_item >= L columns per item (columns >= L of an item are never read); mask None
+      or a bool / int64 tensor of the same shape; table [L * K, d] float32.  Position (item i, level h) is row
+      (ids[b, i * ld_item + h] + h * K) * (mask != 0) of table: a padded id (-1, mask 0) is row 0.
+      sep: None or d float32 elements, the position behind each item.
+      prefix_table [rows, d]: position 0 is its row remainder(prefix_idx[b] or prefix_idx[b, 0], rows), or its row 0 for
+      every b without prefix_idx (a [1, d] parameter).
+    mask_out [B, T] bool (None without need_mask): True at the prefix, mask != 0 at an id position and at a separator
+    that of its item's last level.  x has the operators' bits: it is a gather.
+    An index outside the table is never used as an address, where the operators would raise a device assert: it is
+    clamped into the table here (row 0 or the last row) and its token is dropped by sid_embed_bwd."""
+    who = "sid_embed_fwd"
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] % max(int(L), 1):
+        raise RqHipError(f"{who}: table must be float32 [L * K, d] with L={L}, got {table.dtype} {tuple(table.shape)}")
+    d, K = table.shape[1], table.shape[0] // max(int(L), 1)
+    if sep is not None and (sep.dtype != torch.float32 or sep.numel() != d):
+        raise RqHipError(f"{who}: sep must hold {d} float32 elements, got {sep.dtype} {tuple(sep.shape)}")
+    if prefix_table is not None and (prefix_table.dtype != torch.float32 or prefix_table.dim() != 2
+                                     or prefix_table.shape[1] != d or prefix_table.shape[0] < 1):
+        raise RqHipError(f"{who}: prefix_table must be float32 [rows >= 1, {d}], got {prefix_table.dtype} "
+                         f"{tuple(prefix_table.shape)}")
+    if prefix_table is None:
+        prefix_idx = None
+    ids, mask, elt, B, items, prefix_idx, ld_p = _sid_embed_plan(who, ids, mask, L, ld_item, d, prefix_idx)
+    _need_gpu(ids, table, sep, prefix_table)
+    table = _aligned16(table.contiguous())
+    sep = None if sep is None else _aligned16(sep.contiguous())
+    prefix_table = None if prefix_table is None else _aligned16(prefix_table.contiguous())
+    T = (prefix_table is not None) + items * (int(L) + (sep is not None))
+    dev = ids.device
+    with torch.cuda.device(dev):
+        x = torch.empty((B, T, d), dtype=torch.float32, device=dev)
+        mask_out = torch.empty((B, T), dtype=torch.bool, device=dev) if need_mask else None
+        rc = _lib.lib().rqhip_sid_embed_fwd(_ptr(ids), _ptr(mask), elt, B, items, int(L), int(ld_item), K, d, _ptr(table),
+                                            _ptr(sep), _ptr(prefix_table), _ptr(prefix_idx), ld_p,
+                                            0 if prefix_table is None else prefix_table.shape[0], _ptr(x),
+                                            _ptr(mask_out), _stream())
+        check(rc, "rqhip_sid_embed_fwd")
+    return x, mask_out
+
+
+def sid_embed_bwd(d_x: Tensor, ids: Tensor, mask: Optional[Tensor], L: int, ld_item: int, K: int, *, has_sep: bool,
+                  prefix_rows: int = 0, prefix_idx: Optional[Tensor] = None, need_table: bool = True,
+                  need_sep: bool = True, need_prefix: bool = True):
+    """The gradients of sid_embed_fwd's x in one launch (rqhip_sid_embed_bwd) -> (d_table [L * K, d], d_sep [d],
+    d_prefix [prefix_rows, d]), None where not wanted or not part of the plan (has_sep; prefix_rows = 0: no prefix).
+    d_x [B, T, d] float32; ids, mask, L, ld_item, prefix_idx: the forward's.  Each gradient is written whole, rows no
+    token reads are zero, and a token whose index lies outside the table is dropped.  No atomics and no host read: the
+    summation order depends on the shape and the ids alone, so the same inputs give the same bits on every run."""
+    who = "sid_embed_bwd"
+    L, K, prefix_rows = int(L), int(K), int(prefix_rows)
+    if d_x.dtype != torch.float32 or d_x.dim() != 3:
+        raise RqHipError(f"{who}: d_x must be a float32 [B, T, d] tensor, got {d_x.dtype} {tuple(d_x.shape)}")
+    d = d_x.shape[2]
+    if K < 1 or prefix_rows < 0:
+        raise RqHipError(f"{who}: K={K}, prefix_rows={prefix_rows}")
+    if not prefix_rows:
+        prefix_idx = None
+    ids, mask, elt, B, items, prefix_idx, ld_p = _sid_embed_plan(who, ids, mask, L, ld_item, d, prefix_idx)
+    T = (prefix_rows > 0) + items * (L + bool(has_sep))
+    if tuple(d_x.shape) != (B, T, d):
+        raise RqHipError(f"{who}: d_x {tuple(d_x.shape)} does not match [{B}, {T}, {d}]")
+    _need_gpu(d_x, ids)
+    d_x = _aligned16(d_x.contiguous())
+    need_sep, need_prefix = need_sep and bool(has_sep), need_prefix and prefix_rows > 0
+    dev = d_x.device
+    with torch.cuda.device(dev):
+        make = torch.zeros if B == 0 else torch.empty      # without rows the sums are empty
+        d_table = make((L * K, d), dtype=torch.float32, device=dev) if need_table else None
+        d_sep = make((d,), dtype=torch.float32, device=dev) if need_sep else None
+        d_prefix = make((prefix_rows, d), dtype=torch.float32, device=dev) if need_prefix else None
+        nbytes = int(_lib.lib().rqhip_sid_embed_bwd_workspace_bytes(B, items, L, K, d))
+        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev) if nbytes else None
+        rc = _lib.lib().rqhip_sid_embed_bwd(_ptr(d_x), _ptr(ids), _ptr(mask), elt, B, items, L, int(ld_item), K, d,
+                                            int(bool(has_sep)), int(prefix_rows > 0), _ptr(prefix_idx), ld_p, prefix_rows,
+                                            _ptr(d_table), _ptr(d_sep), _ptr(d_prefix), _ptr(work), nbytes, _stream())
+        check(rc, "rqhip_sid_embed_bwd")
+    return d_table, d_sep, d_prefix
+
+
 def gumbel_matrix_path_min_rows(set_to: int = 0) -> int:
     """Query (set_to <= 0) or set the batch size from which the Gumbel level runs on the matrix instructions
     (rqhip_gumbel_matrix_path_min_rows); returns the previous value."""

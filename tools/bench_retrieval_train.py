@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) in six arms:
+tails: encoder T = 81, decoder T = 4) in seven arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
@@ -14,6 +14,8 @@ tails: encoder T = 81, decoder T = 4) in six arms:
              one ops.t5_ffn_fwd launch and one ops.t5_ffn_bwd call of two launches
   hip_train+norm+head+ffn+optim  hip_train+norm+head+ffn stepped by rqhip.optim.FlatAdamW (csrc/adamw.hip: one bump launch and
              one update launch per 24 tensors) instead of torch.optim.AdamW; no clipping and no schedule, as in the other arms
+  hip_train+norm+head+ffn+optim+embed  the arm before it with embed_impl = "hip": each stack's input embedding (offsets,
+             mask product, gather, separator, BOS row) as one ops.sid_embed_fwd launch and one ops.sid_embed_bwd launch
 
 The arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
@@ -21,8 +23,8 @@ median and the fastest step per arm over all blocks, the median of each block (t
 between two arms has to exceed), and the peak torch.cuda.max_memory_allocated of a block, as one
 JSON line per arm plus a summary line; --out also writes them to a text file (profiles/retrieval_train_step_norm.txt
 holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run, profiles/retrieval_train_step_ffn.txt a
-five-arm run, profiles/retrieval_optim_tail.txt a six-arm run; profiles/retrieval_train_step.txt is the older two-arm run; none
-of them is to be overwritten or compared
+five-arm run, profiles/retrieval_optim_tail.txt a six-arm run, profiles/retrieval_train_step_embed.txt a run of the last
+two arms; profiles/retrieval_train_step.txt is the older two-arm run; none of them is to be overwritten or compared
 against: two arms are compared within one run only).
 --arms picks a subset, e.g. one arm under a kernel trace to count its launches per step.
 
@@ -47,8 +49,11 @@ from retrieval_cases import synthetic_batch, to_device  # noqa: E402  (tests/ret
 ARMS = {"torch": ("torch", "torch", "torch", "torch"), "hip_train": ("hip_train", "torch", "torch", "torch"),
         "hip_train+norm": ("hip_train", "hip", "torch", "torch"), "hip_train+norm+head": ("hip_train", "hip", "hip", "torch"),
         "hip_train+norm+head+ffn": ("hip_train", "hip", "hip", "hip"),
-        "hip_train+norm+head+ffn+optim": ("hip_train", "hip", "hip", "hip")}
-FLAT_ADAMW = ("hip_train+norm+head+ffn+optim",)      # arms stepped by rqhip.optim.FlatAdamW; the others by torch.optim.AdamW
+        "hip_train+norm+head+ffn+optim": ("hip_train", "hip", "hip", "hip"),
+        "hip_train+norm+head+ffn+optim+embed": ("hip_train", "hip", "hip", "hip")}
+# arms stepped by rqhip.optim.FlatAdamW; the others by torch.optim.AdamW
+FLAT_ADAMW = ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed")
+EMBED_HIP = ("hip_train+norm+head+ffn+optim+embed",)  # arms with embed_impl = "hip"; the others "torch"
 
 
 def make_batch(B, items, L, K, N, dev, seed):
@@ -61,6 +66,7 @@ def block(model, state, batch, arm, warmup, iters):
     """One block of one arm from the common starting weights -> (ms per step, peak bytes, last loss)."""
     model.load_state_dict(state)
     model.attention_impl, model.norm_impl, model.head_impl, model.ffn_impl = ARMS[arm]
+    model.embed_impl = "hip" if arm in EMBED_HIP else "torch"
     model.train()
     if arm in FLAT_ADAMW:
         from rqhip.optim import FlatAdamW
@@ -117,6 +123,7 @@ def main():
     for arm in arms:
         lines.append(json.dumps({"arm": arm, "attention_impl": ARMS[arm][0], "norm_impl": ARMS[arm][1],
                                  "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3],
+                                 **({"embed_impl": "hip"} if arm in EMBED_HIP else {}),
                                  "optimizer": "FlatAdamW" if arm in FLAT_ADAMW else "torch.optim.AdamW", "batch": args.batch,
                                  "steps_timed": len(times[arm]),
                                  "ms_per_step_median": round(statistics.median(times[arm]), 3),
@@ -126,7 +133,8 @@ def main():
     summary = {"summary": "median step, first arm / second arm"}
     for a, b in (("torch", "hip_train"), ("hip_train", "hip_train+norm"), ("hip_train+norm", "hip_train+norm+head"),
                  ("hip_train+norm+head", "hip_train+norm+head+ffn"),
-                 ("hip_train+norm+head+ffn", "hip_train+norm+head+ffn+optim")):
+                 ("hip_train+norm+head+ffn", "hip_train+norm+head+ffn+optim"),
+                 ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed")):
         if a in arms and b in arms:
             summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
             summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)
