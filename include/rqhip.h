@@ -489,6 +489,33 @@ int rqhip_sid_embed_bwd(const float *d_x, const int64_t *ids, const void *mask, 
                         int64_t prefix_idx_ld, int64_t prefix_rows, float *d_table, float *d_sep, float *d_prefix,
                         void *workspace, size_t workspace_bytes, rqhip_stream_t stream);
 
+/* The retrieval model's training batch in one launch (csrc/seq_batch.hip; rqhip/ops.py:seq_batch, data/seq_loader.py):
+ * device-resident user histories + the tokenizer's cached id table + two random integers per row -> every tensor of a
+ * TokenizedSeqBatch.  All tensors int64 and dense unless said otherwise.
+ *   offsets [U + 1], items [nnz]: the histories in CSR form, user r owns items[offsets[r] .. offsets[r + 1]);
+ *   fut [U]: the item that follows user r's history; user [U]: the user ids; rows [B]: user indices, repeats allowed
+ *   table [n_items, w]: the ids of every item (w = levels + the dedup column)
+ *   draws [B, 2] or NULL.  With n_hist = offsets[r + 1] - offsets[r], seq = the history followed by fut[r], n = n_hist + 1:
+ *     NULL     history = the last min(S, n_hist) items, target = fut[r]
+ *     else     start = u0 mod (max(0, n - 3) + 1), end = min(start + 3 + u1 mod (S - 1), n) with (u0, u1) = draws[b]
+ *              read as unsigned; window = seq[start .. end): its last element is the target, the rest the history
+ *              (data/processed.py:seq_window is the same law on the host)
+ *   sem_ids [B, S * w]: the history's table rows, -1 in the slots behind it; seq_mask [B, S * w] bytes (bool): 1 where
+ *   sem_ids holds a table row; sem_ids_fut [B, w]: the target's row; user_ids [B] (the [B, 1] of a batch);
+ *   token_type [B, S * w] and token_type_fut [B, w] (each optional, NULL: not written): column mod w.
+ * An item id outside [0, n_items) is padding: -1 and mask 0 (all -1 for a target), and nothing is read outside the
+ * table.  A user index outside [0, U) gives an empty history, target -1 and user id -1; offsets are clamped into
+ * [0, nnz]: no index taken from device memory is used as an address unchecked.
+ * One thread per 16 bytes of output ids when w is even and table, sem_ids, sem_ids_fut and the token types are 16-byte
+ * aligned (seq_mask 2-byte aligned), else one per id.  Limits (rqhip_seq_batch_supported): 2 <= w <= 9, 2 <= S <= 256,
+ * else RQHIP_EARG; B * (S + 1) * w below 2^31; B = 0 returns RQHIP_OK without a launch.  All argument checks come before
+ * any HIP call; no allocation, copy, memset, sync or workspace (graph-capturable). */
+int rqhip_seq_batch_supported(int w, int S);
+int rqhip_seq_batch(const int64_t *offsets, const int64_t *items, const int64_t *fut, const int64_t *user, int64_t U,
+                    int64_t nnz, const int64_t *rows, int64_t B, const int64_t *draws, const int64_t *table,
+                    int64_t n_items, int w, int S, int64_t *sem_ids, uint8_t *seq_mask, int64_t *sem_ids_fut,
+                    int64_t *user_ids, int64_t *token_type, int64_t *token_type_fut, rqhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Reconstruction loss (modules/loss.py:5-10 ReconstructionLoss, called at modules/rqvae.py:152), fused.
  *   forward : out[b] = sum_d (x_hat[b,d] - x[b,d])^2        x_hat, x: [B,N] with row strides ld_* (elements, >= N)

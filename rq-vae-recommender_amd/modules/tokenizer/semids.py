@@ -92,6 +92,20 @@ class SemanticIdTokenizer(nn.Module):
         return torch.arange(width, device=device).repeat(rows, items)
 
     @torch.no_grad()
+    def tokenize_rows(self, seq_data, rows: Tensor, draws: Optional[Tensor] = None,
+                      token_types: bool = True) -> TokenizedSeqBatch:
+        """The tokenized batch of the users `rows` (int64 [B] indices into `seq_data`, a device-resident
+        data.processed.SeqData) in one launch (ops.seq_batch, csrc/seq_batch.hip): what `forward` returns on the collated
+        `seq_data[r]` rows, without building them.  Needs `cached_ids`; windows are `seq_data.max_seq_len` long.  With
+        `seq_data.subsample` and no `draws`, the two integers per row are drawn here from the device generator; nothing is
+        read by the host."""
+        if self.cached_ids is None:
+            raise RuntimeError("tokenize_rows needs the corpus ids: call precompute_corpus_ids first")
+        if draws is None and seq_data.subsample:
+            draws = torch.randint(0, 2 ** 62, (rows.shape[0], 2), dtype=torch.int64, device=rows.device)
+        return ops.seq_batch(seq_data, rows, self.cached_ids, seq_data.max_seq_len, draws, token_types)
+
+    @torch.no_grad()
     @eval_mode
     def forward(self, batch: SeqBatch) -> TokenizedSeqBatch:
         """Two regimes, as in the reference (semids.py:117-146).  Without a usable cache (none yet, or an item number

@@ -128,6 +128,9 @@ SIGNATURES = {
                                    _vp, _vp]),
     "rqhip_sid_embed_bwd": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _i64,
                                    _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rqhip_seq_batch_supported": (_int, [_int, _int]),
+    "rqhip_seq_batch": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp]),
     "rqhip_recon_loss_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp]),
     "rqhip_recon_loss_backward": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
     "rqhip_recon_loss_forward_spec": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _f32, _vp, _vp, _vp]),

@@ -1079,6 +1079,59 @@ def sid_embed_bwd(d_x: Tensor, ids: Tensor, mask: Optional[Tensor], L: int, ld_i
     return d_table, d_sep, d_prefix
 
 
+def seq_batch_supported(w: int, S: int) -> bool:
+    """Whether seq_batch implements this shape (rqhip_seq_batch_supported): w in 2 .. 9 ids per item, S in 2 .. 256."""
+    return bool(_lib.lib().rqhip_seq_batch_supported(int(w), int(S)))
+
+
+def seq_batch(seq, rows: Tensor, table: Tensor, S: int, draws: Optional[Tensor] = None, token_types: bool = True):
+    """A whole TokenizedSeqBatch in one launch (rqhip_seq_batch) from device-resident histories.
+      seq: the CSR store of a data.processed.SeqData (its int64 tensors `offsets` [U + 1], `items` [nnz], `itemId_fut`
+      [U], `userId` [U]); rows [B] int64 user indices, repeats allowed; table [n_items, w] int64, the tokenizer's
+      cached ids; S the history length of a row.
+      draws None: every row is its user's last min(S, n_hist) items with the stored future item as the target.
+      draws [B, 2] int64 in [0, 2^62): row b is the window data.processed.seq_window(n_hist, *draws[b], S, True).
+    Returns sem_ids [B, S * w] (-1 in padded slots), seq_mask [B, S * w] bool, sem_ids_fut [B, w], user_ids [B, 1] and,
+    with token_types, the two token_type_ids tensors (else None) -- the fields, dtypes and bits of
+    SemanticIdTokenizer.forward on the same windows.  An item id outside the table is padding, never an address.  No
+    host read, no sync and no allocation whose size depends on data."""
+    from data.schemas import TokenizedSeqBatch
+    who = "seq_batch"
+    tensors = {"offsets": seq.offsets, "items": seq.items, "itemId_fut": seq.itemId_fut, "userId": seq.userId, "rows": rows}
+    for name, t in tensors.items():
+        if t.dtype != torch.int64 or t.dim() != 1:
+            raise RqHipError(f"{who}: {name} must be a 1-d int64 tensor, got {t.dtype} {tuple(t.shape)}")
+    U, S = seq.userId.shape[0], int(S)
+    if seq.offsets.shape[0] != U + 1 or seq.itemId_fut.shape[0] != U:
+        raise RqHipError(f"{who}: offsets {tuple(seq.offsets.shape)} and itemId_fut {tuple(seq.itemId_fut.shape)} do not "
+                         f"describe {U} users")
+    if table.dtype != torch.int64 or table.dim() != 2:
+        raise RqHipError(f"{who}: table must be an int64 [n_items, w] tensor, got {table.dtype} {tuple(table.shape)}")
+    n_items, w = table.shape
+    B = rows.shape[0]
+    if draws is not None and (draws.dtype != torch.int64 or tuple(draws.shape) != (B, 2)):
+        raise RqHipError(f"{who}: draws must be an int64 [{B}, 2] tensor, got {draws.dtype} {tuple(draws.shape)}")
+    if not seq_batch_supported(w, S):
+        raise RqHipError(f"{who}: (w, S) = ({w}, {S}) is not supported (w in 2 .. 9, S in 2 .. 256)")
+    dev = _need_gpu(*tensors.values(), table, draws)
+    offsets, items, fut, user, rows = (t.contiguous() for t in tensors.values())
+    table = table.contiguous()
+    draws = None if draws is None else draws.contiguous()
+    with torch.cuda.device(dev):
+        sem_ids = torch.empty((B, S * w), dtype=torch.int64, device=dev)
+        seq_mask = torch.empty((B, S * w), dtype=torch.bool, device=dev)
+        sem_ids_fut = torch.empty((B, w), dtype=torch.int64, device=dev)
+        user_ids = torch.empty((B, 1), dtype=torch.int64, device=dev)
+        tt = torch.empty((B, S * w), dtype=torch.int64, device=dev) if token_types else None
+        tt_fut = torch.empty((B, w), dtype=torch.int64, device=dev) if token_types else None
+        rc = _lib.lib().rqhip_seq_batch(_ptr(offsets), _ptr(items), _ptr(fut), _ptr(user), U, items.shape[0], _ptr(rows), B,
+                                        _ptr(draws), _ptr(table), n_items, w, S, _ptr(sem_ids), _ptr(seq_mask),
+                                        _ptr(sem_ids_fut), _ptr(user_ids), _ptr(tt), _ptr(tt_fut), _stream())
+        check(rc, "rqhip_seq_batch")
+    return TokenizedSeqBatch(user_ids=user_ids, sem_ids=sem_ids, sem_ids_fut=sem_ids_fut, seq_mask=seq_mask,
+                             token_type_ids=tt, token_type_ids_fut=tt_fut)
+
+
 def gumbel_matrix_path_min_rows(set_to: int = 0) -> int:
     """Query (set_to <= 0) or set the batch size from which the Gumbel level runs on the matrix instructions
     (rqhip_gumbel_matrix_path_min_rows); returns the previous value."""
