@@ -450,6 +450,48 @@ int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo, const flo
                      int F, double p, const int64_t *seed, float *d_x, float *d_wi, float *d_wo, void *workspace,
                      rqhip_stream_t stream);
 
+/* A group of 1 <= n <= 8 bias-free linear maps that share their input rows, as one launch forward and at most two
+ * backward (csrc/t5_proj.hip; modules/t5.py, proj_impl = "hip": the q / k / v, the o and the cross-attention K/V
+ * projections).  N rows; all fp32.
+ *   x       [N, d_in] with row stride ld_x >= d_in (elements, a multiple of 4)
+ *   w       a HOST array of n device pointers, w[j] the nn.Linear weight [d_out, d_in] as stored (dense); the entry
+ *           points copy this array and the ones below into the kernels' argument block, so they may be temporaries
+ *   y       a HOST array of n device pointers, y[j] [N, d_out] with its own row stride ld_y[j] >= d_out (a HOST array):
+ *           columns >= d_out of a row and rows >= N are never written, so y[j] may be a position of a decode-cache slab
+ * rqhip_t5_proj_fwd:   y[j] = x . w[j]^T for j < n.  One launch.
+ * rqhip_t5_proj_bwd, from the HOST array d_y of n device pointers, d_y[j] [N, d_out] with row stride ld_dy[j] >= d_out
+ * (a multiple of 4):
+ *     d_x = sum_j d_y[j] . w[j]          d_w[j] = d_y[j]^T . x
+ *   A d_y[j] that is NULL contributes to nothing: it is left out of d_x's sum and its d_w[j] is not written.  d_x
+ *   (dense [N, d_in]) NULL, d_w NULL or an entry d_w[j] NULL: that gradient is not wanted.  At most two launches: one
+ *   for d_x, one for all wanted d_w[j] (dense [d_out, d_in]); none when nothing is wanted or every d_y[j] is NULL (d_x
+ *   is then not written).
+ * Arithmetic contract: that of rqhip_t5_ffn_* above.  All products and sums are fp32 FMAs of v_mfma_f32_16x16x4_f32,
+ * every chain starts from +0, and the order of every chain is a function of the sizes alone:
+ *   - a GROUP of 32 consecutive reduction terms is consumed in the order 0 8 16 24 1 9 17 25 ... 7 15 23 31; 4
+ *     consecutive groups (128 terms) are ONE chain from +0, and a reduction's chains are added in ascending order from
+ *     +0.  y[j] reduces over d_in.  d_x reduces over the concatenation of the (j, term) pairs, ascending in j and then
+ *     in the term, of the d_y[j] that are not NULL: a chain is 128 consecutive terms of that concatenation, across the
+ *     boundaries between the j.  So a row's y[j] depends on neither N, nor the row's position, nor n, nor which other
+ *     weights are in the group; a row's d_x depends on neither N nor the row's position, and with a d_y[j] NULL it has
+ *     the bits of the call on the remaining group (the row-tile height, 16 up to N = 8192, 32 up to 16384 and 64 above,
+ *     changes which workgroup computes a row, not how);
+ *   - d_w[j] reduces over the rows by rqhip_t5_ffn_bwd's rule: blocks of 32 rows (rows 4 ks + kq of a block are the
+ *     k-slots kq of instruction ks = 0 .. 7; rows past N count as zero); with nb = ceil(N / 32), wave w = 0 .. 3 of the
+ *     tile's owning workgroup takes blocks [w nb / 4, (w + 1) nb / 4), starts a fresh chain every 8 blocks and adds
+ *     its chains in ascending order from +0; the result is ((s_0 + s_1) + s_2) + s_3.  The order depends on N alone.
+ * No atomics: the same bits on every run and device.  Rows past N read a valid row and store nothing.
+ * Limits (rqhip_t5_proj_supported): d_in and d_out multiples of 32 in 32 .. 512 and 1 <= n <= 8, else
+ * RQHIP_EUNSUPPORTED; any N >= 0 (N = 0 launches nothing); x, d_x, every w[j] and d_y[j] 16-byte aligned, y[j] and
+ * d_w[j] 4-byte aligned; a null pointer, a row stride below its width (ld_x, ld_dy[j] also: not a multiple of 4) or a
+ * misaligned pointer returns RQHIP_EARG.  All argument checks come before any HIP call; no allocation, copy, memset or
+ * sync (graph-capturable). */
+int rqhip_t5_proj_supported(int d_in, int d_out, int n);
+int rqhip_t5_proj_fwd(const float *x, int64_t ld_x, const float *const *w, float *const *y, const int64_t *ld_y, int n,
+                      int64_t N, int d_in, int d_out, rqhip_stream_t stream);
+int rqhip_t5_proj_bwd(const float *x, int64_t ld_x, const float *const *w, const float *const *d_y, const int64_t *ld_dy,
+                      int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w, rqhip_stream_t stream);
+
 /* The retrieval model's input embedding in one launch forward and one backward (csrc/sid_embed.hip; modules/model.py,
  * embed_impl = "hip"): semantic ids -> a T5 stack's inputs_embeds, for the encoder and the decoder front alike.
  * B rows, `items` items per row, L levels, K codes per level, width d; table [V = L * K, d], x dense [B, T, d], fp32.

@@ -2,9 +2,11 @@
 next item's ids one hierarchy level at a time.  API and state dict of the reference's modules/model.py
 (EncoderDecoderRetrievalModel), so a checkpoint trained there loads here with strict=True.
 
-The T5 body runs on torch operators, or on fused HIP calls chosen by three plain attributes that are handed to both
-stacks whenever they are run: `model.attention_impl` ("torch", the default, "hip" or "hip_train"), `model.norm_impl` and
-`model.ffn_impl` ("torch", the default, or "hip").  What each replaces and when it is taken: modules/t5.py.
+The T5 body runs on torch operators, or on fused HIP calls chosen by four plain attributes that are handed to both
+stacks whenever they are run: `model.attention_impl` ("torch", the default, "hip" or "hip_train"), `model.norm_impl`,
+`model.ffn_impl` and `model.proj_impl` ("torch", the default, or "hip"; the last groups the attention projections, the
+cross-attention K/V of `generate` and the K/V its decode steps write into the cache included).  What each replaces and
+when it is taken: modules/t5.py.
 `model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
 cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
 on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
@@ -112,6 +114,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.head_impl = "torch"  # or "hip": the heads and their losses of `forward` as one fused call
         self.ffn_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.embed_impl = "torch"  # or "hip": each stack's input embedding as one fused call
+        self.proj_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
 
     @property
     def device(self) -> torch.device:
@@ -160,7 +163,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return self._prefix_index_for_codebooks().check_valid_prefix(prefix, batch_size)
 
     def _push_attention_impl(self) -> None:
-        for name in ("attention_impl", "norm_impl", "ffn_impl"):
+        for name in ("attention_impl", "norm_impl", "ffn_impl", "proj_impl"):
             for stack in (self.encoder.encoder, self.t5_decoder):
                 setattr(stack, name, getattr(self, name))
 

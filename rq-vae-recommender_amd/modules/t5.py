@@ -19,9 +19,9 @@ block, [rows, heads, t, 64]) and accepts precomputed cross-attention K/V (`cross
 rows r = b * beams + beam all read user b's encoder output, as the beams of a beam search do.
 
 A stack forward chooses an attention body, a glue and a feed-forward body, then runs ONE loop over its blocks:
-self-attention, cross-attention (decoder), feed-forward, with a glue call between every two bodies.  Each of the three
+self-attention, cross-attention (decoder), feed-forward, with a glue call between every two bodies.  Each of the four
 attributes below is "torch" (the default: the operators above) or names a fused form.  That form is taken for fp32
-device tensors and a shape its kernel supports, under every setting of the other two attributes; otherwise the
+device tensors and a shape its kernel supports, under every setting of the other attributes; otherwise the
 operators run, silently.  The module tree and the state dict are the same on every path.
 
 - `attention_impl` = "hip": every attention call is ONE launch of ops.t5_attention (csrc/t5_attention.hip), fed the
@@ -41,6 +41,14 @@ operators run, silently.  The module tree and the state dict are the same on eve
 - `ffn_impl` = "hip": every feed-forward body is ONE autograd.T5FFNFunction call under grad (csrc/t5_ffn.hip: one
   launch forward, at most two backward, the ReLU output the only [rows, d_ff] tensor kept) or one ops.t5_ffn_fwd
   without that tensor under no_grad, in eval and train mode; in train mode its inner dropout happens in the kernel.
+- `proj_impl` = "hip": the bias-free q / k / v / o Linears around every attention are grouped calls of
+  csrc/t5_proj.hip (one launch forward, at most two backward): a self-attention is ONE call for q, k and v and one for
+  o, a cross-attention one for q and one for o, and `T5Stack.cross_kv` ONE call for the K/V of all blocks (eight
+  weights per call: one call up to four blocks).  Under grad a call is an autograd.T5ProjFunction, whose backward adds
+  the gradients of the shared input inside the kernel; under no_grad it is ops.t5_proj_fwd, and on the decode-cache
+  path that call writes k and v straight into this position of the slabs.  It goes with the operator attention and
+  with the fused one alike, and also needs the stack's attention weights to be fp32 device tensors that are dense and
+  16-byte aligned (`hip_proj_active`).
 
 The fused forms take their dropout seeds as int64s drawn on the device with torch.randint (the default generator:
 torch.manual_seed reproduces a run), none in eval mode or at dropout_rate 0.  The fused attention draws one per call.
@@ -56,12 +64,13 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops
-from rqhip.autograd import T5AddNormFunction, T5AttentionFunction, T5FFNFunction
+from rqhip.autograd import T5AddNormFunction, T5AttentionFunction, T5FFNFunction, T5ProjFunction
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
 NORM_IMPLS = ("torch", "hip")
 FFN_IMPLS = ("torch", "hip")
+PROJ_IMPLS = ("torch", "hip")
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -164,6 +173,17 @@ class _Seeds:
         return self.glue(self.n_glue + i) if self.n_glue else _draw_seed(self.p, self.device)
 
 
+def _project(fused: bool, x: Tensor, linears, outs=None) -> Tuple[Tensor, ...]:
+    """The bias-free Linears `linears` of the same x -> their outputs: the operators one by one, or `fused` ONE call
+    for the group (T5ProjFunction under grad, ops.t5_proj_fwd under no_grad, which writes into `outs` where given)."""
+    if not fused:
+        return tuple(lin(x) for lin in linears)
+    weights = [lin.weight for lin in linears]
+    if torch.is_grad_enabled():
+        return T5ProjFunction.apply(x, *weights)
+    return ops.t5_proj_fwd(x, weights, outs)
+
+
 def _attend(module: nn.Module, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], mask: Optional[Tensor]) -> Tensor:
     scores = torch.matmul(q, k.transpose(-1, -2))
     if bias is not None:
@@ -224,31 +244,32 @@ class T5Attention(nn.Module):
     def _heads(self, x: Tensor) -> Tensor:  # [R, T, inner] -> [R, heads, T, d_kv]
         return x.view(x.shape[0], x.shape[1], self.n_heads, self.d_kv).transpose(1, 2)
 
-    def project_kv(self, x: Tensor) -> KV:
-        return self._heads(self.k(x)), self._heads(self.v(x))
+    def project_kv(self, x: Tensor, fused: bool = False) -> KV:
+        k, v = _project(fused, x, (self.k, self.v))
+        return self._heads(k), self._heads(v)
 
-    def self_attention(self, x: Tensor, bias: Optional[Tensor], mask: Optional[Tensor],
-                       past: Optional[KV]) -> Tuple[Tensor, KV]:
-        q = self._heads(self.q(x))
-        k, v = self.project_kv(x)
+    def self_attention(self, x: Tensor, bias: Optional[Tensor], mask: Optional[Tensor], past: Optional[KV],
+                       fused: bool = False) -> Tuple[Tensor, KV]:
+        """fused: the projections as grouped calls (`_project`): one for q, k and v, one for o."""
+        q, k, v = (self._heads(t) for t in _project(fused, x, (self.q, self.k, self.v)))
         if past is not None:
             k, v = torch.cat([past[0], k], dim=2), torch.cat([past[1], v], dim=2)
         out = _attend(self, q, k, v, bias, mask)
-        return self.o(out.transpose(1, 2).reshape(x.shape[0], x.shape[1], -1)), (k, v)
+        return _project(fused, out.transpose(1, 2).reshape(x.shape[0], x.shape[1], -1), (self.o,))[0], (k, v)
 
-    def cross_attention(self, x: Tensor, kv: KV, mask: Optional[Tensor]) -> Tensor:
+    def cross_attention(self, x: Tensor, kv: KV, mask: Optional[Tensor], fused: bool = False) -> Tensor:
         """Queries x [R, T, d] with R = B * beams over keys / values [B, heads, S, d_kv] of B rows."""
         R, T = x.shape[0], x.shape[1]
         B = kv[0].shape[0]
         beams = R // B
-        q = self._heads(self.q(x))  # [R, H, T, dk]
+        q = self._heads(_project(fused, x, (self.q,))[0])  # [R, H, T, dk]
         if beams != 1:
             q = q.view(B, beams, self.n_heads, T, self.d_kv).transpose(1, 2).reshape(B, self.n_heads, beams * T,
                                                                                       self.d_kv)
         out = _attend(self, q, kv[0], kv[1], None, mask)
         if beams != 1:
             out = out.view(B, self.n_heads, beams, T, self.d_kv).transpose(1, 2).reshape(R, self.n_heads, T, self.d_kv)
-        return self.o(out.transpose(1, 2).reshape(R, T, -1))
+        return _project(fused, out.transpose(1, 2).reshape(R, T, -1), (self.o,))[0]
 
 
 class _OperatorAttention:
@@ -267,27 +288,29 @@ class _OperatorAttention:
         self.mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
         self.bias = stack.block[0].layer[0].SelfAttention.compute_bias(T, keys, past)
         self.past_key_values = past_key_values
+        self.proj = stack.hip_proj_active(inputs_embeds)
         if stack.is_decoder:
             self.cross_kv = stack.cross_kv(encoder_hidden_states) if cross_kv is None else cross_kv
             self.cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
 
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
         return module.self_attention(normed, self.bias, self.mask,
-                                     None if self.past_key_values is None else self.past_key_values[i])
+                                     None if self.past_key_values is None else self.past_key_values[i], self.proj)
 
     def cross_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tensor:
-        return module.cross_attention(normed, self.cross_kv[i], self.cross_mask)
+        return module.cross_attention(normed, self.cross_kv[i], self.cross_mask, self.proj)
 
 
 class _HipAttention:
     """The attention bodies of a stack forward on the "hip" path: the bias table and the byte masks are built once,
     every attention is one launch (`train`: one T5AttentionFunction call, with the attention-weight dropout of train
-    mode in the kernel, from a seed drawn per call)."""
+    mode in the kernel, from a seed drawn per call).  `proj`: the projections around it as grouped calls (`_project`)."""
 
     def __init__(self, stack: "T5Stack", T: int, attention_mask: Optional[Tensor],
                  encoder_attention_mask: Optional[Tensor], cross_kv: Optional[List[KV]],
-                 cache: Optional[T5DecodeCache], train: bool) -> None:
+                 cache: Optional[T5DecodeCache], train: bool, proj: bool) -> None:
         self.train = train
+        self.proj = proj
         self.p = float(stack.config.dropout_rate) if train and stack.training else 0.0
         self.cache = cache
         self.past = 0 if cache is None else cache.pos
@@ -307,25 +330,29 @@ class _HipAttention:
 
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
         """One launch; with a decode cache the K/V projections go straight into block i's slabs."""
-        q = module.q(normed)
         if self.cache is None:
-            k, v = module.k(normed), module.v(normed)
+            q, k, v = _project(self.proj, normed, (module.q, module.k, module.v))
             out = self._launch(module, q, k, v, self.table, self.offset, self.key_mask, self.causal)
-            return module.o(out), (module._heads(k), module._heads(v))
+            return _project(self.proj, out, (module.o,))[0], (module._heads(k), module._heads(v))
         R = normed.shape[0]
         ks, vs = self.cache.slabs[i]
-        x2 = normed.reshape(R, -1)
-        torch.mm(x2, module.k.weight.t(), out=ks[self.past, :R])
-        torch.mm(x2, module.v.weight.t(), out=vs[self.past, :R])
+        if self.proj:  # q into a new tensor, k and v into this position of the slabs: one launch
+            q = _project(True, normed, (module.q, module.k, module.v), [None, ks[self.past, :R], vs[self.past, :R]])[0]
+        else:
+            q = module.q(normed)
+            x2 = normed.reshape(R, -1)
+            torch.mm(x2, module.k.weight.t(), out=ks[self.past, :R])
+            torch.mm(x2, module.v.weight.t(), out=vs[self.past, :R])
         out = ops.t5_attention(q, ks, vs, module.n_heads, bias_by_delta=self.table, bias_offset=self.offset,
                                past=self.past, anc=self.cache.anc[:R])
-        return module.o(out), (ks, vs)
+        return _project(self.proj, out, (module.o,))[0], (ks, vs)
 
     def cross_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tensor:
         """One launch: the beams of a user are the query rows of one K/V group."""
         # a view of the Linear's output
         k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in self.cross_kv[i])
-        return module.o(self._launch(module, module.q(normed), k, v, None, 0, self.cross_mask, False))
+        q = _project(self.proj, normed, (module.q,))[0]
+        return _project(self.proj, self._launch(module, q, k, v, None, 0, self.cross_mask, False), (module.o,))[0]
 
 
 class T5LayerSelfAttention(nn.Module):
@@ -396,11 +423,20 @@ class T5Stack(nn.Module):
         self.attention_impl = "torch"  # or "hip" / "hip_train": see the module docstring
         self.norm_impl = "torch"  # or "hip": see the module docstring
         self.ffn_impl = "torch"  # or "hip": see the module docstring
+        self.proj_impl = "torch"  # or "hip": see the module docstring
         init_t5_weights(self, config)
 
     def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
-        """Cross-attention K/V of every block, computed once per encoder output."""
-        return [blk.layer[1].EncDecAttention.project_kv(encoder_hidden_states) for blk in self.block]
+        """Cross-attention K/V of every block, computed once per encoder output (proj_impl = "hip": by one grouped
+        call for all blocks, one per four blocks beyond that)."""
+        fused = self.hip_proj_active(encoder_hidden_states)
+        atts = [blk.layer[1].EncDecAttention for blk in self.block]
+        if not fused:
+            return [att.project_kv(encoder_hidden_states) for att in atts]
+        linears = [lin for att in atts for lin in (att.k, att.v)]
+        outs = [y for s in range(0, len(linears), ops.T5_PROJ_MAX_GROUP)
+                for y in _project(True, encoder_hidden_states, linears[s:s + ops.T5_PROJ_MAX_GROUP])]
+        return [(att._heads(outs[2 * i]), att._heads(outs[2 * i + 1])) for i, att in enumerate(atts)]
 
     def hip_attention_active(self, x: Tensor, query_length: int, key_length: int,
                              cross_length: Optional[int] = None) -> bool:
@@ -442,6 +478,23 @@ class T5Stack(nn.Module):
         return (self.ffn_impl == "hip" and x.is_cuda
                 and ops.t5_ffn_supported(x.dtype, self.config.d_model, self.config.d_ff))
 
+    def hip_proj_active(self, x: Tensor) -> bool:
+        """Whether the attention projections of a forward of x are grouped "hip" calls (module docstring)."""
+        if self.proj_impl not in PROJ_IMPLS:
+            raise ValueError(f"proj_impl must be one of {PROJ_IMPLS}, got {self.proj_impl!r}")
+        if self.proj_impl != "hip" or not x.is_cuda:
+            return False
+        cfg = self.config
+        inner = cfg.num_heads * cfg.d_kv
+        if not (ops.t5_proj_supported(x.dtype, cfg.d_model, inner, 3)
+                and ops.t5_proj_supported(x.dtype, inner, cfg.d_model)):
+            return False
+        weights = (lin.weight for blk in self.block for layer in list(blk.layer)[:-1]
+                   for att in layer.children() if isinstance(att, T5Attention)
+                   for lin in (att.q, att.k, att.v, att.o))
+        return all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.data_ptr() % 16 == 0
+                   for w in weights)
+
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
@@ -454,7 +507,8 @@ class T5Stack(nn.Module):
                 cross_kv = self.cross_kv(encoder_hidden_states)
             past = 0 if decode_cache is None else decode_cache.pos
             if decode_cache is None and self.hip_train_active(inputs_embeds, T, cross_kv):
-                return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, None, train=True)
+                return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, None, train=True,
+                                     proj=self.hip_proj_active(inputs_embeds))
             cross_length = cross_kv[0][0].shape[2] if self.is_decoder else None
             if self.hip_attention_active(inputs_embeds, T, past + T, cross_length):
                 if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
@@ -462,7 +516,7 @@ class T5Stack(nn.Module):
                     raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
                                      "past_key_values or attention_mask")
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, decode_cache,
-                                     train=False)
+                                     train=False, proj=self.hip_proj_active(inputs_embeds))
             if decode_cache is not None:
                 raise ValueError('decode_cache belongs to the "hip" attention path, which is not active here')
         return _OperatorAttention(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,

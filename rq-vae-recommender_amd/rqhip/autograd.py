@@ -348,6 +348,30 @@ class T5FFNFunction(torch.autograd.Function):
         return d_x, d_wi, d_wo, None, None
 
 
+class T5ProjFunction(torch.autograd.Function):
+    """A group of bias-free linear maps of the same rows (modules/t5.py, proj_impl = "hip") as one launch forward and at
+    most two backward (ops.t5_proj_fwd / ops.t5_proj_bwd): apply(x, *weights) -> (y[0], ..., y[n - 1]), y[j] = x @
+    weights[j].T.  Saved: x and the weights.  An output nobody used arrives without a gradient and is left out of the
+    backward.  Gradients: x and each weight, each only when needed."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, *weights: Tensor):
+        outs = ops.t5_proj_fwd(x, weights)
+        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None (= NULL at the C ABI)
+        ctx.save_for_backward(x, *weights)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *d_ys: Optional[Tensor]):
+        x, *weights = ctx.saved_tensors
+        n = len(weights)
+        if all(g is None for g in d_ys) or not any(ctx.needs_input_grad):
+            return (None,) * (1 + n)
+        d_x, d_w = ops.t5_proj_bwd(x, weights, [_dense(g) for g in d_ys], need_x=ctx.needs_input_grad[0],
+                                   need_w=ctx.needs_input_grad[1:])
+        return (d_x, *d_w)
+
+
 class SidHeadLossFunction(torch.autograd.Function):
     """The retrieval model's L semantic-id heads and their cross-entropy losses (modules/model.py, head_impl = "hip") as
     one call forward and one backward (ops.sid_head_loss_fwd / ops.sid_head_loss_bwd): apply(x, target, *weights) ->

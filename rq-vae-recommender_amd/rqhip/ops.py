@@ -873,6 +873,95 @@ def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: flo
     return d_x, d_wi, d_wo
 
 
+T5_PROJ_MAX_GROUP = 8   # weights per t5_proj_fwd / t5_proj_bwd call
+
+
+def t5_proj_supported(dtype: torch.dtype, d_in: int, d_out: int, n: int = 1) -> bool:
+    """Whether t5_proj_fwd / t5_proj_bwd implement a group of n [d_out, d_in] weights (rqhip_t5_proj_supported): fp32,
+    d_in and d_out multiples of 32 in 32 .. 512, 1 <= n <= 8."""
+    return dtype == torch.float32 and bool(_lib.lib().rqhip_t5_proj_supported(int(d_in), int(d_out), int(n)))
+
+
+def _proj_call(who: str, x: Tensor, weights):
+    """The checks and copies t5_proj_fwd and t5_proj_bwd share -> (x as dense aligned rows, the weights as the kernels
+    read them, their HOST pointer array, N, d_in, d_out)."""
+    weights = list(weights)
+    _need_gpu(x, *weights)
+    x = _norm_rows(x, "x", who)
+    d_in, n = x.shape[-1], len(weights)
+    d_out = weights[0].shape[0] if n and weights[0].dim() == 2 else -1
+    for j, w in enumerate(weights):
+        if w.dtype != torch.float32 or tuple(w.shape) != (d_out, d_in):
+            raise RqHipError(f"{who}: weights[{j}] must be float32 [d_out, {d_in}] like weights[0], got {w.dtype} "
+                             f"{tuple(w.shape)}")
+    if not t5_proj_supported(x.dtype, d_in, d_out, n):
+        raise RqHipError(f"{who}: (d_in, d_out, n) = ({d_in}, {d_out}, {n}) is not supported (multiples of 32 up to 512, "
+                         f"1 <= n <= 8)")
+    weights = [_aligned16(w.contiguous()) for w in weights]
+    w_ptrs = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
+    return x, weights, w_ptrs, (x.numel() // d_in), d_in, d_out
+
+
+def t5_proj_fwd(x: Tensor, weights, outs=None):
+    """n bias-free linear maps of the same rows in one launch (rqhip_t5_proj_fwd) -> (y[0], ..., y[n - 1]), y[j] = x @
+    weights[j].T.  x [..., d_in] float32 with dense rows, weights: n separate [d_out, d_in] matrices, the nn.Linear
+    weights as stored.  y[j] has shape x.shape[:-1] + (d_out,).  outs (optional): a list of n entries, each None (that
+    output is allocated) or a preallocated float32 [N, d_out] view over the N = x.numel() / d_in rows whose last
+    dimension is dense and whose row stride is at least d_out, a position of a decode-cache slab for one; the kernel
+    writes into it and it is returned as it is."""
+    who = "t5_proj_fwd"
+    x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights)
+    n = len(weights)
+    outs = [None] * n if outs is None else list(outs)
+    if len(outs) != n:
+        raise RqHipError(f"{who}: {len(outs)} outs for {n} weights")
+    dev = x.device
+    with torch.cuda.device(dev):
+        for j, o in enumerate(outs):
+            if o is None:
+                outs[j] = torch.empty(x.shape[:-1] + (d_out,), dtype=torch.float32, device=dev)
+            elif (o.dtype != torch.float32 or o.device != dev or tuple(o.shape) != (N, d_out)
+                  or (N > 0 and o.stride(1) != 1) or (N > 1 and o.stride(0) < d_out)):
+                raise RqHipError(f"{who}: outs[{j}] must be a float32 [{N}, {d_out}] view on {dev} with dense rows at "
+                                 f"least {d_out} apart, got {o.dtype} {tuple(o.shape)} strides {tuple(o.stride())}")
+        y_ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        ld_y = (C.c_int64 * n)(*[int(o.stride(0)) if o.dim() == 2 and N > 1 else d_out for o in outs])
+        rc = _lib.lib().rqhip_t5_proj_fwd(_ptr(x), d_in, w_ptrs, y_ptrs, ld_y, n, N, d_in, d_out, _stream())
+        check(rc, "rqhip_t5_proj_fwd")
+    return tuple(outs)
+
+
+def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None):
+    """The gradients of t5_proj_fwd in one call of at most two launches (rqhip_t5_proj_bwd) -> (d_x, [d_w[0], ...]).
+    d_ys: n upstream gradients, each of y[j]'s shape or None; a None contributes nothing to d_x and gets no d_w[j].  d_x
+    (x's shape) is None without need_x or when every d_ys[j] is None; d_w[j] is None where need_w[j] (default: every
+    weight) is false.  No atomics: the same bits on every run."""
+    who = "t5_proj_bwd"
+    shape = x.shape
+    x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights)
+    n = len(weights)
+    d_ys = list(d_ys)
+    need_w = [True] * n if need_w is None else [bool(f) for f in need_w]
+    if len(d_ys) != n or len(need_w) != n:
+        raise RqHipError(f"{who}: {len(d_ys)} d_ys and {len(need_w)} need_w for {n} weights")
+    _need_gpu(*d_ys)
+    d_ys = [_norm_rows(g, f"d_ys[{j}]", who, tuple(shape[:-1]) + (d_out,)) for j, g in enumerate(d_ys)]
+    live = any(g is not None for g in d_ys)
+    dev = x.device
+    with torch.cuda.device(dev):
+        d_x = torch.empty_like(x) if need_x and live else None
+        make = torch.zeros if N == 0 else torch.empty      # without rows the sums are empty
+        d_w = [make((d_out, d_in), dtype=torch.float32, device=dev) if f and g is not None else None
+               for f, g in zip(need_w, d_ys)]
+        g_ptrs = (C.c_void_p * n)(*[_ptr(g) for g in d_ys])
+        ld_dy = (C.c_int64 * n)(*([d_out] * n))
+        dw_ptrs = (C.c_void_p * n)(*[_ptr(g) for g in d_w])
+        rc = _lib.lib().rqhip_t5_proj_bwd(_ptr(x), d_in, w_ptrs, g_ptrs, ld_dy, n, N, d_in, d_out, _ptr(d_x), dw_ptrs,
+                                          _stream())
+        check(rc, "rqhip_t5_proj_bwd")
+    return d_x, d_w
+
+
 def sid_head_loss_supported(dtype: torch.dtype, d: int, K: int, L: int) -> bool:
     """Whether sid_head_loss_fwd / sid_head_loss_bwd implement this shape (rqhip_sid_head_loss_supported): fp32, d a
     multiple of 4 in 4 .. 1024, K in 1 .. 1024 codes, L in 1 .. 8 levels."""

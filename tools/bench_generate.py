@@ -9,14 +9,16 @@ K = 256, L = 3, k = 10, batch 640, 20-item histories, a 12 101-item corpus), two
 
 and, for the kernel path, with either attention implementation (--attention): "torch", the T5 operators, or "hip",
 one ops.t5_attention launch per attention call and slab K/V (modules/t5.py).  `--attention both` alternates the two
-arms --runs times in one process and ends with one summary line of the medians over the runs.
+arms --runs times in one process and ends with one summary line of the medians over the runs.  --proj sets proj_impl
+(modules/t5.py) for every arm: "hip" makes the attention projections grouped ops.t5_proj_fwd launches, the decode
+step's K/V written by them straight into the cache slabs.
 
 Device events around each generate after a warm-up; prints one JSON line per path (ms per generate, users/s).
 Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --stats` run of this tool
 (--path one of them, one --attention arm, --iters small).
 
     python tools/bench_generate.py [--path kernel|reference|both] [--attention torch|hip|both] [--runs 5]
-                                   [--warmup 3] [--iters 10]
+                                   [--proj torch|hip] [--warmup 3] [--iters 10]
 """
 import argparse
 import json
@@ -102,6 +104,7 @@ def main():
     ap.add_argument("--path", choices=["kernel", "reference", "both"], default=None,
                     help="default: both, or kernel with --attention both")
     ap.add_argument("--attention", choices=["torch", "hip", "both"], default="torch")
+    ap.add_argument("--proj", choices=["torch", "hip"], default="torch", help="proj_impl of every arm")
     ap.add_argument("--runs", type=int, default=5, help="alternations of the two arms with --attention both")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
@@ -110,6 +113,7 @@ def main():
         args.path = "kernel" if args.attention == "both" else "both"
     dev = torch.device("cuda")
     model, batch = build(dev)
+    model.proj_impl = args.proj
     B = batch.sem_ids.shape[0]
     paths = ["kernel", "reference"] if args.path == "both" else [args.path]
     if args.attention == "both":
@@ -121,7 +125,7 @@ def main():
                 model.attention_impl = arm
                 med, best = time_path(model, batch, args.warmup, args.iters)
                 medians[arm].append(med)
-                print(json.dumps({"path": "kernel", "attention": arm, "run": run, "batch": B,
+                print(json.dumps({"path": "kernel", "attention": arm, "proj": args.proj, "run": run, "batch": B,
                                   "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),
                                   "iters": args.iters}), flush=True)
         mid = {arm: sorted(v)[len(v) // 2] for arm, v in medians.items()}
@@ -139,7 +143,7 @@ def main():
         finally:
             if path == "reference":
                 mm.ops.beam_step, mm._exponential_like = saved, saved_q
-        print(json.dumps({"path": path, "attention": args.attention, "batch": B,
+        print(json.dumps({"path": path, "attention": args.attention, "proj": args.proj, "batch": B,
                           "k": model.top_k_for_generation, "L": model.num_hierarchies,
                           "K": model.num_embeddings_per_hierarchy, "corpus": int(model.codebooks.shape[0]),
                           "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),

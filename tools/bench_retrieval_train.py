@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) in seven arms:
+tails: encoder T = 81, decoder T = 4) in eight arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
@@ -16,6 +16,8 @@ tails: encoder T = 81, decoder T = 4) in seven arms:
              one update launch per 24 tensors) instead of torch.optim.AdamW; no clipping and no schedule, as in the other arms
   hip_train+norm+head+ffn+optim+embed  the arm before it with embed_impl = "hip": each stack's input embedding (offsets,
              mask product, gather, separator, BOS row) as one ops.sid_embed_fwd launch and one ops.sid_embed_bwd launch
+  hip_train+norm+head+ffn+optim+embed+proj  the arm before it with proj_impl = "hip": the q / k / v, the o and the
+             cross-attention K/V projections as grouped ops.t5_proj_fwd launches and ops.t5_proj_bwd calls of two launches
 
 The arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
@@ -23,8 +25,9 @@ median and the fastest step per arm over all blocks, the median of each block (t
 between two arms has to exceed), and the peak torch.cuda.max_memory_allocated of a block, as one
 JSON line per arm plus a summary line; --out also writes them to a text file (profiles/retrieval_train_step_norm.txt
 holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run, profiles/retrieval_train_step_ffn.txt a
-five-arm run, profiles/retrieval_optim_tail.txt a six-arm run, profiles/retrieval_train_step_embed.txt a run of the last
-two arms; profiles/retrieval_train_step.txt is the older two-arm run; none of them is to be overwritten or compared
+five-arm run, profiles/retrieval_optim_tail.txt a six-arm run, profiles/retrieval_train_step_embed.txt a run of the sixth
+and seventh arm, profiles/retrieval_train_step_proj.txt runs of the last two; profiles/retrieval_train_step.txt is the
+older two-arm run; none of them is to be overwritten or compared
 against: two arms are compared within one run only).
 --arms picks a subset, e.g. one arm under a kernel trace to count its launches per step.
 
@@ -45,15 +48,20 @@ import torch  # noqa: E402
 from modules.model import EncoderDecoderRetrievalModel  # noqa: E402
 from retrieval_cases import synthetic_batch, to_device  # noqa: E402  (tests/retrieval_cases.py)
 
-# arm -> (attention_impl, norm_impl, head_impl, ffn_impl)
-ARMS = {"torch": ("torch", "torch", "torch", "torch"), "hip_train": ("hip_train", "torch", "torch", "torch"),
-        "hip_train+norm": ("hip_train", "hip", "torch", "torch"), "hip_train+norm+head": ("hip_train", "hip", "hip", "torch"),
-        "hip_train+norm+head+ffn": ("hip_train", "hip", "hip", "hip"),
-        "hip_train+norm+head+ffn+optim": ("hip_train", "hip", "hip", "hip"),
-        "hip_train+norm+head+ffn+optim+embed": ("hip_train", "hip", "hip", "hip")}
+# arm -> (attention_impl, norm_impl, head_impl, ffn_impl, proj_impl)
+ARMS = {"torch": ("torch", "torch", "torch", "torch", "torch"),
+        "hip_train": ("hip_train", "torch", "torch", "torch", "torch"),
+        "hip_train+norm": ("hip_train", "hip", "torch", "torch", "torch"),
+        "hip_train+norm+head": ("hip_train", "hip", "hip", "torch", "torch"),
+        "hip_train+norm+head+ffn": ("hip_train", "hip", "hip", "hip", "torch"),
+        "hip_train+norm+head+ffn+optim": ("hip_train", "hip", "hip", "hip", "torch"),
+        "hip_train+norm+head+ffn+optim+embed": ("hip_train", "hip", "hip", "hip", "torch"),
+        "hip_train+norm+head+ffn+optim+embed+proj": ("hip_train", "hip", "hip", "hip", "hip")}
 # arms stepped by rqhip.optim.FlatAdamW; the others by torch.optim.AdamW
-FLAT_ADAMW = ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed")
-EMBED_HIP = ("hip_train+norm+head+ffn+optim+embed",)  # arms with embed_impl = "hip"; the others "torch"
+FLAT_ADAMW = ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed",
+              "hip_train+norm+head+ffn+optim+embed+proj")
+# arms with embed_impl = "hip"; the others "torch"
+EMBED_HIP = ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+proj")
 
 
 def make_batch(B, items, L, K, N, dev, seed):
@@ -65,7 +73,7 @@ def make_batch(B, items, L, K, N, dev, seed):
 def block(model, state, batch, arm, warmup, iters):
     """One block of one arm from the common starting weights -> (ms per step, peak bytes, last loss)."""
     model.load_state_dict(state)
-    model.attention_impl, model.norm_impl, model.head_impl, model.ffn_impl = ARMS[arm]
+    model.attention_impl, model.norm_impl, model.head_impl, model.ffn_impl, model.proj_impl = ARMS[arm]
     model.embed_impl = "hip" if arm in EMBED_HIP else "torch"
     model.train()
     if arm in FLAT_ADAMW:
@@ -122,7 +130,7 @@ def main():
     lines = []
     for arm in arms:
         lines.append(json.dumps({"arm": arm, "attention_impl": ARMS[arm][0], "norm_impl": ARMS[arm][1],
-                                 "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3],
+                                 "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3], "proj_impl": ARMS[arm][4],
                                  **({"embed_impl": "hip"} if arm in EMBED_HIP else {}),
                                  "optimizer": "FlatAdamW" if arm in FLAT_ADAMW else "torch.optim.AdamW", "batch": args.batch,
                                  "steps_timed": len(times[arm]),
@@ -134,7 +142,8 @@ def main():
     for a, b in (("torch", "hip_train"), ("hip_train", "hip_train+norm"), ("hip_train+norm", "hip_train+norm+head"),
                  ("hip_train+norm+head", "hip_train+norm+head+ffn"),
                  ("hip_train+norm+head+ffn", "hip_train+norm+head+ffn+optim"),
-                 ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed")):
+                 ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed"),
+                 ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+proj")):
         if a in arms and b in arms:
             summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
             summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)
