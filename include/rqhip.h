@@ -450,6 +450,35 @@ int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo, const flo
                      int F, double p, const int64_t *seed, float *d_x, float *d_wi, float *d_wo, void *workspace,
                      rqhip_stream_t stream);
 
+/* The "bf16" arithmetic of the same two calls (modules/t5.py, matmul_arith = "bf16"): the parameter lists, limits,
+ * argument checks, workspace size, launch counts and graph capturability of their fp32 twins above.  Storage stays fp32
+ * everywhere: x, y, h, g, the weights and every gradient; no tensor changes shape, stride or owner.
+ * Arithmetic contract ("bf16").
+ *   - Every operand of a matrix instruction is the round-to-nearest-even bf16 rounding (v_cvt_pk_bf16_f32) of the fp32
+ *     value the fp32 arm feeds at that place: x, wi, wo and d_y; the values of the LDS chunk, hd = keep ? h * s : 0
+ *     forward and g backward, each computed in fp32 first; in the weight-gradient kernel g, x, d_y and the recomputed
+ *     hd.  The values are rounded as the fragments are packed (where a value is rounded does not change it).
+ *   - Products are exact and accumulate in fp32 inside v_mfma_f32_16x16x32_bf16.
+ *   - The chain structure is the fp32 arm's: one GROUP of 32 terms is one instruction (the order inside it is the
+ *     instruction's), 4 groups are one chain from +0, and a reduction's chains are added in ascending order from +0.
+ *     Weight gradients: blocks of 32 rows (one instruction each; the lane's rows 4 ks + kq are elements j = ks of both
+ *     fragments, a consistent permutation of the block), a fresh chain every 8 blocks, wave ranges [w nb / 4, (w + 1)
+ *     nb / 4) and ((s_0 + s_1) + s_2) + s_3.
+ *   - Orders depend on the sizes alone and there are no atomics: the same bits on every run and device, and a row's h,
+ *     y, g and d_x depend neither on N nor on the row's position.  (The backward at d > 384 keeps 16-row tiles above
+ *     N = 16384 too; the tile height changes no bit.)
+ *   - h is stored unrounded, the fp32 ReLU of the fp32 accumulation; the backward's active set is h > 0 of that tensor.
+ *     h does not know about the dropout; p = 0 with and without a seed gives the same bits.  Rows past N read a valid
+ *     row and store nothing.
+ * Error against exact arithmetic on the rounded operands: at most (K + 8) 2^-23 sum |a_k| |b_k| per element over a
+ * reduction of K terms (tests/test_gpu_t5_ffn_bf16.py; measured ratios in profiles/t5_bf16_error.txt).  The operand
+ * rounding itself is bf16's: 2^-9 relative per operand. */
+int rqhip_t5_ffn_fwd_bf16(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+                          const int64_t *seed, float *y, float *h, rqhip_stream_t stream);
+int rqhip_t5_ffn_bwd_bf16(const float *x, const float *wi, const float *wo, const float *h, const float *d_y, int64_t N,
+                          int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi, float *d_wo,
+                          void *workspace, rqhip_stream_t stream);
+
 /* A group of 1 <= n <= 8 bias-free linear maps that share their input rows, as one launch forward and at most two
  * backward (csrc/t5_proj.hip; modules/t5.py, proj_impl = "hip": the q / k / v, the o and the cross-attention K/V
  * projections).  N rows; all fp32.
@@ -491,6 +520,18 @@ int rqhip_t5_proj_fwd(const float *x, int64_t ld_x, const float *const *w, float
                       int64_t N, int d_in, int d_out, rqhip_stream_t stream);
 int rqhip_t5_proj_bwd(const float *x, int64_t ld_x, const float *const *w, const float *const *d_y, const int64_t *ld_dy,
                       int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w, rqhip_stream_t stream);
+
+/* The "bf16" arithmetic of the same two calls: everything of their fp32 twins above but the arithmetic, which is the
+ * "bf16" contract of rqhip_t5_ffn_*_bf16.  The operands x, w[j] and d_y[j] are rounded to bf16 (nearest even) as the
+ * fragments are packed, products are exact and accumulate in fp32 inside v_mfma_f32_16x16x32_bf16, one group of 32
+ * terms is one instruction, and groups, chains, the concatenation of the live (j, term) pairs in d_x and the row blocks
+ * of d_w[j] are the fp32 arm's.  So the independence statements hold bit for bit: a row's y[j] depends on neither N,
+ * the row's position, n nor the other weights; d_x with a d_y[j] NULL has the bits of the call on the remaining group. */
+int rqhip_t5_proj_fwd_bf16(const float *x, int64_t ld_x, const float *const *w, float *const *y, const int64_t *ld_y, int n,
+                           int64_t N, int d_in, int d_out, rqhip_stream_t stream);
+int rqhip_t5_proj_bwd_bf16(const float *x, int64_t ld_x, const float *const *w, const float *const *d_y,
+                           const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w,
+                           rqhip_stream_t stream);
 
 /* The retrieval model's input embedding in one launch forward and one backward (csrc/sid_embed.hip; modules/model.py,
  * embed_impl = "hip"): semantic ids -> a T5 stack's inputs_embeds, for the encoder and the decoder front alike.

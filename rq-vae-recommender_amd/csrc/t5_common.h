@@ -1,6 +1,6 @@
 // t5_common.h -- what the T5 kernel files share (t5_attention.hip, t5_add_norm.hip, t5_ffn.hip, sid_head_loss.hip,
-// sid_embed.hip): the dropout decision, its threshold and its two scales, the wave reductions and the entry points'
-// pointer checks.
+// sid_embed.hip, t5_proj.hip): the dropout decision, its threshold and its two scales, the wave reductions, the bf16
+// fragment helpers of the matrix kernels and the entry points' pointer checks.
 #pragma once
 
 #include <math.h>
@@ -60,6 +60,27 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, RQ_WAVE));
     return v;
+}
+
+// ---- the two arithmetics of the matrix kernels (t5_ffn.hip, t5_proj.hip; contracts in include/rqhip.h).  A lane holds
+// the 8 terms 8 kq .. 8 kq + 7 of a group of 32 reduction terms for its row (A) and its column (B).
+//   "fp32"  exact fp32: eight v_mfma_f32_16x16x4_f32, instruction e on term 8 kq + e of every k-slot kq (in the kernels)
+//   "bf16"  each operand rounded to bf16 (nearest even, v_cvt_pk_bf16_f32), then ONE v_mfma_f32_16x16x32_bf16, whose
+//           A / B fragment is exactly that holding: lane l supplies k = 8 (l >> 4) + j, j = 0 .. 7, of row / column
+//           l & 15.  Products of two bf16 values are exact in fp32; the accumulation is fp32.  The helpers below.
+// The C / D layout is the same for both: register r of lane (i, kq) is row 4 kq + r, column i.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ bf16x8 pack_bf16x8(const float (&v)[8]) {
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
+    return o;
+}
+
+// one group of 32 terms on already packed fragments
+__device__ __forceinline__ f32x4 mma_group_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 // ---- the entry points' pointer checks (a null pointer counts as aligned: the null check is a separate one)

@@ -33,6 +33,14 @@
 // ascending order (bounded chain length: the rounding error of a long row count grows with the number of chains,
 // not of rows); the four waves' sums meet in LDS and are added in wave order.  No partial blocks in memory, no
 // atomics, no reduction launch.  hd is recomputed from h and the seed as it is loaded.
+//
+// Second arithmetic, "bf16" (template parameter BF, entry points rqhip_t5_ffn_*_bf16; contract in include/rqhip.h): the
+// same kernels with one v_mfma_f32_16x16x32_bf16 per group in place of the eight fp32 instructions.  The lane's eight
+// terms 8 kq .. 8 kq + 7 of a group are that instruction's A / B fragment as they stand, so loads, LDS, chains and
+// epilogues do not change; the eight registers are rounded to bf16 (nearest even) and packed pairwise in front of the
+// instruction (csrc/t5_common.h).  In the weight-gradient kernel the lane's eight rows 4 ks + kq of a block become the
+// elements j = ks of both fragments, a consistent permutation of the block's 32 rows.  Memory and LDS stay fp32: the
+// rounding happens in registers, so h is stored unrounded and the chunk buffer holds fp32 hd / g.
 #include <math.h>
 
 #include "rqhip_common.h"
@@ -102,15 +110,27 @@ __device__ __forceinline__ void ffn_load_b(const float *at, size_t ld, float (&b
     }
 }
 
-template <int RT>
+// one group of 32 terms.  BF: the "bf16" arithmetic, one instruction per tile on the same eight registers, rounded and
+// packed pairwise (csrc/t5_common.h)
+template <int RT, bool BF>
 __device__ __forceinline__ void ffn_mma(const float (&a)[RT][8], const float (&b)[2][8], f32x4 (&acc)[RT][2]) {
+    if constexpr (BF) {
+        const bf16x8 b0 = pack_bf16x8(b[0]), b1 = pack_bf16x8(b[1]);
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
+        for (int rt = 0; rt < RT; ++rt) {
+            const bf16x8 ar = pack_bf16x8(a[rt]);
+            acc[rt][0] = mma_group_bf16(ar, b0, acc[rt][0]);
+            acc[rt][1] = mma_group_bf16(ar, b1, acc[rt][1]);
+        }
+    } else {
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
+        for (int e = 0; e < 8; ++e)
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-                acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], b[ct][e], acc[rt][ct], 0, 0, 0);
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], b[ct][e], acc[rt][ct], 0, 0, 0);
+    }
 }
 
 // a finished chain joins the sum of the chains before it; the next chain starts from +0
@@ -129,8 +149,9 @@ __device__ __forceinline__ void ffn_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][
 // keeps a round's loads together and in front of the previous round's matrix instructions (csrc/mlp_small.hip)
 #define FFN_FENCE __builtin_amdgcn_sched_barrier(0)
 
-// RT: 16-row tiles per workgroup; NP: column pairs (32 output columns) per wave, >= ceil(d / 128)
-template <int RT, int NP, bool BWD>
+// RT: 16-row tiles per workgroup; NP: column pairs (32 output columns) per wave, >= ceil(d / 128); BF: the "bf16"
+// arithmetic (memory, LDS and the epilogues stay fp32: the operands are rounded as the fragments are packed)
+template <int RT, int NP, bool BWD, bool BF>
 __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
     extern __shared__ __align__(16) float ffn_lds[];
     constexpr int T = 16 * RT;
@@ -184,7 +205,7 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
             if (g < ngd) {
                 float a[RT][8];
                 ffn_load_a<RT>(xs + i * ldx + 8 * kq, ldx, 32 * g, a);
-                ffn_mma<RT>(a, src[gg], run);
+                ffn_mma<RT, BF>(a, src[gg], run);
             }
         }
     };
@@ -204,7 +225,7 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
         ffn_load_a<RT>(hb + i * kFfnLdh + 8 * kq, kFfnLdh, 32 * g, a);
 #pragma unroll
         for (int q = 0; q < NP; ++q)
-            if (w + 4 * q < npairs) ffn_mma<RT>(a, src[q], run[q]);
+            if (w + 4 * q < npairs) ffn_mma<RT, BF>(a, src[q], run[q]);
     };
 
     if (32 * w < F) load1(pb[0], 32 * w, 0);
@@ -326,6 +347,8 @@ struct FfnWgrad {
     int tiles_wi;              // workgroups [0, tiles_wi) own d_wi's tiles, the rest d_wo's
 };
 
+// BF: the "bf16" arithmetic; the lane's eight rows 4 ks + kq of a block are the elements j = ks of both fragments
+template <bool BF>
 __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
     __shared__ float red[4 * 32 * 33];
     const int t = threadIdx.x, lane = t & 63, i = lane & 15, kq = lane >> 4;
@@ -370,13 +393,26 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
             }
             if (n >= p.N) pa[ks] = qb[ks] = f32x2{0.f, 0.f};
         }
+        if constexpr (BF) {
+            bf16x8 fa[2], fb[2];
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
+            for (int ks = 0; ks < 8; ++ks) {
+                fa[0][ks] = (__bf16)pa[ks].x; fa[1][ks] = (__bf16)pa[ks].y;
+                fb[0][ks] = (__bf16)qb[ks].x; fb[1][ks] = (__bf16)qb[ks].y;
+            }
 #pragma unroll
             for (int at = 0; at < 2; ++at)
 #pragma unroll
-                for (int bt = 0; bt < 2; ++bt)
-                    acc[at][bt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ks][at], qb[ks][bt], acc[at][bt], 0, 0, 0);
+                for (int bt = 0; bt < 2; ++bt) acc[at][bt] = mma_group_bf16(fa[at], fb[bt], acc[at][bt]);
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+                for (int at = 0; at < 2; ++at)
+#pragma unroll
+                    for (int bt = 0; bt < 2; ++bt)
+                        acc[at][bt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ks][at], qb[ks][bt], acc[at][bt], 0, 0, 0);
+        }
         if (((b - lo) & (kFfnWgFlush - 1)) == kFfnWgFlush - 1) {
 #pragma unroll
             for (int at = 0; at < 2; ++at)
@@ -441,32 +477,36 @@ int ffn_check(const char *who, int64_t N, int d, int F, double p) {
     return RQHIP_OK;
 }
 
-template <int RT, int NP, bool BWD>
+template <int RT, int NP, bool BWD, bool BF>
 int ffn_rows_launch(const FfnRows &p, hipStream_t s) {
     static LdsGrant grant;
     constexpr int T = 16 * RT;
     const int bytes = (T * (p.d + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
     // granted once per device: the most this instantiation can ask for (d <= 128 NP)
     constexpr int most = (T * (128 * NP + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
-    RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_ffn_rows_kernel<RT, NP, BWD>), most));
-    hipLaunchKernelGGL((t5_ffn_rows_kernel<RT, NP, BWD>), dim3((unsigned)((p.N + T - 1) / T)), dim3(256), (size_t)bytes, s, p);
+    RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_ffn_rows_kernel<RT, NP, BWD, BF>), most));
+    hipLaunchKernelGGL((t5_ffn_rows_kernel<RT, NP, BWD, BF>), dim3((unsigned)((p.N + T - 1) / T)), dim3(256), (size_t)bytes, s, p);
     RQ_CHECK_LAUNCH("t5_ffn_rows_kernel");
     return RQHIP_OK;
 }
 
-template <bool BWD>
+template <bool BWD, bool BF>
 int ffn_rows(const FfnRows &p, hipStream_t s) {
     const int np = (p.d / 32 + 3) / 4, rt = ffn_row_tiles(p.N);
-    if (rt == 1) {
-        if (np == 1) return ffn_rows_launch<1, 1, BWD>(p, s);
-        if (np == 2) return ffn_rows_launch<1, 2, BWD>(p, s);
-        if (np == 3) return ffn_rows_launch<1, 3, BWD>(p, s);
-        return ffn_rows_launch<1, 4, BWD>(p, s);
+    // The "bf16" backward at d > 384 keeps 16-row tiles at every N: its 32-row instantiation would spill to scratch
+    // (so does the fp32 one, 44 bytes per lane, which stays as it is).  The tile height changes no bit.
+    constexpr bool kShortOnly = BF && BWD;
+    if (rt == 1 || (kShortOnly && np == 4)) {
+        if (np == 1) return ffn_rows_launch<1, 1, BWD, BF>(p, s);
+        if (np == 2) return ffn_rows_launch<1, 2, BWD, BF>(p, s);
+        if (np == 3) return ffn_rows_launch<1, 3, BWD, BF>(p, s);
+        return ffn_rows_launch<1, 4, BWD, BF>(p, s);
     }
-    if (np == 1) return ffn_rows_launch<2, 1, BWD>(p, s);
-    if (np == 2) return ffn_rows_launch<2, 2, BWD>(p, s);
-    if (np == 3) return ffn_rows_launch<2, 3, BWD>(p, s);
-    return ffn_rows_launch<2, 4, BWD>(p, s);
+    if (np == 1) return ffn_rows_launch<2, 1, BWD, BF>(p, s);
+    if (np == 2) return ffn_rows_launch<2, 2, BWD, BF>(p, s);
+    if (np == 3) return ffn_rows_launch<2, 3, BWD, BF>(p, s);
+    if constexpr (!kShortOnly) return ffn_rows_launch<2, 4, BWD, BF>(p, s);
+    return RQHIP_EUNSUPPORTED;      // not reached: np == 4 left above
 }
 
 }  // namespace
@@ -482,53 +522,58 @@ extern "C" size_t rqhip_t5_ffn_bwd_workspace_bytes(int64_t N, int d, int F) {
     return (size_t)N * (size_t)F * sizeof(float);
 }
 
-extern "C" int rqhip_t5_ffn_fwd(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
-                                const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
-    const int rc = ffn_check("t5_ffn_fwd", N, d, F, p);
+namespace {
+
+// the entry points of both arithmetics; `who` names the one called in the messages
+template <bool BF>
+int ffn_fwd(const char *who, const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+            const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
+    const int rc = ffn_check(who, N, d, F, p);
     if (rc != RQHIP_OK) return rc;
     if (N == 0) return RQHIP_OK;
     const unsigned th = dropout_threshold(p);
     if (any_null(x, wi, wo, y)) {
-        set_error("t5_ffn_fwd: null pointer (x, wi, wo, y)");
+        set_error("%s: null pointer (x, wi, wo, y)", who);
         return RQHIP_EARG;
     }
     if (th && !seed) {
-        set_error("t5_ffn_fwd: dropout (p=%g) needs the seed, a one-element int64 device pointer", p);
+        set_error("%s: dropout (p=%g) needs the seed, a one-element int64 device pointer", who, p);
         return RQHIP_EARG;
     }
     if (!all_aligned16(x, wi, wo, y, h)) {
-        set_error("t5_ffn_fwd: x, wi, wo, y and h must be 16-byte aligned");
+        set_error("%s: x, wi, wo, y and h must be 16-byte aligned", who);
         return RQHIP_EARG;
     }
     FfnRows a;
     a.x = x, a.w1 = wi, a.w2 = wo, a.h_in = nullptr, a.mid = h, a.out = y;
     a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
     a.N = N, a.d = d, a.F = F;
-    return ffn_rows<false>(a, reinterpret_cast<hipStream_t>(stream));
+    return ffn_rows<false, BF>(a, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo, const float *h, const float *d_y,
-                                int64_t N, int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi,
-                                float *d_wo, void *workspace, rqhip_stream_t stream) {
-    const int rc = ffn_check("t5_ffn_bwd", N, d, F, p);
+template <bool BF>
+int ffn_bwd(const char *who, const float *x, const float *wi, const float *wo, const float *h, const float *d_y, int64_t N,
+            int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi, float *d_wo, void *workspace,
+            rqhip_stream_t stream) {
+    const int rc = ffn_check(who, N, d, F, p);
     if (rc != RQHIP_OK) return rc;
     if (N == 0 || (!d_x && !d_wi && !d_wo)) return RQHIP_OK;
     const unsigned th = dropout_threshold(p);
     if (any_null(x, wi, wo, h, d_y)) {
-        set_error("t5_ffn_bwd: null pointer (x, wi, wo, h, d_y)");
+        set_error("%s: null pointer (x, wi, wo, h, d_y)", who);
         return RQHIP_EARG;
     }
     if (th && !seed) {
-        set_error("t5_ffn_bwd: dropout (p=%g) needs the seed, a one-element int64 device pointer", p);
+        set_error("%s: dropout (p=%g) needs the seed, a one-element int64 device pointer", who, p);
         return RQHIP_EARG;
     }
     if (d_wi && !workspace) {
-        set_error("t5_ffn_bwd: d_wi needs a workspace of rqhip_t5_ffn_bwd_workspace_bytes(N, d, F) = %zu bytes",
+        set_error("%s: d_wi needs a workspace of rqhip_t5_ffn_bwd_workspace_bytes(N, d, F) = %zu bytes", who,
                   rqhip_t5_ffn_bwd_workspace_bytes(N, d, F));
         return RQHIP_EWORKSPACE;
     }
     if (!all_aligned16(x, wi, wo, h, d_y, d_x, d_wi, d_wo, workspace)) {
-        set_error("t5_ffn_bwd: x, wi, wo, h, d_y, d_x, d_wi, d_wo and the workspace must be 16-byte aligned");
+        set_error("%s: x, wi, wo, h, d_y, d_x, d_wi, d_wo and the workspace must be 16-byte aligned", who);
         return RQHIP_EARG;
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -538,7 +583,7 @@ extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo
         a.x = d_y, a.w1 = wo, a.w2 = wi, a.h_in = h, a.mid = g, a.out = d_x;
         a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
         a.N = N, a.d = d, a.F = F;
-        const int rc1 = ffn_rows<true>(a, s);
+        const int rc1 = ffn_rows<true, BF>(a, s);
         if (rc1 != RQHIP_OK) return rc1;
     }
     if (d_wi || d_wo) {
@@ -548,8 +593,32 @@ extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo
         q.N = N, q.d = d, q.F = F;
         const int tiles = (d / 32) * (F / 32);
         q.tiles_wi = d_wi ? tiles : 0;
-        hipLaunchKernelGGL(t5_ffn_wgrad_kernel, dim3((unsigned)(q.tiles_wi + (d_wo ? tiles : 0))), dim3(256), 0, s, q);
+        hipLaunchKernelGGL(t5_ffn_wgrad_kernel<BF>, dim3((unsigned)(q.tiles_wi + (d_wo ? tiles : 0))), dim3(256), 0, s, q);
         RQ_CHECK_LAUNCH("t5_ffn_wgrad_kernel");
     }
     return RQHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int rqhip_t5_ffn_fwd(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+                                const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
+    return ffn_fwd<false>("t5_ffn_fwd", x, wi, wo, N, d, F, p, seed, y, h, stream);
+}
+
+extern "C" int rqhip_t5_ffn_fwd_bf16(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+                                     const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
+    return ffn_fwd<true>("t5_ffn_fwd_bf16", x, wi, wo, N, d, F, p, seed, y, h, stream);
+}
+
+extern "C" int rqhip_t5_ffn_bwd(const float *x, const float *wi, const float *wo, const float *h, const float *d_y,
+                                int64_t N, int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi,
+                                float *d_wo, void *workspace, rqhip_stream_t stream) {
+    return ffn_bwd<false>("t5_ffn_bwd", x, wi, wo, h, d_y, N, d, F, p, seed, d_x, d_wi, d_wo, workspace, stream);
+}
+
+extern "C" int rqhip_t5_ffn_bwd_bf16(const float *x, const float *wi, const float *wo, const float *h, const float *d_y,
+                                     int64_t N, int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi,
+                                     float *d_wo, void *workspace, rqhip_stream_t stream) {
+    return ffn_bwd<true>("t5_ffn_bwd_bf16", x, wi, wo, h, d_y, N, d, F, p, seed, d_x, d_wi, d_wo, workspace, stream);
 }

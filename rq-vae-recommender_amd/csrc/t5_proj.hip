@@ -28,6 +28,10 @@
 // reduces over all N rows: blocks of 32 rows, wave w of 4 takes the contiguous range of blocks [w nb / 4, (w + 1) nb /
 // 4), starts a fresh chain every 8 blocks and adds the finished chains in ascending order; the four waves' sums meet in
 // LDS and are added in wave order.  No partial blocks in memory, no atomics, no reduction launch.
+//
+// Second arithmetic, "bf16" (template parameter BF, entry points rqhip_t5_proj_*_bf16): t5_ffn.hip's, one
+// v_mfma_f32_16x16x32_bf16 per group on the same eight registers, rounded to bf16 and packed in front of it
+// (csrc/t5_common.h); loads, chains and stores do not change.
 #include "rqhip_common.h"
 #include "t5_common.h"
 
@@ -88,15 +92,27 @@ __device__ __forceinline__ void proj_load_a(const float *at, float (&a)[8]) {
     a[4] = hi.x; a[5] = hi.y; a[6] = hi.z; a[7] = hi.w;
 }
 
-template <int RT>
+// one group of 32 terms.  BF: the "bf16" arithmetic, one instruction per tile on the same eight registers, rounded and
+// packed pairwise (csrc/t5_common.h)
+template <int RT, bool BF>
 __device__ __forceinline__ void proj_mma(const float (&a)[RT][8], const float (&b)[2][8], f32x4 (&acc)[RT][2]) {
+    if constexpr (BF) {
+        const bf16x8 b0 = pack_bf16x8(b[0]), b1 = pack_bf16x8(b[1]);
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
+        for (int rt = 0; rt < RT; ++rt) {
+            const bf16x8 ar = pack_bf16x8(a[rt]);
+            acc[rt][0] = mma_group_bf16(ar, b0, acc[rt][0]);
+            acc[rt][1] = mma_group_bf16(ar, b1, acc[rt][1]);
+        }
+    } else {
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
+        for (int e = 0; e < 8; ++e)
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-                acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], b[ct][e], acc[rt][ct], 0, 0, 0);
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], b[ct][e], acc[rt][ct], 0, 0, 0);
+    }
 }
 
 // a finished chain joins the sum of the chains before it; the next chain starts from +0
@@ -115,8 +131,8 @@ __device__ __forceinline__ void proj_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT]
 // keeps a step's loads together and in front of the previous step's matrix instructions (csrc/mlp_small.hip)
 #define PROJ_FENCE __builtin_amdgcn_sched_barrier(0)
 
-// RT: 16-row tiles per workgroup
-template <bool BWD, int RT>
+// RT: 16-row tiles per workgroup; BF: the "bf16" arithmetic (the operands are rounded as the fragments are packed)
+template <bool BWD, int RT, bool BF>
 __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
     const int t = threadIdx.x, lane = t & 63, i = lane & 15, kq = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -151,10 +167,10 @@ __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
     load(a0, b0);
     for (int it = 0; it < total; it += 2) {
         if (it + 1 < total) load(a1, b1);
-        PROJ_FENCE; proj_mma<RT>(a0, b0, run); PROJ_FENCE;
+        PROJ_FENCE; proj_mma<RT, BF>(a0, b0, run); PROJ_FENCE;
         if (it + 1 < total) {
             if (it + 2 < total) load(a0, b0);
-            PROJ_FENCE; proj_mma<RT>(a1, b1, run); PROJ_FENCE;
+            PROJ_FENCE; proj_mma<RT, BF>(a1, b1, run); PROJ_FENCE;
         }
         // kProjChainGroups is even: a chain ends behind an odd step, or with the reduction
         if (((it + 1) & (kProjChainGroups - 1)) == kProjChainGroups - 1 || it + 2 >= total) proj_close<RT>(sum, run);
@@ -190,6 +206,8 @@ struct ProjWgrad {
     int tiles;                      // 32 x 32 tiles per job: workgroup b owns tile b % tiles of job b / tiles
 };
 
+// BF: the "bf16" arithmetic; the lane's eight rows 4 ks + kq of a block are the elements j = ks of both fragments
+template <bool BF>
 __global__ __launch_bounds__(256) void t5_proj_wgrad_kernel(const ProjWgrad p) {
     __shared__ float red[4 * 32 * 33];
     const int t = threadIdx.x, lane = t & 63, i = lane & 15, kq = lane >> 4;
@@ -225,13 +243,26 @@ __global__ __launch_bounds__(256) void t5_proj_wgrad_kernel(const ProjWgrad p) {
             const long long n = b * kProjWgBlock + 4 * ks + kq;
             if (n >= p.N) pa[ks] = qb[ks] = f32x2{0.f, 0.f};
         }
+        if constexpr (BF) {
+            bf16x8 fa[2], fb[2];
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
+            for (int ks = 0; ks < 8; ++ks) {
+                fa[0][ks] = (__bf16)pa[ks].x; fa[1][ks] = (__bf16)pa[ks].y;
+                fb[0][ks] = (__bf16)qb[ks].x; fb[1][ks] = (__bf16)qb[ks].y;
+            }
 #pragma unroll
             for (int at = 0; at < 2; ++at)
 #pragma unroll
-                for (int bt = 0; bt < 2; ++bt)
-                    acc[at][bt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ks][at], qb[ks][bt], acc[at][bt], 0, 0, 0);
+                for (int bt = 0; bt < 2; ++bt) acc[at][bt] = mma_group_bf16(fa[at], fb[bt], acc[at][bt]);
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+                for (int at = 0; at < 2; ++at)
+#pragma unroll
+                    for (int bt = 0; bt < 2; ++bt)
+                        acc[at][bt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ks][at], qb[ks][bt], acc[at][bt], 0, 0, 0);
+        }
         if (((b - lo) & (kProjWgFlush - 1)) == kProjWgFlush - 1) {
 #pragma unroll
             for (int at = 0; at < 2; ++at)
@@ -296,33 +327,26 @@ bool proj_ld_ok(int64_t ld, int width) { return ld >= width && ld % 4 == 0; }
 // 16-row tiles per workgroup: a function of N alone, and the chains do not depend on it
 int proj_row_tiles(long long N) { return N > kProjTallFrom ? 4 : N > kProjTallFrom / 2 ? 2 : 1; }
 
-template <bool BWD, int RT>
+template <bool BWD, int RT, bool BF>
 int proj_rows_launch_rt(const ProjRows &a, int cols, hipStream_t s) {
     const dim3 grid((unsigned)((a.N + 16 * RT - 1) / (16 * RT)), (unsigned)((cols + kProjChunk - 1) / kProjChunk));
-    hipLaunchKernelGGL((t5_proj_rows_kernel<BWD, RT>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((t5_proj_rows_kernel<BWD, RT, BF>), grid, dim3(256), 0, s, a);
     RQ_CHECK_LAUNCH("t5_proj_rows_kernel");
     return RQHIP_OK;
 }
 
-template <bool BWD>
+template <bool BWD, bool BF>
 int proj_rows_launch(const ProjRows &a, int cols, hipStream_t s) {
     const int rt = proj_row_tiles(a.N);
-    if (rt == 1) return proj_rows_launch_rt<BWD, 1>(a, cols, s);
-    if (rt == 2) return proj_rows_launch_rt<BWD, 2>(a, cols, s);
-    return proj_rows_launch_rt<BWD, 4>(a, cols, s);
+    if (rt == 1) return proj_rows_launch_rt<BWD, 1, BF>(a, cols, s);
+    if (rt == 2) return proj_rows_launch_rt<BWD, 2, BF>(a, cols, s);
+    return proj_rows_launch_rt<BWD, 4, BF>(a, cols, s);
 }
 
-}  // namespace
-
-}  // namespace rqhip
-
-using namespace rqhip;
-
-extern "C" int rqhip_t5_proj_supported(int d_in, int d_out, int n) { return proj_supported(d_in, d_out, n) ? 1 : 0; }
-
-extern "C" int rqhip_t5_proj_fwd(const float *x, int64_t ld_x, const float *const *w, float *const *y, const int64_t *ld_y,
-                                 int n, int64_t N, int d_in, int d_out, rqhip_stream_t stream) {
-    const char *who = "t5_proj_fwd";
+// the entry points of both arithmetics; `who` names the one called in the messages
+template <bool BF>
+int proj_fwd(const char *who, const float *x, int64_t ld_x, const float *const *w, float *const *y, const int64_t *ld_y,
+             int n, int64_t N, int d_in, int d_out, rqhip_stream_t stream) {
     const int rc = proj_check(who, n, N, d_in, d_out);
     if (rc != RQHIP_OK) return rc;
     if (N == 0) return RQHIP_OK;
@@ -352,13 +376,13 @@ extern "C" int rqhip_t5_proj_fwd(const float *x, int64_t ld_x, const float *cons
                   (long long)ld_x, d_in);
         return RQHIP_EARG;
     }
-    return proj_rows_launch<false>(a, n * d_out, reinterpret_cast<hipStream_t>(stream));
+    return proj_rows_launch<false, BF>(a, n * d_out, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int rqhip_t5_proj_bwd(const float *x, int64_t ld_x, const float *const *w, const float *const *d_y,
-                                 const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x,
-                                 float *const *d_w, rqhip_stream_t stream) {
-    const char *who = "t5_proj_bwd";
+template <bool BF>
+int proj_bwd(const char *who, const float *x, int64_t ld_x, const float *const *w, const float *const *d_y,
+             const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w,
+             rqhip_stream_t stream) {
     const int rc = proj_check(who, n, N, d_in, d_out);
     if (rc != RQHIP_OK) return rc;
     if (N == 0) return RQHIP_OK;
@@ -397,14 +421,44 @@ extern "C" int rqhip_t5_proj_bwd(const float *x, int64_t ld_x, const float *cons
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (d_x && na) {
         a.out[0] = d_x, a.ld_o[0] = d_in, a.N = N, a.n = na, a.d_in = d_in, a.d_out = d_out;
-        const int rc1 = proj_rows_launch<true>(a, d_in, s);
+        const int rc1 = proj_rows_launch<true, BF>(a, d_in, s);
         if (rc1 != RQHIP_OK) return rc1;
     }
     if (nq) {
         q.x = x, q.ld_x = ld_x, q.N = N, q.d_in = d_in, q.d_out = d_out;
         q.tiles = (d_in / 32) * (d_out / 32);
-        hipLaunchKernelGGL(t5_proj_wgrad_kernel, dim3((unsigned)(nq * q.tiles)), dim3(256), 0, s, q);
+        hipLaunchKernelGGL(t5_proj_wgrad_kernel<BF>, dim3((unsigned)(nq * q.tiles)), dim3(256), 0, s, q);
         RQ_CHECK_LAUNCH("t5_proj_wgrad_kernel");
     }
     return RQHIP_OK;
+}
+
+}  // namespace
+
+}  // namespace rqhip
+
+using namespace rqhip;
+
+extern "C" int rqhip_t5_proj_supported(int d_in, int d_out, int n) { return proj_supported(d_in, d_out, n) ? 1 : 0; }
+
+extern "C" int rqhip_t5_proj_fwd(const float *x, int64_t ld_x, const float *const *w, float *const *y, const int64_t *ld_y,
+                                 int n, int64_t N, int d_in, int d_out, rqhip_stream_t stream) {
+    return proj_fwd<false>("t5_proj_fwd", x, ld_x, w, y, ld_y, n, N, d_in, d_out, stream);
+}
+
+extern "C" int rqhip_t5_proj_fwd_bf16(const float *x, int64_t ld_x, const float *const *w, float *const *y,
+                                      const int64_t *ld_y, int n, int64_t N, int d_in, int d_out, rqhip_stream_t stream) {
+    return proj_fwd<true>("t5_proj_fwd_bf16", x, ld_x, w, y, ld_y, n, N, d_in, d_out, stream);
+}
+
+extern "C" int rqhip_t5_proj_bwd(const float *x, int64_t ld_x, const float *const *w, const float *const *d_y,
+                                 const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x,
+                                 float *const *d_w, rqhip_stream_t stream) {
+    return proj_bwd<false>("t5_proj_bwd", x, ld_x, w, d_y, ld_dy, n, N, d_in, d_out, d_x, d_w, stream);
+}
+
+extern "C" int rqhip_t5_proj_bwd_bf16(const float *x, int64_t ld_x, const float *const *w, const float *const *d_y,
+                                      const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x,
+                                      float *const *d_w, rqhip_stream_t stream) {
+    return proj_bwd<true>("t5_proj_bwd_bf16", x, ld_x, w, d_y, ld_dy, n, N, d_in, d_out, d_x, d_w, stream);
 }

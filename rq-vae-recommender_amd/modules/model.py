@@ -7,6 +7,9 @@ stacks whenever they are run: `model.attention_impl` ("torch", the default, "hip
 `model.ffn_impl` and `model.proj_impl` ("torch", the default, or "hip"; the last groups the attention projections, the
 cross-attention K/V of `generate` and the K/V its decode steps write into the cache included).  What each replaces and
 when it is taken: modules/t5.py.
+`model.matmul_arith` ("fp32", the default, or "bf16") goes to both stacks with them: the arithmetic of the "hip"
+feed-forward and the "hip" projections (bf16 operands, fp32 accumulation, fp32 storage; modules/t5.py).  It has no
+effect on the "torch" bodies, nor on the attention, the norms, the heads or the embedding, which stay fp32.
 `model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
 cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
 on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
@@ -41,7 +44,7 @@ from torch import Tensor
 
 from data.schemas import TokenizedSeqBatch
 from modules.sid_prefix import SemIdPrefixIndex
-from modules.t5 import T5Config, T5EncoderModel, T5Stack
+from modules.t5 import MATMUL_ARITHS, T5Config, T5EncoderModel, T5Stack
 from rqhip import ops
 from rqhip._lib import RqHipError
 from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
@@ -115,6 +118,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.ffn_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.embed_impl = "torch"  # or "hip": each stack's input embedding as one fused call
         self.proj_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
+        self.matmul_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
 
     @property
     def device(self) -> torch.device:
@@ -163,7 +167,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return self._prefix_index_for_codebooks().check_valid_prefix(prefix, batch_size)
 
     def _push_attention_impl(self) -> None:
-        for name in ("attention_impl", "norm_impl", "ffn_impl", "proj_impl"):
+        if self.matmul_arith not in MATMUL_ARITHS:
+            raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
+        for name in ("attention_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith"):
             for stack in (self.encoder.encoder, self.t5_decoder):
                 setattr(stack, name, getattr(self, name))
 

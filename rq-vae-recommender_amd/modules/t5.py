@@ -50,6 +50,13 @@ operators run, silently.  The module tree and the state dict are the same on eve
   with the fused one alike, and also needs the stack's attention weights to be fp32 device tensors that are dense and
   16-byte aligned (`hip_proj_active`).
 
+`matmul_arith` = "fp32" (the default) or "bf16" is the arithmetic of the two matrix forms above, wherever the "hip"
+feed-forward or the "hip" projections are taken: under grad (autograd.T5FFNBf16Function / T5ProjBf16Function) and under
+no_grad, in `T5Stack.cross_kv` and in the decode step's call that writes K/V into the cache slabs.  "bf16" rounds every
+operand of a matrix product to bf16 and accumulates in fp32 (include/rqhip.h); weights, activations, gradients and
+the state dict stay fp32.  With the "torch" bodies it has no effect: the operators stay fp32, and so do the attention
+itself, the norms and the glue.
+
 The fused forms take their dropout seeds as int64s drawn on the device with torch.randint (the default generator:
 torch.manual_seed reproduces a run), none in eval mode or at dropout_rate 0.  The fused attention draws one per call.
 With the "hip" glue a stack forward draws once before its first body, one seed per glue call and behind them one per
@@ -64,13 +71,15 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops
-from rqhip.autograd import T5AddNormFunction, T5AttentionFunction, T5FFNFunction, T5ProjFunction
+from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5FFNBf16Function, T5FFNFunction, T5ProjBf16Function,
+                            T5ProjFunction)
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
 NORM_IMPLS = ("torch", "hip")
 FFN_IMPLS = ("torch", "hip")
 PROJ_IMPLS = ("torch", "hip")
+MATMUL_ARITHS = ops.T5_ARITHS  # ("fp32", "bf16")
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -173,15 +182,17 @@ class _Seeds:
         return self.glue(self.n_glue + i) if self.n_glue else _draw_seed(self.p, self.device)
 
 
-def _project(fused: bool, x: Tensor, linears, outs=None) -> Tuple[Tensor, ...]:
+def _project(fused, x: Tensor, linears, outs=None) -> Tuple[Tensor, ...]:
     """The bias-free Linears `linears` of the same x -> their outputs: the operators one by one, or `fused` ONE call
-    for the group (T5ProjFunction under grad, ops.t5_proj_fwd under no_grad, which writes into `outs` where given)."""
+    for the group (T5ProjFunction under grad, ops.t5_proj_fwd under no_grad, which writes into `outs` where given).
+    fused: False, or what T5Stack.proj_arm returns: True for the "fp32" arithmetic, "bf16" for that one."""
     if not fused:
         return tuple(lin(x) for lin in linears)
     weights = [lin.weight for lin in linears]
+    bf16 = fused == "bf16"
     if torch.is_grad_enabled():
-        return T5ProjFunction.apply(x, *weights)
-    return ops.t5_proj_fwd(x, weights, outs)
+        return (T5ProjBf16Function if bf16 else T5ProjFunction).apply(x, *weights)
+    return ops.t5_proj_fwd(x, weights, outs, arith="bf16") if bf16 else ops.t5_proj_fwd(x, weights, outs)
 
 
 def _attend(module: nn.Module, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], mask: Optional[Tensor]) -> Tensor:
@@ -244,20 +255,20 @@ class T5Attention(nn.Module):
     def _heads(self, x: Tensor) -> Tensor:  # [R, T, inner] -> [R, heads, T, d_kv]
         return x.view(x.shape[0], x.shape[1], self.n_heads, self.d_kv).transpose(1, 2)
 
-    def project_kv(self, x: Tensor, fused: bool = False) -> KV:
+    def project_kv(self, x: Tensor, fused=False) -> KV:
         k, v = _project(fused, x, (self.k, self.v))
         return self._heads(k), self._heads(v)
 
     def self_attention(self, x: Tensor, bias: Optional[Tensor], mask: Optional[Tensor], past: Optional[KV],
-                       fused: bool = False) -> Tuple[Tensor, KV]:
-        """fused: the projections as grouped calls (`_project`): one for q, k and v, one for o."""
+                       fused=False) -> Tuple[Tensor, KV]:
+        """fused: the projections as grouped calls (`_project`, which names its values): one for q, k and v, one for o."""
         q, k, v = (self._heads(t) for t in _project(fused, x, (self.q, self.k, self.v)))
         if past is not None:
             k, v = torch.cat([past[0], k], dim=2), torch.cat([past[1], v], dim=2)
         out = _attend(self, q, k, v, bias, mask)
         return _project(fused, out.transpose(1, 2).reshape(x.shape[0], x.shape[1], -1), (self.o,))[0], (k, v)
 
-    def cross_attention(self, x: Tensor, kv: KV, mask: Optional[Tensor], fused: bool = False) -> Tensor:
+    def cross_attention(self, x: Tensor, kv: KV, mask: Optional[Tensor], fused=False) -> Tensor:
         """Queries x [R, T, d] with R = B * beams over keys / values [B, heads, S, d_kv] of B rows."""
         R, T = x.shape[0], x.shape[1]
         B = kv[0].shape[0]
@@ -288,7 +299,7 @@ class _OperatorAttention:
         self.mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
         self.bias = stack.block[0].layer[0].SelfAttention.compute_bias(T, keys, past)
         self.past_key_values = past_key_values
-        self.proj = stack.hip_proj_active(inputs_embeds)
+        self.proj = stack.proj_arm(inputs_embeds)
         if stack.is_decoder:
             self.cross_kv = stack.cross_kv(encoder_hidden_states) if cross_kv is None else cross_kv
             self.cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
@@ -304,11 +315,12 @@ class _OperatorAttention:
 class _HipAttention:
     """The attention bodies of a stack forward on the "hip" path: the bias table and the byte masks are built once,
     every attention is one launch (`train`: one T5AttentionFunction call, with the attention-weight dropout of train
-    mode in the kernel, from a seed drawn per call).  `proj`: the projections around it as grouped calls (`_project`)."""
+    mode in the kernel, from a seed drawn per call).  `proj`: the projections around it as grouped calls (`_project`,
+    T5Stack.proj_arm's value)."""
 
     def __init__(self, stack: "T5Stack", T: int, attention_mask: Optional[Tensor],
                  encoder_attention_mask: Optional[Tensor], cross_kv: Optional[List[KV]],
-                 cache: Optional[T5DecodeCache], train: bool, proj: bool) -> None:
+                 cache: Optional[T5DecodeCache], train: bool, proj) -> None:
         self.train = train
         self.proj = proj
         self.p = float(stack.config.dropout_rate) if train and stack.training else 0.0
@@ -337,7 +349,8 @@ class _HipAttention:
         R = normed.shape[0]
         ks, vs = self.cache.slabs[i]
         if self.proj:  # q into a new tensor, k and v into this position of the slabs: one launch
-            q = _project(True, normed, (module.q, module.k, module.v), [None, ks[self.past, :R], vs[self.past, :R]])[0]
+            q = _project(self.proj, normed, (module.q, module.k, module.v),
+                         [None, ks[self.past, :R], vs[self.past, :R]])[0]
         else:
             q = module.q(normed)
             x2 = normed.reshape(R, -1)
@@ -383,11 +396,14 @@ class T5DenseReluDense(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         return self.wo(self.dropout(F.relu(self.wi(x))))
 
-    def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor]) -> Tensor:
-        """forward as one fused call (the "hip" feed-forward body), its dropout at rate p from `seed`."""
+    def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor], arith: str = "fp32") -> Tensor:
+        """forward as one fused call (the "hip" feed-forward body), its dropout at rate p from `seed`, in the
+        arithmetic `arith` (MATMUL_ARITHS)."""
+        bf16 = arith == "bf16"
         if torch.is_grad_enabled():
-            return T5FFNFunction.apply(x, self.wi.weight, self.wo.weight, p, seed)
-        return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False)[0]
+            return (T5FFNBf16Function if bf16 else T5FFNFunction).apply(x, self.wi.weight, self.wo.weight, p, seed)
+        kw = {"arith": arith} if bf16 else {}
+        return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False, **kw)[0]
 
 
 class T5LayerFF(nn.Module):
@@ -424,18 +440,19 @@ class T5Stack(nn.Module):
         self.norm_impl = "torch"  # or "hip": see the module docstring
         self.ffn_impl = "torch"  # or "hip": see the module docstring
         self.proj_impl = "torch"  # or "hip": see the module docstring
+        self.matmul_arith = "fp32"  # or "bf16": the arithmetic of the "hip" feed-forward and projections (docstring)
         init_t5_weights(self, config)
 
     def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
         """Cross-attention K/V of every block, computed once per encoder output (proj_impl = "hip": by one grouped
         call for all blocks, one per four blocks beyond that)."""
-        fused = self.hip_proj_active(encoder_hidden_states)
+        fused = self.proj_arm(encoder_hidden_states)
         atts = [blk.layer[1].EncDecAttention for blk in self.block]
         if not fused:
             return [att.project_kv(encoder_hidden_states) for att in atts]
         linears = [lin for att in atts for lin in (att.k, att.v)]
         outs = [y for s in range(0, len(linears), ops.T5_PROJ_MAX_GROUP)
-                for y in _project(True, encoder_hidden_states, linears[s:s + ops.T5_PROJ_MAX_GROUP])]
+                for y in _project(fused, encoder_hidden_states, linears[s:s + ops.T5_PROJ_MAX_GROUP])]
         return [(att._heads(outs[2 * i]), att._heads(outs[2 * i + 1])) for i, att in enumerate(atts)]
 
     def hip_attention_active(self, x: Tensor, query_length: int, key_length: int,
@@ -495,6 +512,19 @@ class T5Stack(nn.Module):
         return all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.data_ptr() % 16 == 0
                    for w in weights)
 
+    def arith(self) -> str:
+        """matmul_arith, validated."""
+        if self.matmul_arith not in MATMUL_ARITHS:
+            raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
+        return self.matmul_arith
+
+    def proj_arm(self, x: Tensor):
+        """hip_proj_active(x) with the arithmetic of the grouped calls: False, True ("fp32") or "bf16" (`_project`)."""
+        arith = self.arith()
+        if not self.hip_proj_active(x):
+            return False
+        return "bf16" if arith == "bf16" else True
+
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
@@ -508,7 +538,7 @@ class T5Stack(nn.Module):
             past = 0 if decode_cache is None else decode_cache.pos
             if decode_cache is None and self.hip_train_active(inputs_embeds, T, cross_kv):
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, None, train=True,
-                                     proj=self.hip_proj_active(inputs_embeds))
+                                     proj=self.proj_arm(inputs_embeds))
             cross_length = cross_kv[0][0].shape[2] if self.is_decoder else None
             if self.hip_attention_active(inputs_embeds, T, past + T, cross_length):
                 if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
@@ -516,7 +546,7 @@ class T5Stack(nn.Module):
                     raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
                                      "past_key_values or attention_mask")
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, decode_cache,
-                                     train=False, proj=self.hip_proj_active(inputs_embeds))
+                                     train=False, proj=self.proj_arm(inputs_embeds))
             if decode_cache is not None:
                 raise ValueError('decode_cache belongs to the "hip" attention path, which is not active here')
         return _OperatorAttention(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
@@ -553,6 +583,7 @@ class T5Stack(nn.Module):
                                          past_key_values, cross_kv, decode_cache)
         fused_glue = self.hip_norm_active(inputs_embeds)
         fused_ffn = self.hip_ffn_active(inputs_embeds)
+        arith = self.arith()
         p = float(self.config.dropout_rate) if self.training else 0.0
         layers = [layer for blk in self.block for layer in blk.layer]
         seeds = _Seeds(p, inputs_embeds.device, len(layers) + 1 if fused_glue else 0,
@@ -572,7 +603,7 @@ class T5Stack(nn.Module):
                 x, normed = glue(k, x, attention.cross_attention(i, blk.layer[1].EncDecAttention, normed))
             dense = blk.layer[-1].DenseReluDense
             k += 1
-            x, normed = glue(k, x, dense.forward_hip(normed, p, seeds.ffn(i)) if fused_ffn else dense(normed))
+            x, normed = glue(k, x, dense.forward_hip(normed, p, seeds.ffn(i), arith) if fused_ffn else dense(normed))
         return (normed, new_kv) if use_cache else normed
 
 

@@ -117,9 +117,13 @@ SIGNATURES = {
     "rqhip_t5_ffn_bwd_workspace_bytes": (_sz, [_i64, _int, _int]),
     "rqhip_t5_ffn_fwd": (_int, [_vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp]),
     "rqhip_t5_ffn_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_fwd_bf16": (_int, [_vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_bwd_bf16": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rqhip_t5_proj_supported": (_int, [_int, _int, _int]),
     "rqhip_t5_proj_fwd": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp]),
     "rqhip_t5_proj_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp]),
+    "rqhip_t5_proj_fwd_bf16": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp]),
+    "rqhip_t5_proj_bwd_bf16": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp]),
     "rqhip_sid_head_loss_supported": (_int, [_int, _int, _int]),
     "rqhip_sid_head_loss_fwd": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp,
                                        _vp, _vp]),

@@ -324,15 +324,24 @@ class T5AddNormFunction(torch.autograd.Function):
         return d_x, d_y, d_w, None, None, None, None
 
 
+def _arith_kw(ctx) -> dict:
+    """The `arith` keyword of the ops calls of ctx's Function: none for "fp32", the ops' default."""
+    arith = ctx._forward_cls.arith
+    return {} if arith == "fp32" else {"arith": arith}
+
+
 class T5FFNFunction(torch.autograd.Function):
     """The T5 feed-forward body (modules/t5.py, ffn_impl = "hip") as one launch forward and at most two backward
     (ops.t5_ffn_fwd / ops.t5_ffn_bwd): apply(x, wi, wo, p, seed) -> y = dropout(relu(x @ wi.T), p) @ wo.T.  Saved: x, the
     ReLU output h, the two weights and the seed; the dropout decisions are recomputed.  Gradients: x, wi and wo, each
-    only when needed."""
+    only when needed.  `arith` is the class's arithmetic (ops.T5_ARITHS), forward and backward alike: this class is the
+    "fp32" arm, T5FFNBf16Function the "bf16" one; t5_ffn_function(arith) picks."""
+
+    arith = "fp32"
 
     @staticmethod
     def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor]):
-        y, h = ops.t5_ffn_fwd(x, wi, wo, p, seed)
+        y, h = ops.t5_ffn_fwd(x, wi, wo, p, seed, **_arith_kw(ctx))
         ctx.save_for_backward(x, h, wi, wo, seed)
         ctx.p = p
         return y
@@ -344,19 +353,35 @@ class T5FFNFunction(torch.autograd.Function):
         if not (need_x or need_wi or need_wo):
             return None, None, None, None, None
         d_x, d_wi, d_wo = ops.t5_ffn_bwd(x, wi, wo, h, _dense(d_y), ctx.p, seed, need_x=need_x, need_wi=need_wi,
-                                         need_wo=need_wo)
+                                         need_wo=need_wo, **_arith_kw(ctx))
         return d_x, d_wi, d_wo, None, None
+
+
+class T5FFNBf16Function(T5FFNFunction):
+    """T5FFNFunction in the "bf16" arithmetic (rqhip_t5_ffn_*_bf16): the same saved tensors, all float32."""
+
+    arith = "bf16"
+
+
+def t5_ffn_function(arith: str = "fp32"):
+    """The feed-forward Function of an arithmetic."""
+    if arith not in ops.T5_ARITHS:
+        raise ops.RqHipError(f"t5_ffn_function: arith must be one of {ops.T5_ARITHS}, got {arith!r}")
+    return T5FFNBf16Function if arith == "bf16" else T5FFNFunction
 
 
 class T5ProjFunction(torch.autograd.Function):
     """A group of bias-free linear maps of the same rows (modules/t5.py, proj_impl = "hip") as one launch forward and at
     most two backward (ops.t5_proj_fwd / ops.t5_proj_bwd): apply(x, *weights) -> (y[0], ..., y[n - 1]), y[j] = x @
     weights[j].T.  Saved: x and the weights.  An output nobody used arrives without a gradient and is left out of the
-    backward.  Gradients: x and each weight, each only when needed."""
+    backward.  Gradients: x and each weight, each only when needed.  `arith` as T5FFNFunction's: this class is the "fp32"
+    arm, T5ProjBf16Function the "bf16" one; t5_proj_function(arith) picks."""
+
+    arith = "fp32"
 
     @staticmethod
     def forward(ctx, x: Tensor, *weights: Tensor):
-        outs = ops.t5_proj_fwd(x, weights)
+        outs = ops.t5_proj_fwd(x, weights, **_arith_kw(ctx))
         ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None (= NULL at the C ABI)
         ctx.save_for_backward(x, *weights)
         return outs
@@ -368,8 +393,21 @@ class T5ProjFunction(torch.autograd.Function):
         if all(g is None for g in d_ys) or not any(ctx.needs_input_grad):
             return (None,) * (1 + n)
         d_x, d_w = ops.t5_proj_bwd(x, weights, [_dense(g) for g in d_ys], need_x=ctx.needs_input_grad[0],
-                                   need_w=ctx.needs_input_grad[1:])
+                                   need_w=ctx.needs_input_grad[1:], **_arith_kw(ctx))
         return (d_x, *d_w)
+
+
+class T5ProjBf16Function(T5ProjFunction):
+    """T5ProjFunction in the "bf16" arithmetic (rqhip_t5_proj_*_bf16)."""
+
+    arith = "bf16"
+
+
+def t5_proj_function(arith: str = "fp32"):
+    """The projection Function of an arithmetic."""
+    if arith not in ops.T5_ARITHS:
+        raise ops.RqHipError(f"t5_proj_function: arith must be one of {ops.T5_ARITHS}, got {arith!r}")
+    return T5ProjBf16Function if arith == "bf16" else T5ProjFunction
 
 
 class SidHeadLossFunction(torch.autograd.Function):

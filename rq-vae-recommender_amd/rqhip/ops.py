@@ -808,6 +808,18 @@ def t5_add_norm_bwd(x_new: Tensor, rstd: Tensor, w: Tensor, d_n: Optional[Tensor
     return d_x, (d_x if shared else d_y), d_w
 
 
+T5_ARITHS = ("fp32", "bf16")   # the arithmetics of t5_ffn_* and t5_proj_* (include/rqhip.h): storage is fp32 in both
+
+
+def _arith_entry(who: str, arith: str):
+    """The C entry point of `who` in the arithmetic `arith`: "fp32" (exact fp32 products) or "bf16" (operands rounded to
+    bf16, exact products, fp32 accumulation)."""
+    if arith not in T5_ARITHS:
+        raise RqHipError(f"{who}: arith must be one of {T5_ARITHS}, got {arith!r}")
+    name = f"rqhip_{who}" + ("_bf16" if arith == "bf16" else "")
+    return getattr(_lib.lib(), name), name
+
+
 def t5_ffn_supported(dtype: torch.dtype, d: int, F: int) -> bool:
     """Whether t5_ffn_fwd / t5_ffn_bwd implement this (d_model, d_ff) (rqhip_t5_ffn_supported): fp32, d a multiple of 32
     in 32 .. 512, F a multiple of 32 in 32 .. 8192."""
@@ -829,31 +841,37 @@ def _ffn_call(who: str, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optio
     return x, _aligned16(wi.contiguous()), _aligned16(wo.contiguous()), (x.numel() // d), d, F, seed_ptr
 
 
-def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *, need_h: bool = True):
+def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *, need_h: bool = True,
+               arith: str = "fp32"):
     """The T5 feed-forward body in one launch (rqhip_t5_ffn_fwd) -> (y, h or None): h = relu(x @ wi.T), y = dropout(h, p)
     @ wo.T.  x [..., d] float32, wi [F, d] and wo [d, F] the two Linear weights as stored; y has x's shape, h is
     [..., F] (the one tensor t5_ffn_bwd needs; not stored without need_h).  The mask is t5_attention_dropout_keep(seed,
     1, 1, N, F, p)[0, 0] over the N = x.numel() / d rows; `seed` is a one-element int64 device tensor the host never
-    reads."""
+    reads.  arith: "fp32", or "bf16" (rqhip_t5_ffn_fwd_bf16: every matrix operand rounded to bf16, fp32 accumulation;
+    all tensors stay float32 and h is stored unrounded)."""
+    fn, fn_name = _arith_entry("t5_ffn_fwd", arith)
     _need_gpu(x, wi, wo, seed)
     x, wi, wo, N, d, F, seed_ptr = _ffn_call("t5_ffn_fwd", x, wi, wo, p, seed)
     dev = x.device
     with torch.cuda.device(dev):
         y = torch.empty_like(x)
         h = torch.empty(x.shape[:-1] + (F,), dtype=torch.float32, device=dev) if need_h else None
-        rc = _lib.lib().rqhip_t5_ffn_fwd(_ptr(x), _ptr(wi), _ptr(wo), N, d, F, float(p), seed_ptr, _ptr(y), _ptr(h), _stream())
-        check(rc, "rqhip_t5_ffn_fwd")
+        rc = fn(_ptr(x), _ptr(wi), _ptr(wo), N, d, F, float(p), seed_ptr, _ptr(y), _ptr(h), _stream())
+        check(rc, fn_name)
     return y, h
 
 
 def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *,
-               need_x: bool = True, need_wi: bool = True, need_wo: bool = True):
+               need_x: bool = True, need_wi: bool = True, need_wo: bool = True, return_g: bool = False,
+               arith: str = "fp32"):
     """The gradients of t5_ffn_fwd in one call of at most two launches (rqhip_t5_ffn_bwd) -> (d_x, d_wi, d_wo), None
     where not needed.  x, wi, wo, p, seed: the forward's; h: its second result; d_y: the gradient of y.  The dropout
     decisions are recomputed from the seed; the weight gradients are summed without atomics in an order that depends on
-    the shape alone.  The [N, F] workspace comes from torch's allocator."""
-    _need_gpu(x, wi, wo, h, d_y, seed)
+    the shape alone.  The [N, F] workspace comes from torch's allocator.  return_g: a fourth result, the workspace as the
+    tensor g of h's shape when need_wi (else None).  arith: "fp32" or "bf16", as t5_ffn_fwd's (rqhip_t5_ffn_bwd_bf16)."""
     who = "t5_ffn_bwd"
+    fn, fn_name = _arith_entry(who, arith)
+    _need_gpu(x, wi, wo, h, d_y, seed)
     x, wi, wo, N, d, F, seed_ptr = _ffn_call(who, x, wi, wo, p, seed)
     h = _norm_rows(h, "h", who, x.shape[:-1] + (F,))
     d_y = _norm_rows(d_y, "d_y", who, x.shape)
@@ -867,9 +885,11 @@ def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: flo
         if need_wi and N > 0:
             nbytes = int(_lib.lib().rqhip_t5_ffn_bwd_workspace_bytes(N, d, F))
             work = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        rc = _lib.lib().rqhip_t5_ffn_bwd(_ptr(x), _ptr(wi), _ptr(wo), _ptr(h), _ptr(d_y), N, d, F, float(p), seed_ptr,
-                                         _ptr(d_x), _ptr(d_wi), _ptr(d_wo), _ptr(work), _stream())
-        check(rc, "rqhip_t5_ffn_bwd")
+        rc = fn(_ptr(x), _ptr(wi), _ptr(wo), _ptr(h), _ptr(d_y), N, d, F, float(p), seed_ptr, _ptr(d_x), _ptr(d_wi),
+                _ptr(d_wo), _ptr(work), _stream())
+        check(rc, fn_name)
+    if return_g:
+        return d_x, d_wi, d_wo, (work.view(h.shape) if work is not None else None)
     return d_x, d_wi, d_wo
 
 
@@ -902,14 +922,16 @@ def _proj_call(who: str, x: Tensor, weights):
     return x, weights, w_ptrs, (x.numel() // d_in), d_in, d_out
 
 
-def t5_proj_fwd(x: Tensor, weights, outs=None):
+def t5_proj_fwd(x: Tensor, weights, outs=None, *, arith: str = "fp32"):
     """n bias-free linear maps of the same rows in one launch (rqhip_t5_proj_fwd) -> (y[0], ..., y[n - 1]), y[j] = x @
     weights[j].T.  x [..., d_in] float32 with dense rows, weights: n separate [d_out, d_in] matrices, the nn.Linear
     weights as stored.  y[j] has shape x.shape[:-1] + (d_out,).  outs (optional): a list of n entries, each None (that
     output is allocated) or a preallocated float32 [N, d_out] view over the N = x.numel() / d_in rows whose last
     dimension is dense and whose row stride is at least d_out, a position of a decode-cache slab for one; the kernel
-    writes into it and it is returned as it is."""
+    writes into it and it is returned as it is.  arith: "fp32", or "bf16" (rqhip_t5_proj_fwd_bf16: x and the weights
+    rounded to bf16 as operands, fp32 accumulation; all tensors stay float32)."""
     who = "t5_proj_fwd"
+    fn, fn_name = _arith_entry(who, arith)
     x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights)
     n = len(weights)
     outs = [None] * n if outs is None else list(outs)
@@ -926,17 +948,19 @@ def t5_proj_fwd(x: Tensor, weights, outs=None):
                                  f"least {d_out} apart, got {o.dtype} {tuple(o.shape)} strides {tuple(o.stride())}")
         y_ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
         ld_y = (C.c_int64 * n)(*[int(o.stride(0)) if o.dim() == 2 and N > 1 else d_out for o in outs])
-        rc = _lib.lib().rqhip_t5_proj_fwd(_ptr(x), d_in, w_ptrs, y_ptrs, ld_y, n, N, d_in, d_out, _stream())
-        check(rc, "rqhip_t5_proj_fwd")
+        rc = fn(_ptr(x), d_in, w_ptrs, y_ptrs, ld_y, n, N, d_in, d_out, _stream())
+        check(rc, fn_name)
     return tuple(outs)
 
 
-def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None):
+def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None, *, arith: str = "fp32"):
     """The gradients of t5_proj_fwd in one call of at most two launches (rqhip_t5_proj_bwd) -> (d_x, [d_w[0], ...]).
     d_ys: n upstream gradients, each of y[j]'s shape or None; a None contributes nothing to d_x and gets no d_w[j].  d_x
     (x's shape) is None without need_x or when every d_ys[j] is None; d_w[j] is None where need_w[j] (default: every
-    weight) is false.  No atomics: the same bits on every run."""
+    weight) is false.  No atomics: the same bits on every run.  arith: "fp32" or "bf16", as t5_proj_fwd's
+    (rqhip_t5_proj_bwd_bf16)."""
     who = "t5_proj_bwd"
+    fn, fn_name = _arith_entry(who, arith)
     shape = x.shape
     x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights)
     n = len(weights)
@@ -956,9 +980,8 @@ def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None):
         g_ptrs = (C.c_void_p * n)(*[_ptr(g) for g in d_ys])
         ld_dy = (C.c_int64 * n)(*([d_out] * n))
         dw_ptrs = (C.c_void_p * n)(*[_ptr(g) for g in d_w])
-        rc = _lib.lib().rqhip_t5_proj_bwd(_ptr(x), d_in, w_ptrs, g_ptrs, ld_dy, n, N, d_in, d_out, _ptr(d_x), dw_ptrs,
-                                          _stream())
-        check(rc, "rqhip_t5_proj_bwd")
+        rc = fn(_ptr(x), d_in, w_ptrs, g_ptrs, ld_dy, n, N, d_in, d_out, _ptr(d_x), dw_ptrs, _stream())
+        check(rc, fn_name)
     return d_x, d_w
 
 

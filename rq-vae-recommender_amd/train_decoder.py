@@ -19,7 +19,12 @@ What differs:
     kernel does not implement the shape (modules/model.py, modules/t5.py).
   * clip, schedule and AdamW run on the device (rqhip/optim.py:FlatAdamW with the InverseSquareRootScheduler attached);
     the loss is read back every `log_every` iterations only, next to `optimizer.grad_norm` and `optimizer.device_lr()`.
-  * amp=True raises: the kernels are fp32.  push_vae_to_hf=True raises: it needs the network.  Datasets other than
+  * amp=True with mixed_precision_type="bf16" sets `model.matmul_arith = "bf16"` (modules/t5.py): the matrix products
+    of the "hip" feed-forward, and of the "hip" projections where `model.proj_impl` selects them (train has no parameter
+    for it: the model's default is "torch"), take bf16 operands and accumulate in fp32.  There is no autocast: weights,
+    activations, gradients, the checkpoint, the attention, the norms, the heads, the embedding and the optimizer stay
+    fp32, and the "torch" bodies are not affected.  amp=True with any other type raises: those kernels are fp32 or
+    bf16-operand only.  push_vae_to_hf=True raises: it needs the network.  Datasets other than
     AMAZON raise, as in the reference.
 wandb is optional: with `wandb_logging=True` and no wandb module, metrics are printed.
 
@@ -125,10 +130,11 @@ def train(
     del split_batches, vae_hf_model_name
     if dataset != RecDataset.AMAZON:
         raise Exception(f"Dataset currently not supported: {dataset}.")
-    if amp:
+    if amp and mixed_precision_type != "bf16":
         raise NotImplementedError(
-            f"amp=True ({mixed_precision_type}): the fused T5 kernels (attention, add/norm, feed-forward, heads, embedding) "
-            "and the device optimizer are fp32 only")
+            f"amp=True ({mixed_precision_type}): the fused T5 kernels (attention, add/norm, heads, embedding) and the "
+            'device optimizer are fp32 only; the feed-forward and projection kernels are fp32 or, with '
+            'mixed_precision_type="bf16", bf16-operand')
     if push_vae_to_hf:
         raise NotImplementedError("push_vae_to_hf=True needs the network (huggingface_hub); upload the RQ-VAE checkpoint "
                                   "separately")
@@ -173,6 +179,8 @@ def train(
         num_user_bins=num_user_bins).to(device)
     model.attention_impl, model.norm_impl, model.ffn_impl = attention_impl, norm_impl, ffn_impl
     model.head_impl, model.embed_impl = head_impl, embed_impl
+    if amp:
+        model.matmul_arith = "bf16"
 
     optimizer = FlatAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     lr_scheduler = InverseSquareRootScheduler(optimizer=optimizer, warmup_steps=10000)

@@ -11,14 +11,17 @@ and, for the kernel path, with either attention implementation (--attention): "t
 one ops.t5_attention launch per attention call and slab K/V (modules/t5.py).  `--attention both` alternates the two
 arms --runs times in one process and ends with one summary line of the medians over the runs.  --proj sets proj_impl
 (modules/t5.py) for every arm: "hip" makes the attention projections grouped ops.t5_proj_fwd launches, the decode
-step's K/V written by them straight into the cache slabs.
+step's K/V written by them straight into the cache slabs; --ffn sets ffn_impl likewise.  --arith sets matmul_arith, the
+arithmetic of those two "hip" forms ("bf16": bf16 operands, fp32 accumulation); `--arith both` alternates fp32 and bf16
+--runs times on one --attention arm of the kernel path and ends with a summary line.
 
 Device events around each generate after a warm-up; prints one JSON line per path (ms per generate, users/s).
 Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --stats` run of this tool
 (--path one of them, one --attention arm, --iters small).
 
     python tools/bench_generate.py [--path kernel|reference|both] [--attention torch|hip|both] [--runs 5]
-                                   [--proj torch|hip] [--warmup 3] [--iters 10]
+                                   [--proj torch|hip] [--ffn torch|hip] [--arith fp32|bf16|both] [--warmup 3]
+                                   [--iters 10]
 """
 import argparse
 import json
@@ -105,7 +108,10 @@ def main():
                     help="default: both, or kernel with --attention both")
     ap.add_argument("--attention", choices=["torch", "hip", "both"], default="torch")
     ap.add_argument("--proj", choices=["torch", "hip"], default="torch", help="proj_impl of every arm")
-    ap.add_argument("--runs", type=int, default=5, help="alternations of the two arms with --attention both")
+    ap.add_argument("--ffn", choices=["torch", "hip"], default="torch", help="ffn_impl of every arm")
+    ap.add_argument("--arith", choices=["fp32", "bf16", "both"], default="fp32",
+                    help='matmul_arith of the "hip" projections and feed-forward')
+    ap.add_argument("--runs", type=int, default=5, help="alternations of the two arms with --attention / --arith both")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
@@ -113,9 +119,30 @@ def main():
         args.path = "kernel" if args.attention == "both" else "both"
     dev = torch.device("cuda")
     model, batch = build(dev)
-    model.proj_impl = args.proj
+    model.proj_impl, model.ffn_impl = args.proj, args.ffn
     B = batch.sem_ids.shape[0]
     paths = ["kernel", "reference"] if args.path == "both" else [args.path]
+    if args.arith == "both":
+        if args.attention == "both" or args.path not in ("kernel", "both"):
+            ap.error("--arith both compares the two arithmetics on one --attention arm of --path kernel")
+        model.attention_impl = args.attention
+        medians = {"fp32": [], "bf16": []}
+        for run in range(args.runs):
+            for arm in ("fp32", "bf16"):
+                model.matmul_arith = arm
+                med, best = time_path(model, batch, args.warmup, args.iters)
+                medians[arm].append(med)
+                print(json.dumps({"path": "kernel", "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
+                                  "arith": arm, "run": run, "batch": B, "ms_per_generate_median": round(med, 3),
+                                  "ms_per_generate_min": round(best, 3), "iters": args.iters}), flush=True)
+        mid = {arm: sorted(v)[len(v) // 2] for arm, v in medians.items()}
+        print(json.dumps({"path": "kernel", "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
+                          "arith": "both", "runs": args.runs, "batch": B, "run_medians_fp32": [round(v, 3) for v in medians["fp32"]],
+                          "run_medians_bf16": [round(v, 3) for v in medians["bf16"]],
+                          "ms_per_generate_fp32": round(mid["fp32"], 3), "ms_per_generate_bf16": round(mid["bf16"], 3),
+                          "bf16_over_fp32": round(mid["bf16"] / mid["fp32"], 4)}), flush=True)
+        return
+    model.matmul_arith = args.arith
     if args.attention == "both":
         if args.path != "kernel":
             ap.error("--attention both compares the two arms of --path kernel")
@@ -125,7 +152,8 @@ def main():
                 model.attention_impl = arm
                 med, best = time_path(model, batch, args.warmup, args.iters)
                 medians[arm].append(med)
-                print(json.dumps({"path": "kernel", "attention": arm, "proj": args.proj, "run": run, "batch": B,
+                print(json.dumps({"path": "kernel", "attention": arm, "proj": args.proj, "ffn": args.ffn,
+                                  "arith": args.arith, "run": run, "batch": B,
                                   "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),
                                   "iters": args.iters}), flush=True)
         mid = {arm: sorted(v)[len(v) // 2] for arm, v in medians.items()}
@@ -143,7 +171,8 @@ def main():
         finally:
             if path == "reference":
                 mm.ops.beam_step, mm._exponential_like = saved, saved_q
-        print(json.dumps({"path": path, "attention": args.attention, "proj": args.proj, "batch": B,
+        print(json.dumps({"path": path, "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
+                          "arith": args.arith, "batch": B,
                           "k": model.top_k_for_generation, "L": model.num_hierarchies,
                           "K": model.num_embeddings_per_hierarchy, "corpus": int(model.codebooks.shape[0]),
                           "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) in eight arms:
+tails: encoder T = 81, decoder T = 4) in ten arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
@@ -18,6 +18,10 @@ tails: encoder T = 81, decoder T = 4) in eight arms:
              mask product, gather, separator, BOS row) as one ops.sid_embed_fwd launch and one ops.sid_embed_bwd launch
   hip_train+norm+head+ffn+optim+embed+proj  the arm before it with proj_impl = "hip": the q / k / v, the o and the
              cross-attention K/V projections as grouped ops.t5_proj_fwd launches and ops.t5_proj_bwd calls of two launches
+  hip_train+norm+head+ffn+optim+embed+bf16  the seventh arm with matmul_arith = "bf16": the feed-forward's matrix
+             products on bf16 operands with fp32 accumulation (rqhip_t5_ffn_*_bf16), everything stored in fp32
+  hip_train+norm+head+ffn+optim+embed+proj+bf16  the eighth arm with matmul_arith = "bf16": the feed-forward and the
+             grouped projections on bf16 operands (rqhip_t5_ffn_*_bf16, rqhip_t5_proj_*_bf16)
 
 The arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
@@ -26,7 +30,8 @@ between two arms has to exceed), and the peak torch.cuda.max_memory_allocated of
 JSON line per arm plus a summary line; --out also writes them to a text file (profiles/retrieval_train_step_norm.txt
 holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run, profiles/retrieval_train_step_ffn.txt a
 five-arm run, profiles/retrieval_optim_tail.txt a six-arm run, profiles/retrieval_train_step_embed.txt a run of the sixth
-and seventh arm, profiles/retrieval_train_step_proj.txt runs of the last two; profiles/retrieval_train_step.txt is the
+and seventh arm, profiles/retrieval_train_step_proj.txt runs of the seventh and eighth,
+profiles/retrieval_train_step_bf16.txt runs of those two and their bf16 forms; profiles/retrieval_train_step.txt is the
 older two-arm run; none of them is to be overwritten or compared
 against: two arms are compared within one run only).
 --arms picks a subset, e.g. one arm under a kernel trace to count its launches per step.
@@ -56,12 +61,16 @@ ARMS = {"torch": ("torch", "torch", "torch", "torch", "torch"),
         "hip_train+norm+head+ffn": ("hip_train", "hip", "hip", "hip", "torch"),
         "hip_train+norm+head+ffn+optim": ("hip_train", "hip", "hip", "hip", "torch"),
         "hip_train+norm+head+ffn+optim+embed": ("hip_train", "hip", "hip", "hip", "torch"),
-        "hip_train+norm+head+ffn+optim+embed+proj": ("hip_train", "hip", "hip", "hip", "hip")}
+        "hip_train+norm+head+ffn+optim+embed+proj": ("hip_train", "hip", "hip", "hip", "hip"),
+        "hip_train+norm+head+ffn+optim+embed+bf16": ("hip_train", "hip", "hip", "hip", "torch"),
+        "hip_train+norm+head+ffn+optim+embed+proj+bf16": ("hip_train", "hip", "hip", "hip", "hip")}
+# arms with matmul_arith = "bf16"; the others "fp32"
+BF16 = ("hip_train+norm+head+ffn+optim+embed+bf16", "hip_train+norm+head+ffn+optim+embed+proj+bf16")
 # arms stepped by rqhip.optim.FlatAdamW; the others by torch.optim.AdamW
 FLAT_ADAMW = ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed",
-              "hip_train+norm+head+ffn+optim+embed+proj")
+              "hip_train+norm+head+ffn+optim+embed+proj") + BF16
 # arms with embed_impl = "hip"; the others "torch"
-EMBED_HIP = ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+proj")
+EMBED_HIP = ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+proj") + BF16
 
 
 def make_batch(B, items, L, K, N, dev, seed):
@@ -75,6 +84,7 @@ def block(model, state, batch, arm, warmup, iters):
     model.load_state_dict(state)
     model.attention_impl, model.norm_impl, model.head_impl, model.ffn_impl, model.proj_impl = ARMS[arm]
     model.embed_impl = "hip" if arm in EMBED_HIP else "torch"
+    model.matmul_arith = "bf16" if arm in BF16 else "fp32"
     model.train()
     if arm in FLAT_ADAMW:
         from rqhip.optim import FlatAdamW
@@ -132,6 +142,7 @@ def main():
         lines.append(json.dumps({"arm": arm, "attention_impl": ARMS[arm][0], "norm_impl": ARMS[arm][1],
                                  "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3], "proj_impl": ARMS[arm][4],
                                  **({"embed_impl": "hip"} if arm in EMBED_HIP else {}),
+                                 **({"matmul_arith": "bf16"} if arm in BF16 else {}),
                                  "optimizer": "FlatAdamW" if arm in FLAT_ADAMW else "torch.optim.AdamW", "batch": args.batch,
                                  "steps_timed": len(times[arm]),
                                  "ms_per_step_median": round(statistics.median(times[arm]), 3),
@@ -143,7 +154,9 @@ def main():
                  ("hip_train+norm+head", "hip_train+norm+head+ffn"),
                  ("hip_train+norm+head+ffn", "hip_train+norm+head+ffn+optim"),
                  ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed"),
-                 ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+proj")):
+                 ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+proj"),
+                 ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+bf16"),
+                 ("hip_train+norm+head+ffn+optim+embed+proj", "hip_train+norm+head+ffn+optim+embed+proj+bf16")):
         if a in arms and b in arms:
             summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
             summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)
