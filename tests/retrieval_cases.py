@@ -1,10 +1,11 @@
 """What the retrieval-model tests share: the accuracy gate, the bit comparisons, the synthetic batch, the small, tiny,
-default and fixture models, the switch between kernel implementations and the operator restatements of the beam step
-and of the attention inputs.
+default and fixture models, the switch between kernel implementations, the operator restatements of the beam step
+and of the attention inputs, and the log of a train-mode step's dropout masks with its replay on the operators.
 
 Test infrastructure like tests/parity_gate.py: imported by the tests and by tools/bench_retrieval_train.py and
 tools/bench_generate.py (which put tests/ on sys.path); the product package never imports it, and it imports the product
 only inside its functions."""
+import collections
 import contextlib
 import copy
 import functools
@@ -109,11 +110,12 @@ LAYERS = 2
 
 
 @functools.lru_cache(maxsize=None)
-def small_model(seed, d_ff, perturb_norms, device="cuda"):
+def small_model(seed, d_ff, perturb_norms, device="cuda", items=2):
     """(fp32 model on the device, its fp64 copy on the host, the batch on both) -- built once: d_model 64, 2 heads, 2
-    layers, K = 16, L = 3, batch 3 with one padded row; encoder T = 9, decoder T = 4."""
+    layers, K = 16, L = 3, batch 3 with one padded row; decoder T = 4, encoder T = 4 * items (three ids and the separator
+    per item of the history)."""
     from modules.model import EncoderDecoderRetrievalModel
-    B, items, L, K, N = 3, 2, 3, 16, 200
+    B, L, K, N = 3, 3, 16, 200
     g = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
     corpus = torch.randint(0, K, (N, L), generator=g)
@@ -348,3 +350,199 @@ def _padding(R, T, g):
     if R > 1:
         keep[1] = False
     return keep.to("cuda")
+
+
+# ---- train-mode steps: the dropout masks a step used, logged site by site, and their replay on the operators
+#
+# A site is one dropout of a forward.  Their order is the same on every path (modules/t5.py): per stack the input
+# embeddings, then per block the self-attention weights, the sub-layer output, (decoder) the cross-attention weights,
+# the sub-layer output, the feed-forward's inner activation, the sub-layer output -- the last of these is the final p_in
+# -- and the final norm's output.
+
+
+class SiteMismatch(AssertionError):
+    """A replay met a dropout the log does not hold, holds with another shape or rate, or left sites of the log over."""
+
+
+Site = collections.namedtuple("Site", "kind p keep seed")          # kind: attention, glue_in, glue_out, ffn, operator
+Call = collections.namedtuple("Call", "op direction seed p shapes")  # one spied ops call; seed: its value or None
+
+
+class MaskLog:
+    """The keep masks of one forward in chronological order (`sites`), and the fused ops calls that were spied while
+    they were recorded (`calls`, backward calls included)."""
+
+    def __init__(self, sites=(), calls=()):
+        self.sites, self.calls = list(sites), list(calls)
+
+    def __len__(self):
+        return len(self.sites)
+
+    def swapped(self, i, keep):
+        """A copy in which site i has the mask `keep`."""
+        assert keep.shape == self.sites[i].keep.shape and keep.dtype == torch.bool
+        sites = list(self.sites)
+        sites[i] = sites[i]._replace(keep=keep)
+        return MaskLog(sites, self.calls)
+
+    def without(self, i):
+        """A copy that lacks site i."""
+        return MaskLog(self.sites[:i] + self.sites[i + 1:], self.calls)
+
+    def fused(self, direction):
+        return [c for c in self.calls if c.direction == direction]
+
+
+def _dropped(x, keep, p):
+    return x * keep.to(x.device) * (1.0 / (1.0 - p))
+
+
+def _seed_value(seed):
+    return None if seed is None else int(seed)
+
+
+@contextlib.contextmanager
+def _patched(owner, **replacements):
+    saved = {name: getattr(owner, name) for name in replacements}
+    for name, fn in replacements.items():
+        setattr(owner, name, fn)
+    try:
+        yield
+    finally:
+        for name, fn in saved.items():
+            setattr(owner, name, fn)
+
+
+@contextlib.contextmanager
+def recording(draw_seed=0):
+    """Inside the block every dropout of a model step is logged -> the MaskLog.  Fused sites: the three ops entry
+    points the Functions of rqhip/autograd.py call are spied, with their _bwd counterparts, and a forward call's masks
+    are rebuilt from its own seed, p and shapes by the kernels' published decision (ops.t5_attention_dropout_keep, in
+    the conventions of test_gpu_t5_add_norm.py:_masks and test_gpu_t5_ffn.py:_keep).  Operator sites:
+    torch.nn.functional.dropout is a stand-in that draws an explicit Bernoulli mask from a generator seeded with
+    `draw_seed` and applies x * keep * (1 / (1 - p))."""
+    from rqhip import ops
+    log = MaskLog()
+    g = torch.Generator().manual_seed(draw_seed)
+    o = {n: getattr(ops, n) for n in ("t5_attention_fwd_train", "t5_attention_bwd", "t5_add_norm_fwd", "t5_add_norm_bwd",
+                                      "t5_ffn_fwd", "t5_ffn_bwd")}
+
+    def site(kind, p, keep, seed, shape):
+        log.sites.append(Site(kind, float(p), keep.view(shape), _seed_value(seed)))
+
+    def attention_fwd(q, k, v, n_heads, **kw):
+        p, seed = kw.get("p", 0.0), kw.get("seed")
+        log.calls.append(Call("attention", "fwd", _seed_value(seed), (p,), (q.shape, k.shape, v.shape)))
+        if p > 0:
+            R, Tq, Tk = q.shape[0], q.shape[1], k.shape[1]
+            site("attention", p, ops.t5_attention_dropout_keep(seed, R, n_heads, Tq, Tk, p), seed, (R, n_heads, Tq, Tk))
+        return o["t5_attention_fwd_train"](q, k, v, n_heads, **kw)
+
+    def attention_bwd(q, k, v, out, lse, d_out, n_heads, **kw):
+        log.calls.append(Call("attention", "bwd", _seed_value(kw.get("seed")), (kw.get("p", 0.0),),
+                              (q.shape, k.shape, v.shape)))
+        return o["t5_attention_bwd"](q, k, v, out, lse, d_out, n_heads, **kw)
+
+    def add_norm_fwd(x, y, w, eps, p_in=0.0, p_out=0.0, seed=None):
+        from test_gpu_t5_add_norm import _masks
+        log.calls.append(Call("glue", "fwd", _seed_value(seed), (p_in, p_out), (y.shape,)))
+        d = y.shape[-1]
+        keep_in, keep_out = _masks(seed, y.numel() // d, d, p_in, p_out) if p_in > 0 or p_out > 0 else (None, None)
+        if keep_in is not None:
+            site("glue_in", p_in, keep_in, seed, y.shape)
+        if keep_out is not None:
+            site("glue_out", p_out, keep_out, seed, y.shape)
+        return o["t5_add_norm_fwd"](x, y, w, eps, p_in, p_out, seed)
+
+    def add_norm_bwd(x_new, rstd, w, d_n, d_xnew, p_in=0.0, p_out=0.0, seed=None, **kw):
+        log.calls.append(Call("glue", "bwd", _seed_value(seed), (p_in, p_out), (x_new.shape,)))
+        return o["t5_add_norm_bwd"](x_new, rstd, w, d_n, d_xnew, p_in, p_out, seed, **kw)
+
+    def ffn_fwd(x, wi, wo, p=0.0, seed=None, **kw):
+        from test_gpu_t5_ffn import _keep
+        F_ = wi.shape[0]
+        log.calls.append(Call("ffn", "fwd", _seed_value(seed), (p,), (x.shape, x.shape[:-1] + (F_,))))
+        keep = _keep(seed, x.numel() // x.shape[-1], F_, p)
+        if keep is not None:
+            site("ffn", p, keep, seed, x.shape[:-1] + (F_,))
+        return o["t5_ffn_fwd"](x, wi, wo, p, seed, **kw)
+
+    def ffn_bwd(x, wi, wo, h, d_y, p=0.0, seed=None, **kw):
+        log.calls.append(Call("ffn", "bwd", _seed_value(seed), (p,), (x.shape, h.shape)))
+        return o["t5_ffn_bwd"](x, wi, wo, h, d_y, p, seed, **kw)
+
+    def drawn(input, p=0.5, training=True, inplace=False):
+        if not training or p == 0:
+            return input
+        keep = torch.rand(input.shape, generator=g) >= p
+        log.sites.append(Site("operator", float(p), keep.to(input.device), None))
+        return _dropped(input, keep, p)
+
+    with _patched(ops, t5_attention_fwd_train=attention_fwd, t5_attention_bwd=attention_bwd, t5_add_norm_fwd=add_norm_fwd,
+                  t5_add_norm_bwd=add_norm_bwd, t5_ffn_fwd=ffn_fwd, t5_ffn_bwd=ffn_bwd), _patched(F, dropout=drawn):
+        yield log
+
+
+@contextlib.contextmanager
+def replaying(log):
+    """Inside the block torch.nn.functional.dropout hands out the masks of `log` in order.  A dropout the log does not
+    hold, or holds with another shape or rate, raises SiteMismatch with the site's index and shape; so does a block
+    that ends (without another error) with sites left over."""
+    at = [0]
+
+    def popped(input, p=0.5, training=True, inplace=False):
+        if not training or p == 0:
+            return input
+        i, shape = at[0], tuple(input.shape)
+        if i >= len(log.sites):
+            raise SiteMismatch(f"site {i}: the model drops a tensor of shape {shape} at p = {p}, the log ends after "
+                               f"{len(log.sites)} sites")
+        s = log.sites[i]
+        if tuple(s.keep.shape) != shape or s.p != float(p):
+            raise SiteMismatch(f"site {i}: the model drops a tensor of shape {shape} at p = {p}, the log holds the "
+                               f"{s.kind} mask of shape {tuple(s.keep.shape)} at p = {s.p}")
+        at[0] += 1
+        return _dropped(input, s.keep, p)
+
+    with _patched(F, dropout=popped):
+        yield
+    if at[0] != len(log.sites):
+        s = log.sites[at[0]]
+        raise SiteMismatch(f"site {at[0]}: the log's {s.kind} mask of shape {tuple(s.keep.shape)} at p = {s.p} and "
+                           f"{len(log.sites) - at[0] - 1} sites behind it were never asked for")
+
+
+@contextlib.contextmanager
+def setting(model, *, attention="torch", norm="torch", ffn="torch", head="torch", embed="torch", proj="torch"):
+    """`impls` with the model's two other choices, embed_impl and proj_impl; after the block those are "torch" too."""
+    with impls(model, attention=attention, norm=norm, ffn=ffn, head=head):
+        try:
+            model.embed_impl, model.proj_impl = embed, proj
+            model._push_attention_impl()
+            yield model
+        finally:
+            model.embed_impl = model.proj_impl = "torch"
+
+
+def _train_step(model, batch, seed):
+    training = model.training
+    try:
+        return loss_and_grads(model.train(), batch, seed=seed)
+    finally:
+        model.train(training)
+        model.zero_grad(set_to_none=True)
+
+
+def record_step(model, batch, seed=None, draw_seed=0):
+    """One train-mode forward and backward of `model` as it is set up -> (loss, gradients, MaskLog).  `seed`:
+    torch.manual_seed before the step (the fused sites' seeds); `draw_seed`: the generator of the operator sites.  The
+    model comes back in the mode it had."""
+    with recording(draw_seed) as log:
+        loss, grads = _train_step(model, batch, seed)
+    return loss, grads, log
+
+
+def replay_step(model, batch, log):
+    """record_step's loss and gradients of `model`, every mask taken from `log` (replaying)."""
+    with replaying(log):
+        return _train_step(model, batch, None)
