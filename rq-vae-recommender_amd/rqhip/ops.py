@@ -546,8 +546,9 @@ def t5_attention_supported(dtype: torch.dtype, d_kv: int, n_heads: int, Tq: int,
 
 
 def _token_rows(t: Tensor, name: str, copy: bool = True) -> Tensor:
-    """A float32 [rows, T, inner] tensor whose tokens lie at one row stride (unit column stride); copies otherwise, or
-    raises when `copy` is False (the K/V slabs: the point of them is that nothing copies them)."""
+    """A float32 [rows, T, inner] tensor whose tokens lie at one row stride (unit column stride) from a 16-byte boundary;
+    copies otherwise (also a contiguous view that starts off the boundary, which contiguous() alone hands back), or raises
+    when `copy` is False (the K/V slabs: the point of them is that nothing copies them)."""
     if t.dtype != torch.float32 or t.dim() != 3:
         raise RqHipError(f"t5_attention: {name} must be a float32 [rows, T, heads * 64] tensor, got {t.dtype} "
                          f"{tuple(t.shape)}")
@@ -555,7 +556,7 @@ def _token_rows(t: Tensor, name: str, copy: bool = True) -> Tensor:
         if not copy:
             raise RqHipError(f"t5_attention: {name} must be a 16-byte aligned [positions, rows, heads * 64] slab with "
                              f"one row stride (a multiple of 4), got strides {tuple(t.stride())}")
-        t = t.contiguous()
+        t = _aligned16(t.contiguous())
     return t
 
 

@@ -1,6 +1,7 @@
 """What the retrieval-model tests share: the accuracy gate, the bit comparisons, the synthetic batch, the small, tiny,
 default and fixture models, the switch between kernel implementations, the operator restatements of the beam step
-and of the attention inputs, and the log of a train-mode step's dropout masks with its replay on the operators.
+and of the attention inputs, the fused attention's operator references, gates and training case, and the log of a
+train-mode step's dropout masks with its replay on the operators.
 
 Test infrastructure like tests/parity_gate.py: imported by the tests and by tools/bench_retrieval_train.py and
 tools/bench_generate.py (which put tests/ on sys.path); the product package never imports it, and it imports the product
@@ -9,6 +10,7 @@ import collections
 import contextlib
 import copy
 import functools
+import types
 
 import numpy as np
 import torch
@@ -350,6 +352,139 @@ def _padding(R, T, g):
     if R > 1:
         keep[1] = False
     return keep.to("cuda")
+
+
+# ---- the fused attention against the operators: the inference kernel's reference and gate (test_gpu_t5_attention.py's
+# docstring), the training pair's reference, lse gate and case (test_gpu_t5_attention_backward.py's docstring)
+
+_EVAL = types.SimpleNamespace(dropout=0.0, training=False)
+
+F32_MIN = torch.finfo(torch.float32).min   # what is ADDED to a masked score, in the fp64 reference too
+
+
+def attention_operators(q, k, v, H, bias, keep, dtype):
+    """modules/t5.py's sequence (head transposes, _attend, transpose back) in `dtype`.  q [R, Tq, H*64], k / v
+    [R, Tk, H*64], bias [1, H, Tq, Tk] or None, keep [R, 1, Tq or 1, Tk] bool or None."""
+    from modules.t5 import _attend
+
+    def heads(x):
+        return x.to(dtype).view(x.shape[0], x.shape[1], H, 64).transpose(1, 2)
+
+    mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
+    bias = None if bias is None else bias.to(dtype)
+    if dtype == torch.float32:
+        out = _attend(_EVAL, heads(q), heads(k), heads(v), bias, mask)
+    else:  # _attend's sequence with its softmax in `dtype` too (its `.float()` is the identity in fp32 only)
+        scores = torch.matmul(heads(q), heads(k).transpose(-1, -2))
+        if bias is not None:
+            scores = scores + bias
+        if mask is not None:
+            scores = scores + mask
+        out = torch.matmul(torch.softmax(scores, dim=-1), heads(v))
+    return out.transpose(1, 2).reshape(q.shape[0], q.shape[1], -1)
+
+
+def attention_gate(name, out, q, k, v, H, bias, keep):
+    """Prints and asserts the inference kernel's gate (e_kernel <= 4 e_torch, equality at Tk = 1); k / v already expanded
+    to one K/V per query row.  Returns the largest |score|."""
+    out64 = attention_operators(q, k, v, H, bias, keep, torch.float64)
+    out32 = attention_operators(q, k, v, H, bias, keep, torch.float32)
+    e_kernel, e_torch = err(out, out64), err(out32, out64)
+    smax = float(torch.einsum("rihd,rjhd->rhij", q.double().view(*q.shape[:2], H, 64),
+                              k.double().view(*k.shape[:2], H, 64)).abs().max())
+    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
+    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f} max|score| {smax:.1f}")
+    assert torch.isfinite(out).all()
+    if k.shape[1] == 1:
+        assert e_kernel == e_torch
+    else:
+        assert e_kernel <= 4 * e_torch
+    return smax
+
+
+def attention_train_operators(q, k, v, H, table, offset, keep, drop, p, d_out, dtype):
+    """`_attend`'s sequence with its head transposes in `dtype` under autograd -> (out, lse, dq, dk, dv, dtable).
+    table [n_delta, H] or None (bias[h, i, j] = table[j - i + offset, h]); keep [R, 1, Tq or 1, Tk] bool or None;
+    drop [R, H, Tq, Tk] bool or None."""
+    Tq, Tk = q.shape[1], k.shape[1]
+    q, k, v = (x.detach().to(dtype).requires_grad_() for x in (q, k, v))
+    leaves = [q, k, v]
+
+    def heads(x):
+        return x.view(x.shape[0], x.shape[1], H, 64).transpose(1, 2)
+
+    scores = torch.matmul(heads(q), heads(k).transpose(-1, -2))
+    if table is not None:
+        table = table.detach().to(dtype).requires_grad_()
+        leaves.append(table)
+        i = torch.arange(Tq, device=q.device)[:, None]
+        j = torch.arange(Tk, device=q.device)[None, :]
+        scores = scores + table[(j - i) + offset].permute(2, 0, 1).unsqueeze(0)
+    if keep is not None:
+        scores = scores + (~keep).to(dtype) * F32_MIN
+    lse = torch.logsumexp(scores.detach(), dim=-1)
+    weights = torch.softmax(scores, dim=-1)
+    if drop is not None:
+        weights = weights * (drop.to(dtype) / (1 - p))
+    out = torch.matmul(weights, heads(v)).transpose(1, 2).reshape(q.shape[0], Tq, -1)
+    grads = torch.autograd.grad(out, leaves, d_out.to(dtype))
+    return (out.detach(), lse) + tuple(grads) + ((None,) if table is None else ())
+
+
+def lse_gate(name, lse, lse64):
+    """max|lse - lse64| / max|lse64| <= 1e-6, the error measure of the module docstring: a score is a 64-term fp32 dot
+    product whose error is relative to its terms, not to a sum that may cancel to nothing, so an element-wise relative
+    bound is not one fp32 can meet.  Rows with every key masked (|lse| = 3.4e38) are measured apart from the others, so
+    that their size does not hide the others' error."""
+    big = lse64.abs() > 1e30
+    for what, sel in (("masked rows", big), ("other rows", ~big)):
+        if bool(sel.any()):
+            e = err(lse[sel], lse64[sel])
+            print(f"{name} lse, {what}: e_kernel {e:.3e}")
+            assert e <= 1e-6, name
+
+
+def attention_train_case(name, q, k, v, H, *, table=None, offset=0, key_mask=None, causal=False, p=0.0, seed=None,
+                         seed_d_out=0, masked_row=None):
+    """One shape through fwd_train and bwd: p = 0 bits of the inference kernel, every gate (no floor: the rule of
+    test_gpu_t5_attention_backward.py's docstring), the fully masked row on its own, and a second run with identical
+    bits.  Returns the kernel's tensors."""
+    from rqhip import ops
+    R, Tq, Tk = q.shape[0], q.shape[1], k.shape[1]
+    dev = q.device
+    d_out = torch.randn(R, Tq, H * 64, generator=torch.Generator().manual_seed(1000 + seed_d_out)).to(dev)
+    kw = dict(bias_by_delta=table, bias_offset=offset, key_mask=key_mask, causal=causal)
+
+    def run():
+        out, lse = ops.t5_attention_fwd_train(q, k, v, H, p=p, seed=seed, **kw)
+        return (out, lse) + tuple(ops.t5_attention_bwd(q, k, v, out, lse, d_out, H, p=p, seed=seed, **kw))
+
+    with torch.no_grad():
+        got = run()
+        if p == 0:
+            assert same_bits(got[0], ops.t5_attention(q, k, v, H, **kw))
+    keep = None if key_mask is None else key_mask[:, None, None, :]
+    if causal:
+        tri = torch.ones(Tq, Tk, dtype=torch.bool, device=dev).tril()[None, None]
+        keep = tri if keep is None else keep & tri
+    drop = ops.t5_attention_dropout_keep(seed, R, H, Tq, Tk, p) if p > 0 else None
+    ref64 = attention_train_operators(q, k, v, H, table, offset, keep, drop, p, d_out, torch.float64)
+    ref32 = attention_train_operators(q, k, v, H, table, offset, keep, drop, p, d_out, torch.float32)
+    lse_gate(name, got[1], ref64[1])
+    gate(f"{name} out", got[0], ref32[0], ref64[0], 4, floor=0.0)
+    for n, x, x32, x64 in zip(("dq", "dk", "dv", "dtable"), got[2:], ref32[2:], ref64[2:]):
+        assert (x is None) == (x64 is None)
+        if x is not None:
+            gate(f"{name} {n}", x, x32, x64, 8, floor=0.0)
+    if masked_row is not None and Tk > 1:     # every key masked: uniform P, dS != 0, no special case anywhere
+        assert not bool(key_mask[masked_row].any()) and bool(ref64[2][masked_row].any())
+        for n, x, x32, x64 in zip(("dq", "dk", "dv"), got[2:5], ref32[2:5], ref64[2:5]):
+            gate(f"{name} {n} of the fully masked row", x[masked_row], x32[masked_row], x64[masked_row], 8, floor=0.0)
+    with torch.no_grad():
+        again = run()
+    for x, y in zip(got, again):
+        assert (x is None and y is None) or same_bits(x, y)
+    return got + (d_out,)
 
 
 # ---- train-mode steps: the dropout masks a step used, logged site by site, and their replay on the operators

@@ -5,58 +5,16 @@ operator generate, itself (seeded replay) and its own graph capture.
 Kernel gate: e = max|out - out64| / max|out64| for the kernel and for the operators in fp32 on the same inputs;
 e_kernel <= 4 e_torch (one rounding for another summation order and one for another exp, over the operators' own
 error), equality when Tk = 1 (both are exact).  Measured ratios: profiles/retrieval_generate.txt."""
-import types
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_golden
-from retrieval_cases import (CASES, GAP, _bias_module, _cache_free_generate, _close, _inputs, _padding, _Replay, build_model,
-                             compare_beams, default_model_and_batch, err, fixture_batch, same_bits)
+from retrieval_cases import (CASES, GAP, _bias_module, _cache_free_generate, _close, _inputs, _padding, _Replay,
+                             attention_gate as _gate, build_model, compare_beams, default_model_and_batch, fixture_batch,
+                             same_bits)
 
 pytestmark = pytest.mark.gpu
-
-_EVAL = types.SimpleNamespace(dropout=0.0, training=False)
-
-
-def _operators(q, k, v, H, bias, keep, dtype):
-    """modules/t5.py's sequence (head transposes, _attend, transpose back) in `dtype`.  q [R, Tq, H*64], k / v
-    [R, Tk, H*64], bias [1, H, Tq, Tk] or None, keep [R, 1, Tq or 1, Tk] bool or None."""
-    from modules.t5 import _attend
-
-    def heads(x):
-        return x.to(dtype).view(x.shape[0], x.shape[1], H, 64).transpose(1, 2)
-
-    mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
-    bias = None if bias is None else bias.to(dtype)
-    if dtype == torch.float32:
-        out = _attend(_EVAL, heads(q), heads(k), heads(v), bias, mask)
-    else:  # _attend's sequence with its softmax in `dtype` too (its `.float()` is the identity in fp32 only)
-        scores = torch.matmul(heads(q), heads(k).transpose(-1, -2))
-        if bias is not None:
-            scores = scores + bias
-        if mask is not None:
-            scores = scores + mask
-        out = torch.matmul(torch.softmax(scores, dim=-1), heads(v))
-    return out.transpose(1, 2).reshape(q.shape[0], q.shape[1], -1)
-
-
-def _gate(name, out, q, k, v, H, bias, keep):
-    """Prints and asserts the gate of the module docstring; k / v already expanded to one K/V per query row."""
-    out64 = _operators(q, k, v, H, bias, keep, torch.float64)
-    out32 = _operators(q, k, v, H, bias, keep, torch.float32)
-    e_kernel, e_torch = err(out, out64), err(out32, out64)
-    smax = float(torch.einsum("rihd,rjhd->rhij", q.double().view(*q.shape[:2], H, 64),
-                              k.double().view(*k.shape[:2], H, 64)).abs().max())
-    ratio = e_kernel / e_torch if e_torch > 0 else (0.0 if e_kernel == 0 else float("inf"))
-    print(f"{name}: e_kernel {e_kernel:.3e} e_torch {e_torch:.3e} ratio {ratio:.2f} max|score| {smax:.1f}")
-    assert torch.isfinite(out).all()
-    if k.shape[1] == 1:
-        assert e_kernel == e_torch
-    else:
-        assert e_kernel <= 4 * e_torch
-    return smax
 
 
 @pytest.mark.parametrize("H", [1, 6, 8])

@@ -6,108 +6,23 @@ Gate: e = max|x - x64| / max|x64| per tensor, for the kernel and for the same op
 inputs.  e_kernel <= 4 e_torch for `out` (the forward test's gate); e_kernel <= 8 e_torch for dq, dk, dv and the bias
 table's gradient (they pass through the recomputed P and through D: two more fp32 roundings than the operators' saved
 weights have).  A tensor whose fp64 reference is exactly zero must be exactly zero.  lse against fp64 logsumexp at 1e-6
-relative in the same measure (_lse_gate).  With dropout the reference multiplies the weights by keep / (1 - p), keep from
-ops.t5_attention_dropout_keep: the contract the kernels' three recomputations of the decision are held to.
+relative in the same measure (retrieval_cases.lse_gate).  With dropout the reference multiplies the weights by
+keep / (1 - p), keep from ops.t5_attention_dropout_keep: the contract the kernels' three recomputations of the decision
+are held to.
 The gate itself is retrieval_cases.gate with floor 0.  Measured ratios: profiles/retrieval_train_step.txt."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_golden
-from retrieval_cases import (CASES, _bias_module, _inputs, _padding, build_model, check_forward, default_model_and_batch, err,
-                             fixture_batch, gate, same_bits, seed as _seed)
+from retrieval_cases import (CASES, F32_MIN, _bias_module, _inputs, _padding, attention_train_case as _case, build_model,
+                             check_forward, default_model_and_batch, fixture_batch, gate, same_bits, seed as _seed)
 
 pytestmark = pytest.mark.gpu
-
-F32_MIN = torch.finfo(torch.float32).min   # what is ADDED to a masked score, in the fp64 reference too
-
-
-def _operators(q, k, v, H, table, offset, keep, drop, p, d_out, dtype):
-    """`_attend`'s sequence with its head transposes in `dtype` under autograd -> (out, lse, dq, dk, dv, dtable).
-    table [n_delta, H] or None (bias[h, i, j] = table[j - i + offset, h]); keep [R, 1, Tq or 1, Tk] bool or None;
-    drop [R, H, Tq, Tk] bool or None."""
-    Tq, Tk = q.shape[1], k.shape[1]
-    q, k, v = (x.detach().to(dtype).requires_grad_() for x in (q, k, v))
-    leaves = [q, k, v]
-
-    def heads(x):
-        return x.view(x.shape[0], x.shape[1], H, 64).transpose(1, 2)
-
-    scores = torch.matmul(heads(q), heads(k).transpose(-1, -2))
-    if table is not None:
-        table = table.detach().to(dtype).requires_grad_()
-        leaves.append(table)
-        i = torch.arange(Tq, device=q.device)[:, None]
-        j = torch.arange(Tk, device=q.device)[None, :]
-        scores = scores + table[(j - i) + offset].permute(2, 0, 1).unsqueeze(0)
-    if keep is not None:
-        scores = scores + (~keep).to(dtype) * F32_MIN
-    lse = torch.logsumexp(scores.detach(), dim=-1)
-    weights = torch.softmax(scores, dim=-1)
-    if drop is not None:
-        weights = weights * (drop.to(dtype) / (1 - p))
-    out = torch.matmul(weights, heads(v)).transpose(1, 2).reshape(q.shape[0], Tq, -1)
-    grads = torch.autograd.grad(out, leaves, d_out.to(dtype))
-    return (out.detach(), lse) + tuple(grads) + ((None,) if table is None else ())
-
-
-def _lse_gate(name, lse, lse64):
-    """max|lse - lse64| / max|lse64| <= 1e-6, the error measure of the module docstring: a score is a 64-term fp32 dot
-    product whose error is relative to its terms, not to a sum that may cancel to nothing, so an element-wise relative
-    bound is not one fp32 can meet.  Rows with every key masked (|lse| = 3.4e38) are measured apart from the others, so
-    that their size does not hide the others' error."""
-    big = lse64.abs() > 1e30
-    for what, sel in (("masked rows", big), ("other rows", ~big)):
-        if bool(sel.any()):
-            e = err(lse[sel], lse64[sel])
-            print(f"{name} lse, {what}: e_kernel {e:.3e}")
-            assert e <= 1e-6, name
 
 
 def _gate(name, got, ref32, ref64, factor):
     gate(name, got, ref32, ref64, factor, floor=0.0)       # no floor here: the docstring's rule
-
-
-def _case(name, q, k, v, H, *, table=None, offset=0, key_mask=None, causal=False, p=0.0, seed=None, seed_d_out=0,
-          masked_row=None):
-    """One shape through fwd_train and bwd: p = 0 bits of the inference kernel, every gate, the fully masked row on its
-    own, and a second run with identical bits.  Returns the kernel's tensors."""
-    from rqhip import ops
-    R, Tq, Tk = q.shape[0], q.shape[1], k.shape[1]
-    dev = q.device
-    d_out = torch.randn(R, Tq, H * 64, generator=torch.Generator().manual_seed(1000 + seed_d_out)).to(dev)
-    kw = dict(bias_by_delta=table, bias_offset=offset, key_mask=key_mask, causal=causal)
-
-    def run():
-        out, lse = ops.t5_attention_fwd_train(q, k, v, H, p=p, seed=seed, **kw)
-        return (out, lse) + tuple(ops.t5_attention_bwd(q, k, v, out, lse, d_out, H, p=p, seed=seed, **kw))
-
-    with torch.no_grad():
-        got = run()
-        if p == 0:
-            assert same_bits(got[0], ops.t5_attention(q, k, v, H, **kw))
-    keep = None if key_mask is None else key_mask[:, None, None, :]
-    if causal:
-        tri = torch.ones(Tq, Tk, dtype=torch.bool, device=dev).tril()[None, None]
-        keep = tri if keep is None else keep & tri
-    drop = ops.t5_attention_dropout_keep(seed, R, H, Tq, Tk, p) if p > 0 else None
-    ref64 = _operators(q, k, v, H, table, offset, keep, drop, p, d_out, torch.float64)
-    ref32 = _operators(q, k, v, H, table, offset, keep, drop, p, d_out, torch.float32)
-    _lse_gate(name, got[1], ref64[1])
-    _gate(f"{name} out", got[0], ref32[0], ref64[0], 4)
-    for n, x, x32, x64 in zip(("dq", "dk", "dv", "dtable"), got[2:], ref32[2:], ref64[2:]):
-        assert (x is None) == (x64 is None)
-        if x is not None:
-            _gate(f"{name} {n}", x, x32, x64, 8)
-    if masked_row is not None and Tk > 1:     # every key masked: uniform P, dS != 0, no special case anywhere
-        assert not bool(key_mask[masked_row].any()) and bool(ref64[2][masked_row].any())
-        for n, x, x32, x64 in zip(("dq", "dk", "dv"), got[2:5], ref32[2:5], ref64[2:5]):
-            _gate(f"{name} {n} of the fully masked row", x[masked_row], x32[masked_row], x64[masked_row], 8)
-    with torch.no_grad():
-        again = run()
-    for x, y in zip(got, again):
-        assert (x is None and y is None) or same_bits(x, y)
-    return got + (d_out,)
 
 
 def _encoder(T, H, p=0.0, seed=None):
