@@ -340,6 +340,60 @@ int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const f
                            const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *d_q, float *d_k,
                            float *d_v, float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream);
 
+/* The same attention beyond 256 tokens (csrc/t5_attention_long.hip): inference, training forward and backward for
+ * 1 <= Tq, Tk <= 2048 (rqhip_t5_attention_long_supported: d_kv = 64, any H >= 1; shorter lengths are accepted too).  The
+ * mathematics, the T5 semantics, q / k / v / out, bias_by_delta, bias_offset, key_mask, causal, the K/V groups (R / Rk
+ * query rows read group b) and the dropout decision are those of rqhip_t5_attention* above; the bits are not, because the
+ * keys are walked in chunks of RQHIP_T5_ATTENTION_LONG_CHUNK with an online softmax, by workgroups of
+ * RQHIP_T5_ATTENTION_LONG_QBLOCK query rows that never hold more than one chunk of K/V in LDS.  Dense K/V only: past must
+ * be 0 and anc NULL (else RQHIP_EUNSUPPORTED; the cached decode step never has more keys than levels and stays on
+ * rqhip_t5_attention).
+ *   Forward, per query row and per chunk of keys, ascending, from m = -inf, l = 0, o = 0:
+ *     s_j = q . k_j + bias (+ finfo(float32).min when masked);  m' = max(m, max_j s_j);  alpha = expf(m - m');
+ *     p_j = expf(s_j - m');  l = l * alpha + sum_j p_j;  p_j = 0 where the dropout drops (i, j);
+ *     o = o * alpha + sum_j p_j v_j (the chunk's sum formed from zero, keys ascending);  m = m'
+ *   and out = o / l behind the last chunk.  A score (and, in the backward, a dP) is four chains of sixteen products
+ *   each, features ascending, added as (c0 + c1) + (c2 + c3): shorter chains round less where scores reach 40, and the
+ *   backward's scores have the forward's bits.  The backward likewise forms each chunk's share of d_q, d_k and d_v from
+ *   zero and adds the chunks in ascending order.  The dropout mask is applied to the UNNORMALISED chunk weights while l
+ *   accumulates every weight, dropped or not; the scale 1.0f / (1.0f - (float)p) multiplies out = o / l once, at the end
+ *   (training forward only).  No chunk is skipped under `causal`: a row with every key masked is the uniform average of
+ *   ALL Tk rows of V, as with the operators.
+ *   rqhip_t5_attention_long_fwd_train (Rk = R): out, lse [R, H, Tq] = m + log(l), and ml [R, H, Tq, 2] = the pair
+ *     (m, l), which the backward reads: lse cannot carry log(l) beside m = -FLT_MAX.
+ *   rqhip_t5_attention_long_bwd (Rk = R): d_q [R, Tq, H * 64], d_k, d_v [R, Tk, H * 64] (dense) and, with a bias table,
+ *     d_bias_by_delta [n_delta, H] (zero outside the deltas of the call).  P_ij = expf(s_ij - m_i) / l_i is recomputed;
+ *     dP, dS, dQ, dK, dV as in rqhip_t5_attention_bwd.  D_i is sum_j P_ij dP_ij from a first loop over the keys, not
+ *     dO_i . O_i: it is made of the very dP it is subtracted from, so a row with one live key (P = 1, the others exactly
+ *     0) has D = dP and dS = 0 exactly, and the rounding of the 64-term products cancels in dP - D.  out and lse stay part
+ *     of the call (what autograd saves) and must be non-NULL.  A query-major launch writes d_q, D and per-workgroup sums
+ *     of dS along the diagonals j - i, a key-major launch d_k and d_v, a small launch adds the diagonal sums in ascending
+ *     (row, workgroup) order.  Nothing of size Tq x Tk is stored: `workspace` (16-byte aligned,
+ *     rqhip_t5_attention_long_bwd_workspace_bytes(R, H, Tq, Tk) bytes, which grow with R * H * (Tq + Tk)) holds D and at
+ *     most four diagonal rows per (row, head).
+ * Tq <= Tk with a bias table or causal.  Pointers 16-byte aligned, strides multiples of 4; every argument check precedes
+ * the first HIP call.  No float atomics, fixed reduction orders: the same bits on every run, and a row's bits depend on
+ * Tq, Tk and that row's data only (not on R, the beams or the grid).  No allocation, copy, memset or sync. */
+#define RQHIP_T5_ATTENTION_LONG_CHUNK 128   /* keys per chunk */
+#define RQHIP_T5_ATTENTION_LONG_QBLOCK 64   /* query rows per workgroup */
+int rqhip_t5_attention_long_supported(int d_kv, int H, int Tq, int Tk);
+int rqhip_t5_attention_long(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, int64_t R,
+                            int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta,
+                            int bias_offset, const uint8_t *key_mask, int causal, int past, const int32_t *anc, float *out,
+                            int64_t ld_out, rqhip_stream_t stream);
+int rqhip_t5_attention_long_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                      int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta,
+                                      int n_delta, int bias_offset, const uint8_t *key_mask, int causal, double p,
+                                      const int64_t *seed, float *out, int64_t ld_out, float *lse, float *ml,
+                                      rqhip_stream_t stream);
+size_t rqhip_t5_attention_long_bwd_workspace_bytes(int64_t R, int H, int Tq, int Tk);
+int rqhip_t5_attention_long_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                const float *out, int64_t ld_out, const float *lse, const float *ml, const float *d_out,
+                                int64_t ld_do, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
+                                const float *bias_by_delta, int n_delta, int bias_offset, const uint8_t *key_mask,
+                                int causal, double p, const int64_t *seed, float *d_q, float *d_k, float *d_v,
+                                float *d_bias_by_delta, void *workspace, size_t workspace_bytes, rqhip_stream_t stream);
+
 /* "Add-norm": the glue between two T5 sub-layers in one launch (csrc/t5_add_norm.hip; modules/t5.py, norm_impl = "hip"):
  * the dropout of a sub-layer's output y, the residual add, the NEXT RMS norm and, behind a stack's final norm, its
  * dropout.  x (the residual stream, or NULL), y, x_new, n are dense [N, d] fp32, w [d], rstd [N]; all arithmetic is fp32

@@ -7,6 +7,9 @@ stacks whenever they are run: `model.attention_impl` ("torch", the default, "hip
 `model.ffn_impl` and `model.proj_impl` ("torch", the default, or "hip"; the last groups the attention projections, the
 cross-attention K/V of `generate` and the K/V its decode steps write into the cache included).  What each replaces and
 when it is taken: modules/t5.py.
+`model.attention_long_impl` ("torch", the default, or "hip") goes to both stacks with them: with "hip" beside a fused
+`attention_impl`, an attention call beyond the 256 tokens of csrc/t5_attention.hip is a call of
+csrc/t5_attention_long.hip (up to 2048 tokens) instead of the operators, call by call (modules/t5.py).
 `model.matmul_arith` ("fp32", the default, or "bf16") goes to both stacks with them: the arithmetic of the "hip"
 feed-forward and the "hip" projections (bf16 operands, fp32 accumulation, fp32 storage; modules/t5.py).  It has no
 effect on the "torch" bodies, nor on the attention, the norms, the heads or the embedding, which stay fp32.
@@ -113,6 +116,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self._prefix_index: Optional[SemIdPrefixIndex] = None
         self._prefix_key = None
         self.attention_impl = "torch"  # or "hip" / "hip_train"; handed to both T5 stacks whenever they are run
+        self.attention_long_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.norm_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.head_impl = "torch"  # or "hip": the heads and their losses of `forward` as one fused call
         self.ffn_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
@@ -169,7 +173,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
     def _push_attention_impl(self) -> None:
         if self.matmul_arith not in MATMUL_ARITHS:
             raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
-        for name in ("attention_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith"):
+        for name in ("attention_impl", "attention_long_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith"):
             for stack in (self.encoder.encoder, self.t5_decoder):
                 setattr(stack, name, getattr(self, name))
 
@@ -339,7 +343,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         x = self.bos_token.unsqueeze(0).expand(B, 1, -1)
         self_kv: Optional[List] = None
         slabs = None
-        if dec.hip_attention_active(enc_out, 1, self.num_hierarchies, enc_out.shape[1]):
+        if dec.hip_attention_active(enc_out, 1, self.num_hierarchies, enc_out.shape[1], cached=True):
             slabs = dec.new_decode_cache(self.num_hierarchies, B * k, enc_out.device)
         ids = scores = None
         for h in range(self.num_hierarchies):

@@ -34,6 +34,15 @@ operators run, silently.  The module tree and the state dict are the same on eve
   weights, and one backward launch that recomputes them.  In train mode with dropout_rate > 0 the attention-weight
   dropout happens in the kernel; every other dropout stays torch's.  It needs one K/V per query row (beams = 1), no
   operator-format cache and a shape the backward supports.  A decode_cache under grad raises.
+  `attention_long_impl` = "hip" (default "torch") goes with either: the kernel above stops at 256 queries or keys, and
+  a forward with a longer attention call falls back to the operators as a whole.  With "hip" each attention call is
+  chosen on its own: the kernel above where it supports the call's (Tq, Tk), else csrc/t5_attention_long.hip
+  (ops.t5_attention_long, autograd.T5AttentionLongFunction; up to 2048 tokens, the keys walked in chunks with an online
+  softmax, nothing of size Tq x Tk stored).  In a long-history decoder forward the self-attention stays on the short
+  kernel and the cross-attention is a long call; in `generate` the cached self-attention (never more keys than levels)
+  stays on the short kernel and slabs, and the cross-attention over the encoder output is ONE long launch per block and
+  step, the beams of a user as the query rows of one K/V group.  With the default every answer and every launch is what
+  it was without the attribute.
 - `norm_impl` = "hip": the glue -- the dropout of a sub-layer's output, the residual add and the next sub-layer's RMS
   norm -- is ONE autograd.T5AddNormFunction call (csrc/t5_add_norm.hip), in eval and train mode, with and without grad:
   2 * layers + 1 calls per encoder forward, 3 * layers + 1 per decoder forward, the first on the input embeddings
@@ -71,11 +80,12 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops
-from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5FFNBf16Function, T5FFNFunction, T5ProjBf16Function,
-                            T5ProjFunction)
+from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5AttentionLongFunction, T5FFNBf16Function,
+                            T5FFNFunction, T5ProjBf16Function, T5ProjFunction)
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
+ATTENTION_LONG_IMPLS = ("torch", "hip")
 NORM_IMPLS = ("torch", "hip")
 FFN_IMPLS = ("torch", "hip")
 PROJ_IMPLS = ("torch", "hip")
@@ -323,6 +333,7 @@ class _HipAttention:
                  cache: Optional[T5DecodeCache], train: bool, proj) -> None:
         self.train = train
         self.proj = proj
+        self.long = stack.long_attention()  # calls the short kernel does not support go to the long one
         self.p = float(stack.config.dropout_rate) if train and stack.training else 0.0
         self.cache = cache
         self.past = 0 if cache is None else cache.pos
@@ -334,11 +345,15 @@ class _HipAttention:
 
     def _launch(self, module: T5Attention, q: Tensor, k: Tensor, v: Tensor, table: Optional[Tensor], offset: int,
                 key_mask: Optional[Tensor], causal: bool) -> Tensor:
+        long = self.long and not ops.t5_attention_supported(q.dtype, module.d_kv, module.n_heads, q.shape[1],
+                                                            k.shape[1])
         if self.train:
-            return T5AttentionFunction.apply(q, k, v, table, module.n_heads, offset, key_mask, causal, self.p,
-                                             _draw_seed(self.p, q.device))
-        return ops.t5_attention(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset, key_mask=key_mask,
-                                causal=causal)
+            function = T5AttentionLongFunction if long else T5AttentionFunction
+            return function.apply(q, k, v, table, module.n_heads, offset, key_mask, causal, self.p,
+                                  _draw_seed(self.p, q.device))
+        attention = ops.t5_attention_long if long else ops.t5_attention
+        return attention(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset, key_mask=key_mask,
+                         causal=causal)
 
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
         """One launch; with a decode cache the K/V projections go straight into block i's slabs."""
@@ -437,6 +452,7 @@ class T5Stack(nn.Module):
         self.final_layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         self.dropout = nn.Dropout(config.dropout_rate)
         self.attention_impl = "torch"  # or "hip" / "hip_train": see the module docstring
+        self.attention_long_impl = "torch"  # or "hip": the fused attention beyond 256 tokens (module docstring)
         self.norm_impl = "torch"  # or "hip": see the module docstring
         self.ffn_impl = "torch"  # or "hip": see the module docstring
         self.proj_impl = "torch"  # or "hip": see the module docstring
@@ -455,31 +471,46 @@ class T5Stack(nn.Module):
                 for y in _project(fused, encoder_hidden_states, linears[s:s + ops.T5_PROJ_MAX_GROUP])]
         return [(att._heads(outs[2 * i]), att._heads(outs[2 * i + 1])) for i, att in enumerate(atts)]
 
+    def long_attention(self) -> bool:
+        """attention_long_impl == "hip", validated."""
+        if self.attention_long_impl not in ATTENTION_LONG_IMPLS:
+            raise ValueError(f"attention_long_impl must be one of {ATTENTION_LONG_IMPLS}, got "
+                             f"{self.attention_long_impl!r}")
+        return self.attention_long_impl == "hip"
+
+    def _call_supported(self, short, dtype, query_length: int, key_length: int, long: bool) -> bool:
+        """Whether one attention call has a kernel: the existing one (`short`: its support table), else, with `long`,
+        the long one."""
+        cfg = self.config
+        return short(dtype, cfg.d_kv, cfg.num_heads, query_length, key_length) or (
+            long and ops.t5_attention_long_supported(dtype, cfg.d_kv, cfg.num_heads, query_length, key_length))
+
     def hip_attention_active(self, x: Tensor, query_length: int, key_length: int,
-                             cross_length: Optional[int] = None) -> bool:
-        """Whether a forward of x with these lengths takes the "hip" path (module docstring)."""
+                             cross_length: Optional[int] = None, cached: bool = False) -> bool:
+        """Whether a forward of x with these lengths takes the "hip" path (module docstring).  `cached`: the
+        self-attention reads a decode cache, which only the existing kernel does."""
         if self.attention_impl not in ATTENTION_IMPLS:
             raise ValueError(f"attention_impl must be one of {ATTENTION_IMPLS}, got {self.attention_impl!r}")
+        long = self.long_attention()
         if self.attention_impl not in ("hip", "hip_train") or not x.is_cuda or torch.is_grad_enabled():
             return False
         if self.training and self.config.dropout_rate > 0:
             return False
-        cfg = self.config
-        ok = ops.t5_attention_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, key_length)
+        ok = self._call_supported(ops.t5_attention_supported, x.dtype, query_length, key_length, long and not cached)
         if ok and cross_length is not None:
-            ok = ops.t5_attention_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, cross_length)
+            ok = self._call_supported(ops.t5_attention_supported, x.dtype, query_length, cross_length, long)
         return ok
 
     def hip_train_active(self, x: Tensor, query_length: int, cross_kv: Optional[List[KV]]) -> bool:
         """Whether a forward of x under grad takes the "hip_train" path (module docstring)."""
+        long = self.long_attention()
         if self.attention_impl != "hip_train" or not x.is_cuda or not torch.is_grad_enabled():
             return False
-        cfg = self.config
-        ok = ops.t5_attention_bwd_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, query_length)
+        ok = self._call_supported(ops.t5_attention_bwd_supported, x.dtype, query_length, query_length, long)
         if ok and self.is_decoder:
             ck = cross_kv[0][0]
-            ok = ck.shape[0] == x.shape[0] and ck.dtype == x.dtype and ops.t5_attention_bwd_supported(
-                x.dtype, cfg.d_kv, cfg.num_heads, query_length, ck.shape[2])
+            ok = ck.shape[0] == x.shape[0] and ck.dtype == x.dtype and self._call_supported(
+                ops.t5_attention_bwd_supported, x.dtype, query_length, ck.shape[2], long)
         return ok
 
     def hip_norm_active(self, x: Tensor) -> bool:
@@ -532,6 +563,7 @@ class T5Stack(nn.Module):
                         past_key_values, cross_kv, decode_cache):
         """The attention body of this forward (module docstring): _HipAttention where it applies, else the operators."""
         R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
+        self.long_attention()  # an unknown attention_long_impl raises on every path
         if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
             if self.is_decoder and cross_kv is None:
                 cross_kv = self.cross_kv(encoder_hidden_states)
@@ -540,7 +572,7 @@ class T5Stack(nn.Module):
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, None, train=True,
                                      proj=self.proj_arm(inputs_embeds))
             cross_length = cross_kv[0][0].shape[2] if self.is_decoder else None
-            if self.hip_attention_active(inputs_embeds, T, past + T, cross_length):
+            if self.hip_attention_active(inputs_embeds, T, past + T, cross_length, cached=decode_cache is not None):
                 if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
                                                  or past >= decode_cache.steps or R > decode_cache.rows):
                     raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "

@@ -297,6 +297,31 @@ class T5AttentionFunction(torch.autograd.Function):
         return dq, dk, dv, dtable, None, None, None, None, None, None
 
 
+class T5AttentionLongFunction(torch.autograd.Function):
+    """T5AttentionFunction for the lengths beyond its kernel (ops.t5_attention_long_fwd_train / ops.t5_attention_long_bwd,
+    up to 2048 tokens): the same arguments and gradients.  Saved: q, k, v, out, the row log-sum-exp, each row's (max, sum)
+    pair, the table, the mask and the seed; the weights and the dropout decisions are recomputed chunk by chunk."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, bias_by_delta: Optional[Tensor], n_heads: int, bias_offset: int,
+                key_mask: Optional[Tensor], causal: bool, p: float, seed: Optional[Tensor]):
+        out, lse, ml = ops.t5_attention_long_fwd_train(q, k, v, n_heads, bias_by_delta=bias_by_delta,
+                                                       bias_offset=bias_offset, key_mask=key_mask, causal=causal, p=p,
+                                                       seed=seed)
+        ctx.save_for_backward(q, k, v, out, lse, ml, bias_by_delta, key_mask, seed)
+        ctx.call = (n_heads, bias_offset, causal, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        q, k, v, out, lse, ml, table, mask, seed = ctx.saved_tensors
+        n_heads, bias_offset, causal, p = ctx.call
+        dq, dk, dv, dtable = ops.t5_attention_long_bwd(q, k, v, out, lse, ml, d_out, n_heads, bias_by_delta=table,
+                                                       bias_offset=bias_offset, key_mask=mask, causal=causal, p=p,
+                                                       seed=seed)
+        return dq, dk, dv, dtable, None, None, None, None, None, None
+
+
 class T5AddNormFunction(torch.autograd.Function):
     """The glue between two T5 sub-layers (modules/t5.py, norm_impl = "hip") as one launch forward and one backward
     (ops.t5_add_norm_fwd / ops.t5_add_norm_bwd): apply(x or None, y, w, eps, p_in, p_out, seed) -> (x_new, n) with

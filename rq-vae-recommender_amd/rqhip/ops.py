@@ -725,6 +725,101 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
     return dq, dk, dv, dtable
 
 
+T5_ATTENTION_LONG_CHUNK = 128   # RQHIP_T5_ATTENTION_LONG_CHUNK: keys a workgroup holds in LDS at a time
+T5_ATTENTION_LONG_QBLOCK = 64   # RQHIP_T5_ATTENTION_LONG_QBLOCK: query rows of a workgroup
+
+
+def t5_attention_long_supported(dtype: torch.dtype, d_kv: int, n_heads: int, Tq: int, Tk: int) -> bool:
+    """Whether t5_attention_long, t5_attention_long_fwd_train and t5_attention_long_bwd implement this shape
+    (rqhip_t5_attention_long_supported): fp32, d_kv = 64, Tq and Tk <= 2048."""
+    return dtype == torch.float32 and bool(
+        _lib.lib().rqhip_t5_attention_long_supported(int(d_kv), int(n_heads), int(Tq), int(Tk)))
+
+
+def t5_attention_long(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
+                      bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False) -> Tensor:
+    """t5_attention's dense form for up to 2048 tokens in one launch (rqhip_t5_attention_long, csrc/t5_attention_long.hip):
+    the keys are walked in chunks of T5_ATTENTION_LONG_CHUNK with an online softmax.  q [R, Tq, n_heads * 64], k, v
+    [Rk, Tk, n_heads * 64], R a multiple of Rk; bias_by_delta, bias_offset, key_mask and causal as in t5_attention.  No
+    ancestor table and no `past`: the cached decode step stays on t5_attention."""
+    _need_gpu(q, k, v, bias_by_delta, key_mask)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _ = _attention_args("t5_attention_long", q, k, v, n_heads,
+                                                                                bias_by_delta, key_mask)
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_long(
+            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
+            _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
+            _ptr(key_mask), int(bool(causal)), 0, None, _ptr(out), inner, _stream())
+        check(rc, "rqhip_t5_attention_long")
+    return out
+
+
+def t5_attention_long_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
+                                bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False,
+                                p: float = 0.0, seed: Optional[Tensor] = None):
+    """t5_attention_fwd_train for up to 2048 tokens in one launch (rqhip_t5_attention_long_fwd_train) -> (out
+    [R, Tq, n_heads * 64], lse [R, n_heads, Tq], ml [R, n_heads, Tq, 2]: each row's final running max and sum, which the
+    backward reads).  The dropout decision is t5_attention_dropout_keep(seed, ...), unchanged."""
+    _need_gpu(q, k, v, bias_by_delta, key_mask, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+        "t5_attention_long_fwd_train", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
+        lse = torch.empty((R, int(n_heads), Tq), dtype=torch.float32, device=dev)
+        ml = torch.empty((R, int(n_heads), Tq, 2), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_long_fwd_train(
+            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
+            _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
+            _ptr(key_mask), int(bool(causal)), float(p), seed_ptr, _ptr(out), inner, _ptr(lse), _ptr(ml), _stream())
+        check(rc, "rqhip_t5_attention_long_fwd_train")
+    return out, lse, ml
+
+
+def t5_attention_long_bwd_workspace_bytes(R: int, n_heads: int, Tq: int, Tk: int) -> int:
+    """The scratch t5_attention_long_bwd needs (rqhip_t5_attention_long_bwd_workspace_bytes): grows with
+    R * n_heads * (Tq + Tk)."""
+    return int(_lib.lib().rqhip_t5_attention_long_bwd_workspace_bytes(int(R), int(n_heads), int(Tq), int(Tk)))
+
+
+def t5_attention_long_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, ml: Tensor, d_out: Tensor,
+                          n_heads: int, *, bias_by_delta: Optional[Tensor] = None, bias_offset: int = 0,
+                          key_mask: Optional[Tensor] = None, causal: bool = False, p: float = 0.0,
+                          seed: Optional[Tensor] = None):
+    """The gradients of t5_attention_long_fwd_train (rqhip_t5_attention_long_bwd: a query-major launch, a key-major launch
+    and, with a bias table, a small reduction) -> (dq [R, Tq, inner], dk, dv [R, Tk, inner], dtable [n_delta, n_heads] or
+    None).  The arguments are the forward's, its `out`, `lse` and `ml`, and d_out [R, Tq, inner]; the weights and the
+    dropout decisions are recomputed, nothing of size Tq x Tk is stored."""
+    _need_gpu(q, k, v, out, lse, ml, d_out, bias_by_delta, key_mask, seed)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+        "t5_attention_long_bwd", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
+    out, d_out = _token_rows(out, "out"), _token_rows(d_out, "d_out")
+    if out.shape != q.shape or d_out.shape != q.shape:
+        raise RqHipError(f"t5_attention_long_bwd: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q "
+                         f"{tuple(q.shape)}")
+    lse, ml = _f32c(lse, "lse"), _f32c(ml, "ml")
+    if tuple(lse.shape) != (R, int(n_heads), Tq) or tuple(ml.shape) != (R, int(n_heads), Tq, 2):
+        raise RqHipError(f"t5_attention_long_bwd: lse must be [{R}, {n_heads}, {Tq}] and ml [{R}, {n_heads}, {Tq}, 2], "
+                         f"got {tuple(lse.shape)} and {tuple(ml.shape)}")
+    dev = q.device
+    with torch.cuda.device(dev):
+        dq = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
+        dk = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
+        dv = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
+        dtable = None if bias_by_delta is None else torch.empty_like(bias_by_delta)
+        ws_bytes = t5_attention_long_bwd_workspace_bytes(R, n_heads, Tq, Tk)
+        ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_long_bwd(
+            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), _ptr(out), int(out.stride(1)), _ptr(lse),
+            _ptr(ml), _ptr(d_out), int(d_out.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk, _ptr(bias_by_delta),
+            0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset), _ptr(key_mask), int(bool(causal)),
+            float(p), seed_ptr, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dtable), _ptr(ws), ws_bytes, _stream())
+        check(rc, "rqhip_t5_attention_long_bwd")
+    return dq, dk, dv, dtable
+
+
 def t5_add_norm_supported(dtype: torch.dtype, d: int) -> bool:
     """Whether t5_add_norm_fwd / t5_add_norm_bwd implement rows of this width (rqhip_t5_add_norm_supported): fp32, d a
     multiple of 4 in 4 .. 1024."""

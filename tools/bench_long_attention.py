@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Time the retrieval model at the data path's longest history, where the short fused attention does not apply: 256 items
+at 3 levels with the separator and the user token, an encoder sequence of 1025 tokens, batch 64, the model's default
+config (d_model 128, 6 heads, d_ff 1024, 4 layers, K = 256, k = 10).  Two arms, alternated --runs times in one process:
+
+  torch  the operators (attention_impl = "torch"): every attention keeps [B, heads, T, T] fp32 tensors
+  long   attention_impl = "hip_train" with attention_long_impl = "hip": csrc/t5_attention_long.hip for every call the
+         short kernel does not take (modules/t5.py)
+
+and two workloads per arm: one encoder forward + backward (encoder_forward_pass, a scalar of its output, backward) and
+one `generate`.  Per arm and workload: device time per step (device events, median over the iterations of a run, then
+over the runs) and torch.cuda.max_memory_allocated of one step.  The report goes to --out (default
+profiles/t5_attention_long.txt); --ratios FILE appends the `largest e_kernel / e_torch per tensor` line of a
+`pytest -s tests/test_gpu_t5_attention_long.py` log, the error ratios of the kernels against the operators.
+
+    python tools/bench_long_attention.py [--batch 64] [--items 256] [--runs 3] [--warmup 1] [--iters 3] [--out FILE]
+                                         [--ratios PYTEST_LOG]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "rq-vae-recommender_amd"), os.path.join(ROOT, "tests")]
+
+import torch  # noqa: E402
+
+from modules.model import EncoderDecoderRetrievalModel, _strip_dedup_col  # noqa: E402
+from retrieval_cases import _corpus, synthetic_batch, to_device  # noqa: E402  (tests/retrieval_cases.py)
+
+ARMS = {"torch": ("torch", "torch"), "long": ("hip_train", "hip")}
+
+
+def build(batch, items, dev, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    L, K = 3, 256
+    corpus = _corpus(K, L, 20000, g, "cpu")
+    model = EncoderDecoderRetrievalModel(corpus, L, K, num_user_bins=1000).to(dev).eval()
+    return model, to_device(synthetic_batch(corpus, batch, items, g, pad="b_mod_items"), dev)
+
+
+def encoder_step(model, batch):
+    L = model.num_hierarchies
+    model.zero_grad(set_to_none=True)
+    enc, _ = model.encoder_forward_pass(attention_mask=_strip_dedup_col(batch.seq_mask.long(), L + 1, L),
+                                        input_ids=_strip_dedup_col(batch.sem_ids, L + 1, L), user_id=batch.user_ids)
+    enc.square().mean().backward()
+    return enc.shape[1]
+
+
+def generate_step(model, batch):
+    with torch.no_grad():
+        model.generate_next_sem_id(batch)
+
+
+def timed(step, warmup, iters):
+    """(median device ms per step, peak bytes allocated during one step)."""
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    step()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated()
+    times = []
+    for _ in range(iters):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        step()
+        end.record()
+        torch.cuda.synchronize()
+        times.append(start.elapsed_time(end))
+    return statistics.median(times), peak
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--items", type=int, default=256)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "t5_attention_long.txt"))
+    ap.add_argument("--ratios", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda")
+    model, batch = build(args.batch, args.items, dev)
+    tokens = encoder_step(model, batch)
+    results = {(arm, w): [] for arm in ARMS for w in ("encoder fwd+bwd", "generate")}
+    for run in range(args.runs):
+        for arm, (attention, long) in ARMS.items():
+            model.attention_impl, model.attention_long_impl = attention, long
+            for w, step in (("encoder fwd+bwd", encoder_step), ("generate", generate_step)):
+                ms, peak = timed(lambda: step(model, batch), args.warmup, args.iters)
+                results[arm, w].append((ms, peak))
+                print(json.dumps({"run": run, "arm": arm, "workload": w, "ms": round(ms, 3), "peak_MiB": round(peak / 2**20, 1)}),
+                      flush=True)
+            torch.cuda.empty_cache()
+    lines = [f"tools/bench_long_attention.py on {torch.cuda.get_device_name(0)}: batch {args.batch}, {args.items} items, "
+             f"encoder length {tokens}, default model config; median device time per step over {args.runs} alternating "
+             f"runs of {args.iters} steps, torch.cuda.max_memory_allocated of one step", ""]
+    for w in ("encoder fwd+bwd", "generate"):
+        med = {arm: statistics.median(ms for ms, _ in results[arm, w]) for arm in ARMS}
+        peak = {arm: max(p for _, p in results[arm, w]) for arm in ARMS}
+        for arm in ARMS:
+            lines.append(f"{w:16s} {arm:6s} {med[arm]:10.2f} ms   peak {peak[arm] / 2**20:10.1f} MiB   runs "
+                         + " ".join(f"{ms:.2f}" for ms, _ in results[arm, w]))
+        lines.append(f"{w:16s} long / torch: time {med['long'] / med['torch']:.3f}, peak memory "
+                     f"{peak['long'] / peak['torch']:.3f}")
+    if args.ratios:
+        lines.append("")
+        with open(args.ratios) as f:
+            found = [ln.strip() for ln in f if ln.startswith("largest e_kernel / e_torch per tensor")]
+        lines.append("tests/test_gpu_t5_attention_long.py, same library (gates: out 4, dq / dk / dv / dtable 8):")
+        lines += found or ["(no ratio line in the log)"]
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
