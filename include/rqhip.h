@@ -394,6 +394,51 @@ int rqhip_t5_attention_long_bwd(const float *q, int64_t ld_q, const float *k, co
                                 int causal, double p, const int64_t *seed, float *d_q, float *d_k, float *d_v,
                                 float *d_bias_by_delta, void *workspace, size_t workspace_bytes, rqhip_stream_t stream);
 
+/* The "bf16" arithmetic of the same three calls (modules/t5.py, attention_arith = "bf16"): the parameter lists, shapes,
+ * limits, strides, K/V groups and beams, argument checks (the messages carry these names), launch counts, workspace
+ * layout and size (rqhip_t5_attention_long_supported and rqhip_t5_attention_long_bwd_workspace_bytes serve both arms) and
+ * graph capturability of their fp32 twins above; the chunk and the query block are RQHIP_T5_ATTENTION_LONG_CHUNK and
+ * RQHIP_T5_ATTENTION_LONG_QBLOCK.  Storage stays fp32 everywhere: q, k, v, out, lse, (m, l), d_out, d_q, d_k, d_v, the
+ * bias table and its gradient, and the workspace.  The mask and bias semantics and the dropout decision (the same
+ * element index) are unchanged.  Arithmetic contract ("bf16"), in the terms of rqhip_t5_ffn_*_bf16 below:
+ *   - Every operand of a matrix instruction is the round-to-nearest-even bf16 rounding of the fp32 value the fp32 arm
+ *     feeds at that place.  Forward: q, k, v and the unnormalised chunk weights p_j, rounded AFTER the dropout zeroing.
+ *     Backward: q, k, v, d_out, the dropped and scaled P (P o M / (1 - p)) that multiplies d_out for d_v, and dS for d_q
+ *     and d_k.
+ *   - Products are exact and accumulate in fp32 inside v_mfma_f32_16x16x32_bf16.  A score and a dP are ONE chain of two
+ *     instructions (features 0 .. 31, then 32 .. 63) from +0; a chunk's share of o, d_q, d_k and d_v is one chain from
+ *     +0 over the chunk's groups of 32 keys (queries for d_k, d_v) in ascending order, and the chunks are added in
+ *     ascending order as in the fp32 arm.  The order of the 32 terms inside an instruction is the instruction's.  A last
+ *     half group (an odd number of 16-row tiles) multiplies zeros.
+ *   - In fp32 on the UNROUNDED values: bias add, mask add, running max, expf, the row sum l (every weight, dropped or
+ *     not), alpha, o * alpha + chunk, the final divide, 1 / (1 - p), lse, (m, l), D = sum P dP, dS = P (dP - D) and the
+ *     diagonal sums for the table gradient (dS is not rounded on that path).
+ *   - The forward and the three backward passes form a score with one shared function, so the backward's scores have
+ *     the forward's bits.  D is made of the very dP it is subtracted from: a row with one live key gives dS = 0 exactly.
+ *     Under `causal` the first query of a live row returns the bf16 rounding of its first V row exactly.
+ *   - The (m, l) pair (and lse) of a bf16 forward belong to bf16 scores: only the bf16 backward may read them.
+ *   - No float atomics, fixed orders: the same bits on every run; a row's bits depend on Tq, Tk and that row's data
+ *     only, not on R, the beams or the grid.  No allocation, copy, memset or sync.
+ * Error against the fp64 attention on the bf16-rounded q, k, v, d_out, beyond the fp32 arm's own N on those tensors and
+ * with u = 2^-8: out u (P~ |v|), d_v u (P~^T |d_out|), d_q u (|dS| |k|), d_k u (|dS|^T |q|), where P~ = P o M / (1 - p)
+ * (tests/test_gpu_t5_attention_long_bf16.py; measured ratios in profiles/t5_attention_long_bf16.txt). */
+int rqhip_t5_attention_long_bf16(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, int64_t R,
+                                 int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta,
+                                 int bias_offset, const uint8_t *key_mask, int causal, int past, const int32_t *anc,
+                                 float *out, int64_t ld_out, rqhip_stream_t stream);
+int rqhip_t5_attention_long_fwd_train_bf16(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                           int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
+                                           const float *bias_by_delta, int n_delta, int bias_offset,
+                                           const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *out,
+                                           int64_t ld_out, float *lse, float *ml, rqhip_stream_t stream);
+int rqhip_t5_attention_long_bwd_bf16(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                     const float *out, int64_t ld_out, const float *lse, const float *ml,
+                                     const float *d_out, int64_t ld_do, int64_t R, int64_t Rk, int H, int d_kv, int Tq,
+                                     int Tk, const float *bias_by_delta, int n_delta, int bias_offset,
+                                     const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *d_q,
+                                     float *d_k, float *d_v, float *d_bias_by_delta, void *workspace,
+                                     size_t workspace_bytes, rqhip_stream_t stream);
+
 /* "Add-norm": the glue between two T5 sub-layers in one launch (csrc/t5_add_norm.hip; modules/t5.py, norm_impl = "hip"):
  * the dropout of a sub-layer's output y, the residual add, the NEXT RMS norm and, behind a stack's final norm, its
  * dropout.  x (the residual stream, or NULL), y, x_new, n are dense [N, d] fp32, w [d], rstd [N]; all arithmetic is fp32

@@ -13,6 +13,10 @@ csrc/t5_attention_long.hip (up to 2048 tokens) instead of the operators, call by
 `model.matmul_arith` ("fp32", the default, or "bf16") goes to both stacks with them: the arithmetic of the "hip"
 feed-forward and the "hip" projections (bf16 operands, fp32 accumulation, fp32 storage; modules/t5.py).  It has no
 effect on the "torch" bodies, nor on the attention, the norms, the heads or the embedding, which stay fp32.
+`model.attention_arith` ("fp32", the default, or "bf16") goes to both stacks with them: the arithmetic of the long
+attention calls that `attention_long_impl` = "hip" takes (bf16 matrix operands, fp32 softmax and storage; modules/t5.py),
+`generate`'s cross-attention included.  The short kernel and the cached decode step stay fp32.  It is set on the model:
+train_decoder.train has no parameter for it.
 `model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
 cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
 on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
@@ -47,7 +51,7 @@ from torch import Tensor
 
 from data.schemas import TokenizedSeqBatch
 from modules.sid_prefix import SemIdPrefixIndex
-from modules.t5 import MATMUL_ARITHS, T5Config, T5EncoderModel, T5Stack
+from modules.t5 import ATTENTION_ARITHS, MATMUL_ARITHS, T5Config, T5EncoderModel, T5Stack
 from rqhip import ops
 from rqhip._lib import RqHipError
 from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
@@ -123,6 +127,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.embed_impl = "torch"  # or "hip": each stack's input embedding as one fused call
         self.proj_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.matmul_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
+        self.attention_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
 
     @property
     def device(self) -> torch.device:
@@ -173,7 +178,10 @@ class EncoderDecoderRetrievalModel(nn.Module):
     def _push_attention_impl(self) -> None:
         if self.matmul_arith not in MATMUL_ARITHS:
             raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
-        for name in ("attention_impl", "attention_long_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith"):
+        if self.attention_arith not in ATTENTION_ARITHS:
+            raise ValueError(f"attention_arith must be one of {ATTENTION_ARITHS}, got {self.attention_arith!r}")
+        for name in ("attention_impl", "attention_long_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith",
+                     "attention_arith"):
             for stack in (self.encoder.encoder, self.t5_decoder):
                 setattr(stack, name, getattr(self, name))
 

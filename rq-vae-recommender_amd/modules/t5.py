@@ -66,6 +66,18 @@ operand of a matrix product to bf16 and accumulates in fp32 (include/rqhip.h); w
 the state dict stay fp32.  With the "torch" bodies it has no effect: the operators stay fp32, and so do the attention
 itself, the norms and the glue.
 
+`attention_arith` = "fp32" (the default) or "bf16" is the arithmetic of the LONG attention calls alone, wherever
+`attention_long_impl` = "hip" takes one: the inference launch (ops.t5_attention_long, `generate`'s cross-attention
+included), and under grad the forward and backward of autograd.T5AttentionLongBf16Function.  "bf16" rounds q, k, v,
+d_out, the unnormalised weights and dS to bf16 as matrix operands and keeps the softmax, its sums and every stored
+tensor fp32 (include/rqhip.h, rqhip_t5_attention_long_*_bf16).  The short kernel (up to 256 tokens), and with it the
+cached decode step, stays fp32; `matmul_arith` does not touch the attention and this attribute does not touch the matrix
+forms.  With `attention_long_impl` = "torch" or host tensors it has no effect.  It is an attribute of the model or the
+stack, set by the caller: train_decoder.train has no parameter for it.  Measured on an MI355X at batch 64 and 1025
+encoder tokens in one alternating run (profiles/t5_attention_long_bf16.txt): one encoder forward + backward 46.8 ms
+against the fp32 arm's 75.3 ms and the operators' 72.1 ms, one `generate` 12.4 against 15.5 and 31.9 ms, at the fp32
+arm's peak memory; the four bf16 kernels take 0.53 of their fp32 twins' device time.
+
 The fused forms take their dropout seeds as int64s drawn on the device with torch.randint (the default generator:
 torch.manual_seed reproduces a run), none in eval mode or at dropout_rate 0.  The fused attention draws one per call.
 With the "hip" glue a stack forward draws once before its first body, one seed per glue call and behind them one per
@@ -80,8 +92,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops
-from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5AttentionLongFunction, T5FFNBf16Function,
-                            T5FFNFunction, T5ProjBf16Function, T5ProjFunction)
+from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5FFNBf16Function, T5FFNFunction,
+                            T5ProjBf16Function, T5ProjFunction, t5_attention_long_function)
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
@@ -90,6 +102,7 @@ NORM_IMPLS = ("torch", "hip")
 FFN_IMPLS = ("torch", "hip")
 PROJ_IMPLS = ("torch", "hip")
 MATMUL_ARITHS = ops.T5_ARITHS  # ("fp32", "bf16")
+ATTENTION_ARITHS = ops.T5_ARITHS  # of the long attention calls
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -326,7 +339,7 @@ class _HipAttention:
     """The attention bodies of a stack forward on the "hip" path: the bias table and the byte masks are built once,
     every attention is one launch (`train`: one T5AttentionFunction call, with the attention-weight dropout of train
     mode in the kernel, from a seed drawn per call).  `proj`: the projections around it as grouped calls (`_project`,
-    T5Stack.proj_arm's value)."""
+    T5Stack.proj_arm's value).  The long calls run in the stack's attention_arith."""
 
     def __init__(self, stack: "T5Stack", T: int, attention_mask: Optional[Tensor],
                  encoder_attention_mask: Optional[Tensor], cross_kv: Optional[List[KV]],
@@ -334,6 +347,9 @@ class _HipAttention:
         self.train = train
         self.proj = proj
         self.long = stack.long_attention()  # calls the short kernel does not support go to the long one
+        arith = stack.attention_arithmetic()
+        self.long_kw = {} if arith == "fp32" else {"arith": arith}  # the keyword only off the default
+        self.long_function = t5_attention_long_function(arith)
         self.p = float(stack.config.dropout_rate) if train and stack.training else 0.0
         self.cache = cache
         self.past = 0 if cache is None else cache.pos
@@ -348,12 +364,14 @@ class _HipAttention:
         long = self.long and not ops.t5_attention_supported(q.dtype, module.d_kv, module.n_heads, q.shape[1],
                                                             k.shape[1])
         if self.train:
-            function = T5AttentionLongFunction if long else T5AttentionFunction
+            function = self.long_function if long else T5AttentionFunction
             return function.apply(q, k, v, table, module.n_heads, offset, key_mask, causal, self.p,
                                   _draw_seed(self.p, q.device))
-        attention = ops.t5_attention_long if long else ops.t5_attention
-        return attention(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset, key_mask=key_mask,
-                         causal=causal)
+        if long:
+            return ops.t5_attention_long(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset,
+                                         key_mask=key_mask, causal=causal, **self.long_kw)
+        return ops.t5_attention(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset, key_mask=key_mask,
+                                causal=causal)
 
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
         """One launch; with a decode cache the K/V projections go straight into block i's slabs."""
@@ -457,6 +475,7 @@ class T5Stack(nn.Module):
         self.ffn_impl = "torch"  # or "hip": see the module docstring
         self.proj_impl = "torch"  # or "hip": see the module docstring
         self.matmul_arith = "fp32"  # or "bf16": the arithmetic of the "hip" feed-forward and projections (docstring)
+        self.attention_arith = "fp32"  # or "bf16": the arithmetic of the long attention calls (module docstring)
         init_t5_weights(self, config)
 
     def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
@@ -477,6 +496,12 @@ class T5Stack(nn.Module):
             raise ValueError(f"attention_long_impl must be one of {ATTENTION_LONG_IMPLS}, got "
                              f"{self.attention_long_impl!r}")
         return self.attention_long_impl == "hip"
+
+    def attention_arithmetic(self) -> str:
+        """attention_arith, validated."""
+        if self.attention_arith not in ATTENTION_ARITHS:
+            raise ValueError(f"attention_arith must be one of {ATTENTION_ARITHS}, got {self.attention_arith!r}")
+        return self.attention_arith
 
     def _call_supported(self, short, dtype, query_length: int, key_length: int, long: bool) -> bool:
         """Whether one attention call has a kernel: the existing one (`short`: its support table), else, with `long`,
@@ -564,6 +589,7 @@ class T5Stack(nn.Module):
         """The attention body of this forward (module docstring): _HipAttention where it applies, else the operators."""
         R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
         self.long_attention()  # an unknown attention_long_impl raises on every path
+        self.attention_arithmetic()  # and so does an unknown attention_arith
         if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
             if self.is_decoder and cross_kv is None:
                 cross_kv = self.cross_kv(encoder_hidden_states)

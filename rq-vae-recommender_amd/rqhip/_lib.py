@@ -117,6 +117,13 @@ SIGNATURES = {
     "rqhip_t5_attention_long_bwd": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int,
                                            _int, _int, _int, _vp, _int, _int, _vp, _int, C.c_double, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _sz, _vp]),
+    "rqhip_t5_attention_long_bf16": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _int, _int,
+                                            _vp, _int, _int, _vp, _vp, _i64, _vp]),
+    "rqhip_t5_attention_long_fwd_train_bf16": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp,
+                                                      _int, _int, _vp, _int, C.c_double, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "rqhip_t5_attention_long_bwd_bf16": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int,
+                                                _int, _int, _int, _vp, _int, _int, _vp, _int, C.c_double, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _sz, _vp]),
     "rqhip_t5_add_norm_supported": (_int, [_int]),
     "rqhip_t5_add_norm_bwd_workspace_bytes": (_sz, [_i64, _int]),
     "rqhip_t5_add_norm_fwd": (_int, [_vp, _vp, _vp, _i64, _int, _f32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),

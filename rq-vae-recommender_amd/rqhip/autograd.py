@@ -297,17 +297,28 @@ class T5AttentionFunction(torch.autograd.Function):
         return dq, dk, dv, dtable, None, None, None, None, None, None
 
 
+def _arith_kw(ctx) -> dict:
+    """The `arith` keyword of the ops calls of ctx's Function: none for "fp32", the ops' default."""
+    arith = ctx._forward_cls.arith
+    return {} if arith == "fp32" else {"arith": arith}
+
+
 class T5AttentionLongFunction(torch.autograd.Function):
     """T5AttentionFunction for the lengths beyond its kernel (ops.t5_attention_long_fwd_train / ops.t5_attention_long_bwd,
     up to 2048 tokens): the same arguments and gradients.  Saved: q, k, v, out, the row log-sum-exp, each row's (max, sum)
-    pair, the table, the mask and the seed; the weights and the dropout decisions are recomputed chunk by chunk."""
+    pair, the table, the mask and the seed; the weights and the dropout decisions are recomputed chunk by chunk.  `arith`
+    is the class's arithmetic (ops.T5_ARITHS), forward and backward alike, so the (m, l) pair a forward saves is read by
+    the backward of its own arithmetic only: this class is the "fp32" arm, T5AttentionLongBf16Function the "bf16" one;
+    t5_attention_long_function(arith) picks."""
+
+    arith = "fp32"
 
     @staticmethod
     def forward(ctx, q: Tensor, k: Tensor, v: Tensor, bias_by_delta: Optional[Tensor], n_heads: int, bias_offset: int,
                 key_mask: Optional[Tensor], causal: bool, p: float, seed: Optional[Tensor]):
         out, lse, ml = ops.t5_attention_long_fwd_train(q, k, v, n_heads, bias_by_delta=bias_by_delta,
                                                        bias_offset=bias_offset, key_mask=key_mask, causal=causal, p=p,
-                                                       seed=seed)
+                                                       seed=seed, **_arith_kw(ctx))
         ctx.save_for_backward(q, k, v, out, lse, ml, bias_by_delta, key_mask, seed)
         ctx.call = (n_heads, bias_offset, causal, p)
         return out
@@ -318,8 +329,22 @@ class T5AttentionLongFunction(torch.autograd.Function):
         n_heads, bias_offset, causal, p = ctx.call
         dq, dk, dv, dtable = ops.t5_attention_long_bwd(q, k, v, out, lse, ml, d_out, n_heads, bias_by_delta=table,
                                                        bias_offset=bias_offset, key_mask=mask, causal=causal, p=p,
-                                                       seed=seed)
+                                                       seed=seed, **_arith_kw(ctx))
         return dq, dk, dv, dtable, None, None, None, None, None, None
+
+
+class T5AttentionLongBf16Function(T5AttentionLongFunction):
+    """T5AttentionLongFunction in the "bf16" arithmetic (rqhip_t5_attention_long_*_bf16): the same saved tensors, all
+    float32."""
+
+    arith = "bf16"
+
+
+def t5_attention_long_function(arith: str = "fp32"):
+    """The long-attention Function of an arithmetic."""
+    if arith not in ops.T5_ARITHS:
+        raise ops.RqHipError(f"t5_attention_long_function: arith must be one of {ops.T5_ARITHS}, got {arith!r}")
+    return T5AttentionLongBf16Function if arith == "bf16" else T5AttentionLongFunction
 
 
 class T5AddNormFunction(torch.autograd.Function):
@@ -347,12 +372,6 @@ class T5AddNormFunction(torch.autograd.Function):
         d_x, d_y, d_w = ops.t5_add_norm_bwd(x_new, rstd, w, _dense(d_n), _dense(d_xnew), p_in, p_out, seed,
                                             need_x=has_x and ctx.needs_input_grad[0], need_y=ctx.needs_input_grad[1])
         return d_x, d_y, d_w, None, None, None, None
-
-
-def _arith_kw(ctx) -> dict:
-    """The `arith` keyword of the ops calls of ctx's Function: none for "fp32", the ops' default."""
-    arith = ctx._forward_cls.arith
-    return {} if arith == "fp32" else {"arith": arith}
 
 
 class T5FFNFunction(torch.autograd.Function):

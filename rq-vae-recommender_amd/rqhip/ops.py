@@ -725,6 +725,19 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
     return dq, dk, dv, dtable
 
 
+# the arithmetics of t5_ffn_*, t5_proj_* and t5_attention_long* (include/rqhip.h): storage is fp32 in both
+T5_ARITHS = ("fp32", "bf16")
+
+
+def _arith_entry(who: str, arith: str):
+    """The C entry point of `who` in the arithmetic `arith`: "fp32" (exact fp32 products) or "bf16" (operands rounded to
+    bf16, exact products, fp32 accumulation)."""
+    if arith not in T5_ARITHS:
+        raise RqHipError(f"{who}: arith must be one of {T5_ARITHS}, got {arith!r}")
+    name = f"rqhip_{who}" + ("_bf16" if arith == "bf16" else "")
+    return getattr(_lib.lib(), name), name
+
+
 T5_ATTENTION_LONG_CHUNK = 128   # RQHIP_T5_ATTENTION_LONG_CHUNK: keys a workgroup holds in LDS at a time
 T5_ATTENTION_LONG_QBLOCK = 64   # RQHIP_T5_ATTENTION_LONG_QBLOCK: query rows of a workgroup
 
@@ -737,31 +750,37 @@ def t5_attention_long_supported(dtype: torch.dtype, d_kv: int, n_heads: int, Tq:
 
 
 def t5_attention_long(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
-                      bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False) -> Tensor:
+                      bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False,
+                      arith: str = "fp32") -> Tensor:
     """t5_attention's dense form for up to 2048 tokens in one launch (rqhip_t5_attention_long, csrc/t5_attention_long.hip):
     the keys are walked in chunks of T5_ATTENTION_LONG_CHUNK with an online softmax.  q [R, Tq, n_heads * 64], k, v
     [Rk, Tk, n_heads * 64], R a multiple of Rk; bias_by_delta, bias_offset, key_mask and causal as in t5_attention.  No
-    ancestor table and no `past`: the cached decode step stays on t5_attention."""
+    ancestor table and no `past`: the cached decode step stays on t5_attention.  arith: "fp32", or "bf16"
+    (rqhip_t5_attention_long_bf16: q, k, v and the unnormalised weights rounded to bf16 as matrix operands, the softmax in
+    fp32 on unrounded values; all tensors stay float32)."""
+    fn, fn_name = _arith_entry("t5_attention_long", arith)
     _need_gpu(q, k, v, bias_by_delta, key_mask)
     q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _ = _attention_args("t5_attention_long", q, k, v, n_heads,
                                                                                 bias_by_delta, key_mask)
     dev = q.device
     with torch.cuda.device(dev):
         out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
-        rc = _lib.lib().rqhip_t5_attention_long(
-            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
-            _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
-            _ptr(key_mask), int(bool(causal)), 0, None, _ptr(out), inner, _stream())
-        check(rc, "rqhip_t5_attention_long")
+        rc = fn(_ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
+                _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
+                _ptr(key_mask), int(bool(causal)), 0, None, _ptr(out), inner, _stream())
+        check(rc, fn_name)
     return out
 
 
 def t5_attention_long_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
                                 bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False,
-                                p: float = 0.0, seed: Optional[Tensor] = None):
+                                p: float = 0.0, seed: Optional[Tensor] = None, arith: str = "fp32"):
     """t5_attention_fwd_train for up to 2048 tokens in one launch (rqhip_t5_attention_long_fwd_train) -> (out
     [R, Tq, n_heads * 64], lse [R, n_heads, Tq], ml [R, n_heads, Tq, 2]: each row's final running max and sum, which the
-    backward reads).  The dropout decision is t5_attention_dropout_keep(seed, ...), unchanged."""
+    backward reads).  The dropout decision is t5_attention_dropout_keep(seed, ...), unchanged.  arith: "fp32" or "bf16",
+    as t5_attention_long's (rqhip_t5_attention_long_fwd_train_bf16); lse and ml of a "bf16" forward are read by the
+    "bf16" backward only."""
+    fn, fn_name = _arith_entry("t5_attention_long_fwd_train", arith)
     _need_gpu(q, k, v, bias_by_delta, key_mask, seed)
     q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
         "t5_attention_long_fwd_train", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
@@ -770,11 +789,10 @@ def t5_attention_long_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *
         out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
         lse = torch.empty((R, int(n_heads), Tq), dtype=torch.float32, device=dev)
         ml = torch.empty((R, int(n_heads), Tq, 2), dtype=torch.float32, device=dev)
-        rc = _lib.lib().rqhip_t5_attention_long_fwd_train(
-            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
-            _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
-            _ptr(key_mask), int(bool(causal)), float(p), seed_ptr, _ptr(out), inner, _ptr(lse), _ptr(ml), _stream())
-        check(rc, "rqhip_t5_attention_long_fwd_train")
+        rc = fn(_ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk,
+                _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset),
+                _ptr(key_mask), int(bool(causal)), float(p), seed_ptr, _ptr(out), inner, _ptr(lse), _ptr(ml), _stream())
+        check(rc, fn_name)
     return out, lse, ml
 
 
@@ -787,11 +805,13 @@ def t5_attention_long_bwd_workspace_bytes(R: int, n_heads: int, Tq: int, Tk: int
 def t5_attention_long_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, ml: Tensor, d_out: Tensor,
                           n_heads: int, *, bias_by_delta: Optional[Tensor] = None, bias_offset: int = 0,
                           key_mask: Optional[Tensor] = None, causal: bool = False, p: float = 0.0,
-                          seed: Optional[Tensor] = None):
+                          seed: Optional[Tensor] = None, arith: str = "fp32"):
     """The gradients of t5_attention_long_fwd_train (rqhip_t5_attention_long_bwd: a query-major launch, a key-major launch
     and, with a bias table, a small reduction) -> (dq [R, Tq, inner], dk, dv [R, Tk, inner], dtable [n_delta, n_heads] or
     None).  The arguments are the forward's, its `out`, `lse` and `ml`, and d_out [R, Tq, inner]; the weights and the
-    dropout decisions are recomputed, nothing of size Tq x Tk is stored."""
+    dropout decisions are recomputed, nothing of size Tq x Tk is stored.  arith: the forward's ("fp32", or "bf16":
+    rqhip_t5_attention_long_bwd_bf16)."""
+    fn, fn_name = _arith_entry("t5_attention_long_bwd", arith)
     _need_gpu(q, k, v, out, lse, ml, d_out, bias_by_delta, key_mask, seed)
     q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
         "t5_attention_long_bwd", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
@@ -811,12 +831,12 @@ def t5_attention_long_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Ten
         dtable = None if bias_by_delta is None else torch.empty_like(bias_by_delta)
         ws_bytes = t5_attention_long_bwd_workspace_bytes(R, n_heads, Tq, Tk)
         ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.float32, device=dev)
-        rc = _lib.lib().rqhip_t5_attention_long_bwd(
-            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), _ptr(out), int(out.stride(1)), _ptr(lse),
-            _ptr(ml), _ptr(d_out), int(d_out.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk, _ptr(bias_by_delta),
-            0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset), _ptr(key_mask), int(bool(causal)),
-            float(p), seed_ptr, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dtable), _ptr(ws), ws_bytes, _stream())
-        check(rc, "rqhip_t5_attention_long_bwd")
+        rc = fn(_ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), _ptr(out), int(out.stride(1)), _ptr(lse),
+                _ptr(ml), _ptr(d_out), int(d_out.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk, _ptr(bias_by_delta),
+                0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset), _ptr(key_mask),
+                int(bool(causal)), float(p), seed_ptr, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dtable), _ptr(ws), ws_bytes,
+                _stream())
+        check(rc, fn_name)
     return dq, dk, dv, dtable
 
 
@@ -902,18 +922,6 @@ def t5_add_norm_bwd(x_new: Tensor, rstd: Tensor, w: Tensor, d_n: Optional[Tensor
                                               _stream())
         check(rc, "rqhip_t5_add_norm_bwd")
     return d_x, (d_x if shared else d_y), d_w
-
-
-T5_ARITHS = ("fp32", "bf16")   # the arithmetics of t5_ffn_* and t5_proj_* (include/rqhip.h): storage is fp32 in both
-
-
-def _arith_entry(who: str, arith: str):
-    """The C entry point of `who` in the arithmetic `arith`: "fp32" (exact fp32 products) or "bf16" (operands rounded to
-    bf16, exact products, fp32 accumulation)."""
-    if arith not in T5_ARITHS:
-        raise RqHipError(f"{who}: arith must be one of {T5_ARITHS}, got {arith!r}")
-    name = f"rqhip_{who}" + ("_bf16" if arith == "bf16" else "")
-    return getattr(_lib.lib(), name), name
 
 
 def t5_ffn_supported(dtype: torch.dtype, d: int, F: int) -> bool:

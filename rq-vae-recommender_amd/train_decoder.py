@@ -24,8 +24,10 @@ What differs:
     for it: the model's default is "torch"), take bf16 operands and accumulate in fp32.  There is no autocast: weights,
     activations, gradients, the checkpoint, the attention, the norms, the heads, the embedding and the optimizer stay
     fp32, and the "torch" bodies are not affected.  amp=True with any other type raises: those kernels are fp32 or
-    bf16-operand only.  push_vae_to_hf=True raises: it needs the network.  Datasets other than
-    AMAZON raise, as in the reference.
+    bf16-operand only.  The bf16 arm of the long attention calls is `model.attention_arith = "bf16"` (modules/t5.py),
+    an attribute set on the model: train has no parameter for it, nor for `model.attention_long_impl`, and amp does
+    not set it.  push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
+    reference.
 wandb is optional: with `wandb_logging=True` and no wandb module, metrics are printed.
 
 Not done: replaying the step from a captured hipGraph (the loader's calls make no host read and no data-dependent

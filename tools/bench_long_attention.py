@@ -1,20 +1,23 @@
 #!/usr/bin/env python3
 """Time the retrieval model at the data path's longest history, where the short fused attention does not apply: 256 items
 at 3 levels with the separator and the user token, an encoder sequence of 1025 tokens, batch 64, the model's default
-config (d_model 128, 6 heads, d_ff 1024, 4 layers, K = 256, k = 10).  Two arms, alternated --runs times in one process:
+config (d_model 128, 6 heads, d_ff 1024, 4 layers, K = 256, k = 10).  The arms of --arms (default torch,long), alternated
+--runs times in one process:
 
-  torch  the operators (attention_impl = "torch"): every attention keeps [B, heads, T, T] fp32 tensors
-  long   attention_impl = "hip_train" with attention_long_impl = "hip": csrc/t5_attention_long.hip for every call the
-         short kernel does not take (modules/t5.py)
+  torch      the operators (attention_impl = "torch"): every attention keeps [B, heads, T, T] fp32 tensors
+  long       attention_impl = "hip_train" with attention_long_impl = "hip": csrc/t5_attention_long.hip for every call
+             the short kernel does not take (modules/t5.py)
+  long+bf16  the same with attention_arith = "bf16": those calls on bf16 matrix operands (rqhip_t5_attention_long_*_bf16)
 
 and two workloads per arm: one encoder forward + backward (encoder_forward_pass, a scalar of its output, backward) and
 one `generate`.  Per arm and workload: device time per step (device events, median over the iterations of a run, then
 over the runs) and torch.cuda.max_memory_allocated of one step.  The report goes to --out (default
-profiles/t5_attention_long.txt); --ratios FILE appends the `largest e_kernel / e_torch per tensor` line of a
-`pytest -s tests/test_gpu_t5_attention_long.py` log, the error ratios of the kernels against the operators.
+profiles/t5_attention_long.txt, or profiles/t5_attention_long_bf16_bench.txt for a run with the long+bf16 arm, so that
+the two-arm report is not overwritten); --ratios FILE appends the `largest ... per tensor` lines of a `pytest -s
+tests/test_gpu_t5_attention_long*.py` log, the error ratios of the kernels.
 
-    python tools/bench_long_attention.py [--batch 64] [--items 256] [--runs 3] [--warmup 1] [--iters 3] [--out FILE]
-                                         [--ratios PYTEST_LOG]
+    python tools/bench_long_attention.py [--arms torch,long[,long+bf16]] [--batch 64] [--items 256] [--runs 3]
+                                         [--warmup 1] [--iters 3] [--out FILE] [--ratios PYTEST_LOG]
 """
 import argparse
 import json
@@ -30,7 +33,10 @@ import torch  # noqa: E402
 from modules.model import EncoderDecoderRetrievalModel, _strip_dedup_col  # noqa: E402
 from retrieval_cases import _corpus, synthetic_batch, to_device  # noqa: E402  (tests/retrieval_cases.py)
 
-ARMS = {"torch": ("torch", "torch"), "long": ("hip_train", "hip")}
+# arm -> (attention_impl, attention_long_impl, attention_arith)
+ARMS = {"torch": ("torch", "torch", "fp32"), "long": ("hip_train", "hip", "fp32"),
+        "long+bf16": ("hip_train", "hip", "bf16")}
+DEFAULT_ARMS = "torch,long"
 
 
 def build(batch, items, dev, seed=0):
@@ -78,21 +84,28 @@ def timed(step, warmup, iters):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--arms", default=DEFAULT_ARMS, help=f"comma-separated, of {', '.join(ARMS)}")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--items", type=int, default=256)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "t5_attention_long.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--ratios", default=None)
     args = ap.parse_args()
+    arms = args.arms.split(",")
+    if not arms or any(arm not in ARMS for arm in arms) or len(set(arms)) != len(arms):
+        ap.error(f"--arms takes distinct names of {', '.join(ARMS)}")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "t5_attention_long_bf16_bench.txt" if "long+bf16" in arms
+                                else "t5_attention_long.txt")
     dev = torch.device("cuda")
     model, batch = build(args.batch, args.items, dev)
     tokens = encoder_step(model, batch)
-    results = {(arm, w): [] for arm in ARMS for w in ("encoder fwd+bwd", "generate")}
+    results = {(arm, w): [] for arm in arms for w in ("encoder fwd+bwd", "generate")}
     for run in range(args.runs):
-        for arm, (attention, long) in ARMS.items():
-            model.attention_impl, model.attention_long_impl = attention, long
+        for arm in arms:
+            model.attention_impl, model.attention_long_impl, model.attention_arith = ARMS[arm]
             for w, step in (("encoder fwd+bwd", encoder_step), ("generate", generate_step)):
                 ms, peak = timed(lambda: step(model, batch), args.warmup, args.iters)
                 results[arm, w].append((ms, peak))
@@ -103,18 +116,22 @@ def main():
              f"encoder length {tokens}, default model config; median device time per step over {args.runs} alternating "
              f"runs of {args.iters} steps, torch.cuda.max_memory_allocated of one step", ""]
     for w in ("encoder fwd+bwd", "generate"):
-        med = {arm: statistics.median(ms for ms, _ in results[arm, w]) for arm in ARMS}
-        peak = {arm: max(p for _, p in results[arm, w]) for arm in ARMS}
-        for arm in ARMS:
-            lines.append(f"{w:16s} {arm:6s} {med[arm]:10.2f} ms   peak {peak[arm] / 2**20:10.1f} MiB   runs "
+        med = {arm: statistics.median(ms for ms, _ in results[arm, w]) for arm in arms}
+        peak = {arm: max(p for _, p in results[arm, w]) for arm in arms}
+        width = max(len(arm) for arm in arms + ["torch"])
+        for arm in arms:
+            lines.append(f"{w:16s} {arm:{width}s} {med[arm]:10.2f} ms   peak {peak[arm] / 2**20:10.1f} MiB   runs "
                          + " ".join(f"{ms:.2f}" for ms, _ in results[arm, w]))
-        lines.append(f"{w:16s} long / torch: time {med['long'] / med['torch']:.3f}, peak memory "
-                     f"{peak['long'] / peak['torch']:.3f}")
+        for a, b in (("long", "torch"), ("long+bf16", "torch"), ("long+bf16", "long")):
+            if a in arms and b in arms:
+                lines.append(f"{w:16s} {a} / {b}: time {med[a] / med[b]:.3f}, peak memory {peak[a] / peak[b]:.3f}")
     if args.ratios:
         lines.append("")
         with open(args.ratios) as f:
-            found = [ln.strip() for ln in f if ln.startswith("largest e_kernel / e_torch per tensor")]
-        lines.append("tests/test_gpu_t5_attention_long.py, same library (gates: out 4, dq / dk / dv / dtable 8):")
+            found = [ln.strip() for ln in f if ln.startswith(("largest e_kernel / e_torch per tensor",
+                                                               "largest |err| / gate per tensor"))]
+        lines.append("tests/test_gpu_t5_attention_long*.py, same library (fp32 arm: e_kernel / e_torch, gates out 4, dq / dk "
+                     "/ dv / dtable 8; bf16 arm: |err| / its elementwise gate):")
         lines += found or ["(no ratio line in the log)"]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
