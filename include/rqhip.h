@@ -280,6 +280,27 @@ int rqhip_beam_step(const float *logits, int64_t ld_logits, const float *noise, 
                     int64_t *out_ids, float *out_scores, int64_t *out_parent, void *workspace, size_t workspace_bytes,
                     rqhip_stream_t stream);
 
+/* Exact beam step -- one hierarchy step of the deterministic constrained beam search (model.beam_impl = "exact") in one
+ * launch (csrc/beam_step.hip): every corpus-valid child of every kept beam is scored, no random numbers.  Arguments as
+ * rqhip_beam_step without `noise`, `n_cands` and the workspace.  Row r = b * beams_in + beam of the B * beams_in rows:
+ *   m = max_c x[c], s = sum_c expf(x[c] - m), lp[c] = (x[c] - m) - logf(s): the log-softmax form, which (unlike the
+ *   sampling step's logf(p)) does not underflow to -inf for an unlikely code.  fp32 throughout, fixed reduction order.
+ *   Candidate j = beam * K + c of user b: score = lp[c] + parent_scores[b, beam] (lp[c] alone at h = 0), or -inf unless
+ *   parent_ids[b, beam, 0:h] ++ c is a prefix of some corpus row (the exact test of rqhip_prefix_lookup, confirmed
+ *   against the corpus row).  A NaN score counts as -inf.
+ *   Per user the k best candidates, descending, equal scores (-inf included) to the lower j -- the stable descending
+ *   sort of the [beams_in * K] score row, so the whole output is determined, the -inf beams included:
+ *   out_ids [B, k, h+1] = parent ids ++ code, out_scores [B, k], out_parent [B, k] = b * beams_in + beam.
+ *   A -inf beam in the output means that fewer than k corpus prefixes of length h + 1 extend the user's finite beams.
+ * Limits: K <= 4096, k <= 64, beams_in <= 64, k <= beams_in * K, beams_in = 1 at h = 0,
+ * h + 1 <= min(H, RQHIP_MAX_PREFIX_LEN); outside them RQHIP_EUNSUPPORTED / RQHIP_EARG with the limit named in
+ * rqhip_last_error(); every argument check runs before any HIP call.  The same bits on every run; no atomics,
+ * allocation, copy or sync (graph-capturable). */
+int rqhip_beam_topk_step(const float *logits, int64_t ld_logits, const float *parent_scores, const int64_t *parent_ids,
+                         int h, int64_t B, int beams_in, int K, int k, const void *index, size_t index_bytes,
+                         const int64_t *corpus, int64_t N, int H, int64_t ld, int64_t *out_ids, float *out_scores,
+                         int64_t *out_parent, rqhip_stream_t stream);
+
 /* T5 attention for inference (modules/t5.py:_attend) in one launch, fp32 throughout (csrc/t5_attention.hip):
  *   out[r, i, h*64 : h*64+64] = softmax_j(q[r, i, h] . k[b, j, h] + bias + mask) . v[b, :, h]      b = r / (R / Rk)
  * with T5's semantics: no 1/sqrt(d) scaling, d_kv = 64, masked scores get finfo(float32).min ADDED (a row with every key

@@ -19,6 +19,9 @@
 // is distinct and the maximum is unique; 0 is below every real key and marks a retired slot.  No atomics, fixed
 // reduction orders: the same bits on every run.  No allocation, copy or sync in the launch path (graph-capturable once
 // the LDS attribute has been raised by a first eager call, as everywhere in this library).
+//
+// The exact step of model.beam_impl = "exact" (rqhip_beam_topk_step, no noise: every code is a candidate) shares the keys
+// and the tournament; it is described at beam_topk_step_kernel below.
 #include "rqhip_common.h"
 #include "sid_hash.h"
 
@@ -195,7 +198,157 @@ __global__ __launch_bounds__(256) void beam_step_kernel(
     }
 }
 
+// The exact step (rqhip_beam_topk_step): every code of every row is a candidate, nothing is drawn.  beams_in * K keys do
+// not fit in LDS and need not: under the total order (score descending, then j = beam * K + c ascending) the k best of
+// a user lie among the m = min(k, K) best of each row.
+//
+//   phase A (one wave per row, rows strided over the waves): lp[c] = (x[c] - max) - logf(sum expf(x - max)) in fp32,
+//            score = lp[c] (+ the parent beam's score when h > 0), NaN -> -inf; a code whose (h+1)-prefix is not in the
+//            corpus scores -inf: the parent prefix is hashed once per row, then one sid_hash_step and one probe per
+//            code.  The order images go into the wave's [K] slice and wave_top takes the m best, ties to the lower code:
+//            candidate beam * m + rank, which orders equal scores exactly as beam * K + c does.
+//   phase B (wave 0): the k best of the beams_in * m candidates, ties (-inf included) to the lower candidate.
+//   phase C (all threads): ids = parent ids ++ code, scores, the global parent row.
+//
+// wave_top's two preconditions hold by construction: no key is 0 (a NaN is made -inf BEFORE f32_order, which maps
+// every other value above 0), and it is never asked for more keys than its slice holds (m <= K, k <= beams_in * m).
+__global__ __launch_bounds__(256) void beam_topk_step_kernel(
+    const float *__restrict__ logits, long long ld_logits, const float *__restrict__ parent_scores,
+    const int64_t *__restrict__ parent_ids, int h, int beams_in, int K, int m, int k, const int *__restrict__ table,
+    unsigned mask, const int64_t *__restrict__ corpus, long long N, long long ld, int64_t *__restrict__ out_ids,
+    float *__restrict__ out_scores, int64_t *__restrict__ out_parent) {
+    extern __shared__ unsigned lds[];
+    __shared__ int win_idx[kBeamMaxTopK];
+    __shared__ unsigned win_key[kBeamMaxTopK];
+
+    const int nw = blockDim.x / RQ_WAVE;
+    const int wave = threadIdx.x / RQ_WAVE, lane = threadIdx.x & (RQ_WAVE - 1);
+    const long long b = blockIdx.x;
+    const int C = beams_in * m;
+    unsigned *rowkeys = lds + (size_t)wave * K;      // [K] per wave
+    unsigned *ckey = lds + (size_t)nw * K;           // [C] order image of each candidate's score
+    int *ccode = reinterpret_cast<int *>(ckey + C);  // [C] code of each candidate
+
+    const unsigned neg_inf = f32_order(-INFINITY);
+    const size_t slots = (size_t)mask + 1;
+    const int *tab = table + (size_t)h * slots;
+
+    // ---- phase A: log-softmax, validity of every code, the m best of the row
+    for (int beam = wave; beam < beams_in; beam += nw) {
+        const long long row = b * beams_in + beam;
+        const float *x = logits + (size_t)row * (size_t)ld_logits;
+        float mx = -INFINITY;
+        for (int c = lane; c < K; c += RQ_WAVE) mx = fmaxf(mx, x[c]);
+        mx = wave_max_f32(mx);
+        float s = 0.f;
+        for (int c = lane; c < K; c += RQ_WAVE) s += expf(x[c] - mx);
+        s = wave_sum_f32(s);
+        const float ls = logf(s);
+        const bool add_base = parent_scores != nullptr;
+        const float base = add_base ? parent_scores[row] : 0.f;
+        const int64_t *par = parent_ids + (size_t)row * (size_t)h;  // not read when h == 0
+        unsigned hpar = kSidHashSeed;
+        for (int t = 0; t < h; ++t) hpar = sid_hash_step(hpar, par[t]);
+        for (int c = lane; c < K; c += RQ_WAVE) {
+            float sc = (x[c] - mx) - ls;
+            if (add_base) sc = sc + base;
+            if (!(sc == sc)) sc = -INFINITY;  // NaN: its all-ones pattern would map to the retired mark
+            unsigned key = f32_order(sc);
+            if (key != neg_inf) {
+                bool found = false;
+                if (N > 0) {
+                    unsigned slot = sid_hash_final(sid_hash_step(hpar, (int64_t)c)) & mask;
+                    for (;;) {
+                        const int prev = tab[slot];
+                        if (prev == -1) break;
+                        const int64_t *other = corpus + (size_t)prev * (size_t)ld;
+                        bool same = other[h] == (int64_t)c;
+                        for (int t = 0; t < h && same; ++t) same = other[t] == par[t];
+                        if (same) {
+                            found = true;
+                            break;
+                        }
+                        slot = (slot + 1) & mask;
+                    }
+                }
+                if (!found) key = neg_inf;
+            }
+            rowkeys[c] = key;
+        }
+        wave_top(rowkeys, K, m, lane, [&](int r, int c, unsigned v) {
+            ckey[beam * m + r] = v;
+            ccode[beam * m + r] = c;
+        });
+    }
+    __syncthreads();
+
+    // ---- phase B: the k best candidates of the user
+    if (wave == 0) {
+        wave_top(ckey, C, k, lane, [&](int r, int j, unsigned v) {
+            win_idx[r] = j;
+            win_key[r] = v;
+        });
+    }
+    __syncthreads();
+
+    // ---- phase C: outputs
+    const int h1 = h + 1;
+    for (int e = threadIdx.x; e < k * h1; e += blockDim.x) {
+        const int i = e / h1, t = e - i * h1;
+        const int j = win_idx[i];
+        const int beam = j / m;
+        const int64_t v = t < h ? parent_ids[((size_t)b * beams_in + beam) * (size_t)h + t] : (int64_t)ccode[j];
+        out_ids[((size_t)b * k + i) * (size_t)h1 + t] = v;
+    }
+    for (int i = threadIdx.x; i < k; i += blockDim.x) {
+        out_scores[(size_t)b * k + i] = f32_from_order(win_key[i]);
+        out_parent[(size_t)b * k + i] = b * beams_in + win_idx[i] / m;
+    }
+}
+
 int beam_waves(int beams_in) { return beams_in < kBeamMaxWaves ? beams_in : kBeamMaxWaves; }
+
+int topk_keep(int K, int k) { return k < K ? k : K; }  // candidates kept per row
+
+size_t topk_lds_bytes(int beams_in, int K, int k) {
+    return ((size_t)beam_waves(beams_in) * (size_t)K + 2 * (size_t)beams_in * (size_t)topk_keep(K, k)) * sizeof(unsigned);
+}
+
+int check_topk_args(int64_t B, int beams_in, int K, int k, int h) {
+    if (B < 0 || beams_in < 1 || K < 1 || k < 1 || h < 0) {
+        set_error("beam_topk_step: bad sizes (B=%lld, beams_in=%d, K=%d, k=%d, h=%d)", (long long)B, beams_in, K, k, h);
+        return RQHIP_EARG;
+    }
+    if (h == 0 && beams_in != 1) {
+        set_error("beam_topk_step: h = 0 takes beams_in = 1 (got %d)", beams_in);
+        return RQHIP_EARG;
+    }
+    if ((long long)k > (long long)beams_in * (long long)K) {
+        set_error("beam_topk_step: k=%d exceeds the beams_in * K = %lld candidates", k, (long long)beams_in * K);
+        return RQHIP_EARG;
+    }
+    if (K > kBeamMaxK) {
+        set_error("beam_topk_step: K=%d exceeds K <= %d", K, kBeamMaxK);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (k > kBeamMaxTopK) {
+        set_error("beam_topk_step: k=%d exceeds k <= %d", k, kBeamMaxTopK);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (beams_in > kBeamMaxTopK) {
+        set_error("beam_topk_step: beams_in=%d exceeds beams_in <= %d", beams_in, kBeamMaxTopK);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (h + 1 > RQHIP_MAX_PREFIX_LEN) {
+        set_error("beam_topk_step: h + 1 = %d exceeds h + 1 <= RQHIP_MAX_PREFIX_LEN = %d", h + 1, RQHIP_MAX_PREFIX_LEN);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (B >= (1ll << 31)) {
+        set_error("beam_topk_step: B=%lld exceeds one workgroup per user (B < 2^31)", (long long)B);
+        return RQHIP_EUNSUPPORTED;
+    }
+    return RQHIP_OK;
+}
 
 size_t beam_lds_bytes(int beams_in, int K, int n) {
     return ((size_t)beam_waves(beams_in) * (size_t)K + 2 * (size_t)beams_in * (size_t)n) * sizeof(unsigned);
@@ -302,5 +455,51 @@ extern "C" int rqhip_beam_step(const float *logits, int64_t ld_logits, const flo
                        beams_in, K, n_cands, k, reinterpret_cast<const int *>(index), (unsigned)(slots_for(N) - 1),
                        corpus, (long long)N, (long long)ld, out_ids, out_scores, out_parent);
     RQ_CHECK_LAUNCH("beam_step_kernel");
+    return RQHIP_OK;
+}
+
+extern "C" int rqhip_beam_topk_step(const float *logits, int64_t ld_logits, const float *parent_scores,
+                                    const int64_t *parent_ids, int h, int64_t B, int beams_in, int K, int k,
+                                    const void *index, size_t index_bytes, const int64_t *corpus, int64_t N, int H,
+                                    int64_t ld, int64_t *out_ids, float *out_scores, int64_t *out_parent,
+                                    rqhip_stream_t stream) {
+    if (int rc = check_topk_args(B, beams_in, K, k, h)) return rc;
+    if (N < 0 || H < 1 || H > RQHIP_MAX_PREFIX_LEN || ld < H || (N > 0 && !corpus)) {
+        set_error("beam_topk_step: bad corpus (N=%lld, H=%d, ld=%lld; 1 <= H <= %d, ld >= H)", (long long)N, H,
+                  (long long)ld, RQHIP_MAX_PREFIX_LEN);
+        return RQHIP_EARG;
+    }
+    if (N >= (1ll << 30)) {
+        set_error("beam_topk_step: N=%lld exceeds the 2^30 rows the prefix index holds", (long long)N);
+        return RQHIP_EUNSUPPORTED;
+    }
+    if (h + 1 > H) {
+        set_error("beam_topk_step: prefix length h + 1 = %d exceeds the corpus' H = %d id levels", h + 1, H);
+        return RQHIP_EARG;
+    }
+    if (ld_logits < K) {
+        set_error("beam_topk_step: ld_logits=%lld < K=%d", (long long)ld_logits, K);
+        return RQHIP_EARG;
+    }
+    if (B > 0 && (!logits || !out_ids || !out_scores || !out_parent || (h > 0 && (!parent_scores || !parent_ids)))) {
+        set_error("beam_topk_step: null pointer (logits, outputs; parent_scores / parent_ids when h > 0)");
+        return RQHIP_EARG;
+    }
+    if (!index || index_bytes < rqhip_prefix_index_bytes(N, H)) {
+        set_error("beam_topk_step: index buffer too small for N=%lld, H=%d", (long long)N, H);
+        return RQHIP_EWORKSPACE;
+    }
+    if (B == 0) return RQHIP_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = topk_lds_bytes(beams_in, K, k);
+    if (lds > 64 * 1024) {
+        static LdsGrant grant;
+        RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(beam_topk_step_kernel), (int)lds));
+    }
+    hipLaunchKernelGGL(beam_topk_step_kernel, dim3((unsigned)B), dim3(RQ_WAVE * beam_waves(beams_in)), lds, s, logits,
+                       (long long)ld_logits, h > 0 ? parent_scores : nullptr, h > 0 ? parent_ids : nullptr, h, beams_in,
+                       K, topk_keep(K, k), k, reinterpret_cast<const int *>(index), (unsigned)(slots_for(N) - 1), corpus,
+                       (long long)N, (long long)ld, out_ids, out_scores, out_parent);
+    RQ_CHECK_LAUNCH("beam_topk_step_kernel");
     return RQHIP_OK;
 }

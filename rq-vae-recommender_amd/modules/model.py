@@ -41,6 +41,20 @@ the host and no allocation depends on data, so a whole `generate` can be capture
 Sampling: the reference's `torch.multinomial(probas, n, replacement=False)` is ATen's exponential race
 `topk(p / q, n)` with `q = empty_like(p).exponential_(1)`.  `_exponential_like` draws the same q from the same
 generator, so a seeded `generate` consumes the RNG as the reference's does.
+
+`model.beam_impl = "exact"` (default "sample", the search above, unchanged in bits and in RNG use) makes `generate` the
+deterministic constrained beam search: at every level EVERY corpus-valid child of every kept beam is scored, and the k
+best are kept, by ONE ops.beam_topk_step launch per step (csrc/beam_step.hip) in place of the noise draw and
+ops.beam_step.  A child's score is its parent's score plus the log-softmax value (x - max) - log(sum exp(x - max)) of its
+code, in fp32 -- a log-softmax value, which unlike the sampling step's log(softmax) does not underflow to -inf for an
+unlikely code.  Equal scores (-inf included) go to the lower candidate number beam * K + code, i.e. the stable
+descending sort of a user's [beams * K] scores, so the whole output is determined: no noise is drawn, no generator is
+touched, and two calls return the same bits.  It needs k <= K (not k <= n_cands).  A beam it reports as -inf means
+"fewer than k corpus items share the kept prefixes": every kept finite beam is a corpus prefix and so has at least one
+valid child, hence with a finite parent the search never loses a beam to chance, and a user's number of finite beams
+never decreases from level to level.  Everything around the step -- encoder, cross K/V, the decode caches reordered by
+the step's parent rows, the head, every *_impl / *_arith attribute, the returned shapes and dtypes -- is the same, and
+the call is capturable into a graph with no noise baked in.  Any other value raises ValueError at `generate`.
 """
 from typing import List, NamedTuple, Optional
 
@@ -58,6 +72,7 @@ from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
 
 HEAD_IMPLS = ("torch", "hip")
 EMBED_IMPLS = ("torch", "hip")
+BEAM_IMPLS = ("sample", "exact")
 
 
 class ModelOutput(NamedTuple):
@@ -128,6 +143,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.proj_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.matmul_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.attention_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
+        self.beam_impl = "sample"  # or "exact": the search of `generate` (module docstring)
 
     @property
     def device(self) -> torch.device:
@@ -319,7 +335,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, attention_mask, input_ids, user_id=None):
-        """Sampling beam search over the hierarchy levels.
+        """Beam search over the hierarchy levels: the reference's sampling search (beam_impl = "sample"), or the exact
+        constrained search (beam_impl = "exact", module docstring), which replaces the noise draw and ops.beam_step below
+        by one ops.beam_topk_step over all K codes per beam and needs k <= K.
 
         Step 0 decodes BOS on the B users and keeps the best k of n_cands = min(64, K) samples; every later step runs
         the B * k beams' newest id through the decoder (self-attention cache reordered by parent beam; cross-attention
@@ -331,7 +349,13 @@ class EncoderDecoderRetrievalModel(nn.Module):
         corpus prefix)."""
         k = self.top_k_for_generation
         n_cands = min(64, self.num_embeddings_per_hierarchy)
-        if k > n_cands:
+        if self.beam_impl not in BEAM_IMPLS:
+            raise ValueError(f"beam_impl must be one of {BEAM_IMPLS}, got {self.beam_impl!r}")
+        exact = self.beam_impl == "exact"
+        if exact and k > self.num_embeddings_per_hierarchy:
+            raise ValueError(f"top_k_for_generation={k} exceeds the K={self.num_embeddings_per_hierarchy} codes of the "
+                             f"first step (num_embeddings_per_hierarchy)")
+        if not exact and k > n_cands:
             raise ValueError(f"top_k_for_generation={k} exceeds the n_cands={n_cands} samples of the first step "
                              f"(min(64, num_embeddings_per_hierarchy))")
         if not self.codebooks.is_cuda or not input_ids.is_cuda:
@@ -368,8 +392,11 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 hidden, self_kv = dec(x, encoder_attention_mask=enc_mask, past_key_values=self_kv, use_cache=True,
                                       cross_kv=cross_kv)
             logits = F.linear(hidden[:, -1], self.decoder_mlp[h].weight)
-            noise = _exponential_like(logits)
-            ids, scores, parent = ops.beam_step(logits, noise, scores, ids, index._index, index._corpus, n_cands, k)
+            if exact:
+                ids, scores, parent = ops.beam_topk_step(logits, scores, ids, index._index, index._corpus, k)
+            else:
+                noise = _exponential_like(logits)
+                ids, scores, parent = ops.beam_step(logits, noise, scores, ids, index._index, index._corpus, n_cands, k)
         return ids, scores
 
     @torch.no_grad()

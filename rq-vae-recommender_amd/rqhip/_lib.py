@@ -100,6 +100,8 @@ SIGNATURES = {
     "rqhip_beam_step_workspace_bytes": (_sz, [_i64, _int, _int, _int, _int]),
     "rqhip_beam_step": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _vp, _sz, _vp, _i64, _int,
                                _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rqhip_beam_topk_step": (_int, [_vp, _i64, _vp, _vp, _int, _i64, _int, _int, _int, _vp, _sz, _vp, _i64, _int, _i64,
+                                    _vp, _vp, _vp, _vp]),
     "rqhip_t5_attention_supported": (_int, [_int, _int, _int, _int]),
     "rqhip_t5_attention": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _int, _int, _vp, _int,
                                   _int, _vp, _i64, _i64, _vp, _i64, _vp]),

@@ -539,6 +539,54 @@ def beam_step(logits: Tensor, noise: Tensor, parent_scores: Optional[Tensor], pa
     return ids, scores, parent
 
 
+def beam_topk_step(logits: Tensor, parent_scores: Optional[Tensor], parent_ids: Optional[Tensor], index: Tensor,
+                   corpus: Tensor, k: int):
+    """One hierarchy step of the exact constrained beam search in one launch (rqhip_beam_topk_step): every code of every
+    row is scored by its log-softmax value plus the parent's score, codes whose prefix is not in the corpus score -inf,
+    and each user keeps the k best, equal scores (-inf included) to the lower candidate beam * K + code.  No noise.
+
+    logits [B * beams_in, K] fp32 (unit column stride; a row stride is passed through as it is), parent_scores
+    [B, beams_in] fp32 and parent_ids [B, beams_in, h] int64, both None at the first step (beams_in = 1); index / corpus
+    as from prefix_index_build.  Returns ids [B, k, h+1] int64, scores [B, k] fp32 and parent [B, k] int64 (the global
+    row b * beams_in + beam each kept candidate came from).  Shapes decide every allocation; nothing is read back."""
+    _need_gpu(logits, parent_scores, parent_ids, index, corpus)
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise RqHipError(f"beam_topk_step: logits must be a float32 [rows, K] tensor, got {logits.dtype} "
+                         f"{tuple(logits.shape)}")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    rows, K = logits.shape
+    if parent_ids is None:
+        if parent_scores is not None:
+            raise RqHipError("beam_topk_step: parent_scores without parent_ids")
+        h, beams_in = 0, 1
+    else:
+        if parent_ids.dtype != torch.int64 or parent_ids.dim() != 3 or parent_scores is None:
+            raise RqHipError("beam_topk_step: parent_ids must be int64 [B, beams_in, h] and come with parent_scores")
+        beams_in, h = parent_ids.shape[1], parent_ids.shape[2]
+        parent_ids = parent_ids.contiguous()
+        parent_scores = _f32c(parent_scores, "parent_scores")
+    if beams_in < 1 or rows % beams_in != 0:
+        raise RqHipError(f"beam_topk_step: {rows} logit rows are not B * beams_in with beams_in = {beams_in}")
+    B = rows // beams_in
+    if parent_ids is not None and (parent_ids.shape[0] != B or tuple(parent_scores.shape) != (B, beams_in)):
+        raise RqHipError(f"beam_topk_step: parent_ids {tuple(parent_ids.shape)} / parent_scores "
+                         f"{tuple(parent_scores.shape)} do not match B = {B}, beams_in = {beams_in}")
+    corpus = _i64_rows(corpus, "corpus")
+    N, H = corpus.shape
+    dev = logits.device
+    with torch.cuda.device(dev):
+        ids = torch.empty((B, k, h + 1), dtype=torch.int64, device=dev)
+        scores = torch.empty((B, k), dtype=torch.float32, device=dev)
+        parent = torch.empty((B, k), dtype=torch.int64, device=dev)
+        rc = _lib.lib().rqhip_beam_topk_step(_ptr(logits), int(logits.stride(0)) if rows > 1 else K, _ptr(parent_scores),
+                                             _ptr(parent_ids), h, B, beams_in, K, int(k), _ptr(index), index.numel(),
+                                             _ptr(corpus), N, H, _row_stride(corpus), _ptr(ids), _ptr(scores),
+                                             _ptr(parent), _stream())
+        check(rc, "rqhip_beam_topk_step")
+    return ids, scores, parent
+
+
 def t5_attention_supported(dtype: torch.dtype, d_kv: int, n_heads: int, Tq: int, Tk: int) -> bool:
     """Whether t5_attention implements this shape (rqhip_t5_attention_supported): fp32, d_kv = 64, Tq and Tk <= 256."""
     return dtype == torch.float32 and bool(

@@ -29,6 +29,8 @@ What differs:
     not set it.  push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
     reference.
 wandb is optional: with `wandb_logging=True` and no wandb module, metrics are printed.
+The full eval here reports one draw of the sampling beam search; evaluate_decoder.py evaluates a checkpoint with the
+exact constrained search (`model.beam_impl = "exact"`), whose metrics do not depend on the seed.
 
 Not done: replaying the step from a captured hipGraph (the loader's calls make no host read and no data-dependent
 allocation, so they can be recorded), and training on several ranks.

@@ -13,15 +13,19 @@ arms --runs times in one process and ends with one summary line of the medians o
 (modules/t5.py) for every arm: "hip" makes the attention projections grouped ops.t5_proj_fwd launches, the decode
 step's K/V written by them straight into the cache slabs; --ffn sets ffn_impl likewise.  --arith sets matmul_arith, the
 arithmetic of those two "hip" forms ("bf16": bf16 operands, fp32 accumulation); `--arith both` alternates fp32 and bf16
---runs times on one --attention arm of the kernel path and ends with a summary line.
+--runs times on one --attention arm of the kernel path and ends with a summary line.  --beam sets beam_impl
+(modules/model.py) of the kernel path: "sample", the reference's sampling search (a noise draw and one ops.beam_step per
+level), or "exact", the deterministic constrained search (one ops.beam_topk_step per level, no noise); `--beam both`
+alternates the two --runs times on one --attention arm and ends with a summary line of the medians over the runs' block
+medians and their spread.
 
 Device events around each generate after a warm-up; prints one JSON line per path (ms per generate, users/s).
 Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --stats` run of this tool
 (--path one of them, one --attention arm, --iters small).
 
     python tools/bench_generate.py [--path kernel|reference|both] [--attention torch|hip|both] [--runs 5]
-                                   [--proj torch|hip] [--ffn torch|hip] [--arith fp32|bf16|both] [--warmup 3]
-                                   [--iters 10]
+                                   [--proj torch|hip] [--ffn torch|hip] [--arith fp32|bf16|both]
+                                   [--beam sample|exact|both] [--warmup 3] [--iters 10]
 """
 import argparse
 import json
@@ -111,17 +115,44 @@ def main():
     ap.add_argument("--ffn", choices=["torch", "hip"], default="torch", help="ffn_impl of every arm")
     ap.add_argument("--arith", choices=["fp32", "bf16", "both"], default="fp32",
                     help='matmul_arith of the "hip" projections and feed-forward')
-    ap.add_argument("--runs", type=int, default=5, help="alternations of the two arms with --attention / --arith both")
+    ap.add_argument("--beam", choices=["sample", "exact", "both"], default="sample", help="beam_impl of the kernel path")
+    ap.add_argument("--runs", type=int, default=5,
+                    help="alternations of the two arms with --attention / --arith / --beam both")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
     if args.path is None:
-        args.path = "kernel" if args.attention == "both" else "both"
+        args.path = "kernel" if args.attention == "both" or args.beam != "sample" else "both"
     dev = torch.device("cuda")
     model, batch = build(dev)
     model.proj_impl, model.ffn_impl = args.proj, args.ffn
     B = batch.sem_ids.shape[0]
     paths = ["kernel", "reference"] if args.path == "both" else [args.path]
+    if args.beam != "sample" and (args.path != "kernel" or args.arith == "both" or args.attention == "both"):
+        ap.error("--beam exact / both applies to --path kernel on one --attention arm and one --arith")
+    if args.beam == "both":
+        model.attention_impl, model.matmul_arith = args.attention, args.arith
+        medians = {"sample": [], "exact": []}
+        for run in range(args.runs):
+            for arm in ("sample", "exact"):
+                model.beam_impl = arm
+                med, best = time_path(model, batch, args.warmup, args.iters)
+                medians[arm].append(med)
+                print(json.dumps({"path": "kernel", "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
+                                  "arith": args.arith, "beam": arm, "run": run, "batch": B,
+                                  "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),
+                                  "iters": args.iters}), flush=True)
+        mid = {arm: sorted(v)[len(v) // 2] for arm, v in medians.items()}
+        print(json.dumps({"path": "kernel", "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
+                          "arith": args.arith, "beam": "both", "runs": args.runs, "batch": B,
+                          "run_medians_sample": [round(v, 3) for v in medians["sample"]],
+                          "run_medians_exact": [round(v, 3) for v in medians["exact"]],
+                          "ms_per_generate_sample": round(mid["sample"], 3), "ms_per_generate_exact": round(mid["exact"], 3),
+                          "spread_sample": round(max(medians["sample"]) - min(medians["sample"]), 3),
+                          "spread_exact": round(max(medians["exact"]) - min(medians["exact"]), 3),
+                          "exact_over_sample": round(mid["exact"] / mid["sample"], 4)}), flush=True)
+        return
+    model.beam_impl = args.beam
     if args.arith == "both":
         if args.attention == "both" or args.path not in ("kernel", "both"):
             ap.error("--arith both compares the two arithmetics on one --attention arm of --path kernel")
@@ -172,7 +203,7 @@ def main():
             if path == "reference":
                 mm.ops.beam_step, mm._exponential_like = saved, saved_q
         print(json.dumps({"path": path, "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
-                          "arith": args.arith, "batch": B,
+                          "arith": args.arith, "beam": model.beam_impl if path == "kernel" else "sample", "batch": B,
                           "k": model.top_k_for_generation, "L": model.num_hierarchies,
                           "K": model.num_embeddings_per_hierarchy, "corpus": int(model.codebooks.shape[0]),
                           "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),
