@@ -653,6 +653,57 @@ int rqhip_t5_proj_bwd_bf16(const float *x, int64_t ld_x, const float *const *w, 
                            const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w,
                            rqhip_stream_t stream);
 
+/* bf16 weight images for the "bf16" arithmetic of the four calls above (csrc/t5_images.hip; modules/t5.py,
+ * weight_images = "bf16").  The image of a row-major fp32 matrix w [rows, cols] is the dense bf16 matrix img [rows, cols]
+ * with img[r][c] = the round-to-nearest-even bf16 rounding of w[r][c] -- the compiler's (__bf16) conversion, the very
+ * bits the "bf16" arithmetic packs into a fragment (a NaN stays a NaN; the largest finite fp32 values round to inf) --
+ * and its transposed image is img_t [cols, rows], img_t[c][r] = img[r][c].  An element is a 16-bit pattern. */
+typedef uint16_t rqhip_bf16_t;
+/* One launch makes the images of any number of matrices.  The job table is built on the host and lives in DEVICE memory:
+ *   rqhip_bf16_images_job_bytes(n_jobs)   bytes of a table of n_jobs jobs (0 for n_jobs < 0)
+ *   rqhip_bf16_images_fill_jobs           writes the table for the device pointers src[j] [rows[j], cols[j]], img[j] and
+ *       img_t[j] (an entry, or img_t itself, NULL: no transposed image) into the HOST buffer host_jobs (8-byte aligned)
+ *       and returns the launch's workgroup count in *n_tiles: one per 32 x 32 tile, the jobs' tiles in ascending j.  It
+ *       makes no HIP call.  A null host_jobs, src, img, rows, cols, n_tiles, src[j] or img[j], a pointer that is not
+ *       16-byte aligned or n_jobs < 0 returns RQHIP_EARG; rows[j] or cols[j] not a positive multiple of 32 (every tile
+ *       is full: the shapes rqhip_t5_ffn_supported and rqhip_t5_proj_supported admit), or more than 2^31 - 1 tiles,
+ *       returns RQHIP_EUNSUPPORTED.  The caller copies the table to the device and rebuilds it only when a pointer
+ *       changes.
+ *   rqhip_bf16_images(jobs, n_jobs, n_tiles, stream)   with the DEVICE copy of the table: exactly one kernel launch
+ *       and nothing else -- no copy, allocation, memset, host read or sync (graph-capturable).  A workgroup finds its
+ *       job from the table's tile prefix sums; a tile goes through LDS, so that the loads and the stores of both images
+ *       are contiguous.  n_jobs == 0 returns RQHIP_OK and launches nothing; a null table or one that is not 16-byte
+ *       aligned, n_jobs < 0, n_tiles < n_jobs or n_tiles > 2^31 - 1 returns RQHIP_EARG before any HIP call.  src must
+ *       not overlap an image. */
+size_t rqhip_bf16_images_job_bytes(int n_jobs);
+int rqhip_bf16_images_fill_jobs(void *host_jobs, const float *const *src, rqhip_bf16_t *const *img,
+                                rqhip_bf16_t *const *img_t, const int64_t *rows, const int64_t *cols, int n_jobs,
+                                int64_t *n_tiles);
+int rqhip_bf16_images(const void *jobs, int n_jobs, int64_t n_tiles, rqhip_stream_t stream);
+
+/* The "bf16" arithmetic reading its weights from images: the parameter lists of the *_bf16 calls with the weight
+ * pointers typed as images, and their limits, argument checks (shared; the messages name the entry point called),
+ * workspace size, launch plan and launch counts.  Each call reads the images whose ROWS hold its reduction terms:
+ *   rqhip_t5_ffn_fwd_bf16w    wi16 [F, d], wo16 [d, F]                       the images of wi and wo
+ *   rqhip_t5_ffn_bwd_bf16w    wi16t [d, F], wo16t [F, d]                     their transposed images
+ *   rqhip_t5_proj_fwd_bf16w   w16[j] [d_out, d_in]                           (a HOST array of n device pointers)
+ *   rqhip_t5_proj_bwd_bf16w   w16t[j] [d_in, d_out]                          the transposed images (likewise)
+ * Arithmetic contract: results are those of `*_bf16` on the weights the images were made from, bit for bit, for every
+ * output (y, h, d_x, the workspace's g, d_wi, d_wo, d_w[j]).  An image element is the rounded operand itself, a lane's
+ * eight terms of a column are one 16-byte load, groups, chains and their order are unchanged, and which lane serves a
+ * column does not enter its sum.  Keeping the images current is the caller's business: a stale image gives the result
+ * of *_bf16 on the OLD weights.  The weight gradients read no weights. */
+int rqhip_t5_ffn_fwd_bf16w(const float *x, const rqhip_bf16_t *wi16, const rqhip_bf16_t *wo16, int64_t N, int d, int F,
+                           double p, const int64_t *seed, float *y, float *h, rqhip_stream_t stream);
+int rqhip_t5_ffn_bwd_bf16w(const float *x, const rqhip_bf16_t *wi16t, const rqhip_bf16_t *wo16t, const float *h,
+                           const float *d_y, int64_t N, int d, int F, double p, const int64_t *seed, float *d_x,
+                           float *d_wi, float *d_wo, void *workspace, rqhip_stream_t stream);
+int rqhip_t5_proj_fwd_bf16w(const float *x, int64_t ld_x, const rqhip_bf16_t *const *w16, float *const *y,
+                            const int64_t *ld_y, int n, int64_t N, int d_in, int d_out, rqhip_stream_t stream);
+int rqhip_t5_proj_bwd_bf16w(const float *x, int64_t ld_x, const rqhip_bf16_t *const *w16t, const float *const *d_y,
+                            const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w,
+                            rqhip_stream_t stream);
+
 /* The retrieval model's input embedding in one launch forward and one backward (csrc/sid_embed.hip; modules/model.py,
  * embed_impl = "hip"): semantic ids -> a T5 stack's inputs_embeds, for the encoder and the decoder front alike.
  * B rows, `items` items per row, L levels, K codes per level, width d; table [V = L * K, d], x dense [B, T, d], fp32.

@@ -41,7 +41,16 @@
 // instruction (csrc/t5_common.h).  In the weight-gradient kernel the lane's eight rows 4 ks + kq of a block become the
 // elements j = ks of both fragments, a consistent permutation of the block's 32 rows.  Memory and LDS stay fp32: the
 // rounding happens in registers, so h is stored unrounded and the chunk buffer holds fp32 hd / g.
+//
+// Weight images (template parameter IMG of the row kernel, with BF only; entry points rqhip_t5_ffn_*_bf16w): the weights
+// come from bf16 images (csrc/t5_images.hip), which hold the values the "bf16" arithmetic rounds them to.  The reduction
+// always runs along an image's rows -- forward wi16 [F, d] and wo16 [d, F], backward the TRANSPOSED images wo16t [F, d]
+// and wi16t [d, F] -- so a lane's 8 terms of a column tile are ONE 16-byte load, which is the instruction's B fragment as
+// it stands: no conversion, half the registers in the operand buffers, and the backward serves column 16 ct + i like
+// the forward.  Which lane serves a column does not enter its sum, so every output has the bits of the BF arm.
 #include <math.h>
+
+#include <type_traits>
 
 #include "rqhip_common.h"
 #include "t5_common.h"
@@ -66,7 +75,8 @@ bool ffn_supported(int d, int F) {
 
 struct FfnRows {
     const float *x;            // forward: x [N, d]; backward: d_y [N, d]
-    const float *w1, *w2;      // forward: wi [F, d], wo [d, F]; backward: wo, wi
+    const float *w1, *w2;      // forward: wi [F, d], wo [d, F]; backward: wo, wi.  IMG: the bf16 images behind these
+                               // pointers, forward wi16 [F, d], wo16 [d, F]; backward wo16t [F, d], wi16t [d, F]
     const float *h_in;         // backward: h [N, F]
     float *mid;                // forward: h (or null); backward: g (or null)
     float *out;                // forward: y; backward: d_x (null: phase 2 is skipped)
@@ -110,6 +120,13 @@ __device__ __forceinline__ void ffn_load_b(const float *at, size_t ld, float (&b
     }
 }
 
+// the same operand from a bf16 image whose rows hold the reduction terms: `at` as for KN = false; the 16 bytes are the
+// lane's fragment of a column tile
+__device__ __forceinline__ void ffn_load_b(const __bf16 *at, size_t ld, bf16x8 (&b)[2]) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) b[ct] = *reinterpret_cast<const bf16x8 *>(at + (size_t)(16 * ct) * ld);
+}
+
 // one group of 32 terms.  BF: the "bf16" arithmetic, one instruction per tile on the same eight registers, rounded and
 // packed pairwise (csrc/t5_common.h)
 template <int RT, bool BF>
@@ -133,6 +150,18 @@ __device__ __forceinline__ void ffn_mma(const float (&a)[RT][8], const float (&b
     }
 }
 
+// the "bf16" arithmetic on weight fragments that come packed from an image
+template <int RT, bool BF>
+__device__ __forceinline__ void ffn_mma(const float (&a)[RT][8], const bf16x8 (&b)[2], f32x4 (&acc)[RT][2]) {
+    static_assert(BF, "weight images belong to the bf16 arithmetic");
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const bf16x8 ar = pack_bf16x8(a[rt]);
+        acc[rt][0] = mma_group_bf16(ar, b[0], acc[rt][0]);
+        acc[rt][1] = mma_group_bf16(ar, b[1], acc[rt][1]);
+    }
+}
+
 // a finished chain joins the sum of the chains before it; the next chain starts from +0
 template <int RT>
 __device__ __forceinline__ void ffn_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][2]) {
@@ -150,9 +179,15 @@ __device__ __forceinline__ void ffn_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][
 #define FFN_FENCE __builtin_amdgcn_sched_barrier(0)
 
 // RT: 16-row tiles per workgroup; NP: column pairs (32 output columns) per wave, >= ceil(d / 128); BF: the "bf16"
-// arithmetic (memory, LDS and the epilogues stay fp32: the operands are rounded as the fragments are packed)
-template <int RT, int NP, bool BWD, bool BF>
+// arithmetic (memory, LDS and the epilogues stay fp32: the operands are rounded as the fragments are packed); IMG: the
+// weights are bf16 images read along their rows (the backward's are the transposed ones)
+template <int RT, int NP, bool BWD, bool BF, bool IMG = false>
 __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
+    static_assert(BF || !IMG, "weight images belong to the bf16 arithmetic");
+    constexpr bool KN = BWD && !IMG;               // the reduction runs down the columns of the weights as stored
+    using WT = std::conditional_t<IMG, __bf16, float>;
+    using WB = std::conditional_t<IMG, bf16x8[2], float[2][8]>;      // a group's weight operand for two column tiles
+    const WT *w1 = reinterpret_cast<const WT *>(p.w1), *w2 = reinterpret_cast<const WT *>(p.w2);
     extern __shared__ __align__(16) float ffn_lds[];
     constexpr int T = 16 * RT;
     const int d = p.d, F = p.F, ldx = d + 4;
@@ -186,19 +221,20 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
     constexpr int RG = 2;                          // groups per round of phase 1: two rounds are one chain
     static_assert(kFfnChainGroups == 2 * RG, "a chain is closed after every second round");
     const int nr1 = (ngd + RG - 1) / RG;
-    const size_t ld1 = BWD ? (size_t)F : (size_t)d, ld2 = BWD ? (size_t)d : (size_t)F;
-    float pb[2][RG][2][8];                         // phase 1: two rounds
-    float qb[2][NP][2][8];                         // phase 2: two groups
-    auto load1 = [&](float (&dst)[RG][2][8], int fw, int r) {
+    const size_t ld1 = KN ? (size_t)F : (size_t)d, ld2 = KN ? (size_t)d : (size_t)F;
+    WB pb[2][RG];                                  // phase 1: two rounds
+    WB qb[2][NP];                                  // phase 2: two groups
+    auto load1 = [&](WB (&dst)[RG], int fw, int r) {
 #pragma unroll
         for (int gg = 0; gg < RG; ++gg) {
             const int g = min(RG * r + gg, ngd - 1);      // past d: a valid group is read and not used
-            const float *at = BWD ? p.w1 + (size_t)(32 * g + 8 * kq) * F + fw + 2 * i
-                                  : p.w1 + (size_t)(fw + i) * d + 32 * g + 8 * kq;
-            ffn_load_b<BWD>(at, ld1, dst[gg]);
+            const WT *at = KN ? w1 + (size_t)(32 * g + 8 * kq) * F + fw + 2 * i
+                              : w1 + (size_t)(fw + i) * d + 32 * g + 8 * kq;
+            if constexpr (IMG) ffn_load_b(at, ld1, dst[gg]);
+            else ffn_load_b<KN>(at, ld1, dst[gg]);
         }
     };
-    auto comp1 = [&](const float (&src)[RG][2][8], int r, f32x4 (&run)[RT][2]) {
+    auto comp1 = [&](const WB (&src)[RG], int r, f32x4 (&run)[RT][2]) {
 #pragma unroll
         for (int gg = 0; gg < RG; ++gg) {
             const int g = RG * r + gg;
@@ -209,18 +245,19 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
             }
         }
     };
-    auto load2 = [&](float (&dst)[NP][2][8], int f0, int g) {
+    auto load2 = [&](WB (&dst)[NP], int f0, int g) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
             const int pair = w + 4 * q;
             if (pair < npairs) {
-                const float *at = BWD ? p.w2 + (size_t)(f0 + 32 * g + 8 * kq) * d + 32 * pair + 2 * i
-                                      : p.w2 + (size_t)(32 * pair + i) * F + f0 + 32 * g + 8 * kq;
-                ffn_load_b<BWD>(at, ld2, dst[q]);
+                const WT *at = KN ? w2 + (size_t)(f0 + 32 * g + 8 * kq) * d + 32 * pair + 2 * i
+                                  : w2 + (size_t)(32 * pair + i) * F + f0 + 32 * g + 8 * kq;
+                if constexpr (IMG) ffn_load_b(at, ld2, dst[q]);
+                else ffn_load_b<KN>(at, ld2, dst[q]);
             }
         }
     };
-    auto comp2 = [&](const float (&src)[NP][2][8], const float *hb, int g, f32x4 (&run)[NP][RT][2]) {
+    auto comp2 = [&](const WB (&src)[NP], const float *hb, int g, f32x4 (&run)[NP][RT][2]) {
         float a[RT][8];
         ffn_load_a<RT>(hb + i * kFfnLdh + 8 * kq, kFfnLdh, 32 * g, a);
 #pragma unroll
@@ -246,8 +283,13 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const long long grow = m0 + 16 * rt + 4 * kq + r;
-                        const f32x2 v = *reinterpret_cast<const f32x2 *>(p.h_in + (size_t)(grow < p.N ? grow : p.N - 1) * F + fw + 2 * i);
-                        hv[rt][0][r] = v.x; hv[rt][1][r] = v.y;
+                        const float *hr = p.h_in + (size_t)(grow < p.N ? grow : p.N - 1) * F + fw;
+                        if constexpr (KN) {
+                            const f32x2 v = *reinterpret_cast<const f32x2 *>(hr + 2 * i);
+                            hv[rt][0][r] = v.x; hv[rt][1][r] = v.y;
+                        } else {
+                            hv[rt][0][r] = hr[i]; hv[rt][1][r] = hr[16 + i];
+                        }
                     }
             }
             for (int r = 0; r < nr1; r += 2) {
@@ -263,14 +305,14 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
         if (p.out) load2(qb[0], f0, 0);
         FFN_FENCE;
         if (fw < F) {
-            // acc1[rt][ct][r]: row 16 rt + 4 kq + r; column 16 ct + i (forward) or 2 i + ct (backward) of the wave's 32
+            // acc1[rt][ct][r]: row 16 rt + 4 kq + r; column 16 ct + i (forward, images) or 2 i + ct (backward) of the wave's 32
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int row = 16 * rt + 4 * kq + r, lc = 32 * w + (BWD ? 2 * i + ct : 16 * ct + i);
+                        const int row = 16 * rt + 4 * kq + r, lc = 32 * w + (KN ? 2 * i + ct : 16 * ct + i);
                         const long long grow = m0 + row;
                         const unsigned long long f = (unsigned long long)(f0 + lc);
                         float v = acc1[rt][ct][r];
@@ -325,7 +367,7 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
                 const long long grow = m0 + 16 * rt + 4 * kq + r;
                 if (grow >= p.N) continue;
                 float *o = p.out + (size_t)grow * d + 32 * pair;
-                if constexpr (BWD) {
+                if constexpr (KN) {
                     *reinterpret_cast<f32x2 *>(o + 2 * i) = f32x2{acc2[q][rt][0][r], acc2[q][rt][1][r]};
                 } else {
                     o[i] = acc2[q][rt][0][r];
@@ -477,35 +519,36 @@ int ffn_check(const char *who, int64_t N, int d, int F, double p) {
     return RQHIP_OK;
 }
 
-template <int RT, int NP, bool BWD, bool BF>
+template <int RT, int NP, bool BWD, bool BF, bool IMG>
 int ffn_rows_launch(const FfnRows &p, hipStream_t s) {
     static LdsGrant grant;
     constexpr int T = 16 * RT;
     const int bytes = (T * (p.d + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
     // granted once per device: the most this instantiation can ask for (d <= 128 NP)
     constexpr int most = (T * (128 * NP + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
-    RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_ffn_rows_kernel<RT, NP, BWD, BF>), most));
-    hipLaunchKernelGGL((t5_ffn_rows_kernel<RT, NP, BWD, BF>), dim3((unsigned)((p.N + T - 1) / T)), dim3(256), (size_t)bytes, s, p);
+    RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_ffn_rows_kernel<RT, NP, BWD, BF, IMG>), most));
+    hipLaunchKernelGGL((t5_ffn_rows_kernel<RT, NP, BWD, BF, IMG>), dim3((unsigned)((p.N + T - 1) / T)), dim3(256), (size_t)bytes, s, p);
     RQ_CHECK_LAUNCH("t5_ffn_rows_kernel");
     return RQHIP_OK;
 }
 
-template <bool BWD, bool BF>
+template <bool BWD, bool BF, bool IMG>
 int ffn_rows(const FfnRows &p, hipStream_t s) {
     const int np = (p.d / 32 + 3) / 4, rt = ffn_row_tiles(p.N);
     // The "bf16" backward at d > 384 keeps 16-row tiles at every N: its 32-row instantiation would spill to scratch
-    // (so does the fp32 one, 44 bytes per lane, which stays as it is).  The tile height changes no bit.
+    // (so does the fp32 one, 44 bytes per lane, which stays as it is).  The tile height changes no bit.  The image
+    // arm follows the same plan.
     constexpr bool kShortOnly = BF && BWD;
     if (rt == 1 || (kShortOnly && np == 4)) {
-        if (np == 1) return ffn_rows_launch<1, 1, BWD, BF>(p, s);
-        if (np == 2) return ffn_rows_launch<1, 2, BWD, BF>(p, s);
-        if (np == 3) return ffn_rows_launch<1, 3, BWD, BF>(p, s);
-        return ffn_rows_launch<1, 4, BWD, BF>(p, s);
+        if (np == 1) return ffn_rows_launch<1, 1, BWD, BF, IMG>(p, s);
+        if (np == 2) return ffn_rows_launch<1, 2, BWD, BF, IMG>(p, s);
+        if (np == 3) return ffn_rows_launch<1, 3, BWD, BF, IMG>(p, s);
+        return ffn_rows_launch<1, 4, BWD, BF, IMG>(p, s);
     }
-    if (np == 1) return ffn_rows_launch<2, 1, BWD, BF>(p, s);
-    if (np == 2) return ffn_rows_launch<2, 2, BWD, BF>(p, s);
-    if (np == 3) return ffn_rows_launch<2, 3, BWD, BF>(p, s);
-    if constexpr (!kShortOnly) return ffn_rows_launch<2, 4, BWD, BF>(p, s);
+    if (np == 1) return ffn_rows_launch<2, 1, BWD, BF, IMG>(p, s);
+    if (np == 2) return ffn_rows_launch<2, 2, BWD, BF, IMG>(p, s);
+    if (np == 3) return ffn_rows_launch<2, 3, BWD, BF, IMG>(p, s);
+    if constexpr (!kShortOnly) return ffn_rows_launch<2, 4, BWD, BF, IMG>(p, s);
     return RQHIP_EUNSUPPORTED;      // not reached: np == 4 left above
 }
 
@@ -524,8 +567,9 @@ extern "C" size_t rqhip_t5_ffn_bwd_workspace_bytes(int64_t N, int d, int F) {
 
 namespace {
 
-// the entry points of both arithmetics; `who` names the one called in the messages
-template <bool BF>
+// the entry points of both arithmetics; `who` names the one called in the messages.  IMG: wi and wo are the bf16 images
+// the call reads (forward wi16, wo16; backward wo16t, wi16t, passed in the places of wo and wi)
+template <bool BF, bool IMG = false>
 int ffn_fwd(const char *who, const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
             const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
     const int rc = ffn_check(who, N, d, F, p);
@@ -548,10 +592,10 @@ int ffn_fwd(const char *who, const float *x, const float *wi, const float *wo, i
     a.x = x, a.w1 = wi, a.w2 = wo, a.h_in = nullptr, a.mid = h, a.out = y;
     a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
     a.N = N, a.d = d, a.F = F;
-    return ffn_rows<false, BF>(a, reinterpret_cast<hipStream_t>(stream));
+    return ffn_rows<false, BF, IMG>(a, reinterpret_cast<hipStream_t>(stream));
 }
 
-template <bool BF>
+template <bool BF, bool IMG = false>
 int ffn_bwd(const char *who, const float *x, const float *wi, const float *wo, const float *h, const float *d_y, int64_t N,
             int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi, float *d_wo, void *workspace,
             rqhip_stream_t stream) {
@@ -583,7 +627,7 @@ int ffn_bwd(const char *who, const float *x, const float *wi, const float *wo, c
         a.x = d_y, a.w1 = wo, a.w2 = wi, a.h_in = h, a.mid = g, a.out = d_x;
         a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
         a.N = N, a.d = d, a.F = F;
-        const int rc1 = ffn_rows<true, BF>(a, s);
+        const int rc1 = ffn_rows<true, BF, IMG>(a, s);
         if (rc1 != RQHIP_OK) return rc1;
     }
     if (d_wi || d_wo) {
@@ -621,4 +665,18 @@ extern "C" int rqhip_t5_ffn_bwd_bf16(const float *x, const float *wi, const floa
                                      int64_t N, int d, int F, double p, const int64_t *seed, float *d_x, float *d_wi,
                                      float *d_wo, void *workspace, rqhip_stream_t stream) {
     return ffn_bwd<true>("t5_ffn_bwd_bf16", x, wi, wo, h, d_y, N, d, F, p, seed, d_x, d_wi, d_wo, workspace, stream);
+}
+
+extern "C" int rqhip_t5_ffn_fwd_bf16w(const float *x, const rqhip_bf16_t *wi16, const rqhip_bf16_t *wo16, int64_t N, int d,
+                                      int F, double p, const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
+    return ffn_fwd<true, true>("t5_ffn_fwd_bf16w", x, reinterpret_cast<const float *>(wi16),
+                               reinterpret_cast<const float *>(wo16), N, d, F, p, seed, y, h, stream);
+}
+
+extern "C" int rqhip_t5_ffn_bwd_bf16w(const float *x, const rqhip_bf16_t *wi16t, const rqhip_bf16_t *wo16t, const float *h,
+                                      const float *d_y, int64_t N, int d, int F, double p, const int64_t *seed, float *d_x,
+                                      float *d_wi, float *d_wo, void *workspace, rqhip_stream_t stream) {
+    return ffn_bwd<true, true>("t5_ffn_bwd_bf16w", x, reinterpret_cast<const float *>(wi16t),
+                               reinterpret_cast<const float *>(wo16t), h, d_y, N, d, F, p, seed, d_x, d_wi, d_wo, workspace,
+                               stream);
 }

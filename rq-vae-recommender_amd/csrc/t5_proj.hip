@@ -32,6 +32,13 @@
 // Second arithmetic, "bf16" (template parameter BF, entry points rqhip_t5_proj_*_bf16): t5_ffn.hip's, one
 // v_mfma_f32_16x16x32_bf16 per group on the same eight registers, rounded to bf16 and packed in front of it
 // (csrc/t5_common.h); loads, chains and stores do not change.
+//
+// Weight images (template parameter IMG of the row kernel, with BF only; entry points rqhip_t5_proj_*_bf16w):
+// t5_ffn.hip's.  The weights come from bf16 images (csrc/t5_images.hip) and the reduction runs along their rows, forward
+// w16[j] [d_out, d_in], d_x the TRANSPOSED images w16t[j] [d_in, d_out]: one 16-byte load per column tile is the B
+// fragment as it stands, and d_x's lanes serve column 16 ct + i like the forward's.  Bits are the BF arm's.
+#include <type_traits>
+
 #include "rqhip_common.h"
 #include "t5_common.h"
 
@@ -56,7 +63,8 @@ bool proj_supported(int d_in, int d_out, int n) {
 struct ProjRows {
     const float *a[kProjMaxN];      // forward: a[0] = x; d_x: the d_y[j] that are not NULL, in ascending j
     long long ld_a[kProjMaxN];
-    const float *w[kProjMaxN];      // the weights [d_out, d_in] that go with y[j] (forward) or with a[j] (d_x)
+    const float *w[kProjMaxN];      // the weights [d_out, d_in] that go with y[j] (forward) or with a[j] (d_x).  IMG: the
+                                    // bf16 images behind these pointers, forward [d_out, d_in], d_x transposed [d_in, d_out]
     float *out[kProjMaxN];          // forward: y[j]; d_x: out[0] = d_x
     long long ld_o[kProjMaxN];
     long long N;
@@ -83,6 +91,13 @@ __device__ __forceinline__ void proj_load_b(const float *at, size_t ld, float (&
             b[ct][4] = hi.x; b[ct][5] = hi.y; b[ct][6] = hi.z; b[ct][7] = hi.w;
         }
     }
+}
+
+// the same operand from a bf16 image whose rows hold the reduction terms: `at` as for KN = false; the 16 bytes are the
+// lane's fragment of a column tile
+__device__ __forceinline__ void proj_load_b(const __bf16 *at, size_t ld, bf16x8 (&b)[2]) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) b[ct] = *reinterpret_cast<const bf16x8 *>(at + (size_t)(16 * ct) * ld);
 }
 
 __device__ __forceinline__ void proj_load_a(const float *at, float (&a)[8]) {
@@ -115,6 +130,18 @@ __device__ __forceinline__ void proj_mma(const float (&a)[RT][8], const float (&
     }
 }
 
+// the "bf16" arithmetic on weight fragments that come packed from an image
+template <int RT, bool BF>
+__device__ __forceinline__ void proj_mma(const float (&a)[RT][8], const bf16x8 (&b)[2], f32x4 (&acc)[RT][2]) {
+    static_assert(BF, "weight images belong to the bf16 arithmetic");
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const bf16x8 ar = pack_bf16x8(a[rt]);
+        acc[rt][0] = mma_group_bf16(ar, b[0], acc[rt][0]);
+        acc[rt][1] = mma_group_bf16(ar, b[1], acc[rt][1]);
+    }
+}
+
 // a finished chain joins the sum of the chains before it; the next chain starts from +0
 template <int RT>
 __device__ __forceinline__ void proj_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][2]) {
@@ -131,9 +158,14 @@ __device__ __forceinline__ void proj_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT]
 // keeps a step's loads together and in front of the previous step's matrix instructions (csrc/mlp_small.hip)
 #define PROJ_FENCE __builtin_amdgcn_sched_barrier(0)
 
-// RT: 16-row tiles per workgroup; BF: the "bf16" arithmetic (the operands are rounded as the fragments are packed)
-template <bool BWD, int RT, bool BF>
+// RT: 16-row tiles per workgroup; BF: the "bf16" arithmetic (the operands are rounded as the fragments are packed); IMG:
+// the weights are bf16 images read along their rows (d_x's are the transposed ones)
+template <bool BWD, int RT, bool BF, bool IMG = false>
 __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
+    static_assert(BF || !IMG, "weight images belong to the bf16 arithmetic");
+    constexpr bool KN = BWD && !IMG;               // the reduction runs down the columns of the weights as stored
+    using WT = std::conditional_t<IMG, __bf16, float>;
+    using WB = std::conditional_t<IMG, bf16x8[2], float[2][8]>;      // a group's weight operand for two column tiles
     const int t = threadIdx.x, lane = t & 63, i = lane & 15, kq = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const long long m0 = (long long)blockIdx.x * (16 * RT);
@@ -149,13 +181,18 @@ __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
 
     // the steps of the reduction are loaded in order: the next one is group g of segment seg
     int seg = 0, g = 0;
-    auto load = [&](float (&a)[RT][8], float (&b)[2][8]) {
+    auto load = [&](float (&a)[RT][8], WB &b) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
             proj_load_a(p.a[seg] + (size_t)arow[rt] * (size_t)p.ld_a[seg] + 32 * g + 8 * kq, a[rt]);
-        const float *at = BWD ? p.w[seg] + (size_t)(32 * g + 8 * kq) * d_in + c0 + 2 * i
-                              : p.w[jo] + (size_t)(c0 + i) * d_in + 32 * g + 8 * kq;
-        proj_load_b<BWD>(at, (size_t)d_in, b);
+        if constexpr (IMG) {       // row c0 + i of the image: the ld terms of the output column's reduction
+            const size_t ld = BWD ? (size_t)d_out : (size_t)d_in;
+            proj_load_b(reinterpret_cast<const WT *>(p.w[BWD ? seg : jo]) + (size_t)(c0 + i) * ld + 32 * g + 8 * kq, ld, b);
+        } else {
+            const float *at = BWD ? p.w[seg] + (size_t)(32 * g + 8 * kq) * d_in + c0 + 2 * i
+                                  : p.w[jo] + (size_t)(c0 + i) * d_in + 32 * g + 8 * kq;
+            proj_load_b<BWD>(at, (size_t)d_in, b);
+        }
         if (++g == ng) g = 0, ++seg;
     };
     f32x4 sum[RT][2], run[RT][2];      // the sum of the finished chains; the running chain
@@ -163,7 +200,10 @@ __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) sum[rt][ct] = run[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float a0[RT][8], b0[2][8], a1[RT][8], b1[2][8];
+    float a0[RT][8];
+    WB b0;
+    float a1[RT][8];
+    WB b1;
     load(a0, b0);
     for (int it = 0; it < total; it += 2) {
         if (it + 1 < total) load(a1, b1);
@@ -177,7 +217,7 @@ __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
     }
     static_assert(kProjChainGroups % 2 == 0, "chains are closed after every second step");
 
-    // sum[rt][ct][r]: row 16 rt + 4 kq + r; column 16 ct + i (forward) or 2 i + ct (d_x) of the wave's 32
+    // sum[rt][ct][r]: row 16 rt + 4 kq + r; column 16 ct + i (forward, images) or 2 i + ct (d_x) of the wave's 32
     float *o = p.out[jo] + c0;
     const size_t ldo = (size_t)p.ld_o[jo];
 #pragma unroll
@@ -186,7 +226,7 @@ __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
         for (int r = 0; r < 4; ++r) {
             const long long grow = m0 + 16 * rt + 4 * kq + r;
             if (grow >= p.N) continue;
-            if constexpr (BWD) {
+            if constexpr (KN) {
                 *reinterpret_cast<f32x2 *>(o + (size_t)grow * ldo + 2 * i) = f32x2{sum[rt][0][r], sum[rt][1][r]};
             } else {
                 o[(size_t)grow * ldo + i] = sum[rt][0][r];
@@ -327,24 +367,25 @@ bool proj_ld_ok(int64_t ld, int width) { return ld >= width && ld % 4 == 0; }
 // 16-row tiles per workgroup: a function of N alone, and the chains do not depend on it
 int proj_row_tiles(long long N) { return N > kProjTallFrom ? 4 : N > kProjTallFrom / 2 ? 2 : 1; }
 
-template <bool BWD, int RT, bool BF>
+template <bool BWD, int RT, bool BF, bool IMG>
 int proj_rows_launch_rt(const ProjRows &a, int cols, hipStream_t s) {
     const dim3 grid((unsigned)((a.N + 16 * RT - 1) / (16 * RT)), (unsigned)((cols + kProjChunk - 1) / kProjChunk));
-    hipLaunchKernelGGL((t5_proj_rows_kernel<BWD, RT, BF>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((t5_proj_rows_kernel<BWD, RT, BF, IMG>), grid, dim3(256), 0, s, a);
     RQ_CHECK_LAUNCH("t5_proj_rows_kernel");
     return RQHIP_OK;
 }
 
-template <bool BWD, bool BF>
+template <bool BWD, bool BF, bool IMG>
 int proj_rows_launch(const ProjRows &a, int cols, hipStream_t s) {
     const int rt = proj_row_tiles(a.N);
-    if (rt == 1) return proj_rows_launch_rt<BWD, 1, BF>(a, cols, s);
-    if (rt == 2) return proj_rows_launch_rt<BWD, 2, BF>(a, cols, s);
-    return proj_rows_launch_rt<BWD, 4, BF>(a, cols, s);
+    if (rt == 1) return proj_rows_launch_rt<BWD, 1, BF, IMG>(a, cols, s);
+    if (rt == 2) return proj_rows_launch_rt<BWD, 2, BF, IMG>(a, cols, s);
+    return proj_rows_launch_rt<BWD, 4, BF, IMG>(a, cols, s);
 }
 
-// the entry points of both arithmetics; `who` names the one called in the messages
-template <bool BF>
+// the entry points of both arithmetics; `who` names the one called in the messages.  IMG: w[j] are the bf16 images the
+// call reads (forward w16[j], backward the transposed w16t[j])
+template <bool BF, bool IMG = false>
 int proj_fwd(const char *who, const float *x, int64_t ld_x, const float *const *w, float *const *y, const int64_t *ld_y,
              int n, int64_t N, int d_in, int d_out, rqhip_stream_t stream) {
     const int rc = proj_check(who, n, N, d_in, d_out);
@@ -376,10 +417,10 @@ int proj_fwd(const char *who, const float *x, int64_t ld_x, const float *const *
                   (long long)ld_x, d_in);
         return RQHIP_EARG;
     }
-    return proj_rows_launch<false, BF>(a, n * d_out, reinterpret_cast<hipStream_t>(stream));
+    return proj_rows_launch<false, BF, IMG>(a, n * d_out, reinterpret_cast<hipStream_t>(stream));
 }
 
-template <bool BF>
+template <bool BF, bool IMG = false>
 int proj_bwd(const char *who, const float *x, int64_t ld_x, const float *const *w, const float *const *d_y,
              const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w,
              rqhip_stream_t stream) {
@@ -421,7 +462,7 @@ int proj_bwd(const char *who, const float *x, int64_t ld_x, const float *const *
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (d_x && na) {
         a.out[0] = d_x, a.ld_o[0] = d_in, a.N = N, a.n = na, a.d_in = d_in, a.d_out = d_out;
-        const int rc1 = proj_rows_launch<true, BF>(a, d_in, s);
+        const int rc1 = proj_rows_launch<true, BF, IMG>(a, d_in, s);
         if (rc1 != RQHIP_OK) return rc1;
     }
     if (nq) {
@@ -461,4 +502,17 @@ extern "C" int rqhip_t5_proj_bwd_bf16(const float *x, int64_t ld_x, const float 
                                       const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x,
                                       float *const *d_w, rqhip_stream_t stream) {
     return proj_bwd<true>("t5_proj_bwd_bf16", x, ld_x, w, d_y, ld_dy, n, N, d_in, d_out, d_x, d_w, stream);
+}
+
+extern "C" int rqhip_t5_proj_fwd_bf16w(const float *x, int64_t ld_x, const rqhip_bf16_t *const *w16, float *const *y,
+                                       const int64_t *ld_y, int n, int64_t N, int d_in, int d_out, rqhip_stream_t stream) {
+    return proj_fwd<true, true>("t5_proj_fwd_bf16w", x, ld_x, reinterpret_cast<const float *const *>(w16), y, ld_y, n, N, d_in,
+                                d_out, stream);
+}
+
+extern "C" int rqhip_t5_proj_bwd_bf16w(const float *x, int64_t ld_x, const rqhip_bf16_t *const *w16t, const float *const *d_y,
+                                       const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x,
+                                       float *const *d_w, rqhip_stream_t stream) {
+    return proj_bwd<true, true>("t5_proj_bwd_bf16w", x, ld_x, reinterpret_cast<const float *const *>(w16t), d_y, ld_dy, n, N,
+                                d_in, d_out, d_x, d_w, stream);
 }

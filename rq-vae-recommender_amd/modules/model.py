@@ -17,6 +17,10 @@ effect on the "torch" bodies, nor on the attention, the norms, the heads or the 
 attention calls that `attention_long_impl` = "hip" takes (bf16 matrix operands, fp32 softmax and storage; modules/t5.py),
 `generate`'s cross-attention included.  The short kernel and the cached decode step stay fp32.  It is set on the model:
 train_decoder.train has no parameter for it.
+`model.weight_images` ("none", the default, or "bf16") goes to both stacks with them: with "bf16" the calls that already
+take a "hip" matrix body in `matmul_arith` = "bf16" read bf16 images of their weights, which each stack keeps current
+with one refresh launch per change of the weights (modules/t5.py: T5WeightImages); every result keeps its bits, and
+everywhere else the attribute has no effect.  It is set on the model: train_decoder.train has no parameter for it.
 `model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
 cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
 on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
@@ -65,7 +69,7 @@ from torch import Tensor
 
 from data.schemas import TokenizedSeqBatch
 from modules.sid_prefix import SemIdPrefixIndex
-from modules.t5 import ATTENTION_ARITHS, MATMUL_ARITHS, T5Config, T5EncoderModel, T5Stack
+from modules.t5 import ATTENTION_ARITHS, MATMUL_ARITHS, WEIGHT_IMAGES, T5Config, T5EncoderModel, T5Stack
 from rqhip import ops
 from rqhip._lib import RqHipError
 from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
@@ -143,6 +147,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.proj_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.matmul_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.attention_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
+        self.weight_images = "none"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.beam_impl = "sample"  # or "exact": the search of `generate` (module docstring)
 
     @property
@@ -196,8 +201,10 @@ class EncoderDecoderRetrievalModel(nn.Module):
             raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
         if self.attention_arith not in ATTENTION_ARITHS:
             raise ValueError(f"attention_arith must be one of {ATTENTION_ARITHS}, got {self.attention_arith!r}")
+        if self.weight_images not in WEIGHT_IMAGES:
+            raise ValueError(f"weight_images must be one of {WEIGHT_IMAGES}, got {self.weight_images!r}")
         for name in ("attention_impl", "attention_long_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith",
-                     "attention_arith"):
+                     "attention_arith", "weight_images"):
             for stack in (self.encoder.encoder, self.t5_decoder):
                 setattr(stack, name, getattr(self, name))
 

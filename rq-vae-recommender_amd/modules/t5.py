@@ -66,6 +66,24 @@ operand of a matrix product to bf16 and accumulates in fp32 (include/rqhip.h); w
 the state dict stay fp32.  With the "torch" bodies it has no effect: the operators stay fp32, and so do the attention
 itself, the norms and the glue.
 
+`weight_images` = "none" (the default) or "bf16" (WEIGHT_IMAGES) is where the "bf16" matrix forms get their weights.
+With "bf16" every call that already takes a "hip" body in `matmul_arith` = "bf16" reads bf16 IMAGES of its weights
+(csrc/t5_images.hip; rqhip_t5_ffn_*_bf16w / rqhip_t5_proj_*_bf16w): copies that hold the very roundings the bf16 kernels
+form in registers, in both orientations, so that forward and backward load a weight fragment as 16 bytes along a row
+and convert nothing.  Every result keeps the bits of `weight_images` = "none".  Everywhere else -- the "fp32"
+arithmetic, the "torch" bodies, host tensors -- the attribute has no effect, like `matmul_arith` on the operator bodies.
+Each stack owns a T5WeightImages holder (`stack.images`, a plain attribute: no parameter, no buffer, nothing in the
+state dict): one bf16 arena with the images and transposed images of its blocks' wi, wo, q, k, v and o (a decoder's
+cross-attention weights included), the device job table of their one refresh launch, and a `refreshes` counter.  A
+stack forward (and a `cross_kv` call from outside one) compares the holder's KEY -- (data_ptr, _version) of every weight
+and rqhip.optim.generation(), which every FlatAdamW.step() bumps because its kernel writes parameters without touching
+`_version` -- and, if it differs, refreshes all images with ONE launch before its first body; the same weights again
+cost no launch, and a refresh draws no random numbers.  `.to()` and `load_state_dict` drop the holder's contents.  A
+weight written behind the key's back (through a raw pointer by other code than FlatAdamW, or in place through
+`param.data`, which has a version counter of its own) needs `stack.images.invalidate()`.  Under graph capture every
+forward refreshes, since a replay cannot compare keys.  It is an attribute of the model or the stack, set by the
+caller: train_decoder.train has no parameter for it.  Measurements: profiles/t5_weight_images.txt.
+
 `attention_arith` = "fp32" (the default) or "bf16" is the arithmetic of the LONG attention calls alone, wherever
 `attention_long_impl` = "hip" takes one: the inference launch (ops.t5_attention_long, `generate`'s cross-attention
 included), and under grad the forward and backward of autograd.T5AttentionLongBf16Function.  "bf16" rounds q, k, v,
@@ -91,9 +109,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch import Tensor
 
-from rqhip import ops
-from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5FFNBf16Function, T5FFNFunction,
-                            T5ProjBf16Function, T5ProjFunction, t5_attention_long_function)
+from rqhip import ops, optim
+from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5FFNBf16Function, T5FFNBf16ImagesFunction,
+                            T5FFNFunction, T5ProjBf16Function, T5ProjBf16ImagesFunction, T5ProjFunction,
+                            t5_attention_long_function)
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
@@ -103,6 +122,7 @@ FFN_IMPLS = ("torch", "hip")
 PROJ_IMPLS = ("torch", "hip")
 MATMUL_ARITHS = ops.T5_ARITHS  # ("fp32", "bf16")
 ATTENTION_ARITHS = ops.T5_ARITHS  # of the long attention calls
+WEIGHT_IMAGES = ("none", "bf16")  # where the "bf16" matrix forms read their weights: as stored, or from bf16 images
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -205,13 +225,68 @@ class _Seeds:
         return self.glue(self.n_glue + i) if self.n_glue else _draw_seed(self.p, self.device)
 
 
+class T5WeightImages:
+    """The bf16 weight images of one T5Stack (module docstring, `weight_images`): one arena, an (image, transposed
+    image) pair per weight, the device job table of the refresh launch, the key the images were made under, and
+    `refreshes`, the number of refresh launches so far."""
+
+    def __init__(self) -> None:
+        self.refreshes = 0
+        self.invalidate()
+
+    def invalidate(self) -> None:
+        """Forget the images: the next use allocates and refreshes."""
+        self.key = None       # ((data_ptr, _version) of every weight ..., optim.generation()) of the last refresh
+        self.arena = None
+        self.jobs = None
+        self.pairs = {}       # id(weight) -> (image, transposed image)
+
+    @staticmethod
+    def key_of(weights) -> tuple:
+        """What decides whether images of `weights` are current: where each weight lives, how often torch has seen it
+        written (in-place operators, copy_ of load_state_dict, torch.optim steps), and how many FlatAdamW steps, whose
+        kernel writes through raw pointers, this process has made."""
+        return tuple((w.data_ptr(), w._version) for w in weights) + (optim.generation(),)
+
+    def current(self, weights) -> bool:
+        return self.key is not None and self.key == self.key_of(weights)
+
+    def ensure(self, weights) -> "T5WeightImages":
+        """Make the images those of `weights` (a list of fp32 device Parameters): nothing when the key stands, else ONE
+        launch; the arena and the job table are rebuilt only when a weight has moved."""
+        key = self.key_of(weights)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if key == self.key and not capturing:
+            return self
+        if self.key is None or [k[0] for k in key[:-1]] != [k[0] for k in self.key[:-1]]:
+            datas = [w.detach() for w in weights]
+            self.arena, imgs, imgs_t = ops.bf16_images_alloc(datas)
+            self.jobs = ops.bf16_images_jobs(datas, imgs, imgs_t)
+        ops.bf16_images(self.jobs)
+        self.refreshes += 1
+        self.pairs = {id(w): pair for w, pair in zip(weights, zip(self.jobs.tensors[1], self.jobs.tensors[2]))}
+        self.key = key
+        return self
+
+    def of(self, weight: Tensor):
+        """(image, transposed image) of one of the weights of the last `ensure`."""
+        return self.pairs[id(weight)]
+
+
 def _project(fused, x: Tensor, linears, outs=None) -> Tuple[Tensor, ...]:
     """The bias-free Linears `linears` of the same x -> their outputs: the operators one by one, or `fused` ONE call
     for the group (T5ProjFunction under grad, ops.t5_proj_fwd under no_grad, which writes into `outs` where given).
-    fused: False, or what T5Stack.proj_arm returns: True for the "fp32" arithmetic, "bf16" for that one."""
+    fused: False, or what T5Stack.proj_arm returns: True for the "fp32" arithmetic, "bf16" for that one, the stack's
+    T5WeightImages for the "bf16" arithmetic reading the images (the same bits)."""
     if not fused:
         return tuple(lin(x) for lin in linears)
     weights = [lin.weight for lin in linears]
+    if isinstance(fused, T5WeightImages):
+        pairs = [fused.of(w) for w in weights]
+        if torch.is_grad_enabled():
+            return T5ProjBf16ImagesFunction.apply(x, len(weights), *weights, *[p[0] for p in pairs],
+                                                  *[p[1] for p in pairs])
+        return ops.t5_proj_fwd(x, weights, outs, arith="bf16", w_images=[p[0] for p in pairs])
     bf16 = fused == "bf16"
     if torch.is_grad_enabled():
         return (T5ProjBf16Function if bf16 else T5ProjFunction).apply(x, *weights)
@@ -311,7 +386,8 @@ class _OperatorAttention:
 
     def __init__(self, stack: "T5Stack", inputs_embeds: Tensor, attention_mask: Optional[Tensor],
                  encoder_hidden_states: Optional[Tensor], encoder_attention_mask: Optional[Tensor],
-                 past_key_values: Optional[List[KV]], cross_kv: Optional[List[KV]]) -> None:
+                 past_key_values: Optional[List[KV]], cross_kv: Optional[List[KV]],
+                 images: Optional["T5WeightImages"] = None) -> None:
         T, dtype = inputs_embeds.shape[1], inputs_embeds.dtype
         past = 0 if past_key_values is None else past_key_values[0][0].shape[2]
         keys = past + T
@@ -322,9 +398,9 @@ class _OperatorAttention:
         self.mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
         self.bias = stack.block[0].layer[0].SelfAttention.compute_bias(T, keys, past)
         self.past_key_values = past_key_values
-        self.proj = stack.proj_arm(inputs_embeds)
+        self.proj = stack.proj_arm(inputs_embeds, images)
         if stack.is_decoder:
-            self.cross_kv = stack.cross_kv(encoder_hidden_states) if cross_kv is None else cross_kv
+            self.cross_kv = stack.cross_kv(encoder_hidden_states, images) if cross_kv is None else cross_kv
             self.cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
 
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
@@ -429,10 +505,18 @@ class T5DenseReluDense(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         return self.wo(self.dropout(F.relu(self.wi(x))))
 
-    def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor], arith: str = "fp32") -> Tensor:
+    def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor], arith: str = "fp32",
+                    images: Optional[T5WeightImages] = None) -> Tensor:
         """forward as one fused call (the "hip" feed-forward body), its dropout at rate p from `seed`, in the
-        arithmetic `arith` (MATMUL_ARITHS)."""
+        arithmetic `arith` (MATMUL_ARITHS); `images` (with "bf16"): the weights are read from their bf16 images."""
         bf16 = arith == "bf16"
+        if bf16 and images is not None:
+            (wi16, wi16t), (wo16, wo16t) = images.of(self.wi.weight), images.of(self.wo.weight)
+            if torch.is_grad_enabled():
+                return T5FFNBf16ImagesFunction.apply(x, self.wi.weight, self.wo.weight, p, seed, wi16, wo16, wi16t,
+                                                     wo16t)
+            return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False, arith=arith,
+                                  w_images=(wi16, wo16))[0]
         if torch.is_grad_enabled():
             return (T5FFNBf16Function if bf16 else T5FFNFunction).apply(x, self.wi.weight, self.wo.weight, p, seed)
         kw = {"arith": arith} if bf16 else {}
@@ -476,12 +560,52 @@ class T5Stack(nn.Module):
         self.proj_impl = "torch"  # or "hip": see the module docstring
         self.matmul_arith = "fp32"  # or "bf16": the arithmetic of the "hip" feed-forward and projections (docstring)
         self.attention_arith = "fp32"  # or "bf16": the arithmetic of the long attention calls (module docstring)
+        self.weight_images = "none"  # or "bf16": the "bf16" matrix forms read bf16 images of their weights (docstring)
+        self.images = T5WeightImages()  # plain attribute: not a parameter, not a buffer, not in the state dict
         init_t5_weights(self, config)
 
-    def cross_kv(self, encoder_hidden_states: Tensor) -> List[KV]:
+    def _apply(self, fn, *args, **kwargs):
+        self.images.invalidate()  # .to() / .cuda() / .float(): the weights move
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self.images.invalidate()  # load_state_dict: the weights change (their _version says so too)
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def image_weights(self, ffn: bool, proj: bool) -> List[Tensor]:
+        """The weights the holder keeps images of, in block order: the feed-forward's with `ffn`, the attentions'
+        (cross-attention included) with `proj`."""
+        weights = []
+        for blk in self.block:
+            if proj:
+                weights += [lin.weight for layer in list(blk.layer)[:-1] for att in layer.children()
+                            if isinstance(att, T5Attention) for lin in (att.q, att.k, att.v, att.o)]
+            if ffn:
+                dense = blk.layer[-1].DenseReluDense
+                weights += [dense.wi.weight, dense.wo.weight]
+        return weights
+
+    def weight_images_mode(self) -> str:
+        """weight_images, validated."""
+        if self.weight_images not in WEIGHT_IMAGES:
+            raise ValueError(f"weight_images must be one of {WEIGHT_IMAGES}, got {self.weight_images!r}")
+        return self.weight_images
+
+    def current_images(self, x: Tensor) -> Optional[T5WeightImages]:
+        """The holder with current images for a forward of x, refreshed by one launch if its key differs, or None where
+        weight_images does not act: off "bf16" in both attributes, or no "hip" matrix body is taken for x."""
+        if self.weight_images_mode() != "bf16" or self.arith() != "bf16":
+            return None
+        ffn, proj = self.hip_ffn_active(x), self.hip_proj_active(x)
+        if not (ffn or proj):
+            return None
+        return self.images.ensure(self.image_weights(ffn, proj))
+
+    def cross_kv(self, encoder_hidden_states: Tensor, images: Optional[T5WeightImages] = None) -> List[KV]:
         """Cross-attention K/V of every block, computed once per encoder output (proj_impl = "hip": by one grouped
-        call for all blocks, one per four blocks beyond that)."""
-        fused = self.proj_arm(encoder_hidden_states)
+        call for all blocks, one per four blocks beyond that).  images: the forward's current holder; a call from
+        outside a forward checks the holder itself."""
+        fused = self.proj_arm(encoder_hidden_states, images or self.current_images(encoder_hidden_states))
         atts = [blk.layer[1].EncDecAttention for blk in self.block]
         if not fused:
             return [att.project_kv(encoder_hidden_states) for att in atts]
@@ -574,29 +698,32 @@ class T5Stack(nn.Module):
             raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
         return self.matmul_arith
 
-    def proj_arm(self, x: Tensor):
-        """hip_proj_active(x) with the arithmetic of the grouped calls: False, True ("fp32") or "bf16" (`_project`)."""
+    def proj_arm(self, x: Tensor, images: Optional[T5WeightImages] = None):
+        """hip_proj_active(x) with the arithmetic of the grouped calls: False, True ("fp32"), "bf16", or -- "bf16" with
+        the current holder of `current_images` -- that holder (`_project`)."""
         arith = self.arith()
         if not self.hip_proj_active(x):
             return False
-        return "bf16" if arith == "bf16" else True
+        if arith == "bf16":
+            return images if images is not None else "bf16"
+        return True
 
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
     def _attention_body(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                        past_key_values, cross_kv, decode_cache):
+                        past_key_values, cross_kv, decode_cache, images=None):
         """The attention body of this forward (module docstring): _HipAttention where it applies, else the operators."""
         R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
         self.long_attention()  # an unknown attention_long_impl raises on every path
         self.attention_arithmetic()  # and so does an unknown attention_arith
         if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
             if self.is_decoder and cross_kv is None:
-                cross_kv = self.cross_kv(encoder_hidden_states)
+                cross_kv = self.cross_kv(encoder_hidden_states, images)
             past = 0 if decode_cache is None else decode_cache.pos
             if decode_cache is None and self.hip_train_active(inputs_embeds, T, cross_kv):
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, None, train=True,
-                                     proj=self.proj_arm(inputs_embeds))
+                                     proj=self.proj_arm(inputs_embeds, images))
             cross_length = cross_kv[0][0].shape[2] if self.is_decoder else None
             if self.hip_attention_active(inputs_embeds, T, past + T, cross_length, cached=decode_cache is not None):
                 if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
@@ -604,11 +731,11 @@ class T5Stack(nn.Module):
                     raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
                                      "past_key_values or attention_mask")
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, decode_cache,
-                                     train=False, proj=self.proj_arm(inputs_embeds))
+                                     train=False, proj=self.proj_arm(inputs_embeds, images))
             if decode_cache is not None:
                 raise ValueError('decode_cache belongs to the "hip" attention path, which is not active here')
         return _OperatorAttention(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                                  past_key_values, cross_kv)
+                                  past_key_values, cross_kv, images)
 
     def _glue(self, layers, fused: bool, p: float, seeds: _Seeds):
         """glue(k, x, y) -> (x + dropout_k(y), norm_k of that sum): what lies between body k - 1 and body k of a
@@ -637,8 +764,9 @@ class T5Stack(nn.Module):
         [B, S] keep-mask of the encoder output (B rows, R = B * beams).  Returns the hidden states, and with use_cache
         the per-block self-attention (K, V) including these T positions.  decode_cache ("hip" path, T = 1) holds the
         self-attention history instead of past_key_values: this position's K/V are written into it."""
+        images = self.current_images(inputs_embeds)  # refreshed here, before the first body, if their key differs
         attention = self._attention_body(inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                                         past_key_values, cross_kv, decode_cache)
+                                         past_key_values, cross_kv, decode_cache, images)
         fused_glue = self.hip_norm_active(inputs_embeds)
         fused_ffn = self.hip_ffn_active(inputs_embeds)
         arith = self.arith()
@@ -661,7 +789,8 @@ class T5Stack(nn.Module):
                 x, normed = glue(k, x, attention.cross_attention(i, blk.layer[1].EncDecAttention, normed))
             dense = blk.layer[-1].DenseReluDense
             k += 1
-            x, normed = glue(k, x, dense.forward_hip(normed, p, seeds.ffn(i), arith) if fused_ffn else dense(normed))
+            body = dense.forward_hip(normed, p, seeds.ffn(i), arith, images) if fused_ffn else dense(normed)
+            x, normed = glue(k, x, body)
         return (normed, new_kv) if use_cache else normed
 
 

@@ -142,6 +142,13 @@ SIGNATURES = {
     "rqhip_t5_proj_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp]),
     "rqhip_t5_proj_fwd_bf16": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp]),
     "rqhip_t5_proj_bwd_bf16": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp]),
+    "rqhip_bf16_images_job_bytes": (_sz, [_int]),
+    "rqhip_bf16_images_fill_jobs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(_i64)]),
+    "rqhip_bf16_images": (_int, [_vp, _int, _i64, _vp]),
+    "rqhip_t5_ffn_fwd_bf16w": (_int, [_vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_bwd_bf16w": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_proj_fwd_bf16w": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp]),
+    "rqhip_t5_proj_bwd_bf16w": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp]),
     "rqhip_sid_head_loss_supported": (_int, [_int, _int, _int]),
     "rqhip_sid_head_loss_fwd": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp,
                                        _vp, _vp]),

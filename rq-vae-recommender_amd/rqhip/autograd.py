@@ -407,6 +407,34 @@ class T5FFNBf16Function(T5FFNFunction):
     arith = "bf16"
 
 
+class T5FFNBf16ImagesFunction(torch.autograd.Function):
+    """T5FFNBf16Function reading bf16 weight images (rqhip_t5_ffn_*_bf16w; ops.bf16_images): apply(x, wi, wo, p, seed,
+    wi16, wo16, wi16t, wo16t) -> the same y, bit for bit.  The four images are non-differentiable inputs: the forward
+    reads wi16 / wo16, the backward the transposed pair, and the gradients go to the fp32 weights wi and wo exactly as
+    in T5FFNBf16Function (the weight-gradient kernel reads no weights).  Saved: x, h, the weights (for their shapes), the
+    seed and the transposed images -- which must still hold the forward's weights when the backward runs."""
+
+    arith = "bf16"
+
+    @staticmethod
+    def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor], wi16: Tensor, wo16: Tensor,
+                wi16t: Tensor, wo16t: Tensor):
+        y, h = ops.t5_ffn_fwd(x, wi, wo, p, seed, arith="bf16", w_images=(wi16, wo16))
+        ctx.save_for_backward(x, h, wi, wo, seed, wi16t, wo16t)
+        ctx.p = p
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y: Tensor):
+        x, h, wi, wo, seed, wi16t, wo16t = ctx.saved_tensors
+        need_x, need_wi, need_wo = ctx.needs_input_grad[:3]
+        if not (need_x or need_wi or need_wo):
+            return (None,) * 9
+        d_x, d_wi, d_wo = ops.t5_ffn_bwd(x, wi, wo, h, _dense(d_y), ctx.p, seed, need_x=need_x, need_wi=need_wi,
+                                         need_wo=need_wo, arith="bf16", w_images=(wi16t, wo16t))
+        return (d_x, d_wi, d_wo) + (None,) * 6
+
+
 def t5_ffn_function(arith: str = "fp32"):
     """The feed-forward Function of an arithmetic."""
     if arith not in ops.T5_ARITHS:
@@ -445,6 +473,36 @@ class T5ProjBf16Function(T5ProjFunction):
     """T5ProjFunction in the "bf16" arithmetic (rqhip_t5_proj_*_bf16)."""
 
     arith = "bf16"
+
+
+class T5ProjBf16ImagesFunction(torch.autograd.Function):
+    """T5ProjBf16Function reading bf16 weight images (rqhip_t5_proj_*_bf16w): apply(x, n, *weights, *imgs, *imgs_t) with
+    n weights, their n images [d_out, d_in] and their n transposed images [d_in, d_out] -> the same outputs, bit for
+    bit.  The images are non-differentiable inputs; the gradients go to x and the fp32 weights exactly as in
+    T5ProjBf16Function.  The transposed images must still hold the forward's weights when the backward runs."""
+
+    arith = "bf16"
+
+    @staticmethod
+    def forward(ctx, x: Tensor, n: int, *rest: Tensor):
+        weights, imgs, imgs_t = rest[:n], rest[n:2 * n], rest[2 * n:]
+        outs = ops.t5_proj_fwd(x, weights, arith="bf16", w_images=imgs)
+        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None (= NULL at the C ABI)
+        ctx.save_for_backward(x, *weights, *imgs_t)
+        ctx.n = n
+        return outs
+
+    @staticmethod
+    def backward(ctx, *d_ys: Optional[Tensor]):
+        n = ctx.n
+        x, *rest = ctx.saved_tensors
+        weights, imgs_t = rest[:n], rest[n:]
+        need = ctx.needs_input_grad
+        if all(g is None for g in d_ys) or not (need[0] or any(need[2:2 + n])):
+            return (None,) * (2 + 3 * n)
+        d_x, d_w = ops.t5_proj_bwd(x, weights, [_dense(g) for g in d_ys], need_x=need[0], need_w=need[2:2 + n],
+                                   arith="bf16", w_images=imgs_t)
+        return (d_x, None, *d_w) + (None,) * (2 * n)
 
 
 def t5_proj_function(arith: str = "fp32"):

@@ -786,6 +786,28 @@ def _arith_entry(who: str, arith: str):
     return getattr(_lib.lib(), name), name
 
 
+def _image_entry(who: str, arith: str, w_images):
+    """_arith_entry for a call that may read bf16 weight images (bf16_images): with `w_images` the entry point is the
+    "bf16" arithmetic's image-reading twin rqhip_<who>_bf16w, which no other arithmetic has."""
+    if w_images is None:
+        return _arith_entry(who, arith)
+    if arith != "bf16":
+        _arith_entry(who, arith)      # an unknown arithmetic is the first complaint
+        raise RqHipError(f'{who}: w_images belong to arith="bf16" (the images hold bf16 roundings), got arith={arith!r}')
+    name = f"rqhip_{who}_bf16w"
+    return getattr(_lib.lib(), name), name
+
+
+def _image(who: str, img, name: str, shape, dev) -> Tensor:
+    """A bf16 weight image as the kernels read it: a dense, 16-byte aligned bfloat16 tensor of `shape` on `dev`."""
+    if not isinstance(img, Tensor) or img.dtype != torch.bfloat16 or tuple(img.shape) != tuple(shape) or img.device != dev:
+        got = f"{img.dtype} {tuple(img.shape)} on {img.device}" if isinstance(img, Tensor) else repr(type(img))
+        raise RqHipError(f"{who}: {name} must be a bfloat16 {list(shape)} image on {dev} (ops.bf16_images), got {got}")
+    if not img.is_contiguous() or img.data_ptr() % 16:
+        raise RqHipError(f"{who}: {name} must be dense and 16-byte aligned")
+    return img
+
+
 T5_ATTENTION_LONG_CHUNK = 128   # RQHIP_T5_ATTENTION_LONG_CHUNK: keys a workgroup holds in LDS at a time
 T5_ATTENTION_LONG_QBLOCK = 64   # RQHIP_T5_ATTENTION_LONG_QBLOCK: query rows of a workgroup
 
@@ -994,17 +1016,23 @@ def _ffn_call(who: str, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optio
 
 
 def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *, need_h: bool = True,
-               arith: str = "fp32"):
+               arith: str = "fp32", w_images=None):
     """The T5 feed-forward body in one launch (rqhip_t5_ffn_fwd) -> (y, h or None): h = relu(x @ wi.T), y = dropout(h, p)
     @ wo.T.  x [..., d] float32, wi [F, d] and wo [d, F] the two Linear weights as stored; y has x's shape, h is
     [..., F] (the one tensor t5_ffn_bwd needs; not stored without need_h).  The mask is t5_attention_dropout_keep(seed,
     1, 1, N, F, p)[0, 0] over the N = x.numel() / d rows; `seed` is a one-element int64 device tensor the host never
     reads.  arith: "fp32", or "bf16" (rqhip_t5_ffn_fwd_bf16: every matrix operand rounded to bf16, fp32 accumulation;
-    all tensors stay float32 and h is stored unrounded)."""
-    fn, fn_name = _arith_entry("t5_ffn_fwd", arith)
+    all tensors stay float32 and h is stored unrounded).  w_images (arith "bf16" only): the pair (wi16 [F, d], wo16 [d,
+    F]) of bf16 images of wi and wo (bf16_images); the kernel reads them instead of the weights, and every result has
+    the bits of the call without them (rqhip_t5_ffn_fwd_bf16w)."""
+    who = "t5_ffn_fwd"
+    fn, fn_name = _image_entry(who, arith, w_images)
     _need_gpu(x, wi, wo, seed)
-    x, wi, wo, N, d, F, seed_ptr = _ffn_call("t5_ffn_fwd", x, wi, wo, p, seed)
+    x, wi, wo, N, d, F, seed_ptr = _ffn_call(who, x, wi, wo, p, seed)
     dev = x.device
+    if w_images is not None:
+        wi16, wo16 = w_images
+        wi, wo = _image(who, wi16, "w_images[0]", (F, d), dev), _image(who, wo16, "w_images[1]", (d, F), dev)
     with torch.cuda.device(dev):
         y = torch.empty_like(x)
         h = torch.empty(x.shape[:-1] + (F,), dtype=torch.float32, device=dev) if need_h else None
@@ -1015,16 +1043,22 @@ def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional
 
 def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *,
                need_x: bool = True, need_wi: bool = True, need_wo: bool = True, return_g: bool = False,
-               arith: str = "fp32"):
+               arith: str = "fp32", w_images=None):
     """The gradients of t5_ffn_fwd in one call of at most two launches (rqhip_t5_ffn_bwd) -> (d_x, d_wi, d_wo), None
     where not needed.  x, wi, wo, p, seed: the forward's; h: its second result; d_y: the gradient of y.  The dropout
     decisions are recomputed from the seed; the weight gradients are summed without atomics in an order that depends on
     the shape alone.  The [N, F] workspace comes from torch's allocator.  return_g: a fourth result, the workspace as the
-    tensor g of h's shape when need_wi (else None).  arith: "fp32" or "bf16", as t5_ffn_fwd's (rqhip_t5_ffn_bwd_bf16)."""
+    tensor g of h's shape when need_wi (else None).  arith: "fp32" or "bf16", as t5_ffn_fwd's (rqhip_t5_ffn_bwd_bf16).
+    w_images (arith "bf16" only): the pair (wi16t [d, F], wo16t [F, d]) of TRANSPOSED bf16 images of wi and wo, which
+    this call reads instead of the weights; the bits are those of the call without them (rqhip_t5_ffn_bwd_bf16w)."""
     who = "t5_ffn_bwd"
-    fn, fn_name = _arith_entry(who, arith)
+    fn, fn_name = _image_entry(who, arith, w_images)
     _need_gpu(x, wi, wo, h, d_y, seed)
     x, wi, wo, N, d, F, seed_ptr = _ffn_call(who, x, wi, wo, p, seed)
+    if w_images is not None:
+        wi16t, wo16t = w_images
+        wi = _image(who, wi16t, "w_images[0]", (d, F), x.device)
+        wo = _image(who, wo16t, "w_images[1]", (F, d), x.device)
     h = _norm_rows(h, "h", who, x.shape[:-1] + (F,))
     d_y = _norm_rows(d_y, "d_y", who, x.shape)
     dev = x.device
@@ -1054,9 +1088,10 @@ def t5_proj_supported(dtype: torch.dtype, d_in: int, d_out: int, n: int = 1) -> 
     return dtype == torch.float32 and bool(_lib.lib().rqhip_t5_proj_supported(int(d_in), int(d_out), int(n)))
 
 
-def _proj_call(who: str, x: Tensor, weights):
+def _proj_call(who: str, x: Tensor, weights, w_images=None, image_shape=None):
     """The checks and copies t5_proj_fwd and t5_proj_bwd share -> (x as dense aligned rows, the weights as the kernels
-    read them, their HOST pointer array, N, d_in, d_out)."""
+    read them, their HOST pointer array, N, d_in, d_out).  w_images: one bf16 image per weight, whose pointers then
+    stand in the array; image_shape(d_out, d_in) is the shape of each."""
     weights = list(weights)
     _need_gpu(x, *weights)
     x = _norm_rows(x, "x", who)
@@ -1069,22 +1104,31 @@ def _proj_call(who: str, x: Tensor, weights):
     if not t5_proj_supported(x.dtype, d_in, d_out, n):
         raise RqHipError(f"{who}: (d_in, d_out, n) = ({d_in}, {d_out}, {n}) is not supported (multiples of 32 up to 512, "
                          f"1 <= n <= 8)")
-    weights = [_aligned16(w.contiguous()) for w in weights]
+    if w_images is not None:
+        w_images = list(w_images)
+        if len(w_images) != n:
+            raise RqHipError(f"{who}: {len(w_images)} w_images for {n} weights")
+        weights = [_image(who, img, f"w_images[{j}]", image_shape(d_out, d_in), x.device)
+                   for j, img in enumerate(w_images)]
+    else:
+        weights = [_aligned16(w.contiguous()) for w in weights]
     w_ptrs = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
     return x, weights, w_ptrs, (x.numel() // d_in), d_in, d_out
 
 
-def t5_proj_fwd(x: Tensor, weights, outs=None, *, arith: str = "fp32"):
+def t5_proj_fwd(x: Tensor, weights, outs=None, *, arith: str = "fp32", w_images=None):
     """n bias-free linear maps of the same rows in one launch (rqhip_t5_proj_fwd) -> (y[0], ..., y[n - 1]), y[j] = x @
     weights[j].T.  x [..., d_in] float32 with dense rows, weights: n separate [d_out, d_in] matrices, the nn.Linear
     weights as stored.  y[j] has shape x.shape[:-1] + (d_out,).  outs (optional): a list of n entries, each None (that
     output is allocated) or a preallocated float32 [N, d_out] view over the N = x.numel() / d_in rows whose last
     dimension is dense and whose row stride is at least d_out, a position of a decode-cache slab for one; the kernel
     writes into it and it is returned as it is.  arith: "fp32", or "bf16" (rqhip_t5_proj_fwd_bf16: x and the weights
-    rounded to bf16 as operands, fp32 accumulation; all tensors stay float32)."""
+    rounded to bf16 as operands, fp32 accumulation; all tensors stay float32).  w_images (arith "bf16" only): n bf16
+    images [d_out, d_in] of the weights (bf16_images), read instead of them; the bits are those of the call without
+    them (rqhip_t5_proj_fwd_bf16w)."""
     who = "t5_proj_fwd"
-    fn, fn_name = _arith_entry(who, arith)
-    x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights)
+    fn, fn_name = _image_entry(who, arith, w_images)
+    x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights, w_images, lambda o, i: (o, i))
     n = len(weights)
     outs = [None] * n if outs is None else list(outs)
     if len(outs) != n:
@@ -1105,16 +1149,17 @@ def t5_proj_fwd(x: Tensor, weights, outs=None, *, arith: str = "fp32"):
     return tuple(outs)
 
 
-def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None, *, arith: str = "fp32"):
+def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None, *, arith: str = "fp32", w_images=None):
     """The gradients of t5_proj_fwd in one call of at most two launches (rqhip_t5_proj_bwd) -> (d_x, [d_w[0], ...]).
     d_ys: n upstream gradients, each of y[j]'s shape or None; a None contributes nothing to d_x and gets no d_w[j].  d_x
     (x's shape) is None without need_x or when every d_ys[j] is None; d_w[j] is None where need_w[j] (default: every
     weight) is false.  No atomics: the same bits on every run.  arith: "fp32" or "bf16", as t5_proj_fwd's
-    (rqhip_t5_proj_bwd_bf16)."""
+    (rqhip_t5_proj_bwd_bf16).  w_images (arith "bf16" only): n TRANSPOSED bf16 images [d_in, d_out] of the weights,
+    read instead of them; the bits are those of the call without them (rqhip_t5_proj_bwd_bf16w)."""
     who = "t5_proj_bwd"
-    fn, fn_name = _arith_entry(who, arith)
+    fn, fn_name = _image_entry(who, arith, w_images)
     shape = x.shape
-    x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights)
+    x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights, w_images, lambda o, i: (i, o))
     n = len(weights)
     d_ys = list(d_ys)
     need_w = [True] * n if need_w is None else [bool(f) for f in need_w]
@@ -1135,6 +1180,80 @@ def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None, *, a
         rc = fn(_ptr(x), d_in, w_ptrs, g_ptrs, ld_dy, n, N, d_in, d_out, _ptr(d_x), dw_ptrs, _stream())
         check(rc, fn_name)
     return d_x, d_w
+
+
+class Bf16ImageJobs(NamedTuple):
+    """What one bf16_images launch needs: the job table in device memory, its job and tile counts, and the tensors the
+    table points at (kept alive with it)."""
+    table: Tensor
+    n_jobs: int
+    n_tiles: int
+    tensors: tuple
+
+
+def bf16_images_alloc(weights, transposed: bool = True):
+    """Room for the bf16 images of `weights` (float32 [rows, cols] device matrices, both multiples of 32) -> (arena, imgs,
+    imgs_t): ONE bfloat16 allocation and, as views of it, an image [rows, cols] per weight and, with `transposed`, its
+    transpose [cols, rows] (else imgs_t is a list of None).  Nothing is computed: bf16_images fills them."""
+    weights = list(weights)
+    dev = _need_gpu(*weights)
+    for j, w in enumerate(weights):
+        if w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] % 32 or w.shape[1] % 32 or not w.numel():
+            raise RqHipError(f"bf16_images_alloc: weights[{j}] must be a float32 matrix whose sizes are multiples of 32, "
+                             f"got {w.dtype} {tuple(w.shape)}")
+    per = 2 if transposed else 1
+    with torch.cuda.device(dev):
+        arena = torch.empty((per * sum(w.numel() for w in weights),), dtype=torch.bfloat16, device=dev)
+    imgs, imgs_t, at = [], [], 0
+    for w in weights:      # every view starts a multiple of 1024 elements into the arena: 16-byte aligned
+        r, c = w.shape
+        imgs.append(arena[at:at + r * c].view(r, c))
+        at += r * c
+        imgs_t.append(arena[at:at + r * c].view(c, r) if transposed else None)
+        at += r * c if transposed else 0
+    return arena, imgs, imgs_t
+
+
+def bf16_images_jobs(weights, imgs, imgs_t=None) -> Bf16ImageJobs:
+    """The device job table of one bf16_images launch over `weights` (rqhip_bf16_images_fill_jobs, then ONE copy to the
+    device).  weights[j]: a dense, 16-byte aligned float32 [rows, cols] device matrix, read in place; imgs[j] / imgs_t[j]:
+    its bfloat16 image [rows, cols] and transposed image [cols, rows] (imgs_t, or an entry of it, None: not made).  The
+    table holds POINTERS: build it again when a weight or an image moves."""
+    who = "bf16_images_jobs"
+    weights, imgs = list(weights), list(imgs)
+    n = len(weights)
+    imgs_t = [None] * n if imgs_t is None else list(imgs_t)
+    if len(imgs) != n or len(imgs_t) != n:
+        raise RqHipError(f"{who}: {len(imgs)} imgs and {len(imgs_t)} imgs_t for {n} weights")
+    dev = _need_gpu(*weights, *imgs, *imgs_t)
+    for j, w in enumerate(weights):
+        if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous():
+            raise RqHipError(f"{who}: weights[{j}] must be a dense float32 matrix, got {w.dtype} {tuple(w.shape)}")
+        _image(who, imgs[j], f"imgs[{j}]", w.shape, dev)
+        if imgs_t[j] is not None:
+            _image(who, imgs_t[j], f"imgs_t[{j}]", (w.shape[1], w.shape[0]), dev)
+    l = _lib.lib()
+    vp = C.c_void_p * n
+    host = torch.empty((max(int(l.rqhip_bf16_images_job_bytes(n)), 1),), dtype=torch.uint8)
+    n_tiles = C.c_int64(0)
+    rc = l.rqhip_bf16_images_fill_jobs(host.data_ptr(), vp(*[w.data_ptr() for w in weights]),
+                                       vp(*[t.data_ptr() for t in imgs]), vp(*[_ptr(t) for t in imgs_t]),
+                                       (C.c_int64 * n)(*[w.shape[0] for w in weights]),
+                                       (C.c_int64 * n)(*[w.shape[1] for w in weights]), n, C.byref(n_tiles))
+    check(rc, "rqhip_bf16_images_fill_jobs")
+    table = host.to(dev) if n else host
+    return Bf16ImageJobs(table, n, int(n_tiles.value), (tuple(weights), tuple(imgs), tuple(imgs_t)))
+
+
+def bf16_images(jobs: Bf16ImageJobs) -> None:
+    """Make (or refresh) the bf16 images of a job table in ONE launch (rqhip_bf16_images): imgs[j] = the weights rounded
+    to bf16, nearest even, the very operands the "bf16" arithmetic forms in registers, and imgs_t[j] their transposes.
+    No copy, allocation or host read: the call can be captured into a graph."""
+    if jobs.n_jobs == 0:
+        return
+    dev = jobs.table.device
+    with torch.cuda.device(dev):
+        check(_lib.lib().rqhip_bf16_images(jobs.table.data_ptr(), jobs.n_jobs, jobs.n_tiles, _stream()), "rqhip_bf16_images")
 
 
 def sid_head_loss_supported(dtype: torch.dtype, d: int, K: int, L: int) -> bool:

@@ -24,6 +24,16 @@ from ._lib import RqHipError, check
 from .ops import _RAW_DEVICE, _stream as ops_stream
 
 
+# FlatAdamW's kernels write the parameters through raw pointers, which leaves their `_version` counters alone; whoever keeps
+# something derived from parameter VALUES (modules/t5.py: the bf16 weight images) puts this count into its staleness key.
+_generation = 0
+
+
+def generation() -> int:
+    """How many FlatAdamW.step() calls this process has made, over all optimizers."""
+    return _generation
+
+
 class FlatAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, amsgrad: bool = False, *,
                  maximize: bool = False, foreach: Optional[bool] = None, capturable: bool = False, differentiable: bool = False,
@@ -96,6 +106,8 @@ class FlatAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        global _generation
+        _generation += 1        # before anything can fail: a key that changes needlessly costs one refresh
         loss = None
         if closure is not None:
             with torch.enable_grad():

@@ -26,7 +26,9 @@ What differs:
     fp32, and the "torch" bodies are not affected.  amp=True with any other type raises: those kernels are fp32 or
     bf16-operand only.  The bf16 arm of the long attention calls is `model.attention_arith = "bf16"` (modules/t5.py),
     an attribute set on the model: train has no parameter for it, nor for `model.attention_long_impl`, and amp does
-    not set it.  push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
+    not set it.  Reading the bf16 arm's weights from bf16 images, `model.weight_images = "bf16"` (modules/t5.py), is
+    a model attribute of the same kind: no parameter here, and amp goes on setting `matmul_arith` alone; the images
+    follow every FlatAdamW step through rqhip.optim.generation().  push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
     reference.
 wandb is optional: with `wandb_logging=True` and no wandb module, metrics are printed.
 The full eval here reports one draw of the sampling beam search; evaluate_decoder.py evaluates a checkpoint with the

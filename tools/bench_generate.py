@@ -17,7 +17,9 @@ arithmetic of those two "hip" forms ("bf16": bf16 operands, fp32 accumulation); 
 (modules/model.py) of the kernel path: "sample", the reference's sampling search (a noise draw and one ops.beam_step per
 level), or "exact", the deterministic constrained search (one ops.beam_topk_step per level, no noise); `--beam both`
 alternates the two --runs times on one --attention arm and ends with a summary line of the medians over the runs' block
-medians and their spread.
+medians and their spread.  --images sets weight_images (modules/t5.py) under `--arith bf16` on the kernel path: "bf16" reads
+the weights of the two "hip" forms from bf16 images; `--images both` alternates "none" and "bf16" --runs times and ends
+with a summary line of the medians over the runs' block medians and their spread.
 
 Device events around each generate after a warm-up; prints one JSON line per path (ms per generate, users/s).
 Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --stats` run of this tool
@@ -25,7 +27,7 @@ Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --st
 
     python tools/bench_generate.py [--path kernel|reference|both] [--attention torch|hip|both] [--runs 5]
                                    [--proj torch|hip] [--ffn torch|hip] [--arith fp32|bf16|both]
-                                   [--beam sample|exact|both] [--warmup 3] [--iters 10]
+                                   [--images none|bf16|both] [--beam sample|exact|both] [--warmup 3] [--iters 10]
 """
 import argparse
 import json
@@ -115,6 +117,8 @@ def main():
     ap.add_argument("--ffn", choices=["torch", "hip"], default="torch", help="ffn_impl of every arm")
     ap.add_argument("--arith", choices=["fp32", "bf16", "both"], default="fp32",
                     help='matmul_arith of the "hip" projections and feed-forward')
+    ap.add_argument("--images", choices=["none", "bf16", "both"], default="none",
+                    help='weight_images of the "hip" projections and feed-forward under --arith bf16; both alternates')
     ap.add_argument("--beam", choices=["sample", "exact", "both"], default="sample", help="beam_impl of the kernel path")
     ap.add_argument("--runs", type=int, default=5,
                     help="alternations of the two arms with --attention / --arith / --beam both")
@@ -153,6 +157,30 @@ def main():
                           "exact_over_sample": round(mid["exact"] / mid["sample"], 4)}), flush=True)
         return
     model.beam_impl = args.beam
+    if args.images != "none":
+        if args.arith != "bf16" or args.attention == "both" or args.path != "kernel":
+            ap.error("--images bf16 / both applies to --path kernel with --arith bf16 on one --attention arm")
+        model.attention_impl, model.matmul_arith = args.attention, "bf16"
+        arms = ("none", "bf16") if args.images == "both" else ("bf16",)
+        medians = {arm: [] for arm in arms}
+        for run in range(args.runs):
+            for arm in arms:
+                model.weight_images = arm
+                med, best = time_path(model, batch, args.warmup, args.iters)
+                medians[arm].append(med)
+                print(json.dumps({"path": "kernel", "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
+                                  "arith": "bf16", "images": arm, "beam": args.beam, "run": run, "batch": B,
+                                  "ms_per_generate_median": round(med, 3), "ms_per_generate_min": round(best, 3),
+                                  "iters": args.iters}), flush=True)
+        mid = {arm: sorted(v)[len(v) // 2] for arm, v in medians.items()}
+        print(json.dumps({"path": "kernel", "attention": args.attention, "proj": args.proj, "ffn": args.ffn,
+                          "arith": "bf16", "images": args.images, "beam": args.beam, "runs": args.runs, "batch": B,
+                          **{f"run_medians_{arm}": [round(v, 3) for v in medians[arm]] for arm in arms},
+                          **{f"ms_per_generate_{arm}": round(mid[arm], 3) for arm in arms},
+                          **{f"spread_{arm}": round(max(medians[arm]) - min(medians[arm]), 3) for arm in arms},
+                          **({"bf16_over_none": round(mid["bf16"] / mid["none"], 4)} if len(arms) == 2 else {})}),
+              flush=True)
+        return
     if args.arith == "both":
         if args.attention == "both" or args.path not in ("kernel", "both"):
             ap.error("--arith both compares the two arithmetics on one --attention arm of --path kernel")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) in ten arms:
+tails: encoder T = 81, decoder T = 4) in twelve arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
@@ -22,6 +22,8 @@ tails: encoder T = 81, decoder T = 4) in ten arms:
              products on bf16 operands with fp32 accumulation (rqhip_t5_ffn_*_bf16), everything stored in fp32
   hip_train+norm+head+ffn+optim+embed+proj+bf16  the eighth arm with matmul_arith = "bf16": the feed-forward and the
              grouped projections on bf16 operands (rqhip_t5_ffn_*_bf16, rqhip_t5_proj_*_bf16)
+  ...+bf16+img  either bf16 arm with weight_images = "bf16": the same products with the weights read from bf16 images
+             (rqhip_t5_ffn_*_bf16w, rqhip_t5_proj_*_bf16w), refreshed by one launch per stack and step; the same bits
 
 The arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
@@ -31,7 +33,8 @@ JSON line per arm plus a summary line; --out also writes them to a text file (pr
 holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run, profiles/retrieval_train_step_ffn.txt a
 five-arm run, profiles/retrieval_optim_tail.txt a six-arm run, profiles/retrieval_train_step_embed.txt a run of the sixth
 and seventh arm, profiles/retrieval_train_step_proj.txt runs of the seventh and eighth,
-profiles/retrieval_train_step_bf16.txt runs of those two and their bf16 forms; profiles/retrieval_train_step.txt is the
+profiles/retrieval_train_step_bf16.txt runs of those two and their bf16 forms, profiles/t5_weight_images.txt runs of
+the bf16 forms with and without +img; profiles/retrieval_train_step.txt is the
 older two-arm run; none of them is to be overwritten or compared
 against: two arms are compared within one run only).
 --arms picks a subset, e.g. one arm under a kernel trace to count its launches per step.
@@ -63,9 +66,13 @@ ARMS = {"torch": ("torch", "torch", "torch", "torch", "torch"),
         "hip_train+norm+head+ffn+optim+embed": ("hip_train", "hip", "hip", "hip", "torch"),
         "hip_train+norm+head+ffn+optim+embed+proj": ("hip_train", "hip", "hip", "hip", "hip"),
         "hip_train+norm+head+ffn+optim+embed+bf16": ("hip_train", "hip", "hip", "hip", "torch"),
-        "hip_train+norm+head+ffn+optim+embed+proj+bf16": ("hip_train", "hip", "hip", "hip", "hip")}
+        "hip_train+norm+head+ffn+optim+embed+proj+bf16": ("hip_train", "hip", "hip", "hip", "hip"),
+        "hip_train+norm+head+ffn+optim+embed+bf16+img": ("hip_train", "hip", "hip", "hip", "torch"),
+        "hip_train+norm+head+ffn+optim+embed+proj+bf16+img": ("hip_train", "hip", "hip", "hip", "hip")}
+# arms with weight_images = "bf16"; the others "none"
+IMG = ("hip_train+norm+head+ffn+optim+embed+bf16+img", "hip_train+norm+head+ffn+optim+embed+proj+bf16+img")
 # arms with matmul_arith = "bf16"; the others "fp32"
-BF16 = ("hip_train+norm+head+ffn+optim+embed+bf16", "hip_train+norm+head+ffn+optim+embed+proj+bf16")
+BF16 = ("hip_train+norm+head+ffn+optim+embed+bf16", "hip_train+norm+head+ffn+optim+embed+proj+bf16") + IMG
 # arms stepped by rqhip.optim.FlatAdamW; the others by torch.optim.AdamW
 FLAT_ADAMW = ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed",
               "hip_train+norm+head+ffn+optim+embed+proj") + BF16
@@ -85,6 +92,7 @@ def block(model, state, batch, arm, warmup, iters):
     model.attention_impl, model.norm_impl, model.head_impl, model.ffn_impl, model.proj_impl = ARMS[arm]
     model.embed_impl = "hip" if arm in EMBED_HIP else "torch"
     model.matmul_arith = "bf16" if arm in BF16 else "fp32"
+    model.weight_images = "bf16" if arm in IMG else "none"
     model.train()
     if arm in FLAT_ADAMW:
         from rqhip.optim import FlatAdamW
@@ -143,6 +151,7 @@ def main():
                                  "head_impl": ARMS[arm][2], "ffn_impl": ARMS[arm][3], "proj_impl": ARMS[arm][4],
                                  **({"embed_impl": "hip"} if arm in EMBED_HIP else {}),
                                  **({"matmul_arith": "bf16"} if arm in BF16 else {}),
+                                 **({"weight_images": "bf16"} if arm in IMG else {}),
                                  "optimizer": "FlatAdamW" if arm in FLAT_ADAMW else "torch.optim.AdamW", "batch": args.batch,
                                  "steps_timed": len(times[arm]),
                                  "ms_per_step_median": round(statistics.median(times[arm]), 3),
@@ -156,7 +165,9 @@ def main():
                  ("hip_train+norm+head+ffn+optim", "hip_train+norm+head+ffn+optim+embed"),
                  ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+proj"),
                  ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+bf16"),
-                 ("hip_train+norm+head+ffn+optim+embed+proj", "hip_train+norm+head+ffn+optim+embed+proj+bf16")):
+                 ("hip_train+norm+head+ffn+optim+embed+proj", "hip_train+norm+head+ffn+optim+embed+proj+bf16"),
+                 ("hip_train+norm+head+ffn+optim+embed+bf16", "hip_train+norm+head+ffn+optim+embed+bf16+img"),
+                 ("hip_train+norm+head+ffn+optim+embed+proj+bf16", "hip_train+norm+head+ffn+optim+embed+proj+bf16+img")):
         if a in arms and b in arms:
             summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
             summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)
