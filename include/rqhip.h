@@ -704,6 +704,55 @@ int rqhip_t5_proj_bwd_bf16w(const float *x, int64_t ld_x, const rqhip_bf16_t *co
                             const int64_t *ld_dy, int n, int64_t N, int d_in, int d_out, float *d_x, float *const *d_w,
                             rqhip_stream_t stream);
 
+/* bf16 saved activations for the "bf16" feed-forward (csrc/t5_ffn.hip; modules/t5.py, saved_activations = "bf16"): the
+ * forward keeps, and the backward's row kernel hands its weight-gradient kernel, blocked bf16 IMAGES of the operands the
+ * "bf16" arithmetic rounds in registers, in place of fp32 tensors.
+ * The blocked image of an activation [N, C], C a multiple of 32.  With NB = ceil(N / 32), b = n >> 5, rho = n & 31,
+ * kq = rho & 3 and ks = rho >> 2, element (n, c) is bf16 number ((b * C + c) * 32 + 8 * kq + ks) of a buffer of NB * C * 32
+ * bf16: rqhip_t5_ffn_act_image_bytes(N, C) = 64 * NB * C bytes (0 for N < 0 or a C that is no positive multiple of 32).
+ * The eight rows 4 ks + kq, ks = 0 .. 7, of block b and column c are 16 consecutive bytes: the elements j = ks of the
+ * weight-gradient kernel's fragment for lane (i, kq), as the "bf16" contract above assigns them.  An element is the
+ * round-to-nearest-even bf16 rounding of the fp32 value, the (__bf16) conversion of the weight images.  Rows >= N of the
+ * last block are UNSPECIFIED in memory (a 16-row tile that ends the batch leaves half a block without a writer); every
+ * reader treats them as zero or feeds them only to rows it never stores.
+ *   rqhip_t5_ffn_fwd_bf16a   rqhip_t5_ffn_fwd_bf16 with, in place of h, the images hd16 of hd = keep ? h * s : +0 (h at
+ *                            p = 0) [N, F] and x16 of x [N, d]; either NULL: not stored.  y has the bits of
+ *                            rqhip_t5_ffn_fwd_bf16.  One launch; LDS and the arithmetic are unchanged.
+ *   rqhip_t5_ffn_bwd_bf16a   from x16, hd16, the weights and fp32 d_y; no seed:
+ *                              g = hd16 > 0 ? (d_y . wo) * s : 0   (an ordered compare: a NaN is off, as in h > 0)
+ *                              d_x = g . wi      d_wi = bf16(g)^T . x16      d_wo = bf16(d_y)^T . hd16
+ *                            Launch 1 (the row kernel) writes the image dy16 of d_y into the workspace when a weight
+ *                            gradient is wanted, the image g16 of g behind it when d_wi is wanted, and d_x when wanted;
+ *                            with d_wo alone it only stages d_y and writes dy16.  Launch 2 (when a weight gradient is
+ *                            wanted) reads g16, x16, dy16 and hd16, four 16-byte loads per block and lane, with the
+ *                            blocks, chains, wave ranges and sums of rqhip_t5_ffn_bwd_bf16 and no dropout decision.
+ *                            d_x alone: one launch; all three NULL: none.  rqhip_t5_ffn_bwd_bf16a_workspace_bytes(N, d,
+ *                            F) = act_image_bytes(N, d) + act_image_bytes(N, F) (0 for N < 0 or an unsupported shape);
+ *                            required whenever d_wi or d_wo is wanted (else RQHIP_EWORKSPACE), may be NULL otherwise;
+ *                            without d_wi only its first act_image_bytes(N, d) bytes are touched.
+ *   rqhip_t5_ffn_fwd_bf16wa, rqhip_t5_ffn_bwd_bf16wa   the same reading weight images, as rqhip_t5_ffn_*_bf16w.
+ * Arithmetic contract: every output (y, d_x, d_wi, d_wo) has the bits of rqhip_t5_ffn_*_bf16 on the same inputs, and an
+ * image element is the operand that arm packs.  hd enters that arm as a matrix operand only as bf16(hd), which hd16
+ * stores; g, x and d_y enter the weight gradients only rounded; and the arm's active set h > 0 and keep is hd16 > 0 --
+ * with ONE difference: a kept element with h > 0 whose h * s rounds to bf16 zero (h * s <= 2^-134) is OFF here and on in
+ * rqhip_t5_ffn_bwd_bf16 (its g differs); its contribution as an operand is zero in both.
+ * Limits, the checks of N, d, F and p, 16-byte alignment of every pointer, `seed` (forward only) and graph capturability
+ * are those of the twins; a null x16 or hd16 in the backward is RQHIP_EARG.  All argument checks come before any HIP
+ * call. */
+size_t rqhip_t5_ffn_act_image_bytes(int64_t N, int C);
+size_t rqhip_t5_ffn_bwd_bf16a_workspace_bytes(int64_t N, int d, int F);
+int rqhip_t5_ffn_fwd_bf16a(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+                           const int64_t *seed, float *y, rqhip_bf16_t *hd16, rqhip_bf16_t *x16, rqhip_stream_t stream);
+int rqhip_t5_ffn_bwd_bf16a(const rqhip_bf16_t *x16, const float *wi, const float *wo, const rqhip_bf16_t *hd16,
+                           const float *d_y, int64_t N, int d, int F, double p, float *d_x, float *d_wi, float *d_wo,
+                           void *workspace, rqhip_stream_t stream);
+int rqhip_t5_ffn_fwd_bf16wa(const float *x, const rqhip_bf16_t *wi16, const rqhip_bf16_t *wo16, int64_t N, int d, int F,
+                            double p, const int64_t *seed, float *y, rqhip_bf16_t *hd16, rqhip_bf16_t *x16,
+                            rqhip_stream_t stream);
+int rqhip_t5_ffn_bwd_bf16wa(const rqhip_bf16_t *x16, const rqhip_bf16_t *wi16t, const rqhip_bf16_t *wo16t,
+                            const rqhip_bf16_t *hd16, const float *d_y, int64_t N, int d, int F, double p, float *d_x,
+                            float *d_wi, float *d_wo, void *workspace, rqhip_stream_t stream);
+
 /* The retrieval model's input embedding in one launch forward and one backward (csrc/sid_embed.hip; modules/model.py,
  * embed_impl = "hip"): semantic ids -> a T5 stack's inputs_embeds, for the encoder and the decoder front alike.
  * B rows, `items` items per row, L levels, K codes per level, width d; table [V = L * K, d], x dense [B, T, d], fp32.

@@ -48,6 +48,14 @@
 // and wi16t [d, F] -- so a lane's 8 terms of a column tile are ONE 16-byte load, which is the instruction's B fragment as
 // it stands: no conversion, half the registers in the operand buffers, and the backward serves column 16 ct + i like
 // the forward.  Which lane serves a column does not enter its sum, so every output has the bits of the BF arm.
+//
+// Saved activations in bf16 (template parameter ACT of the row kernel, with BF only; t5_ffn_wgrad16_kernel; entry points
+// rqhip_t5_ffn_*_bf16a / _bf16wa): what the backward keeps of the forward, and what the row kernel hands the
+// weight-gradient kernel, are blocked bf16 images (layout in include/rqhip.h) of the very operands the BF arm rounds in
+// registers: hd16 = bf16(keep ? h * s : 0) and x16 forward, g16 and dy16 backward.  A tile's image is written from LDS
+// (the staged rows; the chunk buffer after its barrier), 8 or 16 bytes per (column, kq).  The backward's active set is
+// hd16 > 0, so neither backward kernel hashes a dropout decision, and the weight-gradient kernel's fragment of a column
+// of a block -- rows 4 ks + kq as elements j = ks -- is ONE 16-byte load.  Same operands, same chains: the BF arm's bits.
 #include <math.h>
 
 #include <type_traits>
@@ -80,6 +88,8 @@ struct FfnRows {
     const float *h_in;         // backward: h [N, F]
     float *mid;                // forward: h (or null); backward: g (or null)
     float *out;                // forward: y; backward: d_x (null: phase 2 is skipped)
+    __bf16 *x16;               // ACT: the blocked image of the staged rows (forward x16, backward dy16), or null.  ACT
+                               // also makes `mid` the blocked image hd16 / g16 and `h_in` the image hd16
     const long long *seed;     // one int64 on the device (read only when th != 0)
     unsigned th;               // round(p * 2^32); 0 = no dropout
     float s;                   // 1 / (1 - p)
@@ -175,15 +185,38 @@ __device__ __forceinline__ void ffn_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][
         }
 }
 
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+// The blocked bf16 image of an activation [N, C] (include/rqhip.h): element (n, c) is number ((n >> 5) * C + c) * 32 +
+// 8 * (n & 3) + ((n & 31) >> 2), so the rows 4 ks + kq of a block, ks = 0 .. 7, are 16 consecutive bytes per column.
+// This writes the T = 16 RT rows from m0 (a multiple of T) of `ncols` columns from c0, fp32 in LDS with row stride ld:
+// per (column, kq) the tile's rows 4 ks + kq are 4 (RT = 1: half a block) or 8 consecutive elements, one store.
+template <int RT>
+__device__ __forceinline__ void ffn_store_image(const float *src, int ld, int ncols, __bf16 *img, int C, int c0, long long m0,
+                                                int t) {
+    const int ks0 = (int)(m0 & 31) >> 2;      // the tile's first row of a k-slot within its block: 0, or 4 (RT = 1)
+    __bf16 *base = img + ((size_t)(m0 >> 5) * C + c0) * 32 + ks0;
+    for (int f = t; f < 4 * ncols; f += 256) {
+        const int c = f >> 2, kq = f & 3;
+        const float *col = src + kq * ld + c;
+        std::conditional_t<RT == 1, bf16x4, bf16x8> v;
+#pragma unroll
+        for (int ks = 0; ks < 4 * RT; ++ks) v[ks] = (__bf16)col[4 * ks * ld];
+        *reinterpret_cast<decltype(v) *>(base + (size_t)c * 32 + 8 * kq) = v;
+    }
+}
+
 // keeps a round's loads together and in front of the previous round's matrix instructions (csrc/mlp_small.hip)
 #define FFN_FENCE __builtin_amdgcn_sched_barrier(0)
 
 // RT: 16-row tiles per workgroup; NP: column pairs (32 output columns) per wave, >= ceil(d / 128); BF: the "bf16"
 // arithmetic (memory, LDS and the epilogues stay fp32: the operands are rounded as the fragments are packed); IMG: the
-// weights are bf16 images read along their rows (the backward's are the transposed ones)
-template <int RT, int NP, bool BWD, bool BF, bool IMG = false>
+// weights are bf16 images read along their rows (the backward's are the transposed ones); ACT: the saved activations
+// are blocked bf16 images (FfnRows), and the backward's active set is hd16 > 0 without a dropout decision
+template <int RT, int NP, bool BWD, bool BF, bool IMG = false, bool ACT = false>
 __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
     static_assert(BF || !IMG, "weight images belong to the bf16 arithmetic");
+    static_assert(BF || !ACT, "bf16 saved activations belong to the bf16 arithmetic");
     constexpr bool KN = BWD && !IMG;               // the reduction runs down the columns of the weights as stored
     using WT = std::conditional_t<IMG, __bf16, float>;
     using WB = std::conditional_t<IMG, bf16x8[2], float[2][8]>;      // a group's weight operand for two column tiles
@@ -203,8 +236,15 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
         *reinterpret_cast<f32x4 *>(xs + r * ldx + 4 * c4) = *reinterpret_cast<const f32x4 *>(p.x + (size_t)row * d + 4 * c4);
     }
     __syncthreads();
+    if constexpr (ACT) {
+        if (p.x16) ffn_store_image<RT>(xs, ldx, d, p.x16, d, 0, m0, t);
+        if constexpr (BWD)
+            if (!p.out && !p.mid) return;      // d_wo alone: dy16 was all it needed of this kernel
+    }
 
-    const unsigned long long seed = p.th ? (unsigned long long)*p.seed : 0ull;
+    unsigned long long seed = 0ull;
+    if constexpr (!(ACT && BWD))
+        if (p.th) seed = (unsigned long long)*p.seed;
     const int npairs = d >> 5, ngd = d >> 5;
     f32x4 acc2[NP][RT][2];
 #pragma unroll
@@ -282,13 +322,22 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
                 for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const long long grow = m0 + 16 * rt + 4 * kq + r;
-                        const float *hr = p.h_in + (size_t)(grow < p.N ? grow : p.N - 1) * F + fw;
-                        if constexpr (KN) {
-                            const f32x2 v = *reinterpret_cast<const f32x2 *>(hr + 2 * i);
-                            hv[rt][0][r] = v.x; hv[rt][1][r] = v.y;
+                        if constexpr (ACT) {
+                            // row 16 rt + 4 kq + r of the tile is element 8 r + (that row >> 2) of its column's block;
+                            // rows past N are unspecified there and feed rows that are never stored
+                            const __bf16 *hr = reinterpret_cast<const __bf16 *>(p.h_in) + ((size_t)(m0 >> 5) * F + fw) * 32 +
+                                               8 * r + (((int)(m0 & 31) + 16 * rt) >> 2) + kq;
+                            hv[rt][0][r] = (float)hr[(size_t)(KN ? 2 * i : i) * 32];
+                            hv[rt][1][r] = (float)hr[(size_t)(KN ? 2 * i + 1 : 16 + i) * 32];
                         } else {
-                            hv[rt][0][r] = hr[i]; hv[rt][1][r] = hr[16 + i];
+                            const long long grow = m0 + 16 * rt + 4 * kq + r;
+                            const float *hr = p.h_in + (size_t)(grow < p.N ? grow : p.N - 1) * F + fw;
+                            if constexpr (KN) {
+                                const f32x2 v = *reinterpret_cast<const f32x2 *>(hr + 2 * i);
+                                hv[rt][0][r] = v.x; hv[rt][1][r] = v.y;
+                            } else {
+                                hv[rt][0][r] = hr[i]; hv[rt][1][r] = hr[16 + i];
+                            }
                         }
                     }
             }
@@ -318,21 +367,28 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
                         float v = acc1[rt][ct][r];
                         if constexpr (!BWD) {
                             v = v <= 0.f ? 0.f : v;      // +0 for every pre-activation <= 0; a NaN stays a NaN
-                            if (p.mid && grow < p.N) p.mid[(size_t)grow * F + f] = v;
+                            if constexpr (!ACT)
+                                if (p.mid && grow < p.N) p.mid[(size_t)grow * F + f] = v;
                             if (p.th) v = dropout_keep(seed, (unsigned long long)grow * F + f, p.th) ? v * p.s : 0.f;
                         } else {
                             bool on = hv[rt][ct][r] > 0.f;
                             if (p.th) {
-                                on = on && dropout_keep(seed, (unsigned long long)(grow < p.N ? grow : p.N - 1) * F + f, p.th);
+                                if constexpr (!ACT)      // ACT: hd16 > 0 is already h > 0 and keep
+                                    on = on && dropout_keep(seed, (unsigned long long)(grow < p.N ? grow : p.N - 1) * F + f, p.th);
                                 v = v * p.s;
                             }
                             v = on ? v : 0.f;
-                            if (p.mid && grow < p.N) p.mid[(size_t)grow * F + f] = v;
+                            if constexpr (!ACT)
+                                if (p.mid && grow < p.N) p.mid[(size_t)grow * F + f] = v;
                         }
                         hb[row * kFfnLdh + lc] = v;
                     }
         }
         __syncthreads();
+        if constexpr (ACT)      // the chunk's hd (backward: g) as its image; the buffer is not rewritten before the next barrier
+            if (p.mid)
+                ffn_store_image<RT>(hb, kFfnLdh, F - f0 < kFfnChunk ? F - f0 : kFfnChunk, reinterpret_cast<__bf16 *>(p.mid), F,
+                                    f0, m0, t);
         if (fw + kFfnChunk < F) load1(pb[0], fw + kFfnChunk, 0);
         if (p.out) {
             const int ng = (F - f0 < kFfnChunk ? F - f0 : kFfnChunk) >> 5;
@@ -495,6 +551,100 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
     }
 }
 
+struct FfnWgrad16 {
+    const __bf16 *g, *x;       // blocked images: d_wi [F, d] = g^T . x
+    const __bf16 *dy, *h;      // d_wo [d, F] = d_y^T . hd, h the image hd16
+    float *d_wi, *d_wo;        // either may be null
+    long long N;
+    int d, F;
+    int tiles_wi;
+};
+
+// t5_ffn_wgrad_kernel<true> on blocked bf16 images: the same tiles, blocks, chains, wave ranges and sums, and the same
+// rows 4 ks + kq as elements j = ks -- which the image stores as the lane's 16 bytes of a column.  Lane (i, kq) serves
+// columns 16 at + i of P's 32 and 16 bt + i of Q's: four 16-byte loads per block, contiguous over the wave, no
+// conversion and no dropout decision (hd16 holds hd).  Which lane serves a column does not enter its sum.
+__global__ __launch_bounds__(256) void t5_ffn_wgrad16_kernel(const FfnWgrad16 p) {
+    __shared__ float red[4 * 32 * 33];
+    const int t = threadIdx.x, lane = t & 63, i = lane & 15, kq = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    int tile = blockIdx.x;
+    const bool is_wo = tile >= p.tiles_wi;
+    if (is_wo) tile -= p.tiles_wi;
+    const __bf16 *P = is_wo ? p.dy : p.g, *Q = is_wo ? p.h : p.x;
+    const int lp = is_wo ? p.d : p.F, lq = is_wo ? p.F : p.d;
+    float *out = is_wo ? p.d_wo : p.d_wi;
+    const int a0 = 32 * (tile / (lq >> 5)), b0 = 32 * (tile % (lq >> 5));
+
+    const long long nb = (p.N + kFfnWgBlock - 1) / kFfnWgBlock;
+    const long long lo = w * nb / 4, hi = (w + 1) * nb / 4;
+    f32x4 tot[2][2], acc[2][2];
+#pragma unroll
+    for (int at = 0; at < 2; ++at)
+#pragma unroll
+        for (int bt = 0; bt < 2; ++bt) tot[at][bt] = acc[at][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const __bf16 *pp = P + (size_t)(a0 + i) * 32 + 8 * kq, *qp = Q + (size_t)(b0 + i) * 32 + 8 * kq;
+    // fr[0], fr[1]: P's column tiles; fr[2], fr[3]: Q's
+    auto load = [&](long long b, bf16x8 (&fr)[4]) {
+        const __bf16 *pb = pp + (size_t)b * lp * 32, *qb = qp + (size_t)b * lq * 32;
+        fr[0] = *reinterpret_cast<const bf16x8 *>(pb);
+        fr[1] = *reinterpret_cast<const bf16x8 *>(pb + 16 * 32);
+        fr[2] = *reinterpret_cast<const bf16x8 *>(qb);
+        fr[3] = *reinterpret_cast<const bf16x8 *>(qb + 16 * 32);
+    };
+    auto comp = [&](long long b, bf16x8 (&fr)[4]) {
+        if ((b + 1) * kFfnWgBlock > p.N) {      // the last block: rows past the batch are unspecified in memory and count as zero
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks)
+                if (b * kFfnWgBlock + 4 * ks + kq >= p.N) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) fr[k][ks] = (__bf16)0.f;
+                }
+        }
+#pragma unroll
+        for (int at = 0; at < 2; ++at)
+#pragma unroll
+            for (int bt = 0; bt < 2; ++bt) acc[at][bt] = mma_group_bf16(fr[at], fr[2 + bt], acc[at][bt]);
+        if (((b - lo) & (kFfnWgFlush - 1)) == kFfnWgFlush - 1) {
+#pragma unroll
+            for (int at = 0; at < 2; ++at)
+#pragma unroll
+                for (int bt = 0; bt < 2; ++bt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) tot[at][bt][r] = tot[at][bt][r] + acc[at][bt][r];
+                    acc[at][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
+    };
+    bf16x8 f0[4], f1[4];      // two blocks: the next one's loads are in flight over this one's instructions
+    if (lo < hi) load(lo, f0);
+    for (long long b = lo; b < hi; b += 2) {
+        if (b + 1 < hi) load(b + 1, f1);
+        FFN_FENCE; comp(b, f0); FFN_FENCE;
+        if (b + 1 < hi) {
+            if (b + 2 < hi) load(b + 2, f0);
+            FFN_FENCE; comp(b + 1, f1); FFN_FENCE;
+        }
+    }
+    // acc[at][bt][r]: row 16 at + 4 kq + r, column 16 bt + i of the tile
+    float *mine = red + w * 32 * 33;
+#pragma unroll
+    for (int at = 0; at < 2; ++at)
+#pragma unroll
+        for (int bt = 0; bt < 2; ++bt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                mine[(16 * at + 4 * kq + r) * 33 + 16 * bt + i] = tot[at][bt][r] + acc[at][bt][r];
+    __syncthreads();
+    for (int f = t; f < 32 * 32; f += 256) {
+        const int row = f >> 5, col = f & 31;
+        float v = red[row * 33 + col];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) v = v + red[k * 32 * 33 + row * 33 + col];
+        out[(size_t)(a0 + row) * lq + b0 + col] = v;
+    }
+}
+
 int ffn_row_tiles(long long N) { return N > kFfnTallFrom ? 2 : 1; }
 
 // The checks the entry points share; `who` names the entry point in the message.
@@ -519,36 +669,36 @@ int ffn_check(const char *who, int64_t N, int d, int F, double p) {
     return RQHIP_OK;
 }
 
-template <int RT, int NP, bool BWD, bool BF, bool IMG>
+template <int RT, int NP, bool BWD, bool BF, bool IMG, bool ACT>
 int ffn_rows_launch(const FfnRows &p, hipStream_t s) {
     static LdsGrant grant;
     constexpr int T = 16 * RT;
     const int bytes = (T * (p.d + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
     // granted once per device: the most this instantiation can ask for (d <= 128 NP)
     constexpr int most = (T * (128 * NP + 4) + 2 * T * kFfnLdh) * (int)sizeof(float);
-    RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_ffn_rows_kernel<RT, NP, BWD, BF, IMG>), most));
-    hipLaunchKernelGGL((t5_ffn_rows_kernel<RT, NP, BWD, BF, IMG>), dim3((unsigned)((p.N + T - 1) / T)), dim3(256), (size_t)bytes, s, p);
+    RQ_RETURN_IF_HIP(grant.ensure(reinterpret_cast<const void *>(t5_ffn_rows_kernel<RT, NP, BWD, BF, IMG, ACT>), most));
+    hipLaunchKernelGGL((t5_ffn_rows_kernel<RT, NP, BWD, BF, IMG, ACT>), dim3((unsigned)((p.N + T - 1) / T)), dim3(256), (size_t)bytes, s, p);
     RQ_CHECK_LAUNCH("t5_ffn_rows_kernel");
     return RQHIP_OK;
 }
 
-template <bool BWD, bool BF, bool IMG>
+template <bool BWD, bool BF, bool IMG, bool ACT = false>
 int ffn_rows(const FfnRows &p, hipStream_t s) {
     const int np = (p.d / 32 + 3) / 4, rt = ffn_row_tiles(p.N);
     // The "bf16" backward at d > 384 keeps 16-row tiles at every N: its 32-row instantiation would spill to scratch
     // (so does the fp32 one, 44 bytes per lane, which stays as it is).  The tile height changes no bit.  The image
-    // arm follows the same plan.
+    // arm follows the same plan, and so does the arm with bf16 saved activations.
     constexpr bool kShortOnly = BF && BWD;
     if (rt == 1 || (kShortOnly && np == 4)) {
-        if (np == 1) return ffn_rows_launch<1, 1, BWD, BF, IMG>(p, s);
-        if (np == 2) return ffn_rows_launch<1, 2, BWD, BF, IMG>(p, s);
-        if (np == 3) return ffn_rows_launch<1, 3, BWD, BF, IMG>(p, s);
-        return ffn_rows_launch<1, 4, BWD, BF, IMG>(p, s);
+        if (np == 1) return ffn_rows_launch<1, 1, BWD, BF, IMG, ACT>(p, s);
+        if (np == 2) return ffn_rows_launch<1, 2, BWD, BF, IMG, ACT>(p, s);
+        if (np == 3) return ffn_rows_launch<1, 3, BWD, BF, IMG, ACT>(p, s);
+        return ffn_rows_launch<1, 4, BWD, BF, IMG, ACT>(p, s);
     }
-    if (np == 1) return ffn_rows_launch<2, 1, BWD, BF, IMG>(p, s);
-    if (np == 2) return ffn_rows_launch<2, 2, BWD, BF, IMG>(p, s);
-    if (np == 3) return ffn_rows_launch<2, 3, BWD, BF, IMG>(p, s);
-    if constexpr (!kShortOnly) return ffn_rows_launch<2, 4, BWD, BF, IMG>(p, s);
+    if (np == 1) return ffn_rows_launch<2, 1, BWD, BF, IMG, ACT>(p, s);
+    if (np == 2) return ffn_rows_launch<2, 2, BWD, BF, IMG, ACT>(p, s);
+    if (np == 3) return ffn_rows_launch<2, 3, BWD, BF, IMG, ACT>(p, s);
+    if constexpr (!kShortOnly) return ffn_rows_launch<2, 4, BWD, BF, IMG, ACT>(p, s);
     return RQHIP_EUNSUPPORTED;      // not reached: np == 4 left above
 }
 
@@ -560,6 +710,16 @@ using namespace rqhip;
 
 extern "C" int rqhip_t5_ffn_supported(int d, int F) { return ffn_supported(d, F) ? 1 : 0; }
 
+extern "C" size_t rqhip_t5_ffn_act_image_bytes(int64_t N, int C) {
+    if (N < 0 || C < 32 || C % 32) return 0;
+    return (size_t)((N + kFfnWgBlock - 1) / kFfnWgBlock) * (size_t)C * kFfnWgBlock * sizeof(rqhip_bf16_t);
+}
+
+extern "C" size_t rqhip_t5_ffn_bwd_bf16a_workspace_bytes(int64_t N, int d, int F) {
+    if (N < 0 || !ffn_supported(d, F)) return 0;
+    return rqhip_t5_ffn_act_image_bytes(N, d) + rqhip_t5_ffn_act_image_bytes(N, F);
+}
+
 extern "C" size_t rqhip_t5_ffn_bwd_workspace_bytes(int64_t N, int d, int F) {
     if (N < 0 || !ffn_supported(d, F)) return 0;
     return (size_t)N * (size_t)F * sizeof(float);
@@ -569,9 +729,10 @@ namespace {
 
 // the entry points of both arithmetics; `who` names the one called in the messages.  IMG: wi and wo are the bf16 images
 // the call reads (forward wi16, wo16; backward wo16t, wi16t, passed in the places of wo and wi)
-template <bool BF, bool IMG = false>
+// ACT: h is the blocked bf16 image hd16 behind that pointer and x16 the image of x (either may be null: not stored)
+template <bool BF, bool IMG = false, bool ACT = false>
 int ffn_fwd(const char *who, const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
-            const int64_t *seed, float *y, float *h, rqhip_stream_t stream) {
+            const int64_t *seed, float *y, float *h, rqhip_stream_t stream, rqhip_bf16_t *x16 = nullptr) {
     const int rc = ffn_check(who, N, d, F, p);
     if (rc != RQHIP_OK) return rc;
     if (N == 0) return RQHIP_OK;
@@ -584,15 +745,15 @@ int ffn_fwd(const char *who, const float *x, const float *wi, const float *wo, i
         set_error("%s: dropout (p=%g) needs the seed, a one-element int64 device pointer", who, p);
         return RQHIP_EARG;
     }
-    if (!all_aligned16(x, wi, wo, y, h)) {
-        set_error("%s: x, wi, wo, y and h must be 16-byte aligned", who);
+    if (!all_aligned16(x, wi, wo, y, h, x16)) {
+        set_error(ACT ? "%s: x, wi, wo, y, hd16 and x16 must be 16-byte aligned" : "%s: x, wi, wo, y and h must be 16-byte aligned", who);
         return RQHIP_EARG;
     }
     FfnRows a;
-    a.x = x, a.w1 = wi, a.w2 = wo, a.h_in = nullptr, a.mid = h, a.out = y;
+    a.x = x, a.w1 = wi, a.w2 = wo, a.h_in = nullptr, a.mid = h, a.out = y, a.x16 = reinterpret_cast<__bf16 *>(x16);
     a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
     a.N = N, a.d = d, a.F = F;
-    return ffn_rows<false, BF, IMG>(a, reinterpret_cast<hipStream_t>(stream));
+    return ffn_rows<false, BF, IMG, ACT>(a, reinterpret_cast<hipStream_t>(stream));
 }
 
 template <bool BF, bool IMG = false>
@@ -624,7 +785,7 @@ int ffn_bwd(const char *who, const float *x, const float *wi, const float *wo, c
     float *g = d_wi ? reinterpret_cast<float *>(workspace) : nullptr;
     if (d_x || d_wi) {
         FfnRows a;
-        a.x = d_y, a.w1 = wo, a.w2 = wi, a.h_in = h, a.mid = g, a.out = d_x;
+        a.x = d_y, a.w1 = wo, a.w2 = wi, a.h_in = h, a.mid = g, a.out = d_x, a.x16 = nullptr;
         a.seed = reinterpret_cast<const long long *>(seed), a.th = th, a.s = dropout_scale_f64(p);
         a.N = N, a.d = d, a.F = F;
         const int rc1 = ffn_rows<true, BF, IMG>(a, s);
@@ -639,6 +800,52 @@ int ffn_bwd(const char *who, const float *x, const float *wi, const float *wo, c
         q.tiles_wi = d_wi ? tiles : 0;
         hipLaunchKernelGGL(t5_ffn_wgrad_kernel<BF>, dim3((unsigned)(q.tiles_wi + (d_wo ? tiles : 0))), dim3(256), 0, s, q);
         RQ_CHECK_LAUNCH("t5_ffn_wgrad_kernel");
+    }
+    return RQHIP_OK;
+}
+
+// the backward on bf16 saved activations.  The workspace holds dy16 and, behind it, g16: the row kernel writes both
+// and the weight-gradient kernel reads them.  wi, wo: as ffn_bwd's (IMG: the transposed images)
+template <bool IMG>
+int ffn_bwd_act(const char *who, const rqhip_bf16_t *x16, const float *wi, const float *wo, const rqhip_bf16_t *hd16,
+                const float *d_y, int64_t N, int d, int F, double p, float *d_x, float *d_wi, float *d_wo, void *workspace,
+                rqhip_stream_t stream) {
+    const int rc = ffn_check(who, N, d, F, p);
+    if (rc != RQHIP_OK) return rc;
+    if (N == 0 || (!d_x && !d_wi && !d_wo)) return RQHIP_OK;
+    if (any_null(x16, wi, wo, hd16, d_y)) {
+        set_error("%s: null pointer (x16, wi, wo, hd16, d_y)", who);
+        return RQHIP_EARG;
+    }
+    if ((d_wi || d_wo) && !workspace) {
+        set_error("%s: a weight gradient needs a workspace of rqhip_t5_ffn_bwd_bf16a_workspace_bytes(N, d, F) = %zu bytes", who,
+                  rqhip_t5_ffn_bwd_bf16a_workspace_bytes(N, d, F));
+        return RQHIP_EWORKSPACE;
+    }
+    if (!all_aligned16(x16, wi, wo, hd16, d_y, d_x, d_wi, d_wo, workspace)) {
+        set_error("%s: x16, wi, wo, hd16, d_y, d_x, d_wi, d_wo and the workspace must be 16-byte aligned", who);
+        return RQHIP_EARG;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool wgrad = d_wi || d_wo;
+    __bf16 *dy16 = wgrad ? reinterpret_cast<__bf16 *>(workspace) : nullptr;
+    __bf16 *g16 = d_wi ? reinterpret_cast<__bf16 *>(reinterpret_cast<char *>(workspace) + rqhip_t5_ffn_act_image_bytes(N, d)) : nullptr;
+    {
+        FfnRows a;      // d_wo alone: the kernel stages d_y, writes dy16 and returns
+        a.x = d_y, a.w1 = wo, a.w2 = wi, a.h_in = reinterpret_cast<const float *>(hd16), a.mid = reinterpret_cast<float *>(g16);
+        a.out = d_x, a.x16 = dy16, a.seed = nullptr, a.th = dropout_threshold(p), a.s = dropout_scale_f64(p);
+        a.N = N, a.d = d, a.F = F;
+        const int rc1 = ffn_rows<true, true, IMG, true>(a, s);
+        if (rc1 != RQHIP_OK) return rc1;
+    }
+    if (wgrad) {
+        FfnWgrad16 q;
+        q.g = g16, q.x = reinterpret_cast<const __bf16 *>(x16), q.dy = dy16, q.h = reinterpret_cast<const __bf16 *>(hd16);
+        q.d_wi = d_wi, q.d_wo = d_wo, q.N = N, q.d = d, q.F = F;
+        const int tiles = (d / 32) * (F / 32);
+        q.tiles_wi = d_wi ? tiles : 0;
+        hipLaunchKernelGGL(t5_ffn_wgrad16_kernel, dim3((unsigned)(q.tiles_wi + (d_wo ? tiles : 0))), dim3(256), 0, s, q);
+        RQ_CHECK_LAUNCH("t5_ffn_wgrad16_kernel");
     }
     return RQHIP_OK;
 }
@@ -679,4 +886,32 @@ extern "C" int rqhip_t5_ffn_bwd_bf16w(const float *x, const rqhip_bf16_t *wi16t,
     return ffn_bwd<true, true>("t5_ffn_bwd_bf16w", x, reinterpret_cast<const float *>(wi16t),
                                reinterpret_cast<const float *>(wo16t), h, d_y, N, d, F, p, seed, d_x, d_wi, d_wo, workspace,
                                stream);
+}
+
+extern "C" int rqhip_t5_ffn_fwd_bf16a(const float *x, const float *wi, const float *wo, int64_t N, int d, int F, double p,
+                                      const int64_t *seed, float *y, rqhip_bf16_t *hd16, rqhip_bf16_t *x16,
+                                      rqhip_stream_t stream) {
+    return ffn_fwd<true, false, true>("t5_ffn_fwd_bf16a", x, wi, wo, N, d, F, p, seed, y, reinterpret_cast<float *>(hd16),
+                                      stream, x16);
+}
+
+extern "C" int rqhip_t5_ffn_fwd_bf16wa(const float *x, const rqhip_bf16_t *wi16, const rqhip_bf16_t *wo16, int64_t N, int d,
+                                       int F, double p, const int64_t *seed, float *y, rqhip_bf16_t *hd16, rqhip_bf16_t *x16,
+                                       rqhip_stream_t stream) {
+    return ffn_fwd<true, true, true>("t5_ffn_fwd_bf16wa", x, reinterpret_cast<const float *>(wi16),
+                                     reinterpret_cast<const float *>(wo16), N, d, F, p, seed, y,
+                                     reinterpret_cast<float *>(hd16), stream, x16);
+}
+
+extern "C" int rqhip_t5_ffn_bwd_bf16a(const rqhip_bf16_t *x16, const float *wi, const float *wo, const rqhip_bf16_t *hd16,
+                                      const float *d_y, int64_t N, int d, int F, double p, float *d_x, float *d_wi,
+                                      float *d_wo, void *workspace, rqhip_stream_t stream) {
+    return ffn_bwd_act<false>("t5_ffn_bwd_bf16a", x16, wi, wo, hd16, d_y, N, d, F, p, d_x, d_wi, d_wo, workspace, stream);
+}
+
+extern "C" int rqhip_t5_ffn_bwd_bf16wa(const rqhip_bf16_t *x16, const rqhip_bf16_t *wi16t, const rqhip_bf16_t *wo16t,
+                                       const rqhip_bf16_t *hd16, const float *d_y, int64_t N, int d, int F, double p,
+                                       float *d_x, float *d_wi, float *d_wo, void *workspace, rqhip_stream_t stream) {
+    return ffn_bwd_act<true>("t5_ffn_bwd_bf16wa", x16, reinterpret_cast<const float *>(wi16t),
+                             reinterpret_cast<const float *>(wo16t), hd16, d_y, N, d, F, p, d_x, d_wi, d_wo, workspace, stream);
 }

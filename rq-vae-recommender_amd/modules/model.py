@@ -21,6 +21,10 @@ train_decoder.train has no parameter for it.
 take a "hip" matrix body in `matmul_arith` = "bf16" read bf16 images of their weights, which each stack keeps current
 with one refresh launch per change of the weights (modules/t5.py: T5WeightImages); every result keeps its bits, and
 everywhere else the attribute has no effect.  It is set on the model: train_decoder.train has no parameter for it.
+`model.saved_activations` ("fp32", the default, or "bf16") goes to both stacks with them: with "bf16" the "hip"
+feed-forward under grad in `matmul_arith` = "bf16" saves bf16 images of its two activations in place of fp32 tensors
+(modules/t5.py); the loss and every gradient keep their bits, and everywhere else the attribute has no effect.  It is set
+on the model: train_decoder.train has no parameter for it.
 `model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
 cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
 on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
@@ -69,7 +73,7 @@ from torch import Tensor
 
 from data.schemas import TokenizedSeqBatch
 from modules.sid_prefix import SemIdPrefixIndex
-from modules.t5 import ATTENTION_ARITHS, MATMUL_ARITHS, WEIGHT_IMAGES, T5Config, T5EncoderModel, T5Stack
+from modules.t5 import ATTENTION_ARITHS, MATMUL_ARITHS, SAVED_ACTIVATIONS, WEIGHT_IMAGES, T5Config, T5EncoderModel, T5Stack
 from rqhip import ops
 from rqhip._lib import RqHipError
 from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
@@ -148,6 +152,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.matmul_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.attention_arith = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.weight_images = "none"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
+        self.saved_activations = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.beam_impl = "sample"  # or "exact": the search of `generate` (module docstring)
 
     @property
@@ -203,8 +208,10 @@ class EncoderDecoderRetrievalModel(nn.Module):
             raise ValueError(f"attention_arith must be one of {ATTENTION_ARITHS}, got {self.attention_arith!r}")
         if self.weight_images not in WEIGHT_IMAGES:
             raise ValueError(f"weight_images must be one of {WEIGHT_IMAGES}, got {self.weight_images!r}")
+        if self.saved_activations not in SAVED_ACTIVATIONS:
+            raise ValueError(f"saved_activations must be one of {SAVED_ACTIVATIONS}, got {self.saved_activations!r}")
         for name in ("attention_impl", "attention_long_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith",
-                     "attention_arith", "weight_images"):
+                     "attention_arith", "weight_images", "saved_activations"):
             for stack in (self.encoder.encoder, self.t5_decoder):
                 setattr(stack, name, getattr(self, name))
 

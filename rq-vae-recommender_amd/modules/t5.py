@@ -84,6 +84,22 @@ weight written behind the key's back (through a raw pointer by other code than F
 forward refreshes, since a replay cannot compare keys.  It is an attribute of the model or the stack, set by the
 caller: train_decoder.train has no parameter for it.  Measurements: profiles/t5_weight_images.txt.
 
+`saved_activations` = "fp32" (the default) or "bf16" (SAVED_ACTIVATIONS) is what the "bf16" feed-forward keeps between
+its forward and its backward.  It acts only where the "hip" feed-forward runs under grad with `matmul_arith` = "bf16"
+(autograd.T5FFNBf16SavedFunction; rqhip_t5_ffn_*_bf16a / _bf16wa), with `weight_images` "none" and "bf16" alike: the
+forward then saves blocked bf16 images of dropout(relu(wi(x))) and of x in place of the fp32 ReLU output and the fp32
+x -- 64 * ceil(rows / 32) * (d_model + d_ff) bytes per body against 4 * rows * (d_model + d_ff) -- and no seed; the
+backward's active set is the image's sign, its weight-gradient kernel loads 16-byte bf16 fragments and neither backward
+kernel hashes a dropout decision.  The images hold the very operands the "bf16" arithmetic rounds in registers, so the
+loss and every gradient keep the bits of "fp32" (include/rqhip.h names the one difference, an activation below
+2^-134).  Everywhere else -- under no_grad, the "fp32" arithmetic, the "torch" body, host tensors -- the attribute has
+no effect, like `weight_images` on the operator bodies.  It is an attribute of the model or the stack, set by the caller:
+train_decoder.train has no parameter for it.  Measured on an MI355X beside `weight_images` = "bf16" in alternating runs
+(profiles/t5_saved_activations.txt): at batch 640 a training step goes from 35.5 to 32.2 ms and, with the grouped
+projections, from 32.7 to 29.2 ms, beyond the runs' spreads, at 0.88 of the peak memory (4858 -> 4283 MiB); the
+weight-gradient kernel takes 0.28 of its twin's device time and the two row kernels 0.96 to 1.05 of theirs; at batch 64
+no step-time difference could be measured (9.5 against 9.3 and 8.6 against 8.0 ms inside block spreads of 1.9 to 3.7 ms).
+
 `attention_arith` = "fp32" (the default) or "bf16" is the arithmetic of the LONG attention calls alone, wherever
 `attention_long_impl` = "hip" takes one: the inference launch (ops.t5_attention_long, `generate`'s cross-attention
 included), and under grad the forward and backward of autograd.T5AttentionLongBf16Function.  "bf16" rounds q, k, v,
@@ -111,7 +127,7 @@ from torch import Tensor
 
 from rqhip import ops, optim
 from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5FFNBf16Function, T5FFNBf16ImagesFunction,
-                            T5FFNFunction, T5ProjBf16Function, T5ProjBf16ImagesFunction, T5ProjFunction,
+                            T5FFNBf16SavedFunction, T5FFNFunction, T5ProjBf16Function, T5ProjBf16ImagesFunction, T5ProjFunction,
                             t5_attention_long_function)
 
 KV = Tuple[Tensor, Tensor]
@@ -123,6 +139,7 @@ PROJ_IMPLS = ("torch", "hip")
 MATMUL_ARITHS = ops.T5_ARITHS  # ("fp32", "bf16")
 ATTENTION_ARITHS = ops.T5_ARITHS  # of the long attention calls
 WEIGHT_IMAGES = ("none", "bf16")  # where the "bf16" matrix forms read their weights: as stored, or from bf16 images
+SAVED_ACTIVATIONS = ops.T5_SAVED  # ("fp32", "bf16"): what the "bf16" feed-forward saves for its backward
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
 
 
@@ -506,17 +523,23 @@ class T5DenseReluDense(nn.Module):
         return self.wo(self.dropout(F.relu(self.wi(x))))
 
     def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor], arith: str = "fp32",
-                    images: Optional[T5WeightImages] = None) -> Tensor:
+                    images: Optional[T5WeightImages] = None, saved: str = "fp32") -> Tensor:
         """forward as one fused call (the "hip" feed-forward body), its dropout at rate p from `seed`, in the
-        arithmetic `arith` (MATMUL_ARITHS); `images` (with "bf16"): the weights are read from their bf16 images."""
+        arithmetic `arith` (MATMUL_ARITHS); `images` (with "bf16"): the weights are read from their bf16 images;
+        `saved` (SAVED_ACTIVATIONS; acts with "bf16" under grad): what the call keeps for its backward."""
         bf16 = arith == "bf16"
+        act = bf16 and saved == "bf16" and torch.is_grad_enabled()
         if bf16 and images is not None:
             (wi16, wi16t), (wo16, wo16t) = images.of(self.wi.weight), images.of(self.wo.weight)
+            if act:
+                return T5FFNBf16SavedFunction.apply(x, self.wi.weight, self.wo.weight, p, seed, wi16, wo16, wi16t, wo16t)
             if torch.is_grad_enabled():
                 return T5FFNBf16ImagesFunction.apply(x, self.wi.weight, self.wo.weight, p, seed, wi16, wo16, wi16t,
                                                      wo16t)
             return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False, arith=arith,
                                   w_images=(wi16, wo16))[0]
+        if act:
+            return T5FFNBf16SavedFunction.apply(x, self.wi.weight, self.wo.weight, p, seed)
         if torch.is_grad_enabled():
             return (T5FFNBf16Function if bf16 else T5FFNFunction).apply(x, self.wi.weight, self.wo.weight, p, seed)
         kw = {"arith": arith} if bf16 else {}
@@ -561,6 +584,7 @@ class T5Stack(nn.Module):
         self.matmul_arith = "fp32"  # or "bf16": the arithmetic of the "hip" feed-forward and projections (docstring)
         self.attention_arith = "fp32"  # or "bf16": the arithmetic of the long attention calls (module docstring)
         self.weight_images = "none"  # or "bf16": the "bf16" matrix forms read bf16 images of their weights (docstring)
+        self.saved_activations = "fp32"  # or "bf16": what the "bf16" feed-forward saves for its backward (docstring)
         self.images = T5WeightImages()  # plain attribute: not a parameter, not a buffer, not in the state dict
         init_t5_weights(self, config)
 
@@ -590,6 +614,12 @@ class T5Stack(nn.Module):
         if self.weight_images not in WEIGHT_IMAGES:
             raise ValueError(f"weight_images must be one of {WEIGHT_IMAGES}, got {self.weight_images!r}")
         return self.weight_images
+
+    def saved_activations_mode(self) -> str:
+        """saved_activations, validated."""
+        if self.saved_activations not in SAVED_ACTIVATIONS:
+            raise ValueError(f"saved_activations must be one of {SAVED_ACTIVATIONS}, got {self.saved_activations!r}")
+        return self.saved_activations
 
     def current_images(self, x: Tensor) -> Optional[T5WeightImages]:
         """The holder with current images for a forward of x, refreshed by one launch if its key differs, or None where
@@ -770,6 +800,7 @@ class T5Stack(nn.Module):
         fused_glue = self.hip_norm_active(inputs_embeds)
         fused_ffn = self.hip_ffn_active(inputs_embeds)
         arith = self.arith()
+        saved = self.saved_activations_mode()
         p = float(self.config.dropout_rate) if self.training else 0.0
         layers = [layer for blk in self.block for layer in blk.layer]
         seeds = _Seeds(p, inputs_embeds.device, len(layers) + 1 if fused_glue else 0,
@@ -789,7 +820,7 @@ class T5Stack(nn.Module):
                 x, normed = glue(k, x, attention.cross_attention(i, blk.layer[1].EncDecAttention, normed))
             dense = blk.layer[-1].DenseReluDense
             k += 1
-            body = dense.forward_hip(normed, p, seeds.ffn(i), arith, images) if fused_ffn else dense(normed)
+            body = dense.forward_hip(normed, p, seeds.ffn(i), arith, images, saved) if fused_ffn else dense(normed)
             x, normed = glue(k, x, body)
         return (normed, new_kv) if use_cache else normed
 

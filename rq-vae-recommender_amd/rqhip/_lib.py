@@ -147,6 +147,12 @@ SIGNATURES = {
     "rqhip_bf16_images": (_int, [_vp, _int, _i64, _vp]),
     "rqhip_t5_ffn_fwd_bf16w": (_int, [_vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp]),
     "rqhip_t5_ffn_bwd_bf16w": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_act_image_bytes": (_sz, [_i64, _int]),
+    "rqhip_t5_ffn_bwd_bf16a_workspace_bytes": (_sz, [_i64, _int, _int]),
+    "rqhip_t5_ffn_fwd_bf16a": (_int, [_vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_bwd_bf16a": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_fwd_bf16wa": (_int, [_vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_ffn_bwd_bf16wa": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "rqhip_t5_proj_fwd_bf16w": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp]),
     "rqhip_t5_proj_bwd_bf16w": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp]),
     "rqhip_sid_head_loss_supported": (_int, [_int, _int, _int]),

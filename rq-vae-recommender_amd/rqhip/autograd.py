@@ -435,6 +435,38 @@ class T5FFNBf16ImagesFunction(torch.autograd.Function):
         return (d_x, d_wi, d_wo) + (None,) * 6
 
 
+class T5FFNBf16SavedFunction(torch.autograd.Function):
+    """T5FFNBf16Function with bf16 saved activations (rqhip_t5_ffn_*_bf16a, and _bf16wa with weight images;
+    ops.t5_ffn_fwd(..., saved="bf16")): apply(x, wi, wo, p, seed[, wi16, wo16, wi16t, wo16t]) -> the same y, and in the
+    backward the same gradients, bit for bit.  Saved: the blocked bf16 images hd16 of dropout(relu(x @ wi.T)) and x16 of
+    x, the weights (for their shapes and, without images, their values) and with images the transposed pair -- nothing
+    fp32 of the activations' size, and no seed: the backward's active set is hd16 > 0.  The four images are given
+    together or not at all; they are non-differentiable inputs as in T5FFNBf16ImagesFunction."""
+
+    arith = "bf16"
+
+    @staticmethod
+    def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor], wi16: Optional[Tensor] = None,
+                wo16: Optional[Tensor] = None, wi16t: Optional[Tensor] = None, wo16t: Optional[Tensor] = None):
+        ctx.images = wi16 is not None
+        y, (hd16, x16) = ops.t5_ffn_fwd(x, wi, wo, p, seed, arith="bf16", saved="bf16",
+                                        w_images=(wi16, wo16) if ctx.images else None)
+        ctx.save_for_backward(hd16, x16, wi, wo, *((wi16t, wo16t) if ctx.images else ()))
+        ctx.p = p
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y: Tensor):
+        hd16, x16, wi, wo, *images_t = ctx.saved_tensors
+        need_x, need_wi, need_wo = ctx.needs_input_grad[:3]
+        if not (need_x or need_wi or need_wo):
+            return (None,) * 9
+        d_x, d_wi, d_wo = ops.t5_ffn_bwd(None, wi, wo, (hd16, x16), _dense(d_y), ctx.p, None, need_x=need_x,
+                                         need_wi=need_wi, need_wo=need_wo, arith="bf16", saved="bf16",
+                                         w_images=tuple(images_t) if ctx.images else None)
+        return (d_x, d_wi, d_wo) + (None,) * 6
+
+
 def t5_ffn_function(arith: str = "fp32"):
     """The feed-forward Function of an arithmetic."""
     if arith not in ops.T5_ARITHS:

@@ -1015,8 +1015,54 @@ def _ffn_call(who: str, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optio
     return x, _aligned16(wi.contiguous()), _aligned16(wo.contiguous()), (x.numel() // d), d, F, seed_ptr
 
 
+T5_SAVED = ("fp32", "bf16")   # what t5_ffn_fwd keeps for t5_ffn_bwd: the fp32 h, or blocked bf16 activation images
+
+
+def _saved_entry(who: str, arith: str, w_images, saved: str):
+    """_image_entry for a feed-forward call that may keep bf16 saved activations: with saved="bf16" the entry point is
+    rqhip_<who>_bf16a, or rqhip_<who>_bf16wa with weight images, which only the "bf16" arithmetic has."""
+    if saved not in T5_SAVED:
+        raise RqHipError(f"{who}: saved must be one of {T5_SAVED}, got {saved!r}")
+    if saved == "fp32":
+        return _image_entry(who, arith, w_images)
+    _image_entry(who, arith, w_images)      # an unknown arithmetic, or images off "bf16", is the first complaint
+    if arith != "bf16":
+        raise RqHipError(f'{who}: saved="bf16" belongs to arith="bf16" (the images hold its bf16 operands), got arith={arith!r}')
+    name = f"rqhip_{who}_bf16" + ("wa" if w_images is not None else "a")
+    return getattr(_lib.lib(), name), name
+
+
+def t5_act_image_numel(N: int, C: int) -> int:
+    """bf16 elements of the blocked image of an [N, C] activation (rqhip_t5_ffn_act_image_bytes): 32 * ceil(N / 32) * C."""
+    return int(_lib.lib().rqhip_t5_ffn_act_image_bytes(int(N), int(C))) // 2
+
+
+def t5_act_image_rows(img: Tensor, N: int, C: int) -> Tensor:
+    """The row-major [N, C] bfloat16 tensor of a blocked activation image (include/rqhip.h: element (n, c) is number
+    ((n >> 5) * C + c) * 32 + 8 * (n & 3) + ((n & 31) >> 2) of the buffer).  An index permutation in torch operators, on
+    the image's device: for tests and for looking inside an image, not for a hot path."""
+    N, C = int(N), int(C)
+    nb = (N + 31) // 32
+    if C < 32 or C % 32 or img.dtype != torch.bfloat16 or img.numel() != nb * C * 32:
+        raise RqHipError(f"t5_act_image_rows: an image of [{N}, {C}] is {nb * C * 32} bfloat16 with C a multiple of 32, got "
+                         f"{img.dtype} {tuple(img.shape)}")
+    # buffer [b, c, kq, ks] -> rows [b, ks, kq] (rho = 4 ks + kq), columns c
+    return img.reshape(nb, C, 4, 8).permute(0, 3, 2, 1).reshape(nb * 32, C)[:N].contiguous()
+
+
+def _act_image(who: str, img, name: str, N: int, C: int, dev) -> Tensor:
+    """A blocked activation image as the kernels read it: a dense, 16-byte aligned bfloat16 tensor of its size on `dev`."""
+    n = 32 * ((N + 31) // 32) * C
+    if not isinstance(img, Tensor) or img.dtype != torch.bfloat16 or img.numel() != n or img.device != dev:
+        got = f"{img.dtype} {tuple(img.shape)} on {img.device}" if isinstance(img, Tensor) else repr(type(img))
+        raise RqHipError(f"{who}: {name} must be a bfloat16 image of {n} elements on {dev} (t5_ffn_fwd, saved=\"bf16\"), got {got}")
+    if not img.is_contiguous() or img.data_ptr() % 16:
+        raise RqHipError(f"{who}: {name} must be dense and 16-byte aligned")
+    return img
+
+
 def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *, need_h: bool = True,
-               arith: str = "fp32", w_images=None):
+               arith: str = "fp32", w_images=None, saved: str = "fp32"):
     """The T5 feed-forward body in one launch (rqhip_t5_ffn_fwd) -> (y, h or None): h = relu(x @ wi.T), y = dropout(h, p)
     @ wo.T.  x [..., d] float32, wi [F, d] and wo [d, F] the two Linear weights as stored; y has x's shape, h is
     [..., F] (the one tensor t5_ffn_bwd needs; not stored without need_h).  The mask is t5_attention_dropout_keep(seed,
@@ -1024,9 +1070,12 @@ def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional
     reads.  arith: "fp32", or "bf16" (rqhip_t5_ffn_fwd_bf16: every matrix operand rounded to bf16, fp32 accumulation;
     all tensors stay float32 and h is stored unrounded).  w_images (arith "bf16" only): the pair (wi16 [F, d], wo16 [d,
     F]) of bf16 images of wi and wo (bf16_images); the kernel reads them instead of the weights, and every result has
-    the bits of the call without them (rqhip_t5_ffn_fwd_bf16w)."""
+    the bits of the call without them (rqhip_t5_ffn_fwd_bf16w).  saved (T5_SAVED; "bf16" with arith "bf16" only, with or
+    without w_images): with "bf16" the second result is the pair (hd16, x16) of blocked bf16 images (t5_act_image_rows) of
+    dropout(h) and of x, all that t5_ffn_bwd then needs of the activations (rqhip_t5_ffn_fwd_bf16a / _bf16wa); y keeps
+    its bits.  Without need_h the second result is None either way."""
     who = "t5_ffn_fwd"
-    fn, fn_name = _image_entry(who, arith, w_images)
+    fn, fn_name = _saved_entry(who, arith, w_images, saved)
     _need_gpu(x, wi, wo, seed)
     x, wi, wo, N, d, F, seed_ptr = _ffn_call(who, x, wi, wo, p, seed)
     dev = x.device
@@ -1035,6 +1084,12 @@ def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional
         wi, wo = _image(who, wi16, "w_images[0]", (F, d), dev), _image(who, wo16, "w_images[1]", (d, F), dev)
     with torch.cuda.device(dev):
         y = torch.empty_like(x)
+        if saved == "bf16":
+            hd16 = torch.empty((t5_act_image_numel(N, F),), dtype=torch.bfloat16, device=dev) if need_h else None
+            x16 = torch.empty((t5_act_image_numel(N, d),), dtype=torch.bfloat16, device=dev) if need_h else None
+            rc = fn(_ptr(x), _ptr(wi), _ptr(wo), N, d, F, float(p), seed_ptr, _ptr(y), _ptr(hd16), _ptr(x16), _stream())
+            check(rc, fn_name)
+            return y, ((hd16, x16) if need_h else None)
         h = torch.empty(x.shape[:-1] + (F,), dtype=torch.float32, device=dev) if need_h else None
         rc = fn(_ptr(x), _ptr(wi), _ptr(wo), N, d, F, float(p), seed_ptr, _ptr(y), _ptr(h), _stream())
         check(rc, fn_name)
@@ -1043,16 +1098,21 @@ def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional
 
 def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *,
                need_x: bool = True, need_wi: bool = True, need_wo: bool = True, return_g: bool = False,
-               arith: str = "fp32", w_images=None):
+               arith: str = "fp32", w_images=None, saved: str = "fp32"):
     """The gradients of t5_ffn_fwd in one call of at most two launches (rqhip_t5_ffn_bwd) -> (d_x, d_wi, d_wo), None
     where not needed.  x, wi, wo, p, seed: the forward's; h: its second result; d_y: the gradient of y.  The dropout
     decisions are recomputed from the seed; the weight gradients are summed without atomics in an order that depends on
     the shape alone.  The [N, F] workspace comes from torch's allocator.  return_g: a fourth result, the workspace as the
     tensor g of h's shape when need_wi (else None).  arith: "fp32" or "bf16", as t5_ffn_fwd's (rqhip_t5_ffn_bwd_bf16).
     w_images (arith "bf16" only): the pair (wi16t [d, F], wo16t [F, d]) of TRANSPOSED bf16 images of wi and wo, which
-    this call reads instead of the weights; the bits are those of the call without them (rqhip_t5_ffn_bwd_bf16w)."""
+    this call reads instead of the weights; the bits are those of the call without them (rqhip_t5_ffn_bwd_bf16w).
+    saved="bf16" (arith "bf16" only): x is None and h is the forward's pair (hd16, x16); no seed is read, the active set
+    is hd16 > 0, the workspace holds bf16 images of d_y and g, and every gradient has the bits of the call on the fp32 h
+    (rqhip_t5_ffn_bwd_bf16a / _bf16wa); return_g then gives g as the row-major bfloat16 tensor of its image."""
     who = "t5_ffn_bwd"
-    fn, fn_name = _image_entry(who, arith, w_images)
+    fn, fn_name = _saved_entry(who, arith, w_images, saved)
+    if saved == "bf16":
+        return _ffn_bwd_saved(who, fn, fn_name, wi, wo, h, d_y, p, need_x, need_wi, need_wo, return_g, w_images)
     _need_gpu(x, wi, wo, h, d_y, seed)
     x, wi, wo, N, d, F, seed_ptr = _ffn_call(who, x, wi, wo, p, seed)
     if w_images is not None:
@@ -1076,6 +1136,40 @@ def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: flo
         check(rc, fn_name)
     if return_g:
         return d_x, d_wi, d_wo, (work.view(h.shape) if work is not None else None)
+    return d_x, d_wi, d_wo
+
+
+def _ffn_bwd_saved(who, fn, fn_name, wi, wo, pair, d_y, p, need_x, need_wi, need_wo, return_g, w_images):
+    """t5_ffn_bwd on bf16 saved activations: `pair` is the forward's (hd16, x16)."""
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+        raise RqHipError(f'{who}: with saved="bf16", h is the pair (hd16, x16) of t5_ffn_fwd(..., saved="bf16")')
+    hd16, x16 = pair
+    _need_gpu(wi, wo, hd16, x16, d_y)
+    if not 0.0 <= p < 1.0:
+        raise RqHipError(f"{who}: p={p} outside 0 <= p < 1")
+    d_y, wi, wo, N, d, F, _ = _ffn_call(who, d_y, wi, wo, 0.0, None)    # d_y has x's shape and checks; no seed is read
+    dev = d_y.device
+    if w_images is not None:
+        wi16t, wo16t = w_images
+        wi, wo = _image(who, wi16t, "w_images[0]", (d, F), dev), _image(who, wo16t, "w_images[1]", (F, d), dev)
+    hd16, x16 = _act_image(who, hd16, "hd16", N, F, dev), _act_image(who, x16, "x16", N, d, dev)
+    with torch.cuda.device(dev):
+        d_x = torch.empty_like(d_y) if need_x else None
+        make = torch.zeros if N == 0 else torch.empty      # without rows the sums are empty
+        d_wi = make((F, d), dtype=torch.float32, device=dev) if need_wi else None
+        d_wo = make((d, F), dtype=torch.float32, device=dev) if need_wo else None
+        work = None
+        if (need_wi or need_wo) and N > 0:      # dy16, and behind it g16 when d_wi is wanted
+            n = t5_act_image_numel(N, d) + (t5_act_image_numel(N, F) if need_wi else 0)
+            work = torch.empty((n,), dtype=torch.bfloat16, device=dev)
+        rc = fn(_ptr(x16), _ptr(wi), _ptr(wo), _ptr(hd16), _ptr(d_y), N, d, F, float(p), _ptr(d_x), _ptr(d_wi), _ptr(d_wo),
+                _ptr(work), _stream())
+        check(rc, fn_name)
+    if return_g:
+        g = None
+        if work is not None and need_wi:
+            g = t5_act_image_rows(work[t5_act_image_numel(N, d):], N, F).view(d_y.shape[:-1] + (F,))
+        return d_x, d_wi, d_wo, g
     return d_x, d_wi, d_wo
 
 

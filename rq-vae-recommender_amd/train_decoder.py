@@ -28,7 +28,8 @@ What differs:
     an attribute set on the model: train has no parameter for it, nor for `model.attention_long_impl`, and amp does
     not set it.  Reading the bf16 arm's weights from bf16 images, `model.weight_images = "bf16"` (modules/t5.py), is
     a model attribute of the same kind: no parameter here, and amp goes on setting `matmul_arith` alone; the images
-    follow every FlatAdamW step through rqhip.optim.generation().  push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
+    follow every FlatAdamW step through rqhip.optim.generation().  So is `model.saved_activations = "bf16"`
+    (modules/t5.py), which makes the bf16 feed-forward keep bf16 images of its activations for the backward.  push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
     reference.
 wandb is optional: with `wandb_logging=True` and no wandb module, metrics are printed.
 The full eval here reports one draw of the sampling beam search; evaluate_decoder.py evaluates a checkpoint with the

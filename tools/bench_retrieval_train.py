@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one training step of the retrieval model (forward + backward + AdamW, train mode, dropout 0.1) at the Amazon
 decoder config (d_model 384, 6 heads, d_ff 1024, 4 layers, K = 256, L = 3; batch 64, 20-item histories with padded
-tails: encoder T = 81, decoder T = 4) in twelve arms:
+tails: encoder T = 81, decoder T = 4) in fourteen arms:
 
   torch      the T5 operators: per attention two batched matmuls, the adds, an fp32 softmax, a dropout mask and the
              head transposes, with the [R, H, Tq, Tk] weights saved for autograd
@@ -24,6 +24,8 @@ tails: encoder T = 81, decoder T = 4) in twelve arms:
              grouped projections on bf16 operands (rqhip_t5_ffn_*_bf16, rqhip_t5_proj_*_bf16)
   ...+bf16+img  either bf16 arm with weight_images = "bf16": the same products with the weights read from bf16 images
              (rqhip_t5_ffn_*_bf16w, rqhip_t5_proj_*_bf16w), refreshed by one launch per stack and step; the same bits
+  ...+bf16+img+act  either +img arm with saved_activations = "bf16": the feed-forward saves blocked bf16 images of its
+             two activations in place of fp32 tensors and its backward reads them (rqhip_t5_ffn_*_bf16wa); the same bits
 
 The arms alternate --runs times in one process on one device (same weights at the start of every block, same
 batch); each block is --warmup untimed steps, then --iters steps with a device event pair around each.  Reports the
@@ -34,7 +36,8 @@ holds a three-arm run, profiles/retrieval_train_step_head.txt a four-arm run, pr
 five-arm run, profiles/retrieval_optim_tail.txt a six-arm run, profiles/retrieval_train_step_embed.txt a run of the sixth
 and seventh arm, profiles/retrieval_train_step_proj.txt runs of the seventh and eighth,
 profiles/retrieval_train_step_bf16.txt runs of those two and their bf16 forms, profiles/t5_weight_images.txt runs of
-the bf16 forms with and without +img; profiles/retrieval_train_step.txt is the
+the bf16 forms with and without +img, profiles/t5_saved_activations.txt runs of the +img forms with and without +act;
+profiles/retrieval_train_step.txt is the
 older two-arm run; none of them is to be overwritten or compared
 against: two arms are compared within one run only).
 --arms picks a subset, e.g. one arm under a kernel trace to count its launches per step.
@@ -68,9 +71,13 @@ ARMS = {"torch": ("torch", "torch", "torch", "torch", "torch"),
         "hip_train+norm+head+ffn+optim+embed+bf16": ("hip_train", "hip", "hip", "hip", "torch"),
         "hip_train+norm+head+ffn+optim+embed+proj+bf16": ("hip_train", "hip", "hip", "hip", "hip"),
         "hip_train+norm+head+ffn+optim+embed+bf16+img": ("hip_train", "hip", "hip", "hip", "torch"),
-        "hip_train+norm+head+ffn+optim+embed+proj+bf16+img": ("hip_train", "hip", "hip", "hip", "hip")}
+        "hip_train+norm+head+ffn+optim+embed+proj+bf16+img": ("hip_train", "hip", "hip", "hip", "hip"),
+        "hip_train+norm+head+ffn+optim+embed+bf16+img+act": ("hip_train", "hip", "hip", "hip", "torch"),
+        "hip_train+norm+head+ffn+optim+embed+proj+bf16+img+act": ("hip_train", "hip", "hip", "hip", "hip")}
+# arms with saved_activations = "bf16"; the others "fp32"
+ACT = ("hip_train+norm+head+ffn+optim+embed+bf16+img+act", "hip_train+norm+head+ffn+optim+embed+proj+bf16+img+act")
 # arms with weight_images = "bf16"; the others "none"
-IMG = ("hip_train+norm+head+ffn+optim+embed+bf16+img", "hip_train+norm+head+ffn+optim+embed+proj+bf16+img")
+IMG = ("hip_train+norm+head+ffn+optim+embed+bf16+img", "hip_train+norm+head+ffn+optim+embed+proj+bf16+img") + ACT
 # arms with matmul_arith = "bf16"; the others "fp32"
 BF16 = ("hip_train+norm+head+ffn+optim+embed+bf16", "hip_train+norm+head+ffn+optim+embed+proj+bf16") + IMG
 # arms stepped by rqhip.optim.FlatAdamW; the others by torch.optim.AdamW
@@ -93,6 +100,7 @@ def block(model, state, batch, arm, warmup, iters):
     model.embed_impl = "hip" if arm in EMBED_HIP else "torch"
     model.matmul_arith = "bf16" if arm in BF16 else "fp32"
     model.weight_images = "bf16" if arm in IMG else "none"
+    model.saved_activations = "bf16" if arm in ACT else "fp32"
     model.train()
     if arm in FLAT_ADAMW:
         from rqhip.optim import FlatAdamW
@@ -152,6 +160,7 @@ def main():
                                  **({"embed_impl": "hip"} if arm in EMBED_HIP else {}),
                                  **({"matmul_arith": "bf16"} if arm in BF16 else {}),
                                  **({"weight_images": "bf16"} if arm in IMG else {}),
+                                 **({"saved_activations": "bf16"} if arm in ACT else {}),
                                  "optimizer": "FlatAdamW" if arm in FLAT_ADAMW else "torch.optim.AdamW", "batch": args.batch,
                                  "steps_timed": len(times[arm]),
                                  "ms_per_step_median": round(statistics.median(times[arm]), 3),
@@ -167,7 +176,10 @@ def main():
                  ("hip_train+norm+head+ffn+optim+embed", "hip_train+norm+head+ffn+optim+embed+bf16"),
                  ("hip_train+norm+head+ffn+optim+embed+proj", "hip_train+norm+head+ffn+optim+embed+proj+bf16"),
                  ("hip_train+norm+head+ffn+optim+embed+bf16", "hip_train+norm+head+ffn+optim+embed+bf16+img"),
-                 ("hip_train+norm+head+ffn+optim+embed+proj+bf16", "hip_train+norm+head+ffn+optim+embed+proj+bf16+img")):
+                 ("hip_train+norm+head+ffn+optim+embed+proj+bf16", "hip_train+norm+head+ffn+optim+embed+proj+bf16+img"),
+                 ("hip_train+norm+head+ffn+optim+embed+bf16+img", "hip_train+norm+head+ffn+optim+embed+bf16+img+act"),
+                 ("hip_train+norm+head+ffn+optim+embed+proj+bf16+img",
+                  "hip_train+norm+head+ffn+optim+embed+proj+bf16+img+act")):
         if a in arms and b in arms:
             summary[f"{a} / {b}"] = round(statistics.median(times[a]) / statistics.median(times[b]), 3)
             summary[f"peak {a} / {b}"] = round(peak[a] / peak[b], 3)
