@@ -10,21 +10,18 @@ when it is taken: modules/t5.py.
 `model.attention_long_impl` ("torch", the default, or "hip") goes to both stacks with them: with "hip" beside a fused
 `attention_impl`, an attention call beyond the 256 tokens of csrc/t5_attention.hip is a call of
 csrc/t5_attention_long.hip (up to 2048 tokens) instead of the operators, call by call (modules/t5.py).
-`model.matmul_arith` ("fp32", the default, or "bf16") goes to both stacks with them: the arithmetic of the "hip"
-feed-forward and the "hip" projections (bf16 operands, fp32 accumulation, fp32 storage; modules/t5.py).  It has no
-effect on the "torch" bodies, nor on the attention, the norms, the heads or the embedding, which stay fp32.
+`model.matmul_arith` ("fp32", the default, or "bf16"), `model.weight_images` ("none", the default, or "bf16") and
+`model.saved_activations` ("fp32", the default, or "bf16") go to both stacks with them: which form the "hip" feed-forward
+and the "hip" projections take -- bf16 operands with fp32 accumulation and storage, weights read from bf16 images that each
+stack keeps current with one refresh launch per change of the weights, the feed-forward's two saved activations as bf16
+images under grad.  The last two act on the "bf16" arithmetic alone and keep every bit of it; none of the three has an
+effect on the "torch" bodies, nor on the attention, the norms, the heads or the embedding, which stay fp32
+(modules/t5.py: matmul_forms).  train_decoder.train has no parameter for the last two.
 `model.attention_arith` ("fp32", the default, or "bf16") goes to both stacks with them: the arithmetic of the long
 attention calls that `attention_long_impl` = "hip" takes (bf16 matrix operands, fp32 softmax and storage; modules/t5.py),
 `generate`'s cross-attention included.  The short kernel and the cached decode step stay fp32.  It is set on the model:
 train_decoder.train has no parameter for it.
-`model.weight_images` ("none", the default, or "bf16") goes to both stacks with them: with "bf16" the calls that already
-take a "hip" matrix body in `matmul_arith` = "bf16" read bf16 images of their weights, which each stack keeps current
-with one refresh launch per change of the weights (modules/t5.py: T5WeightImages); every result keeps its bits, and
-everywhere else the attribute has no effect.  It is set on the model: train_decoder.train has no parameter for it.
-`model.saved_activations` ("fp32", the default, or "bf16") goes to both stacks with them: with "bf16" the "hip"
-feed-forward under grad in `matmul_arith` = "bf16" saves bf16 images of its two activations in place of fp32 tensors
-(modules/t5.py); the loss and every gradient keep their bits, and everywhere else the attribute has no effect.  It is set
-on the model: train_decoder.train has no parameter for it.
+All nine are validated against modules/t5.py's STACK_ATTRIBUTES whenever they are handed over.
 `model.head_impl = "hip"` (default "torch") makes the loss of `forward` -- the num_hierarchies heads and their
 cross-entropy losses -- ONE autograd.SidHeadLossFunction call (csrc/sid_head_loss.hip): one call forward, one backward,
 on the decoder's unsliced output and batch.sem_ids_fut as they are, with the decoder_mlp weights as separate pointers
@@ -73,7 +70,7 @@ from torch import Tensor
 
 from data.schemas import TokenizedSeqBatch
 from modules.sid_prefix import SemIdPrefixIndex
-from modules.t5 import ATTENTION_ARITHS, MATMUL_ARITHS, SAVED_ACTIVATIONS, WEIGHT_IMAGES, T5Config, T5EncoderModel, T5Stack
+from modules.t5 import STACK_ATTRIBUTES, T5Config, T5EncoderModel, T5Stack, checked
 from rqhip import ops
 from rqhip._lib import RqHipError
 from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
@@ -202,18 +199,11 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return self._prefix_index_for_codebooks().check_valid_prefix(prefix, batch_size)
 
     def _push_attention_impl(self) -> None:
-        if self.matmul_arith not in MATMUL_ARITHS:
-            raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
-        if self.attention_arith not in ATTENTION_ARITHS:
-            raise ValueError(f"attention_arith must be one of {ATTENTION_ARITHS}, got {self.attention_arith!r}")
-        if self.weight_images not in WEIGHT_IMAGES:
-            raise ValueError(f"weight_images must be one of {WEIGHT_IMAGES}, got {self.weight_images!r}")
-        if self.saved_activations not in SAVED_ACTIVATIONS:
-            raise ValueError(f"saved_activations must be one of {SAVED_ACTIVATIONS}, got {self.saved_activations!r}")
-        for name in ("attention_impl", "attention_long_impl", "norm_impl", "ffn_impl", "proj_impl", "matmul_arith",
-                     "attention_arith", "weight_images", "saved_activations"):
+        """Hand the model's stack attributes (modules/t5.py: STACK_ATTRIBUTES), validated, to both stacks."""
+        for name in STACK_ATTRIBUTES:
+            value = checked(self, name)
             for stack in (self.encoder.encoder, self.t5_decoder):
-                setattr(stack, name, getattr(self, name))
+                setattr(stack, name, value)
 
     def hip_embed_active(self, input_ids: Tensor, attention_mask: Optional[Tensor] = None) -> bool:
         """Whether the "hip" input embedding is taken for these ids and this mask (module docstring)."""

@@ -59,50 +59,51 @@ operators run, silently.  The module tree and the state dict are the same on eve
   with the fused one alike, and also needs the stack's attention weights to be fp32 device tensors that are dense and
   16-byte aligned (`hip_proj_active`).
 
-`matmul_arith` = "fp32" (the default) or "bf16" is the arithmetic of the two matrix forms above, wherever the "hip"
-feed-forward or the "hip" projections are taken: under grad (autograd.T5FFNBf16Function / T5ProjBf16Function) and under
-no_grad, in `T5Stack.cross_kv` and in the decode step's call that writes K/V into the cache slabs.  "bf16" rounds every
-operand of a matrix product to bf16 and accumulates in fp32 (include/rqhip.h); weights, activations, gradients and
-the state dict stay fp32.  With the "torch" bodies it has no effect: the operators stay fp32, and so do the attention
-itself, the norms and the glue.
+Three more attributes say which FORM (ops.T5MatmulForm) the two matrix bodies above take.  `matmul_forms` states the
+rule, once: a body that is not taken has no form, so on the "torch" bodies and on host tensors none of the three has an
+effect; a stack forward (and a `cross_kv` call from outside one) resolves its forms ONCE, before its first body
+(`T5Stack.matmul_plan`), and every feed-forward body and grouped projection call of that forward -- the one autograd
+Function under grad, the one ops call under no_grad, `cross_kv` and the decode step's call that writes K/V into the cache
+slabs included -- reads them.  They are attributes of the model or the stack, set by the caller: train_decoder.train
+sets the first (amp with mixed_precision_type = "bf16") and has no parameter for the other two.
 
-`weight_images` = "none" (the default) or "bf16" (WEIGHT_IMAGES) is where the "bf16" matrix forms get their weights.
-With "bf16" every call that already takes a "hip" body in `matmul_arith` = "bf16" reads bf16 IMAGES of its weights
-(csrc/t5_images.hip; rqhip_t5_ffn_*_bf16w / rqhip_t5_proj_*_bf16w): copies that hold the very roundings the bf16 kernels
-form in registers, in both orientations, so that forward and backward load a weight fragment as 16 bytes along a row
-and convert nothing.  Every result keeps the bits of `weight_images` = "none".  Everywhere else -- the "fp32"
-arithmetic, the "torch" bodies, host tensors -- the attribute has no effect, like `matmul_arith` on the operator bodies.
-Each stack owns a T5WeightImages holder (`stack.images`, a plain attribute: no parameter, no buffer, nothing in the
-state dict): one bf16 arena with the images and transposed images of its blocks' wi, wo, q, k, v and o (a decoder's
-cross-attention weights included), the device job table of their one refresh launch, and a `refreshes` counter.  A
-stack forward (and a `cross_kv` call from outside one) compares the holder's KEY -- (data_ptr, _version) of every weight
-and rqhip.optim.generation(), which every FlatAdamW.step() bumps because its kernel writes parameters without touching
-`_version` -- and, if it differs, refreshes all images with ONE launch before its first body; the same weights again
-cost no launch, and a refresh draws no random numbers.  `.to()` and `load_state_dict` drop the holder's contents.  A
-weight written behind the key's back (through a raw pointer by other code than FlatAdamW, or in place through
-`param.data`, which has a version counter of its own) needs `stack.images.invalidate()`.  Under graph capture every
-forward refreshes, since a replay cannot compare keys.  It is an attribute of the model or the stack, set by the
-caller: train_decoder.train has no parameter for it.  Measurements: profiles/t5_weight_images.txt.
+- `matmul_arith` = "fp32" (the default) or "bf16" is the arithmetic.  "bf16" rounds every operand of a matrix product to
+  bf16 and accumulates in fp32 (include/rqhip.h); weights, activations, gradients and the state dict stay fp32, and so do
+  the attention itself, the norms and the glue.  "fp32" ignores the other two attributes.
+- `weight_images` = "none" (the default) or "bf16" (WEIGHT_IMAGES) is where the "bf16" forms get their weights.  With
+  "bf16" they read bf16 IMAGES of their weights (csrc/t5_images.hip; rqhip_t5_ffn_*_bf16w / rqhip_t5_proj_*_bf16w): copies
+  that hold the very roundings the bf16 kernels form in registers, in both orientations, so that forward and backward
+  load a weight fragment as 16 bytes along a row and convert nothing.  Every result keeps the bits of "none".
+  Each stack owns a T5WeightImages holder (`stack.images`, a plain attribute: no parameter, no buffer, nothing in the
+  state dict): one bf16 arena with the images and transposed images of its blocks' wi, wo, q, k, v and o (a decoder's
+  cross-attention weights included), the device job table of their one refresh launch, and a `refreshes` counter.
+  Resolving the forms compares the holder's KEY -- (data_ptr, _version) of every weight and rqhip.optim.generation(),
+  which every FlatAdamW.step() bumps because its kernel writes parameters without touching `_version` -- and, if it
+  differs, refreshes all images with ONE launch; the same weights again cost no launch, and a refresh draws no random
+  numbers.  `.to()` and `load_state_dict` drop the holder's contents.  A weight written behind the key's back (through a
+  raw pointer by other code than FlatAdamW, or in place through `param.data`, which has a version counter of its own)
+  needs `stack.images.invalidate()`.  Under graph capture every forward refreshes, since a replay cannot compare keys.
+  Measurements: profiles/t5_weight_images.txt.
+- `saved_activations` = "fp32" (the default) or "bf16" (SAVED_ACTIVATIONS) is what the "bf16" feed-forward keeps between
+  its forward and its backward -- the feed-forward alone, and only under grad (rqhip_t5_ffn_*_bf16a / _bf16wa), with
+  `weight_images` "none" and "bf16" alike.  With "bf16" the forward saves blocked bf16 images of dropout(relu(wi(x))) and
+  of x in place of the fp32 ReLU output and the fp32 x -- 64 * ceil(rows / 32) * (d_model + d_ff) bytes per body against
+  4 * rows * (d_model + d_ff) -- and no seed; the backward's active set is the image's sign, its weight-gradient kernel
+  loads 16-byte bf16 fragments and neither backward kernel hashes a dropout decision.  The images hold the very operands
+  the "bf16" arithmetic rounds in registers, so the loss and every gradient keep the bits of "fp32" (include/rqhip.h
+  names the one difference, an activation below 2^-134).  Measured on an MI355X beside `weight_images` = "bf16" in
+  alternating runs (profiles/t5_saved_activations.txt): at batch 640 a training step goes from 35.5 to 32.2 ms and, with
+  the grouped projections, from 32.7 to 29.2 ms, beyond the runs' spreads, at 0.88 of the peak memory (4858 -> 4283 MiB);
+  the weight-gradient kernel takes 0.28 of its twin's device time and the two row kernels 0.96 to 1.05 of theirs; at
+  batch 64 no step-time difference could be measured (9.5 against 9.3 and 8.6 against 8.0 ms inside block spreads of 1.9
+  to 3.7 ms).
 
-`saved_activations` = "fp32" (the default) or "bf16" (SAVED_ACTIVATIONS) is what the "bf16" feed-forward keeps between
-its forward and its backward.  It acts only where the "hip" feed-forward runs under grad with `matmul_arith` = "bf16"
-(autograd.T5FFNBf16SavedFunction; rqhip_t5_ffn_*_bf16a / _bf16wa), with `weight_images` "none" and "bf16" alike: the
-forward then saves blocked bf16 images of dropout(relu(wi(x))) and of x in place of the fp32 ReLU output and the fp32
-x -- 64 * ceil(rows / 32) * (d_model + d_ff) bytes per body against 4 * rows * (d_model + d_ff) -- and no seed; the
-backward's active set is the image's sign, its weight-gradient kernel loads 16-byte bf16 fragments and neither backward
-kernel hashes a dropout decision.  The images hold the very operands the "bf16" arithmetic rounds in registers, so the
-loss and every gradient keep the bits of "fp32" (include/rqhip.h names the one difference, an activation below
-2^-134).  Everywhere else -- under no_grad, the "fp32" arithmetic, the "torch" body, host tensors -- the attribute has
-no effect, like `weight_images` on the operator bodies.  It is an attribute of the model or the stack, set by the caller:
-train_decoder.train has no parameter for it.  Measured on an MI355X beside `weight_images` = "bf16" in alternating runs
-(profiles/t5_saved_activations.txt): at batch 640 a training step goes from 35.5 to 32.2 ms and, with the grouped
-projections, from 32.7 to 29.2 ms, beyond the runs' spreads, at 0.88 of the peak memory (4858 -> 4283 MiB); the
-weight-gradient kernel takes 0.28 of its twin's device time and the two row kernels 0.96 to 1.05 of theirs; at batch 64
-no step-time difference could be measured (9.5 against 9.3 and 8.6 against 8.0 ms inside block spreads of 1.9 to 3.7 ms).
+Each of the nine attributes is validated against STACK_ATTRIBUTES at the top of every forward and `cross_kv` call, on
+every path, whether or not that path consults it.
 
 `attention_arith` = "fp32" (the default) or "bf16" is the arithmetic of the LONG attention calls alone, wherever
 `attention_long_impl` = "hip" takes one: the inference launch (ops.t5_attention_long, `generate`'s cross-attention
-included), and under grad the forward and backward of autograd.T5AttentionLongBf16Function.  "bf16" rounds q, k, v,
+included), and under grad the forward and backward of autograd.T5AttentionLongFunction.  "bf16" rounds q, k, v,
 d_out, the unnormalised weights and dS to bf16 as matrix operands and keeps the softmax, its sums and every stored
 tensor fp32 (include/rqhip.h, rqhip_t5_attention_long_*_bf16).  The short kernel (up to 256 tokens), and with it the
 cached decode step, stays fp32; `matmul_arith` does not touch the attention and this attribute does not touch the matrix
@@ -118,7 +119,7 @@ With the "hip" glue a stack forward draws once before its first body, one seed p
 fused feed-forward; with the operator glue each fused feed-forward draws its own, immediately before its sub-layer.
 """
 import math
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -126,9 +127,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops, optim
-from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5FFNBf16Function, T5FFNBf16ImagesFunction,
-                            T5FFNBf16SavedFunction, T5FFNFunction, T5ProjBf16Function, T5ProjBf16ImagesFunction, T5ProjFunction,
-                            t5_attention_long_function)
+from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5AttentionLongFunction, T5FFNFunction,
+                            T5ProjFunction)
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
@@ -140,7 +140,34 @@ MATMUL_ARITHS = ops.T5_ARITHS  # ("fp32", "bf16")
 ATTENTION_ARITHS = ops.T5_ARITHS  # of the long attention calls
 WEIGHT_IMAGES = ("none", "bf16")  # where the "bf16" matrix forms read their weights: as stored, or from bf16 images
 SAVED_ACTIVATIONS = ops.T5_SAVED  # ("fp32", "bf16"): what the "bf16" feed-forward saves for its backward
+# the attributes of a T5Stack that choose its bodies (the model hands its own to both stacks), and what each may be
+STACK_ATTRIBUTES = {"attention_impl": ATTENTION_IMPLS, "attention_long_impl": ATTENTION_LONG_IMPLS,
+                    "norm_impl": NORM_IMPLS, "ffn_impl": FFN_IMPLS, "proj_impl": PROJ_IMPLS,
+                    "matmul_arith": MATMUL_ARITHS, "attention_arith": ATTENTION_ARITHS, "weight_images": WEIGHT_IMAGES,
+                    "saved_activations": SAVED_ACTIVATIONS}
 MAX_DELTA_BUCKETS = 64  # delta ranges a T5Attention keeps the integer buckets of
+
+
+def checked(owner, name: str):
+    """The attribute `name` (of STACK_ATTRIBUTES) of a stack or a model, validated."""
+    value, allowed = getattr(owner, name), STACK_ATTRIBUTES[name]
+    if value not in allowed:
+        raise ValueError(f"{name} must be one of {allowed}, got {value!r}")
+    return value
+
+
+def matmul_forms(arith: str, weight_images: str, saved_activations: str, ffn_active: bool, proj_active: bool,
+                 grad_enabled: bool):
+    """The forms (ops.T5MatmulForm) of a forward's "hip" feed-forward bodies and grouped projections, from the three
+    attributes (valid values) and which of the two bodies are taken -> (ffn form, proj form).  A body that is not taken
+    has None.  "fp32" ignores the other two attributes; with "bf16" both bodies read weight images where `weight_images`
+    is "bf16", and the feed-forward -- it alone, and only under grad, where there is a backward to save for -- keeps
+    bf16 saved activations where `saved_activations` is "bf16"."""
+    bf16 = arith == "bf16"
+    images = bf16 and weight_images == "bf16"
+    saved = bf16 and saved_activations == "bf16" and grad_enabled
+    return (ops.T5MatmulForm(arith, images, saved) if ffn_active else None,
+            ops.T5MatmulForm(arith, images, False) if proj_active else None)
 
 
 class T5Config:
@@ -290,24 +317,26 @@ class T5WeightImages:
         return self.pairs[id(weight)]
 
 
-def _project(fused, x: Tensor, linears, outs=None) -> Tuple[Tensor, ...]:
-    """The bias-free Linears `linears` of the same x -> their outputs: the operators one by one, or `fused` ONE call
-    for the group (T5ProjFunction under grad, ops.t5_proj_fwd under no_grad, which writes into `outs` where given).
-    fused: False, or what T5Stack.proj_arm returns: True for the "fp32" arithmetic, "bf16" for that one, the stack's
-    T5WeightImages for the "bf16" arithmetic reading the images (the same bits)."""
-    if not fused:
+class MatmulPlan(NamedTuple):
+    """What one stack forward resolved about its matrix bodies (T5Stack.matmul_plan): `matmul_forms`' pair and, where
+    either form reads weight images, the stack's holder with current images."""
+    ffn: Optional[ops.T5MatmulForm] = None
+    proj: Optional[ops.T5MatmulForm] = None
+    images: Optional[T5WeightImages] = None
+
+
+def _project(plan: MatmulPlan, x: Tensor, linears, outs=None) -> Tuple[Tensor, ...]:
+    """The bias-free Linears `linears` of the same x -> their outputs: the operators one by one where the plan has no
+    proj form, else ONE call for the group in that form (T5ProjFunction under grad, ops.t5_proj_fwd under no_grad, which
+    writes into `outs` where given)."""
+    form = plan.proj
+    if form is None:
         return tuple(lin(x) for lin in linears)
     weights = [lin.weight for lin in linears]
-    if isinstance(fused, T5WeightImages):
-        pairs = [fused.of(w) for w in weights]
-        if torch.is_grad_enabled():
-            return T5ProjBf16ImagesFunction.apply(x, len(weights), *weights, *[p[0] for p in pairs],
-                                                  *[p[1] for p in pairs])
-        return ops.t5_proj_fwd(x, weights, outs, arith="bf16", w_images=[p[0] for p in pairs])
-    bf16 = fused == "bf16"
+    imgs, imgs_t = zip(*[plan.images.of(w) for w in weights]) if form.images else ((), ())
     if torch.is_grad_enabled():
-        return (T5ProjBf16Function if bf16 else T5ProjFunction).apply(x, *weights)
-    return ops.t5_proj_fwd(x, weights, outs, arith="bf16") if bf16 else ops.t5_proj_fwd(x, weights, outs)
+        return T5ProjFunction.apply(x, form, *weights, *imgs, *imgs_t)
+    return ops.t5_proj_fwd(x, weights, outs, **form.keywords(imgs))
 
 
 def _attend(module: nn.Module, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], mask: Optional[Tensor]) -> Tensor:
@@ -370,32 +399,31 @@ class T5Attention(nn.Module):
     def _heads(self, x: Tensor) -> Tensor:  # [R, T, inner] -> [R, heads, T, d_kv]
         return x.view(x.shape[0], x.shape[1], self.n_heads, self.d_kv).transpose(1, 2)
 
-    def project_kv(self, x: Tensor, fused=False) -> KV:
-        k, v = _project(fused, x, (self.k, self.v))
-        return self._heads(k), self._heads(v)
+    def project_kv(self, x: Tensor) -> KV:
+        return self._heads(self.k(x)), self._heads(self.v(x))
 
     def self_attention(self, x: Tensor, bias: Optional[Tensor], mask: Optional[Tensor], past: Optional[KV],
-                       fused=False) -> Tuple[Tensor, KV]:
-        """fused: the projections as grouped calls (`_project`, which names its values): one for q, k and v, one for o."""
-        q, k, v = (self._heads(t) for t in _project(fused, x, (self.q, self.k, self.v)))
+                       plan: MatmulPlan = MatmulPlan()) -> Tuple[Tensor, KV]:
+        """plan: with a proj form the projections are grouped calls (`_project`): one for q, k and v, one for o."""
+        q, k, v = (self._heads(t) for t in _project(plan, x, (self.q, self.k, self.v)))
         if past is not None:
             k, v = torch.cat([past[0], k], dim=2), torch.cat([past[1], v], dim=2)
         out = _attend(self, q, k, v, bias, mask)
-        return _project(fused, out.transpose(1, 2).reshape(x.shape[0], x.shape[1], -1), (self.o,))[0], (k, v)
+        return _project(plan, out.transpose(1, 2).reshape(x.shape[0], x.shape[1], -1), (self.o,))[0], (k, v)
 
-    def cross_attention(self, x: Tensor, kv: KV, mask: Optional[Tensor], fused=False) -> Tensor:
+    def cross_attention(self, x: Tensor, kv: KV, mask: Optional[Tensor], plan: MatmulPlan = MatmulPlan()) -> Tensor:
         """Queries x [R, T, d] with R = B * beams over keys / values [B, heads, S, d_kv] of B rows."""
         R, T = x.shape[0], x.shape[1]
         B = kv[0].shape[0]
         beams = R // B
-        q = self._heads(_project(fused, x, (self.q,))[0])  # [R, H, T, dk]
+        q = self._heads(_project(plan, x, (self.q,))[0])  # [R, H, T, dk]
         if beams != 1:
             q = q.view(B, beams, self.n_heads, T, self.d_kv).transpose(1, 2).reshape(B, self.n_heads, beams * T,
                                                                                       self.d_kv)
         out = _attend(self, q, kv[0], kv[1], None, mask)
         if beams != 1:
             out = out.view(B, self.n_heads, beams, T, self.d_kv).transpose(1, 2).reshape(R, self.n_heads, T, self.d_kv)
-        return _project(fused, out.transpose(1, 2).reshape(R, T, -1), (self.o,))[0]
+        return _project(plan, out.transpose(1, 2).reshape(R, T, -1), (self.o,))[0]
 
 
 class _OperatorAttention:
@@ -403,8 +431,7 @@ class _OperatorAttention:
 
     def __init__(self, stack: "T5Stack", inputs_embeds: Tensor, attention_mask: Optional[Tensor],
                  encoder_hidden_states: Optional[Tensor], encoder_attention_mask: Optional[Tensor],
-                 past_key_values: Optional[List[KV]], cross_kv: Optional[List[KV]],
-                 images: Optional["T5WeightImages"] = None) -> None:
+                 past_key_values: Optional[List[KV]], cross_kv: Optional[List[KV]], plan: MatmulPlan) -> None:
         T, dtype = inputs_embeds.shape[1], inputs_embeds.dtype
         past = 0 if past_key_values is None else past_key_values[0][0].shape[2]
         keys = past + T
@@ -415,34 +442,33 @@ class _OperatorAttention:
         self.mask = None if keep is None else (~keep).to(dtype) * torch.finfo(dtype).min
         self.bias = stack.block[0].layer[0].SelfAttention.compute_bias(T, keys, past)
         self.past_key_values = past_key_values
-        self.proj = stack.proj_arm(inputs_embeds, images)
+        self.plan = plan
         if stack.is_decoder:
-            self.cross_kv = stack.cross_kv(encoder_hidden_states, images) if cross_kv is None else cross_kv
+            self.cross_kv = stack.cross_kv(encoder_hidden_states, plan) if cross_kv is None else cross_kv
             self.cross_mask = None if encoder_attention_mask is None else additive_mask(encoder_attention_mask, dtype)
 
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
         return module.self_attention(normed, self.bias, self.mask,
-                                     None if self.past_key_values is None else self.past_key_values[i], self.proj)
+                                     None if self.past_key_values is None else self.past_key_values[i], self.plan)
 
     def cross_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tensor:
-        return module.cross_attention(normed, self.cross_kv[i], self.cross_mask, self.proj)
+        return module.cross_attention(normed, self.cross_kv[i], self.cross_mask, self.plan)
 
 
 class _HipAttention:
     """The attention bodies of a stack forward on the "hip" path: the bias table and the byte masks are built once,
     every attention is one launch (`train`: one T5AttentionFunction call, with the attention-weight dropout of train
-    mode in the kernel, from a seed drawn per call).  `proj`: the projections around it as grouped calls (`_project`,
-    T5Stack.proj_arm's value).  The long calls run in the stack's attention_arith."""
+    mode in the kernel, from a seed drawn per call).  `plan`: with a proj form the projections around it are grouped
+    calls (`_project`).  The long calls run in the stack's attention_arith."""
 
     def __init__(self, stack: "T5Stack", T: int, attention_mask: Optional[Tensor],
                  encoder_attention_mask: Optional[Tensor], cross_kv: Optional[List[KV]],
-                 cache: Optional[T5DecodeCache], train: bool, proj) -> None:
+                 cache: Optional[T5DecodeCache], train: bool, plan: MatmulPlan) -> None:
         self.train = train
-        self.proj = proj
-        self.long = stack.long_attention()  # calls the short kernel does not support go to the long one
-        arith = stack.attention_arithmetic()
-        self.long_kw = {} if arith == "fp32" else {"arith": arith}  # the keyword only off the default
-        self.long_function = t5_attention_long_function(arith)
+        self.plan = plan
+        self.long = stack.attention_long_impl == "hip"  # calls the short kernel does not support go to the long one
+        self.long_arith = stack.attention_arith
+        self.long_kw = {} if self.long_arith == "fp32" else {"arith": self.long_arith}  # the keyword only off the default
         self.p = float(stack.config.dropout_rate) if train and stack.training else 0.0
         self.cache = cache
         self.past = 0 if cache is None else cache.pos
@@ -457,9 +483,8 @@ class _HipAttention:
         long = self.long and not ops.t5_attention_supported(q.dtype, module.d_kv, module.n_heads, q.shape[1],
                                                             k.shape[1])
         if self.train:
-            function = self.long_function if long else T5AttentionFunction
-            return function.apply(q, k, v, table, module.n_heads, offset, key_mask, causal, self.p,
-                                  _draw_seed(self.p, q.device))
+            call = (q, k, v, table, module.n_heads, offset, key_mask, causal, self.p, _draw_seed(self.p, q.device))
+            return T5AttentionLongFunction.apply(*call, self.long_arith) if long else T5AttentionFunction.apply(*call)
         if long:
             return ops.t5_attention_long(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset,
                                          key_mask=key_mask, causal=causal, **self.long_kw)
@@ -469,13 +494,13 @@ class _HipAttention:
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
         """One launch; with a decode cache the K/V projections go straight into block i's slabs."""
         if self.cache is None:
-            q, k, v = _project(self.proj, normed, (module.q, module.k, module.v))
+            q, k, v = _project(self.plan, normed, (module.q, module.k, module.v))
             out = self._launch(module, q, k, v, self.table, self.offset, self.key_mask, self.causal)
-            return _project(self.proj, out, (module.o,))[0], (module._heads(k), module._heads(v))
+            return _project(self.plan, out, (module.o,))[0], (module._heads(k), module._heads(v))
         R = normed.shape[0]
         ks, vs = self.cache.slabs[i]
-        if self.proj:  # q into a new tensor, k and v into this position of the slabs: one launch
-            q = _project(self.proj, normed, (module.q, module.k, module.v),
+        if self.plan.proj:  # q into a new tensor, k and v into this position of the slabs: one launch
+            q = _project(self.plan, normed, (module.q, module.k, module.v),
                          [None, ks[self.past, :R], vs[self.past, :R]])[0]
         else:
             q = module.q(normed)
@@ -484,14 +509,14 @@ class _HipAttention:
             torch.mm(x2, module.v.weight.t(), out=vs[self.past, :R])
         out = ops.t5_attention(q, ks, vs, module.n_heads, bias_by_delta=self.table, bias_offset=self.offset,
                                past=self.past, anc=self.cache.anc[:R])
-        return _project(self.proj, out, (module.o,))[0], (ks, vs)
+        return _project(self.plan, out, (module.o,))[0], (ks, vs)
 
     def cross_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tensor:
         """One launch: the beams of a user are the query rows of one K/V group."""
         # a view of the Linear's output
         k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in self.cross_kv[i])
-        q = _project(self.proj, normed, (module.q,))[0]
-        return _project(self.proj, self._launch(module, q, k, v, None, 0, self.cross_mask, False), (module.o,))[0]
+        q = _project(self.plan, normed, (module.q,))[0]
+        return _project(self.plan, self._launch(module, q, k, v, None, 0, self.cross_mask, False), (module.o,))[0]
 
 
 class T5LayerSelfAttention(nn.Module):
@@ -522,28 +547,14 @@ class T5DenseReluDense(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         return self.wo(self.dropout(F.relu(self.wi(x))))
 
-    def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor], arith: str = "fp32",
-                    images: Optional[T5WeightImages] = None, saved: str = "fp32") -> Tensor:
-        """forward as one fused call (the "hip" feed-forward body), its dropout at rate p from `seed`, in the
-        arithmetic `arith` (MATMUL_ARITHS); `images` (with "bf16"): the weights are read from their bf16 images;
-        `saved` (SAVED_ACTIVATIONS; acts with "bf16" under grad): what the call keeps for its backward."""
-        bf16 = arith == "bf16"
-        act = bf16 and saved == "bf16" and torch.is_grad_enabled()
-        if bf16 and images is not None:
-            (wi16, wi16t), (wo16, wo16t) = images.of(self.wi.weight), images.of(self.wo.weight)
-            if act:
-                return T5FFNBf16SavedFunction.apply(x, self.wi.weight, self.wo.weight, p, seed, wi16, wo16, wi16t, wo16t)
-            if torch.is_grad_enabled():
-                return T5FFNBf16ImagesFunction.apply(x, self.wi.weight, self.wo.weight, p, seed, wi16, wo16, wi16t,
-                                                     wo16t)
-            return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False, arith=arith,
-                                  w_images=(wi16, wo16))[0]
-        if act:
-            return T5FFNBf16SavedFunction.apply(x, self.wi.weight, self.wo.weight, p, seed)
+    def forward_hip(self, x: Tensor, p: float, seed: Optional[Tensor], plan: MatmulPlan) -> Tensor:
+        """forward as one fused call (the "hip" feed-forward body) in the plan's ffn form, its dropout at rate p from
+        `seed`: T5FFNFunction under grad, ops.t5_ffn_fwd without the tensors a backward would need under no_grad."""
+        form, wi, wo = plan.ffn, self.wi.weight, self.wo.weight
+        (wi16, wi16t), (wo16, wo16t) = (plan.images.of(wi), plan.images.of(wo)) if form.images else ((None, None),) * 2
         if torch.is_grad_enabled():
-            return (T5FFNBf16Function if bf16 else T5FFNFunction).apply(x, self.wi.weight, self.wo.weight, p, seed)
-        kw = {"arith": arith} if bf16 else {}
-        return ops.t5_ffn_fwd(x, self.wi.weight, self.wo.weight, p, seed, need_h=False, **kw)[0]
+            return T5FFNFunction.apply(x, wi, wo, p, seed, form, wi16, wo16, wi16t, wo16t)
+        return ops.t5_ffn_fwd(x, wi, wo, p, seed, need_h=False, **form.keywords((wi16, wo16)))[0]
 
 
 class T5LayerFF(nn.Module):
@@ -609,53 +620,48 @@ class T5Stack(nn.Module):
                 weights += [dense.wi.weight, dense.wo.weight]
         return weights
 
+    def validate(self) -> None:
+        """Every attribute of STACK_ATTRIBUTES is one of its values, or ValueError."""
+        for name in STACK_ATTRIBUTES:
+            checked(self, name)
+
+    # one attribute each, validated
+    def arith(self) -> str:
+        return checked(self, "matmul_arith")
+
+    def attention_arithmetic(self) -> str:
+        return checked(self, "attention_arith")
+
     def weight_images_mode(self) -> str:
-        """weight_images, validated."""
-        if self.weight_images not in WEIGHT_IMAGES:
-            raise ValueError(f"weight_images must be one of {WEIGHT_IMAGES}, got {self.weight_images!r}")
-        return self.weight_images
+        return checked(self, "weight_images")
 
     def saved_activations_mode(self) -> str:
-        """saved_activations, validated."""
-        if self.saved_activations not in SAVED_ACTIVATIONS:
-            raise ValueError(f"saved_activations must be one of {SAVED_ACTIVATIONS}, got {self.saved_activations!r}")
-        return self.saved_activations
+        return checked(self, "saved_activations")
 
-    def current_images(self, x: Tensor) -> Optional[T5WeightImages]:
-        """The holder with current images for a forward of x, refreshed by one launch if its key differs, or None where
-        weight_images does not act: off "bf16" in both attributes, or no "hip" matrix body is taken for x."""
-        if self.weight_images_mode() != "bf16" or self.arith() != "bf16":
-            return None
-        ffn, proj = self.hip_ffn_active(x), self.hip_proj_active(x)
-        if not (ffn or proj):
-            return None
-        return self.images.ensure(self.image_weights(ffn, proj))
+    def matmul_plan(self, x: Tensor) -> MatmulPlan:
+        """What a forward of x does about its matrix bodies, resolved once: `matmul_forms` of the (valid) attributes and
+        of which "hip" bodies x takes, and where a form reads weight images the holder, refreshed here by one launch if
+        its key differs."""
+        ffn, proj = matmul_forms(self.matmul_arith, self.weight_images, self.saved_activations, self.hip_ffn_active(x),
+                                 self.hip_proj_active(x), torch.is_grad_enabled())
+        reads_images = any(form is not None and form.images for form in (ffn, proj))
+        images = self.images.ensure(self.image_weights(ffn is not None, proj is not None)) if reads_images else None
+        return MatmulPlan(ffn, proj, images)
 
-    def cross_kv(self, encoder_hidden_states: Tensor, images: Optional[T5WeightImages] = None) -> List[KV]:
+    def cross_kv(self, encoder_hidden_states: Tensor, plan: Optional[MatmulPlan] = None) -> List[KV]:
         """Cross-attention K/V of every block, computed once per encoder output (proj_impl = "hip": by one grouped
-        call for all blocks, one per four blocks beyond that).  images: the forward's current holder; a call from
-        outside a forward checks the holder itself."""
-        fused = self.proj_arm(encoder_hidden_states, images or self.current_images(encoder_hidden_states))
+        call for all blocks, one per four blocks beyond that).  plan: the forward's; a call from outside a forward
+        validates the attributes and resolves its own."""
+        if plan is None:
+            self.validate()
+            plan = self.matmul_plan(encoder_hidden_states)
         atts = [blk.layer[1].EncDecAttention for blk in self.block]
-        if not fused:
+        if plan.proj is None:
             return [att.project_kv(encoder_hidden_states) for att in atts]
         linears = [lin for att in atts for lin in (att.k, att.v)]
         outs = [y for s in range(0, len(linears), ops.T5_PROJ_MAX_GROUP)
-                for y in _project(fused, encoder_hidden_states, linears[s:s + ops.T5_PROJ_MAX_GROUP])]
+                for y in _project(plan, encoder_hidden_states, linears[s:s + ops.T5_PROJ_MAX_GROUP])]
         return [(att._heads(outs[2 * i]), att._heads(outs[2 * i + 1])) for i, att in enumerate(atts)]
-
-    def long_attention(self) -> bool:
-        """attention_long_impl == "hip", validated."""
-        if self.attention_long_impl not in ATTENTION_LONG_IMPLS:
-            raise ValueError(f"attention_long_impl must be one of {ATTENTION_LONG_IMPLS}, got "
-                             f"{self.attention_long_impl!r}")
-        return self.attention_long_impl == "hip"
-
-    def attention_arithmetic(self) -> str:
-        """attention_arith, validated."""
-        if self.attention_arith not in ATTENTION_ARITHS:
-            raise ValueError(f"attention_arith must be one of {ATTENTION_ARITHS}, got {self.attention_arith!r}")
-        return self.attention_arith
 
     def _call_supported(self, short, dtype, query_length: int, key_length: int, long: bool) -> bool:
         """Whether one attention call has a kernel: the existing one (`short`: its support table), else, with `long`,
@@ -668,10 +674,8 @@ class T5Stack(nn.Module):
                              cross_length: Optional[int] = None, cached: bool = False) -> bool:
         """Whether a forward of x with these lengths takes the "hip" path (module docstring).  `cached`: the
         self-attention reads a decode cache, which only the existing kernel does."""
-        if self.attention_impl not in ATTENTION_IMPLS:
-            raise ValueError(f"attention_impl must be one of {ATTENTION_IMPLS}, got {self.attention_impl!r}")
-        long = self.long_attention()
-        if self.attention_impl not in ("hip", "hip_train") or not x.is_cuda or torch.is_grad_enabled():
+        long = checked(self, "attention_long_impl") == "hip"
+        if checked(self, "attention_impl") not in ("hip", "hip_train") or not x.is_cuda or torch.is_grad_enabled():
             return False
         if self.training and self.config.dropout_rate > 0:
             return False
@@ -682,7 +686,7 @@ class T5Stack(nn.Module):
 
     def hip_train_active(self, x: Tensor, query_length: int, cross_kv: Optional[List[KV]]) -> bool:
         """Whether a forward of x under grad takes the "hip_train" path (module docstring)."""
-        long = self.long_attention()
+        long = checked(self, "attention_long_impl") == "hip"
         if self.attention_impl != "hip_train" or not x.is_cuda or not torch.is_grad_enabled():
             return False
         ok = self._call_supported(ops.t5_attention_bwd_supported, x.dtype, query_length, query_length, long)
@@ -694,22 +698,16 @@ class T5Stack(nn.Module):
 
     def hip_norm_active(self, x: Tensor) -> bool:
         """Whether a forward of x takes the "hip" norm path (module docstring)."""
-        if self.norm_impl not in NORM_IMPLS:
-            raise ValueError(f"norm_impl must be one of {NORM_IMPLS}, got {self.norm_impl!r}")
-        return self.norm_impl == "hip" and x.is_cuda and ops.t5_add_norm_supported(x.dtype, self.config.d_model)
+        return checked(self, "norm_impl") == "hip" and x.is_cuda and ops.t5_add_norm_supported(x.dtype, self.config.d_model)
 
     def hip_ffn_active(self, x: Tensor) -> bool:
         """Whether a forward of x takes the "hip" feed-forward path (module docstring)."""
-        if self.ffn_impl not in FFN_IMPLS:
-            raise ValueError(f"ffn_impl must be one of {FFN_IMPLS}, got {self.ffn_impl!r}")
-        return (self.ffn_impl == "hip" and x.is_cuda
+        return (checked(self, "ffn_impl") == "hip" and x.is_cuda
                 and ops.t5_ffn_supported(x.dtype, self.config.d_model, self.config.d_ff))
 
     def hip_proj_active(self, x: Tensor) -> bool:
         """Whether the attention projections of a forward of x are grouped "hip" calls (module docstring)."""
-        if self.proj_impl not in PROJ_IMPLS:
-            raise ValueError(f"proj_impl must be one of {PROJ_IMPLS}, got {self.proj_impl!r}")
-        if self.proj_impl != "hip" or not x.is_cuda:
+        if checked(self, "proj_impl") != "hip" or not x.is_cuda:
             return False
         cfg = self.config
         inner = cfg.num_heads * cfg.d_kv
@@ -722,38 +720,20 @@ class T5Stack(nn.Module):
         return all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.data_ptr() % 16 == 0
                    for w in weights)
 
-    def arith(self) -> str:
-        """matmul_arith, validated."""
-        if self.matmul_arith not in MATMUL_ARITHS:
-            raise ValueError(f"matmul_arith must be one of {MATMUL_ARITHS}, got {self.matmul_arith!r}")
-        return self.matmul_arith
-
-    def proj_arm(self, x: Tensor, images: Optional[T5WeightImages] = None):
-        """hip_proj_active(x) with the arithmetic of the grouped calls: False, True ("fp32"), "bf16", or -- "bf16" with
-        the current holder of `current_images` -- that holder (`_project`)."""
-        arith = self.arith()
-        if not self.hip_proj_active(x):
-            return False
-        if arith == "bf16":
-            return images if images is not None else "bf16"
-        return True
-
     def new_decode_cache(self, steps: int, rows: int, device) -> T5DecodeCache:
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
     def _attention_body(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                        past_key_values, cross_kv, decode_cache, images=None):
+                        past_key_values, cross_kv, decode_cache, plan: MatmulPlan):
         """The attention body of this forward (module docstring): _HipAttention where it applies, else the operators."""
         R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        self.long_attention()  # an unknown attention_long_impl raises on every path
-        self.attention_arithmetic()  # and so does an unknown attention_arith
         if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
             if self.is_decoder and cross_kv is None:
-                cross_kv = self.cross_kv(encoder_hidden_states, images)
+                cross_kv = self.cross_kv(encoder_hidden_states, plan)
             past = 0 if decode_cache is None else decode_cache.pos
             if decode_cache is None and self.hip_train_active(inputs_embeds, T, cross_kv):
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, None, train=True,
-                                     proj=self.proj_arm(inputs_embeds, images))
+                                     plan=plan)
             cross_length = cross_kv[0][0].shape[2] if self.is_decoder else None
             if self.hip_attention_active(inputs_embeds, T, past + T, cross_length, cached=decode_cache is not None):
                 if decode_cache is not None and (T != 1 or past_key_values is not None or attention_mask is not None
@@ -761,11 +741,11 @@ class T5Stack(nn.Module):
                     raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
                                      "past_key_values or attention_mask")
                 return _HipAttention(self, T, attention_mask, encoder_attention_mask, cross_kv, decode_cache,
-                                     train=False, proj=self.proj_arm(inputs_embeds, images))
+                                     train=False, plan=plan)
             if decode_cache is not None:
                 raise ValueError('decode_cache belongs to the "hip" attention path, which is not active here')
         return _OperatorAttention(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                                  past_key_values, cross_kv, images)
+                                  past_key_values, cross_kv, plan)
 
     def _glue(self, layers, fused: bool, p: float, seeds: _Seeds):
         """glue(k, x, y) -> (x + dropout_k(y), norm_k of that sum): what lies between body k - 1 and body k of a
@@ -794,13 +774,12 @@ class T5Stack(nn.Module):
         [B, S] keep-mask of the encoder output (B rows, R = B * beams).  Returns the hidden states, and with use_cache
         the per-block self-attention (K, V) including these T positions.  decode_cache ("hip" path, T = 1) holds the
         self-attention history instead of past_key_values: this position's K/V are written into it."""
-        images = self.current_images(inputs_embeds)  # refreshed here, before the first body, if their key differs
+        self.validate()
+        plan = self.matmul_plan(inputs_embeds)  # the images are refreshed here, before the first body
         attention = self._attention_body(inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                                         past_key_values, cross_kv, decode_cache, images)
+                                         past_key_values, cross_kv, decode_cache, plan)
         fused_glue = self.hip_norm_active(inputs_embeds)
-        fused_ffn = self.hip_ffn_active(inputs_embeds)
-        arith = self.arith()
-        saved = self.saved_activations_mode()
+        fused_ffn = plan.ffn is not None
         p = float(self.config.dropout_rate) if self.training else 0.0
         layers = [layer for blk in self.block for layer in blk.layer]
         seeds = _Seeds(p, inputs_embeds.device, len(layers) + 1 if fused_glue else 0,
@@ -820,7 +799,7 @@ class T5Stack(nn.Module):
                 x, normed = glue(k, x, attention.cross_attention(i, blk.layer[1].EncDecAttention, normed))
             dense = blk.layer[-1].DenseReluDense
             k += 1
-            body = dense.forward_hip(normed, p, seeds.ffn(i), arith, images, saved) if fused_ffn else dense(normed)
+            body = dense.forward_hip(normed, p, seeds.ffn(i), plan) if fused_ffn else dense(normed)
             x, normed = glue(k, x, body)
         return (normed, new_kv) if use_cache else normed
 

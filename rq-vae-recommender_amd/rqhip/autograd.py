@@ -297,54 +297,32 @@ class T5AttentionFunction(torch.autograd.Function):
         return dq, dk, dv, dtable, None, None, None, None, None, None
 
 
-def _arith_kw(ctx) -> dict:
-    """The `arith` keyword of the ops calls of ctx's Function: none for "fp32", the ops' default."""
-    arith = ctx._forward_cls.arith
-    return {} if arith == "fp32" else {"arith": arith}
-
-
 class T5AttentionLongFunction(torch.autograd.Function):
     """T5AttentionFunction for the lengths beyond its kernel (ops.t5_attention_long_fwd_train / ops.t5_attention_long_bwd,
-    up to 2048 tokens): the same arguments and gradients.  Saved: q, k, v, out, the row log-sum-exp, each row's (max, sum)
-    pair, the table, the mask and the seed; the weights and the dropout decisions are recomputed chunk by chunk.  `arith`
-    is the class's arithmetic (ops.T5_ARITHS), forward and backward alike, so the (m, l) pair a forward saves is read by
-    the backward of its own arithmetic only: this class is the "fp32" arm, T5AttentionLongBf16Function the "bf16" one;
-    t5_attention_long_function(arith) picks."""
-
-    arith = "fp32"
+    up to 2048 tokens): the same arguments and gradients, and a trailing `arith` (ops.T5_ARITHS), the arithmetic of
+    forward and backward alike: the (m, l) pair a forward saves is read by the backward of its own arithmetic only.
+    Saved: q, k, v, out, the row log-sum-exp, each row's (max, sum) pair, the table, the mask and the seed, all float32
+    in both arithmetics; the weights and the dropout decisions are recomputed chunk by chunk."""
 
     @staticmethod
     def forward(ctx, q: Tensor, k: Tensor, v: Tensor, bias_by_delta: Optional[Tensor], n_heads: int, bias_offset: int,
-                key_mask: Optional[Tensor], causal: bool, p: float, seed: Optional[Tensor]):
+                key_mask: Optional[Tensor], causal: bool, p: float, seed: Optional[Tensor], arith: str = "fp32"):
+        arith_kw = {} if arith == "fp32" else {"arith": arith}      # the keyword only off the ops' default
         out, lse, ml = ops.t5_attention_long_fwd_train(q, k, v, n_heads, bias_by_delta=bias_by_delta,
                                                        bias_offset=bias_offset, key_mask=key_mask, causal=causal, p=p,
-                                                       seed=seed, **_arith_kw(ctx))
+                                                       seed=seed, **arith_kw)
         ctx.save_for_backward(q, k, v, out, lse, ml, bias_by_delta, key_mask, seed)
-        ctx.call = (n_heads, bias_offset, causal, p)
+        ctx.call = (n_heads, bias_offset, causal, p, arith_kw)
         return out
 
     @staticmethod
     def backward(ctx, d_out: Tensor):
         q, k, v, out, lse, ml, table, mask, seed = ctx.saved_tensors
-        n_heads, bias_offset, causal, p = ctx.call
+        n_heads, bias_offset, causal, p, arith_kw = ctx.call
         dq, dk, dv, dtable = ops.t5_attention_long_bwd(q, k, v, out, lse, ml, d_out, n_heads, bias_by_delta=table,
                                                        bias_offset=bias_offset, key_mask=mask, causal=causal, p=p,
-                                                       seed=seed, **_arith_kw(ctx))
-        return dq, dk, dv, dtable, None, None, None, None, None, None
-
-
-class T5AttentionLongBf16Function(T5AttentionLongFunction):
-    """T5AttentionLongFunction in the "bf16" arithmetic (rqhip_t5_attention_long_*_bf16): the same saved tensors, all
-    float32."""
-
-    arith = "bf16"
-
-
-def t5_attention_long_function(arith: str = "fp32"):
-    """The long-attention Function of an arithmetic."""
-    if arith not in ops.T5_ARITHS:
-        raise ops.RqHipError(f"t5_attention_long_function: arith must be one of {ops.T5_ARITHS}, got {arith!r}")
-    return T5AttentionLongBf16Function if arith == "bf16" else T5AttentionLongFunction
+                                                       seed=seed, **arith_kw)
+        return dq, dk, dv, dtable, None, None, None, None, None, None, None
 
 
 class T5AddNormFunction(torch.autograd.Function):
@@ -376,172 +354,71 @@ class T5AddNormFunction(torch.autograd.Function):
 
 class T5FFNFunction(torch.autograd.Function):
     """The T5 feed-forward body (modules/t5.py, ffn_impl = "hip") as one launch forward and at most two backward
-    (ops.t5_ffn_fwd / ops.t5_ffn_bwd): apply(x, wi, wo, p, seed) -> y = dropout(relu(x @ wi.T), p) @ wo.T.  Saved: x, the
-    ReLU output h, the two weights and the seed; the dropout decisions are recomputed.  Gradients: x, wi and wo, each
-    only when needed.  `arith` is the class's arithmetic (ops.T5_ARITHS), forward and backward alike: this class is the
-    "fp32" arm, T5FFNBf16Function the "bf16" one; t5_ffn_function(arith) picks."""
-
-    arith = "fp32"
+    (ops.t5_ffn_fwd / ops.t5_ffn_bwd): apply(x, wi, wo, p, seed, form=ops.T5_FP32, wi16=None, wo16=None, wi16t=None,
+    wo16t=None) -> y = dropout(relu(x @ wi.T), p) @ wo.T, in the arithmetic of `form` (an ops.T5MatmulForm), forward and
+    backward alike; every "bf16" form gives the same y and the same gradients, bit for bit.  Gradients: x, wi and wo,
+    each only when needed.
+    form.images: the forward reads the bf16 weight images wi16 / wo16 (ops.bf16_images) and the backward the transposed
+    pair, non-differentiable inputs that must still hold the forward's weights when the backward runs; the gradients go
+    to the fp32 weights all the same (the weight-gradient kernel reads no weights).
+    Saved: x, the ReLU output h, the two weights and the seed (the dropout decisions are recomputed), with images the
+    transposed pair too.  form.saved: instead of x, h and the seed, the blocked bf16 images hd16 of dropout(relu(x @
+    wi.T)) and x16 of x -- nothing fp32 of the activations' size; the backward's active set is hd16 > 0."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor]):
-        y, h = ops.t5_ffn_fwd(x, wi, wo, p, seed, **_arith_kw(ctx))
-        ctx.save_for_backward(x, h, wi, wo, seed)
-        ctx.p = p
+    def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor],
+                form: ops.T5MatmulForm = ops.T5_FP32, wi16: Optional[Tensor] = None, wo16: Optional[Tensor] = None,
+                wi16t: Optional[Tensor] = None, wo16t: Optional[Tensor] = None):
+        y, h = ops.t5_ffn_fwd(x, wi, wo, p, seed, **form.keywords((wi16, wo16)))
+        kept = (*h, wi, wo) if form.saved else (x, h, wi, wo, seed)
+        ctx.save_for_backward(*kept, *((wi16t, wo16t) if form.images else ()))
+        ctx.p, ctx.form = p, form
         return y
 
     @staticmethod
     def backward(ctx, d_y: Tensor):
-        x, h, wi, wo, seed = ctx.saved_tensors
         need_x, need_wi, need_wo = ctx.needs_input_grad[:3]
         if not (need_x or need_wi or need_wo):
-            return None, None, None, None, None
+            return (None,) * 10
+        form, kept = ctx.form, list(ctx.saved_tensors)
+        kw = form.keywords((kept.pop(-2), kept.pop()) if form.images else None)
+        if form.saved:
+            hd16, x16, wi, wo = kept
+            x, h, seed = None, (hd16, x16), None
+        else:
+            x, h, wi, wo, seed = kept
         d_x, d_wi, d_wo = ops.t5_ffn_bwd(x, wi, wo, h, _dense(d_y), ctx.p, seed, need_x=need_x, need_wi=need_wi,
-                                         need_wo=need_wo, **_arith_kw(ctx))
-        return d_x, d_wi, d_wo, None, None
-
-
-class T5FFNBf16Function(T5FFNFunction):
-    """T5FFNFunction in the "bf16" arithmetic (rqhip_t5_ffn_*_bf16): the same saved tensors, all float32."""
-
-    arith = "bf16"
-
-
-class T5FFNBf16ImagesFunction(torch.autograd.Function):
-    """T5FFNBf16Function reading bf16 weight images (rqhip_t5_ffn_*_bf16w; ops.bf16_images): apply(x, wi, wo, p, seed,
-    wi16, wo16, wi16t, wo16t) -> the same y, bit for bit.  The four images are non-differentiable inputs: the forward
-    reads wi16 / wo16, the backward the transposed pair, and the gradients go to the fp32 weights wi and wo exactly as
-    in T5FFNBf16Function (the weight-gradient kernel reads no weights).  Saved: x, h, the weights (for their shapes), the
-    seed and the transposed images -- which must still hold the forward's weights when the backward runs."""
-
-    arith = "bf16"
-
-    @staticmethod
-    def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor], wi16: Tensor, wo16: Tensor,
-                wi16t: Tensor, wo16t: Tensor):
-        y, h = ops.t5_ffn_fwd(x, wi, wo, p, seed, arith="bf16", w_images=(wi16, wo16))
-        ctx.save_for_backward(x, h, wi, wo, seed, wi16t, wo16t)
-        ctx.p = p
-        return y
-
-    @staticmethod
-    def backward(ctx, d_y: Tensor):
-        x, h, wi, wo, seed, wi16t, wo16t = ctx.saved_tensors
-        need_x, need_wi, need_wo = ctx.needs_input_grad[:3]
-        if not (need_x or need_wi or need_wo):
-            return (None,) * 9
-        d_x, d_wi, d_wo = ops.t5_ffn_bwd(x, wi, wo, h, _dense(d_y), ctx.p, seed, need_x=need_x, need_wi=need_wi,
-                                         need_wo=need_wo, arith="bf16", w_images=(wi16t, wo16t))
-        return (d_x, d_wi, d_wo) + (None,) * 6
-
-
-class T5FFNBf16SavedFunction(torch.autograd.Function):
-    """T5FFNBf16Function with bf16 saved activations (rqhip_t5_ffn_*_bf16a, and _bf16wa with weight images;
-    ops.t5_ffn_fwd(..., saved="bf16")): apply(x, wi, wo, p, seed[, wi16, wo16, wi16t, wo16t]) -> the same y, and in the
-    backward the same gradients, bit for bit.  Saved: the blocked bf16 images hd16 of dropout(relu(x @ wi.T)) and x16 of
-    x, the weights (for their shapes and, without images, their values) and with images the transposed pair -- nothing
-    fp32 of the activations' size, and no seed: the backward's active set is hd16 > 0.  The four images are given
-    together or not at all; they are non-differentiable inputs as in T5FFNBf16ImagesFunction."""
-
-    arith = "bf16"
-
-    @staticmethod
-    def forward(ctx, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optional[Tensor], wi16: Optional[Tensor] = None,
-                wo16: Optional[Tensor] = None, wi16t: Optional[Tensor] = None, wo16t: Optional[Tensor] = None):
-        ctx.images = wi16 is not None
-        y, (hd16, x16) = ops.t5_ffn_fwd(x, wi, wo, p, seed, arith="bf16", saved="bf16",
-                                        w_images=(wi16, wo16) if ctx.images else None)
-        ctx.save_for_backward(hd16, x16, wi, wo, *((wi16t, wo16t) if ctx.images else ()))
-        ctx.p = p
-        return y
-
-    @staticmethod
-    def backward(ctx, d_y: Tensor):
-        hd16, x16, wi, wo, *images_t = ctx.saved_tensors
-        need_x, need_wi, need_wo = ctx.needs_input_grad[:3]
-        if not (need_x or need_wi or need_wo):
-            return (None,) * 9
-        d_x, d_wi, d_wo = ops.t5_ffn_bwd(None, wi, wo, (hd16, x16), _dense(d_y), ctx.p, None, need_x=need_x,
-                                         need_wi=need_wi, need_wo=need_wo, arith="bf16", saved="bf16",
-                                         w_images=tuple(images_t) if ctx.images else None)
-        return (d_x, d_wi, d_wo) + (None,) * 6
-
-
-def t5_ffn_function(arith: str = "fp32"):
-    """The feed-forward Function of an arithmetic."""
-    if arith not in ops.T5_ARITHS:
-        raise ops.RqHipError(f"t5_ffn_function: arith must be one of {ops.T5_ARITHS}, got {arith!r}")
-    return T5FFNBf16Function if arith == "bf16" else T5FFNFunction
+                                         need_wo=need_wo, **kw)
+        return (d_x, d_wi, d_wo) + (None,) * 7
 
 
 class T5ProjFunction(torch.autograd.Function):
     """A group of bias-free linear maps of the same rows (modules/t5.py, proj_impl = "hip") as one launch forward and at
-    most two backward (ops.t5_proj_fwd / ops.t5_proj_bwd): apply(x, *weights) -> (y[0], ..., y[n - 1]), y[j] = x @
-    weights[j].T.  Saved: x and the weights.  An output nobody used arrives without a gradient and is left out of the
-    backward.  Gradients: x and each weight, each only when needed.  `arith` as T5FFNFunction's: this class is the "fp32"
-    arm, T5ProjBf16Function the "bf16" one; t5_proj_function(arith) picks."""
-
-    arith = "fp32"
+    most two backward (ops.t5_proj_fwd / ops.t5_proj_bwd): apply(x, form, *tensors) -> (y[0], ..., y[n - 1]), y[j] = x @
+    weights[j].T, in the arithmetic of `form` (an ops.T5MatmulForm).  tensors: the n weights; with form.images their n
+    bf16 images [d_out, d_in] and their n transposed images [d_in, d_out] follow (non-differentiable inputs; the same
+    outputs and gradients, bit for bit; the transposed images must still hold the forward's weights when the backward
+    runs).  Saved: x, the weights and the transposed images.  An output nobody used arrives without a gradient and is
+    left out of the backward.  Gradients: x and each weight, each only when needed."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, *weights: Tensor):
-        outs = ops.t5_proj_fwd(x, weights, **_arith_kw(ctx))
+    def forward(ctx, x: Tensor, form: ops.T5MatmulForm, *tensors: Tensor):
+        n = len(tensors) // 3 if form.images else len(tensors)
+        outs = ops.t5_proj_fwd(x, tensors[:n], **form.keywords(tensors[n:2 * n]))
         ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None (= NULL at the C ABI)
-        ctx.save_for_backward(x, *weights)
+        ctx.save_for_backward(x, *tensors[:n], *tensors[2 * n:])
+        ctx.form, ctx.n = form, n
         return outs
 
     @staticmethod
     def backward(ctx, *d_ys: Optional[Tensor]):
-        x, *weights = ctx.saved_tensors
-        n = len(weights)
-        if all(g is None for g in d_ys) or not any(ctx.needs_input_grad):
-            return (None,) * (1 + n)
-        d_x, d_w = ops.t5_proj_bwd(x, weights, [_dense(g) for g in d_ys], need_x=ctx.needs_input_grad[0],
-                                   need_w=ctx.needs_input_grad[1:], **_arith_kw(ctx))
-        return (d_x, *d_w)
-
-
-class T5ProjBf16Function(T5ProjFunction):
-    """T5ProjFunction in the "bf16" arithmetic (rqhip_t5_proj_*_bf16)."""
-
-    arith = "bf16"
-
-
-class T5ProjBf16ImagesFunction(torch.autograd.Function):
-    """T5ProjBf16Function reading bf16 weight images (rqhip_t5_proj_*_bf16w): apply(x, n, *weights, *imgs, *imgs_t) with
-    n weights, their n images [d_out, d_in] and their n transposed images [d_in, d_out] -> the same outputs, bit for
-    bit.  The images are non-differentiable inputs; the gradients go to x and the fp32 weights exactly as in
-    T5ProjBf16Function.  The transposed images must still hold the forward's weights when the backward runs."""
-
-    arith = "bf16"
-
-    @staticmethod
-    def forward(ctx, x: Tensor, n: int, *rest: Tensor):
-        weights, imgs, imgs_t = rest[:n], rest[n:2 * n], rest[2 * n:]
-        outs = ops.t5_proj_fwd(x, weights, arith="bf16", w_images=imgs)
-        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None (= NULL at the C ABI)
-        ctx.save_for_backward(x, *weights, *imgs_t)
-        ctx.n = n
-        return outs
-
-    @staticmethod
-    def backward(ctx, *d_ys: Optional[Tensor]):
-        n = ctx.n
+        n, need = ctx.n, ctx.needs_input_grad
         x, *rest = ctx.saved_tensors
-        weights, imgs_t = rest[:n], rest[n:]
-        need = ctx.needs_input_grad
         if all(g is None for g in d_ys) or not (need[0] or any(need[2:2 + n])):
-            return (None,) * (2 + 3 * n)
-        d_x, d_w = ops.t5_proj_bwd(x, weights, [_dense(g) for g in d_ys], need_x=need[0], need_w=need[2:2 + n],
-                                   arith="bf16", w_images=imgs_t)
-        return (d_x, None, *d_w) + (None,) * (2 * n)
-
-
-def t5_proj_function(arith: str = "fp32"):
-    """The projection Function of an arithmetic."""
-    if arith not in ops.T5_ARITHS:
-        raise ops.RqHipError(f"t5_proj_function: arith must be one of {ops.T5_ARITHS}, got {arith!r}")
-    return T5ProjBf16Function if arith == "bf16" else T5ProjFunction
+            return (None,) * len(need)
+        d_x, d_w = ops.t5_proj_bwd(x, rest[:n], [_dense(g) for g in d_ys], need_x=need[0], need_w=need[2:2 + n],
+                                   **ctx.form.keywords(rest[n:]))
+        return (d_x, None, *d_w) + (None,) * (len(need) - 2 - n)      # nothing for the form and the images
 
 
 class SidHeadLossFunction(torch.autograd.Function):

@@ -786,16 +786,52 @@ def _arith_entry(who: str, arith: str):
     return getattr(_lib.lib(), name), name
 
 
-def _image_entry(who: str, arith: str, w_images):
-    """_arith_entry for a call that may read bf16 weight images (bf16_images): with `w_images` the entry point is the
-    "bf16" arithmetic's image-reading twin rqhip_<who>_bf16w, which no other arithmetic has."""
-    if w_images is None:
-        return _arith_entry(who, arith)
-    if arith != "bf16":
-        _arith_entry(who, arith)      # an unknown arithmetic is the first complaint
+T5_SAVED = ("fp32", "bf16")   # what t5_ffn_fwd keeps for t5_ffn_bwd: the fp32 h, or blocked bf16 activation images
+
+
+class T5MatmulForm(NamedTuple):
+    """Which form a t5_ffn_* / t5_proj_* call takes: its arithmetic (T5_ARITHS), whether it reads bf16 weight images
+    (bf16_images) and whether the feed-forward keeps bf16 saved activations.  The five legal values are the constants
+    below; images and saved activations hold bf16 roundings, so only the "bf16" arithmetic has them."""
+    arith: str
+    images: bool = False
+    saved: bool = False
+
+    def keywords(self, w_images=None) -> dict:
+        """The keywords that make a t5_ffn_* / t5_proj_* call take this form, reading `w_images` where it has images:
+        each keyword only off its default, so T5_FP32 is the plain call."""
+        kw = {} if self.arith == "fp32" else {"arith": self.arith}
+        if self.images:
+            kw["w_images"] = w_images
+        if self.saved:
+            kw["saved"] = "bf16"
+        return kw
+
+
+T5_FP32 = T5MatmulForm("fp32")
+T5_BF16 = T5MatmulForm("bf16")
+T5_BF16_IMAGES = T5MatmulForm("bf16", images=True)
+T5_BF16_SAVED = T5MatmulForm("bf16", saved=True)
+T5_BF16_IMAGES_SAVED = T5MatmulForm("bf16", images=True, saved=True)
+_T5_ENTRY_SUFFIX = {T5_FP32: "", T5_BF16: "_bf16", T5_BF16_IMAGES: "_bf16w", T5_BF16_SAVED: "_bf16a",
+                    T5_BF16_IMAGES_SAVED: "_bf16wa"}
+
+
+def t5_matmul_entry(who: str, arith: str = "fp32", w_images=None, saved: str = "fp32"):
+    """The keywords of the t5_ffn_* / t5_proj_* call `who` -> (its T5MatmulForm, the C entry point rqhip_<who><suffix>,
+    that name).  Complaints, in this order: an unknown `saved`, an unknown arithmetic, w_images off "bf16", saved="bf16"
+    off "bf16"."""
+    if saved not in T5_SAVED:
+        raise RqHipError(f"{who}: saved must be one of {T5_SAVED}, got {saved!r}")
+    if arith not in T5_ARITHS:
+        raise RqHipError(f"{who}: arith must be one of {T5_ARITHS}, got {arith!r}")
+    if w_images is not None and arith != "bf16":
         raise RqHipError(f'{who}: w_images belong to arith="bf16" (the images hold bf16 roundings), got arith={arith!r}')
-    name = f"rqhip_{who}_bf16w"
-    return getattr(_lib.lib(), name), name
+    if saved == "bf16" and arith != "bf16":
+        raise RqHipError(f'{who}: saved="bf16" belongs to arith="bf16" (the images hold its bf16 operands), got arith={arith!r}')
+    form = T5MatmulForm(arith, w_images is not None, saved == "bf16")
+    name = f"rqhip_{who}{_T5_ENTRY_SUFFIX[form]}"
+    return form, getattr(_lib.lib(), name), name
 
 
 def _image(who: str, img, name: str, shape, dev) -> Tensor:
@@ -1015,23 +1051,6 @@ def _ffn_call(who: str, x: Tensor, wi: Tensor, wo: Tensor, p: float, seed: Optio
     return x, _aligned16(wi.contiguous()), _aligned16(wo.contiguous()), (x.numel() // d), d, F, seed_ptr
 
 
-T5_SAVED = ("fp32", "bf16")   # what t5_ffn_fwd keeps for t5_ffn_bwd: the fp32 h, or blocked bf16 activation images
-
-
-def _saved_entry(who: str, arith: str, w_images, saved: str):
-    """_image_entry for a feed-forward call that may keep bf16 saved activations: with saved="bf16" the entry point is
-    rqhip_<who>_bf16a, or rqhip_<who>_bf16wa with weight images, which only the "bf16" arithmetic has."""
-    if saved not in T5_SAVED:
-        raise RqHipError(f"{who}: saved must be one of {T5_SAVED}, got {saved!r}")
-    if saved == "fp32":
-        return _image_entry(who, arith, w_images)
-    _image_entry(who, arith, w_images)      # an unknown arithmetic, or images off "bf16", is the first complaint
-    if arith != "bf16":
-        raise RqHipError(f'{who}: saved="bf16" belongs to arith="bf16" (the images hold its bf16 operands), got arith={arith!r}')
-    name = f"rqhip_{who}_bf16" + ("wa" if w_images is not None else "a")
-    return getattr(_lib.lib(), name), name
-
-
 def t5_act_image_numel(N: int, C: int) -> int:
     """bf16 elements of the blocked image of an [N, C] activation (rqhip_t5_ffn_act_image_bytes): 32 * ceil(N / 32) * C."""
     return int(_lib.lib().rqhip_t5_ffn_act_image_bytes(int(N), int(C))) // 2
@@ -1061,6 +1080,14 @@ def _act_image(who: str, img, name: str, N: int, C: int, dev) -> Tensor:
     return img
 
 
+def _ffn_grads(like: Tensor, N: int, d: int, F: int, need_x: bool, need_wi: bool, need_wo: bool):
+    """The outputs of a feed-forward backward -> (d_x of `like`'s shape, d_wi [F, d], d_wo [d, F]), None where not needed."""
+    make = torch.zeros if N == 0 else torch.empty      # without rows the sums are empty
+    return (torch.empty_like(like) if need_x else None,
+            make((F, d), dtype=torch.float32, device=like.device) if need_wi else None,
+            make((d, F), dtype=torch.float32, device=like.device) if need_wo else None)
+
+
 def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional[Tensor] = None, *, need_h: bool = True,
                arith: str = "fp32", w_images=None, saved: str = "fp32"):
     """The T5 feed-forward body in one launch (rqhip_t5_ffn_fwd) -> (y, h or None): h = relu(x @ wi.T), y = dropout(h, p)
@@ -1075,7 +1102,7 @@ def t5_ffn_fwd(x: Tensor, wi: Tensor, wo: Tensor, p: float = 0.0, seed: Optional
     dropout(h) and of x, all that t5_ffn_bwd then needs of the activations (rqhip_t5_ffn_fwd_bf16a / _bf16wa); y keeps
     its bits.  Without need_h the second result is None either way."""
     who = "t5_ffn_fwd"
-    fn, fn_name = _saved_entry(who, arith, w_images, saved)
+    _, fn, fn_name = t5_matmul_entry(who, arith, w_images, saved)
     _need_gpu(x, wi, wo, seed)
     x, wi, wo, N, d, F, seed_ptr = _ffn_call(who, x, wi, wo, p, seed)
     dev = x.device
@@ -1110,7 +1137,7 @@ def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: flo
     is hd16 > 0, the workspace holds bf16 images of d_y and g, and every gradient has the bits of the call on the fp32 h
     (rqhip_t5_ffn_bwd_bf16a / _bf16wa); return_g then gives g as the row-major bfloat16 tensor of its image."""
     who = "t5_ffn_bwd"
-    fn, fn_name = _saved_entry(who, arith, w_images, saved)
+    _, fn, fn_name = t5_matmul_entry(who, arith, w_images, saved)
     if saved == "bf16":
         return _ffn_bwd_saved(who, fn, fn_name, wi, wo, h, d_y, p, need_x, need_wi, need_wo, return_g, w_images)
     _need_gpu(x, wi, wo, h, d_y, seed)
@@ -1123,10 +1150,7 @@ def t5_ffn_bwd(x: Tensor, wi: Tensor, wo: Tensor, h: Tensor, d_y: Tensor, p: flo
     d_y = _norm_rows(d_y, "d_y", who, x.shape)
     dev = x.device
     with torch.cuda.device(dev):
-        d_x = torch.empty_like(x) if need_x else None
-        make = torch.zeros if N == 0 else torch.empty      # without rows the sums are empty
-        d_wi = make((F, d), dtype=torch.float32, device=dev) if need_wi else None
-        d_wo = make((d, F), dtype=torch.float32, device=dev) if need_wo else None
+        d_x, d_wi, d_wo = _ffn_grads(x, N, d, F, need_x, need_wi, need_wo)
         work = None
         if need_wi and N > 0:
             nbytes = int(_lib.lib().rqhip_t5_ffn_bwd_workspace_bytes(N, d, F))
@@ -1154,10 +1178,7 @@ def _ffn_bwd_saved(who, fn, fn_name, wi, wo, pair, d_y, p, need_x, need_wi, need
         wi, wo = _image(who, wi16t, "w_images[0]", (d, F), dev), _image(who, wo16t, "w_images[1]", (F, d), dev)
     hd16, x16 = _act_image(who, hd16, "hd16", N, F, dev), _act_image(who, x16, "x16", N, d, dev)
     with torch.cuda.device(dev):
-        d_x = torch.empty_like(d_y) if need_x else None
-        make = torch.zeros if N == 0 else torch.empty      # without rows the sums are empty
-        d_wi = make((F, d), dtype=torch.float32, device=dev) if need_wi else None
-        d_wo = make((d, F), dtype=torch.float32, device=dev) if need_wo else None
+        d_x, d_wi, d_wo = _ffn_grads(d_y, N, d, F, need_x, need_wi, need_wo)
         work = None
         if (need_wi or need_wo) and N > 0:      # dy16, and behind it g16 when d_wi is wanted
             n = t5_act_image_numel(N, d) + (t5_act_image_numel(N, F) if need_wi else 0)
@@ -1221,7 +1242,7 @@ def t5_proj_fwd(x: Tensor, weights, outs=None, *, arith: str = "fp32", w_images=
     images [d_out, d_in] of the weights (bf16_images), read instead of them; the bits are those of the call without
     them (rqhip_t5_proj_fwd_bf16w)."""
     who = "t5_proj_fwd"
-    fn, fn_name = _image_entry(who, arith, w_images)
+    _, fn, fn_name = t5_matmul_entry(who, arith, w_images)
     x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights, w_images, lambda o, i: (o, i))
     n = len(weights)
     outs = [None] * n if outs is None else list(outs)
@@ -1251,7 +1272,7 @@ def t5_proj_bwd(x: Tensor, weights, d_ys, need_x: bool = True, need_w=None, *, a
     (rqhip_t5_proj_bwd_bf16).  w_images (arith "bf16" only): n TRANSPOSED bf16 images [d_in, d_out] of the weights,
     read instead of them; the bits are those of the call without them (rqhip_t5_proj_bwd_bf16w)."""
     who = "t5_proj_bwd"
-    fn, fn_name = _image_entry(who, arith, w_images)
+    _, fn, fn_name = t5_matmul_entry(who, arith, w_images)
     shape = x.shape
     x, weights, w_ptrs, N, d_in, d_out = _proj_call(who, x, weights, w_images, lambda o, i: (i, o))
     n = len(weights)

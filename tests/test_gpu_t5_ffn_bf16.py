@@ -20,6 +20,8 @@ Data: tests/test_gpu_t5_ffn.py:_data (one row scaled by 1e-3, one by 1e3, one al
 bf16's normal range).  Shapes: (d, F) = (32, 32), (64, 96), (128, 256), (384, 1024); N = 1, 15, 16, 17, 31, 32, 33, 200;
 p = 0, 0.1, 0.5; (32, 32) at N = 16401 (the 32-row tile) and (64, 64) at N = 1300 (several chains per wave in the weight
 gradient)."""
+import inspect
+
 import pytest
 import torch
 
@@ -155,8 +157,9 @@ def test_unwanted_outputs_leave_the_others_unchanged():
 
 def test_function_matches_the_direct_calls():
     from rqhip import ops
-    from rqhip.autograd import T5FFNBf16Function, T5FFNFunction, t5_ffn_function
-    assert t5_ffn_function("bf16") is T5FFNBf16Function and t5_ffn_function() is T5FFNFunction
+    from rqhip.autograd import T5FFNFunction
+    assert ops.T5_BF16 == (BF, False, False) and ops.T5_FP32 == ("fp32", False, False)
+    assert inspect.signature(T5FFNFunction.forward).parameters["form"].default is ops.T5_FP32
     R, L, d, F = 5, 13, 64, 96
     x, wi, wo, d_y = _data(R * L, d, F)
     seed = _seed(9)
@@ -167,7 +170,7 @@ def test_function_matches_the_direct_calls():
             y32, _ = ops.t5_ffn_fwd(x, wi, wo, p, seed)
         assert not same_bits(y, y32)
         xs, wis, wos = (t.clone().requires_grad_() for t in (x.view(R, L, d), wi, wo))
-        out = T5FFNBf16Function.apply(xs, wis, wos, p, seed)
+        out = T5FFNFunction.apply(xs, wis, wos, p, seed, ops.T5_BF16)
         assert same_bits(out.view(-1, d), y)
         out.backward(d_y.view(R, L, d))
         assert same_bits(xs.grad.view(-1, d), g[0]) and same_bits(wis.grad, g[1]) and same_bits(wos.grad, g[2])

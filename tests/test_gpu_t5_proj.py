@@ -204,7 +204,7 @@ def test_function_matches_the_direct_calls():
         h_x, h_w = ops.t5_proj_bwd(x, ws, [d_ys[0], None, d_ys[2]])
     xs = x.view(R, L, d_in).clone().requires_grad_()
     wss = [w.clone().requires_grad_() for w in ws]
-    outs = T5ProjFunction.apply(xs, *wss)
+    outs = T5ProjFunction.apply(xs, ops.T5_FP32, *wss)
     assert len(outs) == 3 and all(o.shape == (R, L, d_out) and same_bits(o.view(-1, d_out), y) for o, y in zip(outs, ys))
     d_nc = d_ys[0].view(R, L, d_out).transpose(0, 1).contiguous().transpose(0, 1)       # non-contiguous upstream gradient
     assert not d_nc.is_contiguous()
@@ -213,17 +213,17 @@ def test_function_matches_the_direct_calls():
     # an output nobody used: no gradient for its weight, and it is left out of d_x
     xs = x.clone().requires_grad_()
     wss = [w.clone().requires_grad_() for w in ws]
-    outs = T5ProjFunction.apply(xs, *wss)
+    outs = T5ProjFunction.apply(xs, ops.T5_FP32, *wss)
     torch.autograd.backward([outs[0], outs[2]], [d_ys[0], d_ys[2]])
     assert same_bits(xs.grad, h_x) and wss[1].grad is None
     assert same_bits(wss[0].grad, h_w[0]) and same_bits(wss[2].grad, h_w[2])
     # only the input needs a gradient: frozen weights
     xs = x.clone().requires_grad_()
-    torch.autograd.backward(T5ProjFunction.apply(xs, *ws), d_ys)
+    torch.autograd.backward(T5ProjFunction.apply(xs, ops.T5_FP32, *ws), d_ys)
     assert same_bits(xs.grad, g_x)
     # only some weights do
     w1 = ws[1].clone().requires_grad_()
-    torch.autograd.backward(T5ProjFunction.apply(x, ws[0], w1, ws[2]), d_ys)
+    torch.autograd.backward(T5ProjFunction.apply(x, ops.T5_FP32, ws[0], w1, ws[2]), d_ys)
     assert same_bits(w1.grad, g_w[1])
 
 

@@ -136,8 +136,8 @@ def test_strided_inputs_and_outputs(N):
 
 def test_function_matches_the_direct_calls():
     from rqhip import ops
-    from rqhip.autograd import T5ProjBf16Function, T5ProjFunction, t5_proj_function
-    assert t5_proj_function("bf16") is T5ProjBf16Function and t5_proj_function() is T5ProjFunction
+    from rqhip.autograd import T5ProjFunction
+    assert ops.T5_BF16 == (BF, False, False) and ops.T5_FP32 == ("fp32", False, False)
     R, L, d_in, d_out = 5, 13, 64, 96
     x, ws, d_ys = _data(R * L, d_in, d_out, 3)
     with torch.no_grad():
@@ -146,14 +146,14 @@ def test_function_matches_the_direct_calls():
         h_x, h_w = ops.t5_proj_bwd(x, ws, [d_ys[0], None, d_ys[2]], arith=BF)
     xs = x.view(R, L, d_in).clone().requires_grad_()
     wss = [w.clone().requires_grad_() for w in ws]
-    outs = T5ProjBf16Function.apply(xs, *wss)
+    outs = T5ProjFunction.apply(xs, ops.T5_BF16, *wss)
     assert len(outs) == 3 and all(same_bits(o.view(-1, d_out), y) for o, y in zip(outs, ys))
     torch.autograd.backward(outs, [t.view(R, L, d_out) for t in d_ys])
     assert same_bits(xs.grad.view(-1, d_in), g_x) and all(same_bits(w.grad, g) for w, g in zip(wss, g_w))
     # an output nobody used: no gradient for its weight, and it is left out of d_x
     xs = x.clone().requires_grad_()
     wss = [w.clone().requires_grad_() for w in ws]
-    outs = T5ProjBf16Function.apply(xs, *wss)
+    outs = T5ProjFunction.apply(xs, ops.T5_BF16, *wss)
     torch.autograd.backward([outs[0], outs[2]], [d_ys[0], d_ys[2]])
     assert same_bits(xs.grad, h_x) and wss[1].grad is None
     assert same_bits(wss[0].grad, h_w[0]) and same_bits(wss[2].grad, h_w[2])

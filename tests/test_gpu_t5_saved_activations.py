@@ -213,7 +213,8 @@ def _saved_bytes(fn, args, skip):
 @pytest.mark.parametrize("images", [False, True])
 @pytest.mark.parametrize("N,d,F", [(26, 64, 96), (40, 384, 1024)])
 def test_the_function_saves_bf16_images_and_matches_its_fp32_saving_twin(N, d, F, images):
-    from rqhip.autograd import T5FFNBf16Function, T5FFNBf16ImagesFunction, T5FFNBf16SavedFunction
+    from rqhip import ops
+    from rqhip.autograd import T5FFNFunction
     c = _case(N, d, F, 0.1) if (N, d, F) == (40, 384, 1024) else None
     if c is None:
         g = torch.Generator(device="cuda").manual_seed(9)
@@ -227,13 +228,13 @@ def test_the_function_saves_bf16_images_and_matches_its_fp32_saving_twin(N, d, F
         (wi16, wo16), (wi16t, wo16t) = _images_of([wi, wo])
         extra = (wi16, wo16, wi16t, wo16t)
     results, totals = [], []
-    for fn in (T5FFNBf16ImagesFunction if images else T5FFNBf16Function, T5FFNBf16SavedFunction):
+    for form in (ops.T5MatmulForm(BF, images, False), ops.T5MatmulForm(BF, images, True)):
         leaves = [t.clone().requires_grad_() for t in (x.view(2, N // 2, d), wi, wo)]
-        y, total, seen = _saved_bytes(fn, (*leaves, 0.1, seed, *extra), skip=(*leaves[1:], seed, *extra))
+        y, total, seen = _saved_bytes(T5FFNFunction, (*leaves, 0.1, seed, form, *extra), skip=(*leaves[1:], seed, *extra))
         y.backward(d_y.view(2, N // 2, d))
         results.append([y.detach()] + [t.grad for t in leaves])
         totals.append(total)
-        if fn is T5FFNBf16SavedFunction:
+        if form.saved:
             assert all(t.dtype == torch.bfloat16 for t in seen) and len(seen) == 2
     for a, b in zip(results[1], results[0]):
         assert same_bits(a, b)

@@ -343,16 +343,15 @@ def test_projections_with_a_row_stride_of_x_at_the_c_interface():
 
 
 def test_functions_match_their_bf16_twins():
-    from rqhip.autograd import (T5FFNBf16Function, T5FFNBf16ImagesFunction, T5ProjBf16Function,
-                                T5ProjBf16ImagesFunction)
+    from rqhip import ops
+    from rqhip.autograd import T5FFNFunction, T5ProjFunction
     x, wi, wo, d_y = _ffn_data(26, 64, 96, 9)
     (wi16, wo16), (wi16t, wo16t) = _images_of([wi, wo])
     seed = torch.tensor([77], dtype=torch.int64, device="cuda")
     grads = []
     for images in ((), (wi16, wo16, wi16t, wo16t)):
         leaves = [t.clone().requires_grad_() for t in (x.view(2, 13, 64), wi, wo)]
-        fn = T5FFNBf16ImagesFunction if images else T5FFNBf16Function
-        y = fn.apply(*leaves, 0.1, seed, *images)
+        y = T5FFNFunction.apply(*leaves, 0.1, seed, ops.T5_BF16_IMAGES if images else ops.T5_BF16, *images)
         y.backward(d_y.view(2, 13, 64))
         grads.append([y.detach()] + [t.grad for t in leaves])
     _same("ffn function", grads[1], grads[0])
@@ -362,9 +361,9 @@ def test_functions_match_their_bf16_twins():
     for use in (False, True):
         leaves = [t.clone().requires_grad_() for t in [x] + ws]
         if use:
-            outs = T5ProjBf16ImagesFunction.apply(leaves[0], 3, *leaves[1:], *imgs, *imgs_t)
+            outs = T5ProjFunction.apply(leaves[0], ops.T5_BF16_IMAGES, *leaves[1:], *imgs, *imgs_t)
         else:
-            outs = T5ProjBf16Function.apply(*leaves)
+            outs = T5ProjFunction.apply(leaves[0], ops.T5_BF16, *leaves[1:])
         torch.autograd.backward([outs[0], outs[2]], [d_ys[0], d_ys[2]])       # an output nobody used
         assert leaves[2].grad is None
         grads.append([o.detach() for o in outs] + [leaves[0].grad, leaves[1].grad, leaves[3].grad])

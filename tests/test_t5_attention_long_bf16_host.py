@@ -1,5 +1,5 @@
 """The "bf16" arithmetic of the long fused T5 attention on the host (rqhip_t5_attention_long_*_bf16, the `arith` keyword of
-ops.t5_attention_long*, autograd.t5_attention_long_function, the `attention_arith` attribute of the stacks and the
+ops.t5_attention_long*, the trailing `arith` of autograd.T5AttentionLongFunction, the `attention_arith` attribute of the stacks and the
 model): the argument checks of the three new C entry points (their twins', under their own names), the keyword's default
 and validation, and the attribute's default, validation and lack of effect on host tensors.  No GPU needed."""
 import inspect
@@ -108,13 +108,16 @@ def test_arith_defaults_to_fp32_and_unknown_values_raise_before_any_other_check(
         ops.t5_attention_long_fwd_train(junk, junk, junk, 6, arith="tf32")
     with pytest.raises(RqHipError, match="t5_attention_long_bwd: arith must be one of"):
         ops.t5_attention_long_bwd(junk, junk, junk, junk, junk, junk, junk, 6, arith=None)
-    with pytest.raises(RqHipError, match="t5_attention_long_function: arith must be one of"):
-        autograd.t5_attention_long_function("fp16")
-    assert autograd.t5_attention_long_function() is autograd.T5AttentionLongFunction
-    assert autograd.t5_attention_long_function("fp32") is autograd.T5AttentionLongFunction
-    bf16 = autograd.t5_attention_long_function("bf16")
-    assert bf16 is autograd.T5AttentionLongBf16Function and issubclass(bf16, autograd.T5AttentionLongFunction)
-    assert (autograd.T5AttentionLongFunction.arith, bf16.arith) == ("fp32", "bf16")
+    # the one Function takes the arithmetic as its trailing argument, "fp32" without it, and hands it to the ops
+    call = (junk, junk, junk, None, 6, 0, None, False, 0.0, None)
+    with pytest.raises(RqHipError, match="t5_attention_long_fwd_train: arith must be one of"):
+        autograd.T5AttentionLongFunction.apply(*call, "fp16")
+    params = list(inspect.signature(autograd.T5AttentionLongFunction.forward).parameters.values())
+    assert params[-1].name == "arith" and params[-1].default == "fp32" and len(params) == 1 + len(call) + 1
+    for arith in ("fp32", "bf16"):      # a known one goes on to the next check, which trips over the junk
+        with pytest.raises(Exception) as info:
+            autograd.T5AttentionLongFunction.apply(*call, arith)
+        assert "arith must be one of" not in str(info.value)
 
 
 def test_a_host_tensor_is_refused_after_the_arithmetic_is_resolved():

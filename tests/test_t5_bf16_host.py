@@ -106,14 +106,13 @@ def test_proj_argument_checks_without_gpu():
 def test_ops_reject_an_unknown_arith():
     from rqhip import ops
     from rqhip._lib import RqHipError
-    from rqhip.autograd import t5_ffn_function, t5_proj_function
     assert ops.T5_ARITHS == ("fp32", "bf16")
     x, wi, wo = torch.zeros(3, 32), torch.zeros(64, 32), torch.zeros(32, 64)
     for call in (lambda: ops.t5_ffn_fwd(x, wi, wo, arith="fp16"),
                  lambda: ops.t5_ffn_bwd(x, wi, wo, torch.zeros(3, 64), x, arith="tf32"),
                  lambda: ops.t5_proj_fwd(x, [wi], arith="bfloat16"),
                  lambda: ops.t5_proj_bwd(x, [wi], [torch.zeros(3, 64)], arith=None),
-                 lambda: t5_ffn_function("fp16"), lambda: t5_proj_function("half")):
+                 lambda: ops.t5_matmul_entry("t5_ffn_fwd", "fp16"), lambda: ops.t5_matmul_entry("t5_proj_bwd", "half")):
         with pytest.raises(RqHipError, match="arith must be one of"):
             call()
     # a known one goes on to the next check: these are host tensors
@@ -146,13 +145,15 @@ def test_matmul_arith_is_validated_by_model_and_stack():
     stack = T5Stack(T5Config(16, d_model=32, num_heads=2, d_ff=64, num_layers=1)).eval()
     assert stack.matmul_arith == "fp32" and stack.arith() == "fp32"
     stack.matmul_arith = "bf16"
-    assert stack.arith() == "bf16" and stack.proj_arm(torch.zeros(2, 3, 32)) is False
+    assert stack.arith() == "bf16" and stack.matmul_plan(torch.zeros(2, 3, 32)).proj is None
     stack(torch.randn(2, 3, 32))
     stack.matmul_arith = "bogus"
     with pytest.raises(ValueError, match="matmul_arith"):
         stack(torch.randn(2, 3, 32))
     with pytest.raises(ValueError, match="matmul_arith"):
-        stack.proj_arm(torch.zeros(2, 3, 32))
+        stack.cross_kv(torch.zeros(2, 3, 32))
+    with pytest.raises(ValueError, match="matmul_arith"):
+        stack.arith()
 
 
 def test_amp_with_another_type_still_raises():

@@ -222,7 +222,7 @@ def test_weight_images_is_validated_by_model_and_stack():
     x = torch.randn(2, 3, 32)
     want = stack(x)
     stack.weight_images, stack.matmul_arith = "bf16", "bf16"
-    assert stack.current_images(x) is None and torch.equal(stack(x), want)
+    assert stack.matmul_plan(x) == (None, None, None) and torch.equal(stack(x), want)
     stack.weight_images = "bogus"
     with pytest.raises(ValueError, match="weight_images"):
         stack(x)
