@@ -258,6 +258,51 @@ int rqhip_prefix_lookup(const void *index, size_t index_bytes, const int64_t *co
 int rqhip_topk_first_match(const int64_t *actual, const int64_t *top_k, int64_t B, int K, int D,
                            int64_t *rank, rqhip_stream_t stream);
 
+/* Item index -- from semantic-id tuples to corpus item numbers (csrc/sid_items.hip): the inverse of
+ * SemanticIdTokenizer._lookup (modules/tokenizer/semids.py).  Several items share a tuple; the tokenizer tells them
+ * apart by the dedup column, which the decoder never generates.
+ *   corpus [N, >= L] int64 with row stride ld (>= L) and rank [N] int64, the dedup column: rank[i] = the number of rows
+ *   j < i with row i's L-tuple (rqhip_dedup_rank), so that rows are unique in (tuple, rank) and, within a tuple,
+ *   ascending rank is ascending item number.
+ *   rqhip_sid_item_index_build: fills `index` (rqhip_sid_item_index_bytes(N) bytes -- 0 for N < 0 --, caller-owned,
+ *     opaque, 12 to 20 bytes per item) with the exact map (L-tuple, rank) -> item number.  Build once per corpus; one
+ *     fill and one kernel.  `rank` is copied into the index and not needed afterwards; `corpus`, N, L, ld must be the
+ *     same in every later call: the index stores row numbers, and membership is always decided by comparing the stored
+ *     row's ids and rank with the query, never by a hash alone.  Where a row sits in the index may differ from build to
+ *     build; no answer does.
+ *   rqhip_sid_item_lookup: items[p] = the item with tuple ids[p, 0:L] and rank ids[p, L], or -1 when no corpus row has
+ *     that tuple and rank; ids [P, L + 1] int64 with row stride ld_ids (>= L + 1) -- a row of tokenizer.cached_ids, or of
+ *     batch.sem_ids_fut.  One thread per query.  P = 0 returns RQHIP_OK without a launch.
+ *   rqhip_sid_items_topn: the beams of `generate` expanded to the items a recommender returns, ONE launch, no fill, no
+ *     atomics.  beams [B, k, L] int64 and scores [B, k] fp32, dense, best beam first; history NULL, or [B, T * (L + 1)]
+ *     int64 with row stride ld_hist (>= T * (L + 1)) in the form of batch.sem_ids (a history item with any negative id,
+ *     its rank included, is padding); items [B, n] int64 and item_scores [B, n] fp32, dense.  For user u:
+ *         out = []
+ *         for b in 0 .. k-1:                               -- best beam first
+ *             if not (scores[u,b] > -inf): continue        -- -inf and NaN beams contribute nothing
+ *             if beams[u,b] == beams[u,b'] for an earlier contributing b' < b: continue
+ *             for r in 0, 1, 2, ...:                       -- ascending dedup rank = ascending item number
+ *                 item = map.get((beams[u,b], r));  if item is None: break
+ *                 if history and (beams[u,b], r) is one of u's non-padding history items: continue
+ *                 out.append((item, scores[u,b]));  if len(out) == n: stop
+ *         items[u] = out padded with -1;  item_scores[u] = the beams' scores (their bits), padded with -inf
+ *     Every element of both outputs is written by the call.  One wave per user, lane b owns beam b.  Probe bound: a lane
+ *     walks its tuple's ranks at most twice (count, then write), and each probe of a walk either emits an item, hits a
+ *     distinct history item of the user, or ends the group -- at most n + (distinct history items) + 1 probes per walk.
+ *     The same bits on every run, and on an index built a second time from the same corpus.
+ * Limits: 1 <= L and L + 1 <= RQHIP_MAX_PREFIX_LEN, N < 2^30, ld >= L; for rqhip_sid_items_topn also 1 <= k <= 64,
+ * 1 <= n <= 256, T >= 0, B < 2^31 (B = 0 returns RQHIP_OK without a launch).  Outside them RQHIP_EARG /
+ * RQHIP_EUNSUPPORTED, and RQHIP_EWORKSPACE for an index buffer that is too small, with the limit named in
+ * rqhip_last_error(); every argument check runs before any HIP call.  No allocation, copy or sync (graph-capturable). */
+size_t rqhip_sid_item_index_bytes(int64_t N);
+int rqhip_sid_item_index_build(const int64_t *corpus, int64_t N, int L, int64_t ld, const int64_t *rank, void *index,
+                               size_t index_bytes, rqhip_stream_t stream);
+int rqhip_sid_item_lookup(const void *index, size_t index_bytes, const int64_t *corpus, int64_t N, int L, int64_t ld,
+                          const int64_t *ids, int64_t P, int64_t ld_ids, int64_t *items, rqhip_stream_t stream);
+int rqhip_sid_items_topn(const void *index, size_t index_bytes, const int64_t *corpus, int64_t N, int L, int64_t ld,
+                         const int64_t *beams, const float *scores, int64_t B, int k, const int64_t *history, int64_t T,
+                         int64_t ld_hist, int n, int64_t *items, float *item_scores, rqhip_stream_t stream);
+
 /* Beam step -- one hierarchy step of EncoderDecoderRetrievalModel.generate (modules/model.py) in one launch: softmax,
  * sampling without replacement, log, prefix validity, masked_fill, sort and gathers.  Row r of the B * beams_in rows
  * (beams_in = 1 at h = 0, else the k beams of the previous step; row b * beams_in + beam):

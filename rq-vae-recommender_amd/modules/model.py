@@ -60,6 +60,12 @@ valid child, hence with a finite parent the search never loses a beam to chance,
 never decreases from level to level.  Everything around the step -- encoder, cross K/V, the decode caches reordered by
 the step's parent rows, the head, every *_impl / *_arith attribute, the returned shapes and dtypes -- is the same, and
 the call is capturable into a graph with no noise baked in.  Any other value raises ValueError at `generate`.
+
+`recommend_items(batch)` names items: one `generate_next_sem_id` call, then ONE launch (modules/sid_items.py,
+csrc/sid_items.hip) that expands each user's beams, best first, to the corpus items that carry those tuples -- several
+items can share a tuple, in ascending item number -- without the items of the user's own history, cut at n_items.  The
+item index is cached beside the prefix index by the same rule and is no part of the state dict; `generate`,
+`generate_next_sem_id` and `forward` do not build or touch it.
 """
 from typing import List, NamedTuple, Optional
 
@@ -69,6 +75,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from data.schemas import TokenizedSeqBatch
+from modules.sid_items import SemIdItemIndex
 from modules.sid_prefix import SemIdPrefixIndex
 from modules.t5 import STACK_ATTRIBUTES, T5Config, T5EncoderModel, T5Stack, checked
 from rqhip import ops
@@ -89,6 +96,13 @@ class ModelOutput(NamedTuple):
 class GenerationOutput(NamedTuple):
     sem_ids: Tensor
     log_probas: Tensor
+
+
+class ItemRecommendation(NamedTuple):
+    items: Tensor        # [B, n_items] int64 corpus item numbers, best first, -1 padded
+    scores: Tensor       # [B, n_items] fp32: the log probability of the beam each item came from, -inf padded
+    sem_ids: Tensor      # [B, k, num_hierarchies] int64, as GenerationOutput
+    log_probas: Tensor   # [B, k] fp32, as GenerationOutput
 
 
 def _strip_dedup_col(tensor: Tensor, sem_ids_dim: int, n_layers: int) -> Tensor:
@@ -139,6 +153,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
 
         self._prefix_index: Optional[SemIdPrefixIndex] = None
         self._prefix_key = None
+        self._item_index: Optional[SemIdItemIndex] = None
+        self._item_key = None
         self.attention_impl = "torch"  # or "hip" / "hip_train"; handed to both T5 stacks whenever they are run
         self.attention_long_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.norm_impl = "torch"  # or "hip" (modules/t5.py); handed to both T5 stacks with attention_impl
@@ -191,6 +207,15 @@ class EncoderDecoderRetrievalModel(nn.Module):
             self._prefix_index = SemIdPrefixIndex(cb)
             self._prefix_key = key
         return self._prefix_index
+
+    def _item_index_for_codebooks(self) -> SemIdItemIndex:
+        """The corpus' (tuple, dedup rank) -> item index, cached by the rule of `_prefix_index_for_codebooks`."""
+        cb = self.codebooks
+        key = (cb.data_ptr(), cb.device, cb._version, tuple(cb.shape))
+        if self._item_index is None or self._item_key != key:
+            self._item_index = SemIdItemIndex(cb)
+            self._item_key = key
+        return self._item_index
 
     def _check_valid_prefix(self, prefix: Tensor, batch_size: int = 100000) -> Tensor:
         """Boolean mask: which rows of prefix [P, h] occur as the first h ids of a corpus row."""
@@ -412,3 +437,22 @@ class EncoderDecoderRetrievalModel(nn.Module):
         generated_ids, log_probas = self.generate(attention_mask=attention_mask, input_ids=input_ids,
                                                   user_id=batch.user_ids)
         return GenerationOutput(sem_ids=generated_ids, log_probas=log_probas)
+
+    @torch.no_grad()
+    def recommend_items(self, batch: TokenizedSeqBatch, n_items: Optional[int] = None,
+                        exclude_history: bool = True) -> ItemRecommendation:
+        """The items to recommend to each user of the batch: one `generate_next_sem_id(batch)` call and ONE launch that
+        expands its beams to corpus item numbers (SemIdItemIndex.expand; the semantics are in include/rqhip.h).
+
+        n_items defaults to top_k_for_generation (at most 256).  With exclude_history the items of batch.sem_ids -- the
+        batch's tensor as it is, dedup column included, negative ids being padding -- are never returned.  A user gets
+        fewer than n_items items (-1 / -inf padded) when the finite beams' tuples carry fewer.  After the encoder nothing
+        is read back to the host and no allocation depends on data, as in `generate`."""
+        n_items = self.top_k_for_generation if n_items is None else int(n_items)
+        generated = self.generate_next_sem_id(batch)
+        index = self._item_index_for_codebooks()   # `generate` has moved `codebooks` to the batch's device
+        index.to(generated.sem_ids.device)
+        items, scores = index.expand(generated.sem_ids, generated.log_probas, n_items,
+                                     history=batch.sem_ids if exclude_history else None)
+        return ItemRecommendation(items=items, scores=scores, sem_ids=generated.sem_ids,
+                                  log_probas=generated.log_probas)

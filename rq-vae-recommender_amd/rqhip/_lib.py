@@ -97,6 +97,11 @@ SIGNATURES = {
     "rqhip_prefix_index_build": (_int, [_vp, _i64, _int, _i64, _vp, _sz, _vp]),
     "rqhip_prefix_lookup": (_int, [_vp, _sz, _vp, _i64, _int, _i64, _vp, _i64, _int, _i64, _vp, _vp]),
     "rqhip_topk_first_match": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
+    "rqhip_sid_item_index_bytes": (_sz, [_i64]),
+    "rqhip_sid_item_index_build": (_int, [_vp, _i64, _int, _i64, _vp, _vp, _sz, _vp]),
+    "rqhip_sid_item_lookup": (_int, [_vp, _sz, _vp, _i64, _int, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "rqhip_sid_items_topn": (_int, [_vp, _sz, _vp, _i64, _int, _i64, _vp, _vp, _i64, _int, _vp, _i64, _i64, _int, _vp, _vp,
+                                    _vp]),
     "rqhip_beam_step_workspace_bytes": (_sz, [_i64, _int, _int, _int, _int]),
     "rqhip_beam_step": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _vp, _sz, _vp, _i64, _int,
                                _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -490,6 +490,84 @@ def topk_first_match(actual: Tensor, top_k: Tensor) -> Tensor:
     return rank
 
 
+def sid_item_index_build(corpus: Tensor, rank: Tensor) -> Tensor:
+    """Exact map (L-tuple, dedup rank) -> item number of the corpus (rqhip_sid_item_index_build).  corpus [N,L] int64
+    (row-strided views are fine), rank [N] int64 = the dedup column (dedup_rank) -> opaque uint8 index tensor; keep
+    `corpus` alive and unchanged next to it."""
+    _need_gpu(corpus, rank)
+    corpus = _i64_rows(corpus, "corpus")
+    N, L = corpus.shape
+    if rank.dtype != torch.int64 or rank.dim() != 1 or rank.shape[0] != N:
+        raise RqHipError(f"sid_item_index_build: rank must be an int64 [{N}] tensor, got {rank.dtype} {tuple(rank.shape)}")
+    rank = rank.contiguous()
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        l = _lib.lib()
+        nbytes = l.rqhip_sid_item_index_bytes(N)
+        index = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        rc = l.rqhip_sid_item_index_build(_ptr(corpus), N, L, _row_stride(corpus), _ptr(rank), _ptr(index), nbytes,
+                                          _stream())
+        check(rc, "rqhip_sid_item_index_build")
+    return index
+
+
+def sid_item_lookup(index: Tensor, corpus: Tensor, ids: Tensor) -> Tensor:
+    """items[p] = the corpus row with tuple ids[p, :L] and dedup rank ids[p, L], else -1 (rqhip_sid_item_lookup).
+    ids [P, L+1] int64 (row-strided views are fine) -> int64 [P]."""
+    _need_gpu(index, corpus, ids)
+    corpus = _i64_rows(corpus, "corpus")
+    ids = _i64_rows(ids, "ids")
+    N, L = corpus.shape
+    P = ids.shape[0]
+    if ids.shape[1] != L + 1:
+        raise RqHipError(f"sid_item_lookup: ids {tuple(ids.shape)} must have the corpus' {L} ids and the dedup rank per row")
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        items = torch.empty((P,), dtype=torch.int64, device=dev)
+        rc = _lib.lib().rqhip_sid_item_lookup(_ptr(index), index.numel(), _ptr(corpus), N, L, _row_stride(corpus),
+                                              _ptr(ids), P, _row_stride(ids), _ptr(items), _stream())
+        check(rc, "rqhip_sid_item_lookup")
+    return items
+
+
+def sid_items_topn(index: Tensor, corpus: Tensor, beams: Tensor, scores: Tensor, n: int,
+                   history: Optional[Tensor] = None):
+    """The beams of `generate` expanded to corpus items in ONE launch (rqhip_sid_items_topn; the semantics are in
+    include/rqhip.h).  beams [B,k,L] int64 and scores [B,k] fp32, best first; history None or [B, T*(L+1)] int64 in the
+    form of batch.sem_ids (row-strided views are fine; an item with a negative id is padding) -> items [B,n] int64
+    (-1 padded) and item_scores [B,n] fp32 (-inf padded).  Shapes decide every allocation; nothing is read back."""
+    _need_gpu(index, corpus, beams, scores, history)
+    corpus = _i64_rows(corpus, "corpus")
+    N, L = corpus.shape
+    if beams.dtype != torch.int64 or beams.dim() != 3 or beams.shape[2] != L:
+        raise RqHipError(f"sid_items_topn: beams must be an int64 [B, k, {L}] tensor, got {beams.dtype} {tuple(beams.shape)}")
+    B, k = beams.shape[0], beams.shape[1]
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (B, k):
+        raise RqHipError(f"sid_items_topn: scores must be a float32 [{B}, {k}] tensor, got {scores.dtype} "
+                         f"{tuple(scores.shape)}")
+    T = 0
+    if history is not None:
+        history = _i64_rows(history, "history")
+        if history.shape[0] != B or history.shape[1] % (L + 1) != 0:
+            raise RqHipError(f"sid_items_topn: history {tuple(history.shape)} must be [{B}, T * {L + 1}]: {L} ids and the "
+                             "dedup rank per item")
+        T = history.shape[1] // (L + 1)
+    n = int(n)
+    if not 1 <= n <= 256:
+        raise RqHipError(f"sid_items_topn: n={n} items per user (1 <= n <= 256)")
+    beams, scores = beams.contiguous(), scores.contiguous()
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        items =torch.empty((B, n), dtype=torch.int64, device=dev)
+        item_scores = torch.empty((B, n), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_sid_items_topn(_ptr(index), index.numel(), _ptr(corpus), N, L, _row_stride(corpus),
+                                             _ptr(beams), _ptr(scores), B, k, _ptr(history), T,
+                                             0 if history is None else _row_stride(history), int(n), _ptr(items),
+                                             _ptr(item_scores), _stream())
+        check(rc, "rqhip_sid_items_topn")
+    return items, item_scores
+
+
 def beam_step(logits: Tensor, noise: Tensor, parent_scores: Optional[Tensor], parent_ids: Optional[Tensor],
               index: Tensor, corpus: Tensor, n_cands: int, k: int):
     """One hierarchy step of the retrieval model's beam search in one launch (rqhip_beam_step).
