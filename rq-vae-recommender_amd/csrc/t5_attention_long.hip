@@ -574,7 +574,6 @@ __global__ __launch_bounds__(kLongThreads) void t5_long_bwd_kv_kernel(LongBwdArg
 // The order of the terms inside a group is the instruction's; both operands use the same assignment, so each product
 // meets its partner.  With an odd number of tiles the last half group multiplies zeros: the images are staged in whole
 // groups of 32 rows, rows at and beyond the tensor's end as zeros, and the missing tile's weights are +0.
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kLongLdR = kLongD + 4;      // bf16 row stride of a [row][feature] image: 34 dwords
 constexpr int kLongLdT = kLongChunk + 4;  // bf16 row stride of a [feature][row] image: 66 dwords

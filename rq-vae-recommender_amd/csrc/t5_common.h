@@ -1,6 +1,7 @@
 // t5_common.h -- what the T5 kernel files share (t5_attention.hip, t5_add_norm.hip, t5_ffn.hip, sid_head_loss.hip,
-// sid_embed.hip, t5_proj.hip): the dropout decision, its threshold and its two scales, the wave reductions, the bf16
-// fragment helpers of the matrix kernels and the entry points' pointer checks.
+// sid_embed.hip, t5_proj.hip): the vector types, the dropout decision, its threshold and its two scales, the wave
+// reductions, the bf16 fragment helpers of the matrix kernels and the entry points' pointer checks.
+// The matrix code that t5_ffn.hip and t5_proj.hip share beyond that (operand loaders, group step, chains): t5_matmul.h.
 #pragma once
 
 #include <math.h>
@@ -9,6 +10,7 @@
 
 namespace rqhip {
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- dropout.  The decision is a pure function of a 64-bit seed and a 64-bit element index, documented at
@@ -69,6 +71,7 @@ __device__ __forceinline__ float wave_max(float v) {
 //           A / B fragment is exactly that holding: lane l supplies k = 8 (l >> 4) + j, j = 0 .. 7, of row / column
 //           l & 15.  Products of two bf16 values are exact in fp32; the accumulation is fp32.  The helpers below.
 // The C / D layout is the same for both: register r of lane (i, kq) is row 4 kq + r, column i.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ bf16x8 pack_bf16x8(const float (&v)[8]) {

@@ -1,8 +1,7 @@
 // t5_ffn.hip -- the T5 feed-forward body wo(dropout(relu(wi(x)))) as one launch forward and at most two backward
-// (gfx950; modules/t5.py, ffn_impl = "hip"; semantics and arithmetic contract in include/rqhip.h).  Exact fp32 on
-// v_mfma_f32_16x16x4_f32, operand layout as csrc/mlp_small.hip: lane (i, kq) = (lane & 15, lane >> 4) supplies k-slot kq
-// of row / column i, and of a GROUP of 32 reduction terms it holds the 8 terms 8 kq .. 8 kq + 7, so instruction e of a
-// group consumes term 8 kq + e of every slot (chain order 0 8 16 24 1 9 17 25 ... 7 15 23 31 within a group).
+// (gfx950; modules/t5.py, ffn_impl = "hip"; semantics and arithmetic contract in include/rqhip.h).  The operand layout,
+// the group order, the chain rule, the operand loaders and the weight-gradient rule are csrc/t5_matmul.h's, which
+// csrc/t5_proj.hip uses too.
 //
 // Row kernel (forward, and backward kernel 1: the same structure with the weights in the other orientation).  A
 // workgroup of 4 waves owns T rows; their x (backward: d_y) stays in LDS.  It walks F in chunks of 128 columns:
@@ -12,15 +11,11 @@
 //   phase 2  wave w adds chunk . W2 into the accumulators of its column pairs q = w, w + 4, ... (32 output columns
 //            each) -- they live in registers for the whole walk; y (d_x) is written once at the end.
 // No chain is longer than 128 terms: phase 1 starts a fresh chain every 4 groups of d, phase 2 one per chunk, and the
-// finished chains are added in ascending order.  (One chain over all of d = 384 or F = 1024 passed the test's gates,
-// but with three to four times the operators' error in the worst cases, next to a factor of 4; the library GEMMs sum
-// in such partial chains too.  With chains of 128 the error is the operators' or less: profiles/t5_ffn_error.txt.)
+// finished chains are added in ascending order.
 // One barrier per chunk: chunk c + 1 goes into the other buffer, and nobody can still read that one (a wave passes
 // chunk c's barrier only after every wave has finished phase 2 of chunk c - 1).
-// The weights are read as stored.  Where the reduction runs along a weight's rows (forward: wi [F, d] and wo [d, F])
-// a lane loads its row's 8 terms as two float4; where it runs down the columns (backward: wo, then wi) it loads, for
-// each of its 8 terms, 2 consecutive columns (float2) and serves column 2 j + ct in column tile ct -- a permutation
-// the epilogues undo for free.
+// The weights are read as stored: along their rows forward (wi [F, d] and wo [d, F]), down their columns backward (wo,
+// then wi), where the lane serves column 2 i + ct in column tile ct -- a permutation the epilogues undo for free.
 // Row-tile height: T = 16 up to 16384 rows, 32 above.  A workgroup streams all of wi and wo through L2 whatever T
 // is, so T = 32 halves that traffic; but the model's shapes (5120 and 256 rows) are short of workgroups, not of L2
 // bandwidth: 16-row tiles give 320 and 16 workgroups instead of 160 and 8 on 256 CUs.  The registers of the
@@ -28,26 +23,18 @@
 // accumulators per wave keep at the matrix pipe's issue rate).  T follows N alone, and the chains do not depend on T.
 //
 // Weight-gradient kernel (backward kernel 2): every 32 x 32 tile of d_wi and of d_wo has one owning workgroup, which
-// reduces over all N rows: blocks of 32 rows, wave w of 4 takes the contiguous range of blocks [w nb / 4, (w + 1) nb
-// / 4); within its range a wave starts a fresh chain every 8 blocks (256 rows) and adds the finished chains in
-// ascending order (bounded chain length: the rounding error of a long row count grows with the number of chains,
-// not of rows); the four waves' sums meet in LDS and are added in wave order.  No partial blocks in memory, no
-// atomics, no reduction launch.  hd is recomputed from h and the seed as it is loaded.
+// reduces g^T . x, or d_y^T . hd, over all N rows by the weight-gradient rule of csrc/t5_matmul.h.  hd is recomputed
+// from h and the seed as it is loaded.
 //
 // Second arithmetic, "bf16" (template parameter BF, entry points rqhip_t5_ffn_*_bf16; contract in include/rqhip.h): the
-// same kernels with one v_mfma_f32_16x16x32_bf16 per group in place of the eight fp32 instructions.  The lane's eight
-// terms 8 kq .. 8 kq + 7 of a group are that instruction's A / B fragment as they stand, so loads, LDS, chains and
-// epilogues do not change; the eight registers are rounded to bf16 (nearest even) and packed pairwise in front of the
-// instruction (csrc/t5_common.h).  In the weight-gradient kernel the lane's eight rows 4 ks + kq of a block become the
-// elements j = ks of both fragments, a consistent permutation of the block's 32 rows.  Memory and LDS stay fp32: the
-// rounding happens in registers, so h is stored unrounded and the chunk buffer holds fp32 hd / g.
+// same kernels with one v_mfma_f32_16x16x32_bf16 per group in place of the eight fp32 instructions.  Memory and LDS stay
+// fp32: the rounding happens in registers, so h is stored unrounded and the chunk buffer holds fp32 hd / g.
 //
 // Weight images (template parameter IMG of the row kernel, with BF only; entry points rqhip_t5_ffn_*_bf16w): the weights
 // come from bf16 images (csrc/t5_images.hip), which hold the values the "bf16" arithmetic rounds them to.  The reduction
 // always runs along an image's rows -- forward wi16 [F, d] and wo16 [d, F], backward the TRANSPOSED images wo16t [F, d]
-// and wi16t [d, F] -- so a lane's 8 terms of a column tile are ONE 16-byte load, which is the instruction's B fragment as
-// it stands: no conversion, half the registers in the operand buffers, and the backward serves column 16 ct + i like
-// the forward.  Which lane serves a column does not enter its sum, so every output has the bits of the BF arm.
+// and wi16t [d, F] -- so a lane's 8 terms of a column tile are ONE 16-byte load: no conversion, half the registers in
+// the operand buffers, and the backward serves column 16 ct + i like the forward.  Every output has the bits of the BF arm.
 //
 // Saved activations in bf16 (template parameter ACT of the row kernel, with BF only; t5_ffn_wgrad16_kernel; entry points
 // rqhip_t5_ffn_*_bf16a / _bf16wa): what the backward keeps of the forward, and what the row kernel hands the
@@ -62,20 +49,16 @@
 
 #include "rqhip_common.h"
 #include "t5_common.h"
+#include "t5_matmul.h"
 
 namespace rqhip {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kFfnMaxD = 512, kFfnMaxF = 8192;
 constexpr int kFfnChunk = 128;            // columns of F per step of the walk: 32 per wave
 constexpr int kFfnLdh = kFfnChunk + 4;    // row stride of a chunk buffer in LDS
-constexpr int kFfnChainGroups = 4;        // groups of 32 terms per chain: 128 terms, as a chunk of F
 constexpr long long kFfnTallFrom = 16384; // rows above which the row tile is 32 high
-constexpr int kFfnWgBlock = 32;           // rows per block of the weight-gradient reduction
-constexpr int kFfnWgFlush = 8;            // blocks per chain
 
 bool ffn_supported(int d, int F) {
     return d >= 32 && d <= kFfnMaxD && d % 32 == 0 && F >= 32 && F <= kFfnMaxF && F % 32 == 0;
@@ -100,92 +83,8 @@ struct FfnRows {
 template <int RT>
 __device__ __forceinline__ void ffn_load_a(const float *base, int ld, int off, float (&a)[RT][8]) {
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(base + 16 * rt * ld + off);
-        const f32x4 hi = *reinterpret_cast<const f32x4 *>(base + 16 * rt * ld + off + 4);
-        a[rt][0] = lo.x; a[rt][1] = lo.y; a[rt][2] = lo.z; a[rt][3] = lo.w;
-        a[rt][4] = hi.x; a[rt][5] = hi.y; a[rt][6] = hi.z; a[rt][7] = hi.w;
-    }
+    for (int rt = 0; rt < RT; ++rt) load_a(base + 16 * rt * ld + off, a[rt]);
 }
-
-// the weight operand of one group for two 16-column tiles.  KN = false: `at` points at term 0 of the group in the row
-// of tile 0's column, rows `ld` apart (tile 1: 16 rows on).  KN = true: `at` points at the lane's 2 columns in the row of
-// the group's term 0, terms `ld` apart.
-template <bool KN>
-__device__ __forceinline__ void ffn_load_b(const float *at, size_t ld, float (&b)[2][8]) {
-    if constexpr (KN) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const f32x2 v = *reinterpret_cast<const f32x2 *>(at + (size_t)e * ld);
-            b[0][e] = v.x; b[1][e] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            const f32x4 lo = *reinterpret_cast<const f32x4 *>(at + (size_t)(16 * ct) * ld);
-            const f32x4 hi = *reinterpret_cast<const f32x4 *>(at + (size_t)(16 * ct) * ld + 4);
-            b[ct][0] = lo.x; b[ct][1] = lo.y; b[ct][2] = lo.z; b[ct][3] = lo.w;
-            b[ct][4] = hi.x; b[ct][5] = hi.y; b[ct][6] = hi.z; b[ct][7] = hi.w;
-        }
-    }
-}
-
-// the same operand from a bf16 image whose rows hold the reduction terms: `at` as for KN = false; the 16 bytes are the
-// lane's fragment of a column tile
-__device__ __forceinline__ void ffn_load_b(const __bf16 *at, size_t ld, bf16x8 (&b)[2]) {
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) b[ct] = *reinterpret_cast<const bf16x8 *>(at + (size_t)(16 * ct) * ld);
-}
-
-// one group of 32 terms.  BF: the "bf16" arithmetic, one instruction per tile on the same eight registers, rounded and
-// packed pairwise (csrc/t5_common.h)
-template <int RT, bool BF>
-__device__ __forceinline__ void ffn_mma(const float (&a)[RT][8], const float (&b)[2][8], f32x4 (&acc)[RT][2]) {
-    if constexpr (BF) {
-        const bf16x8 b0 = pack_bf16x8(b[0]), b1 = pack_bf16x8(b[1]);
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            const bf16x8 ar = pack_bf16x8(a[rt]);
-            acc[rt][0] = mma_group_bf16(ar, b0, acc[rt][0]);
-            acc[rt][1] = mma_group_bf16(ar, b1, acc[rt][1]);
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], b[ct][e], acc[rt][ct], 0, 0, 0);
-    }
-}
-
-// the "bf16" arithmetic on weight fragments that come packed from an image
-template <int RT, bool BF>
-__device__ __forceinline__ void ffn_mma(const float (&a)[RT][8], const bf16x8 (&b)[2], f32x4 (&acc)[RT][2]) {
-    static_assert(BF, "weight images belong to the bf16 arithmetic");
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        const bf16x8 ar = pack_bf16x8(a[rt]);
-        acc[rt][0] = mma_group_bf16(ar, b[0], acc[rt][0]);
-        acc[rt][1] = mma_group_bf16(ar, b[1], acc[rt][1]);
-    }
-}
-
-// a finished chain joins the sum of the chains before it; the next chain starts from +0
-template <int RT>
-__device__ __forceinline__ void ffn_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][2]) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sum[rt][ct][r] = sum[rt][ct][r] + run[rt][ct][r];
-            run[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-}
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // The blocked bf16 image of an activation [N, C] (include/rqhip.h): element (n, c) is number ((n >> 5) * C + c) * 32 +
 // 8 * (n & 3) + ((n & 31) >> 2), so the rows 4 ks + kq of a block, ks = 0 .. 7, are 16 consecutive bytes per column.
@@ -205,9 +104,6 @@ __device__ __forceinline__ void ffn_store_image(const float *src, int ld, int nc
         *reinterpret_cast<decltype(v) *>(base + (size_t)c * 32 + 8 * kq) = v;
     }
 }
-
-// keeps a round's loads together and in front of the previous round's matrix instructions (csrc/mlp_small.hip)
-#define FFN_FENCE __builtin_amdgcn_sched_barrier(0)
 
 // RT: 16-row tiles per workgroup; NP: column pairs (32 output columns) per wave, >= ceil(d / 128); BF: the "bf16"
 // arithmetic (memory, LDS and the epilogues stay fp32: the operands are rounded as the fragments are packed); IMG: the
@@ -259,7 +155,7 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
     // matrix instructions of one round run, the next round's loads are in flight; a phase's first round is requested
     // before the other phase ends (phase 2's over the epilogue and the barrier, the next chunk's phase 1 over phase 2).
     constexpr int RG = 2;                          // groups per round of phase 1: two rounds are one chain
-    static_assert(kFfnChainGroups == 2 * RG, "a chain is closed after every second round");
+    static_assert(kChainGroups == 2 * RG, "a chain is closed after every second round");
     const int nr1 = (ngd + RG - 1) / RG;
     const size_t ld1 = KN ? (size_t)F : (size_t)d, ld2 = KN ? (size_t)d : (size_t)F;
     WB pb[2][RG];                                  // phase 1: two rounds
@@ -270,8 +166,8 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
             const int g = min(RG * r + gg, ngd - 1);      // past d: a valid group is read and not used
             const WT *at = KN ? w1 + (size_t)(32 * g + 8 * kq) * F + fw + 2 * i
                               : w1 + (size_t)(fw + i) * d + 32 * g + 8 * kq;
-            if constexpr (IMG) ffn_load_b(at, ld1, dst[gg]);
-            else ffn_load_b<KN>(at, ld1, dst[gg]);
+            if constexpr (IMG) load_b(at, ld1, dst[gg]);
+            else load_b<KN>(at, ld1, dst[gg]);
         }
     };
     auto comp1 = [&](const WB (&src)[RG], int r, f32x4 (&run)[RT][2]) {
@@ -281,7 +177,7 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
             if (g < ngd) {
                 float a[RT][8];
                 ffn_load_a<RT>(xs + i * ldx + 8 * kq, ldx, 32 * g, a);
-                ffn_mma<RT, BF>(a, src[gg], run);
+                mma<RT, BF>(a, src[gg], run);
             }
         }
     };
@@ -292,8 +188,8 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
             if (pair < npairs) {
                 const WT *at = KN ? w2 + (size_t)(f0 + 32 * g + 8 * kq) * d + 32 * pair + 2 * i
                                   : w2 + (size_t)(32 * pair + i) * F + f0 + 32 * g + 8 * kq;
-                if constexpr (IMG) ffn_load_b(at, ld2, dst[q]);
-                else ffn_load_b<KN>(at, ld2, dst[q]);
+                if constexpr (IMG) load_b(at, ld2, dst[q]);
+                else load_b<KN>(at, ld2, dst[q]);
             }
         }
     };
@@ -302,7 +198,7 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
         ffn_load_a<RT>(hb + i * kFfnLdh + 8 * kq, kFfnLdh, 32 * g, a);
 #pragma unroll
         for (int q = 0; q < NP; ++q)
-            if (w + 4 * q < npairs) ffn_mma<RT, BF>(a, src[q], run[q]);
+            if (w + 4 * q < npairs) mma<RT, BF>(a, src[q], run[q]);
     };
 
     if (32 * w < F) load1(pb[0], 32 * w, 0);
@@ -343,16 +239,16 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
             }
             for (int r = 0; r < nr1; r += 2) {
                 if (r + 1 < nr1) load1(pb[1], fw, r + 1);
-                FFN_FENCE; comp1(pb[0], r, run1); FFN_FENCE;
+                T5_FENCE; comp1(pb[0], r, run1); T5_FENCE;
                 if (r + 1 < nr1) {
                     if (r + 2 < nr1) load1(pb[0], fw, r + 2);
-                    FFN_FENCE; comp1(pb[1], r + 1, run1); FFN_FENCE;
+                    T5_FENCE; comp1(pb[1], r + 1, run1); T5_FENCE;
                 }
-                ffn_close<RT>(acc1, run1);      // rounds r and r + 1: 4 groups
+                chain_close<RT>(acc1, run1);      // rounds r and r + 1: 4 groups
             }
         }
         if (p.out) load2(qb[0], f0, 0);
-        FFN_FENCE;
+        T5_FENCE;
         if (fw < F) {
             // acc1[rt][ct][r]: row 16 rt + 4 kq + r; column 16 ct + i (forward, images) or 2 i + ct (backward) of the wave's 32
 #pragma unroll
@@ -401,14 +297,14 @@ __global__ __launch_bounds__(256) void t5_ffn_rows_kernel(const FfnRows p) {
                     for (int ct = 0; ct < 2; ++ct) run2[q][rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int g = 0; g < ng; g += 2) {
                 if (g + 1 < ng) load2(qb[1], f0, g + 1);
-                FFN_FENCE; comp2(qb[0], hb, g, run2); FFN_FENCE;
+                T5_FENCE; comp2(qb[0], hb, g, run2); T5_FENCE;
                 if (g + 1 < ng) {
                     if (g + 2 < ng) load2(qb[0], f0, g + 2);
-                    FFN_FENCE; comp2(qb[1], hb, g + 1, run2); FFN_FENCE;
+                    T5_FENCE; comp2(qb[1], hb, g + 1, run2); T5_FENCE;
                 }
             }
 #pragma unroll
-            for (int q = 0; q < NP; ++q) ffn_close<RT>(acc2[q], run2[q]);
+            for (int q = 0; q < NP; ++q) chain_close<RT>(acc2[q], run2[q]);
         }
     }
     if (!p.out) return;
@@ -462,7 +358,7 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
     const bool drop = is_wo && p.th != 0;
     const unsigned long long seed = drop ? (unsigned long long)*p.seed : 0ull;
 
-    const long long nb = (p.N + kFfnWgBlock - 1) / kFfnWgBlock;
+    const long long nb = (p.N + kWgBlock - 1) / kWgBlock;
     const long long lo = w * nb / 4, hi = (w + 1) * nb / 4;
     f32x4 tot[2][2], acc[2][2];
 #pragma unroll
@@ -474,7 +370,7 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
     auto load = [&](long long b, f32x2 (&pa)[8], f32x2 (&qb)[8]) {
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            const long long n = b * kFfnWgBlock + 4 * ks + kq;
+            const long long n = b * kWgBlock + 4 * ks + kq;
             const long long nn = n < p.N ? n : p.N - 1;
             pa[ks] = *reinterpret_cast<const f32x2 *>(pp + (size_t)nn * lp);
             qb[ks] = *reinterpret_cast<const f32x2 *>(qp + (size_t)nn * lq);
@@ -483,7 +379,7 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
     auto comp = [&](long long b, f32x2 (&pa)[8], f32x2 (&qb)[8]) {
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            const long long n = b * kFfnWgBlock + 4 * ks + kq;
+            const long long n = b * kWgBlock + 4 * ks + kq;
             if (drop) {
                 const unsigned long long e = (unsigned long long)n * p.F + (unsigned long long)(b0 + 2 * i);
                 qb[ks].x = dropout_keep(seed, e, p.th) ? qb[ks].x * p.s : 0.f;
@@ -511,25 +407,16 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad_kernel(const FfnWgrad p) {
                     for (int bt = 0; bt < 2; ++bt)
                         acc[at][bt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ks][at], qb[ks][bt], acc[at][bt], 0, 0, 0);
         }
-        if (((b - lo) & (kFfnWgFlush - 1)) == kFfnWgFlush - 1) {
-#pragma unroll
-            for (int at = 0; at < 2; ++at)
-#pragma unroll
-                for (int bt = 0; bt < 2; ++bt) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) tot[at][bt][r] = tot[at][bt][r] + acc[at][bt][r];
-                    acc[at][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-        }
+        if (((b - lo) & (kWgFlush - 1)) == kWgFlush - 1) chain_close<2>(tot, acc);
     };
     f32x2 pa0[8], qb0[8], pa1[8], qb1[8];      // two blocks: the next one's loads are in flight over this one's instructions
     if (lo < hi) load(lo, pa0, qb0);
     for (long long b = lo; b < hi; b += 2) {
         if (b + 1 < hi) load(b + 1, pa1, qb1);
-        FFN_FENCE; comp(b, pa0, qb0); FFN_FENCE;
+        T5_FENCE; comp(b, pa0, qb0); T5_FENCE;
         if (b + 1 < hi) {
             if (b + 2 < hi) load(b + 2, pa0, qb0);
-            FFN_FENCE; comp(b + 1, pa1, qb1); FFN_FENCE;
+            T5_FENCE; comp(b + 1, pa1, qb1); T5_FENCE;
         }
     }
     // acc[at][bt][r]: row 2 (4 kq + r) + at, column 2 i + bt of the tile (the lanes' own column pairs on both sides)
@@ -576,7 +463,7 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad16_kernel(const FfnWgrad16 p)
     float *out = is_wo ? p.d_wo : p.d_wi;
     const int a0 = 32 * (tile / (lq >> 5)), b0 = 32 * (tile % (lq >> 5));
 
-    const long long nb = (p.N + kFfnWgBlock - 1) / kFfnWgBlock;
+    const long long nb = (p.N + kWgBlock - 1) / kWgBlock;
     const long long lo = w * nb / 4, hi = (w + 1) * nb / 4;
     f32x4 tot[2][2], acc[2][2];
 #pragma unroll
@@ -593,10 +480,10 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad16_kernel(const FfnWgrad16 p)
         fr[3] = *reinterpret_cast<const bf16x8 *>(qb + 16 * 32);
     };
     auto comp = [&](long long b, bf16x8 (&fr)[4]) {
-        if ((b + 1) * kFfnWgBlock > p.N) {      // the last block: rows past the batch are unspecified in memory and count as zero
+        if ((b + 1) * kWgBlock > p.N) {      // the last block: rows past the batch are unspecified in memory and count as zero
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks)
-                if (b * kFfnWgBlock + 4 * ks + kq >= p.N) {
+                if (b * kWgBlock + 4 * ks + kq >= p.N) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) fr[k][ks] = (__bf16)0.f;
                 }
@@ -605,25 +492,16 @@ __global__ __launch_bounds__(256) void t5_ffn_wgrad16_kernel(const FfnWgrad16 p)
         for (int at = 0; at < 2; ++at)
 #pragma unroll
             for (int bt = 0; bt < 2; ++bt) acc[at][bt] = mma_group_bf16(fr[at], fr[2 + bt], acc[at][bt]);
-        if (((b - lo) & (kFfnWgFlush - 1)) == kFfnWgFlush - 1) {
-#pragma unroll
-            for (int at = 0; at < 2; ++at)
-#pragma unroll
-                for (int bt = 0; bt < 2; ++bt) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) tot[at][bt][r] = tot[at][bt][r] + acc[at][bt][r];
-                    acc[at][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-        }
+        if (((b - lo) & (kWgFlush - 1)) == kWgFlush - 1) chain_close<2>(tot, acc);
     };
     bf16x8 f0[4], f1[4];      // two blocks: the next one's loads are in flight over this one's instructions
     if (lo < hi) load(lo, f0);
     for (long long b = lo; b < hi; b += 2) {
         if (b + 1 < hi) load(b + 1, f1);
-        FFN_FENCE; comp(b, f0); FFN_FENCE;
+        T5_FENCE; comp(b, f0); T5_FENCE;
         if (b + 1 < hi) {
             if (b + 2 < hi) load(b + 2, f0);
-            FFN_FENCE; comp(b + 1, f1); FFN_FENCE;
+            T5_FENCE; comp(b + 1, f1); T5_FENCE;
         }
     }
     // acc[at][bt][r]: row 16 at + 4 kq + r, column 16 bt + i of the tile
@@ -712,7 +590,7 @@ extern "C" int rqhip_t5_ffn_supported(int d, int F) { return ffn_supported(d, F)
 
 extern "C" size_t rqhip_t5_ffn_act_image_bytes(int64_t N, int C) {
     if (N < 0 || C < 32 || C % 32) return 0;
-    return (size_t)((N + kFfnWgBlock - 1) / kFfnWgBlock) * (size_t)C * kFfnWgBlock * sizeof(rqhip_bf16_t);
+    return (size_t)((N + kWgBlock - 1) / kWgBlock) * (size_t)C * kWgBlock * sizeof(rqhip_bf16_t);
 }
 
 extern "C" size_t rqhip_t5_ffn_bwd_bf16a_workspace_bytes(int64_t N, int d, int F) {

@@ -20,8 +20,6 @@ namespace rqhip {
 
 namespace {
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kImgTile = 32;
 constexpr int kImgLd = kImgTile + 2;      // LDS row stride in elements: an odd number of words
 

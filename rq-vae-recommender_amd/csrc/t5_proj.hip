@@ -1,10 +1,7 @@
 // t5_proj.hip -- a group of up to 8 bias-free linear maps that share their input rows (the q / k / v, the o and the
 // cross-attention K/V projections of modules/t5.py, proj_impl = "hip") as one launch forward and at most two backward
-// (gfx950; semantics and arithmetic contract in include/rqhip.h).  Exact fp32 on v_mfma_f32_16x16x4_f32 with the operand
-// layout, the group order and the chain rule of csrc/t5_ffn.hip: lane (i, kq) = (lane & 15, lane >> 4) supplies k-slot
-// kq of row / column i and holds the terms 8 kq .. 8 kq + 7 of a GROUP of 32; 4 groups are one chain from +0, and a
-// reduction's chains are added in ascending order from +0.  (The operand loaders below restate t5_ffn.hip's, which
-// keeps them in its own anonymous namespace.)
+// (gfx950; semantics and arithmetic contract in include/rqhip.h).  The operand layout, the group order, the chain rule,
+// the operand loaders and the weight-gradient rule are csrc/t5_matmul.h's, which csrc/t5_ffn.hip uses too.
 //
 // Row kernel (forward, and the data gradient with the weights in the other orientation).  A workgroup of 4 waves owns
 // a tile of 16 rows (more for long batches, below) and ONE chunk of 128 output columns, 32 per wave: grid (row tiles, chunks).  The chain order depends on the
@@ -24,36 +21,26 @@
 // whatever the height, so a taller tile divides that traffic; short batches (the model's 5184 and 256 rows at batch 64)
 // are short of workgroups instead and keep 16.  The height follows N alone, and the chains do not depend on it.
 //
-// Weight-gradient kernel: t5_ffn.hip's.  Every 32 x 32 tile of every wanted d_w[j] has one owning workgroup, which
-// reduces over all N rows: blocks of 32 rows, wave w of 4 takes the contiguous range of blocks [w nb / 4, (w + 1) nb /
-// 4), starts a fresh chain every 8 blocks and adds the finished chains in ascending order; the four waves' sums meet in
-// LDS and are added in wave order.  No partial blocks in memory, no atomics, no reduction launch.
+// Weight-gradient kernel: every 32 x 32 tile of every wanted d_w[j] has one owning workgroup, which reduces d_y[j]^T . x
+// over all N rows by the weight-gradient rule of csrc/t5_matmul.h.
 //
-// Second arithmetic, "bf16" (template parameter BF, entry points rqhip_t5_proj_*_bf16): t5_ffn.hip's, one
-// v_mfma_f32_16x16x32_bf16 per group on the same eight registers, rounded to bf16 and packed in front of it
-// (csrc/t5_common.h); loads, chains and stores do not change.
-//
-// Weight images (template parameter IMG of the row kernel, with BF only; entry points rqhip_t5_proj_*_bf16w):
-// t5_ffn.hip's.  The weights come from bf16 images (csrc/t5_images.hip) and the reduction runs along their rows, forward
-// w16[j] [d_out, d_in], d_x the TRANSPOSED images w16t[j] [d_in, d_out]: one 16-byte load per column tile is the B
-// fragment as it stands, and d_x's lanes serve column 16 ct + i like the forward's.  Bits are the BF arm's.
+// Second arithmetic, "bf16" (template parameter BF, entry points rqhip_t5_proj_*_bf16), and weight images (template
+// parameter IMG of the row kernel, with BF only; entry points rqhip_t5_proj_*_bf16w): as csrc/t5_ffn.hip's.  The images
+// (csrc/t5_images.hip) are read along their rows, forward w16[j] [d_out, d_in], d_x the TRANSPOSED images w16t[j]
+// [d_in, d_out], and d_x's lanes serve column 16 ct + i like the forward's.  Bits are the BF arm's.
 #include <type_traits>
 
 #include "rqhip_common.h"
 #include "t5_common.h"
+#include "t5_matmul.h"
 
 namespace rqhip {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kProjMaxD = 512, kProjMaxN = 8;
 constexpr int kProjChunk = 128;        // output columns per workgroup of the row kernel: 32 per wave
-constexpr int kProjChainGroups = 4;    // groups of 32 terms per chain: 128 terms
 constexpr long long kProjTallFrom = 16384;   // rows above which a row tile is 64 high (32 above half of it)
-constexpr int kProjWgBlock = 32;       // rows per block of the weight-gradient reduction
-constexpr int kProjWgFlush = 8;        // blocks per chain
 
 bool proj_supported(int d_in, int d_out, int n) {
     return d_in >= 32 && d_in <= kProjMaxD && d_in % 32 == 0 && d_out >= 32 && d_out <= kProjMaxD && d_out % 32 == 0 &&
@@ -70,93 +57,6 @@ struct ProjRows {
     long long N;
     int n, d_in, d_out;
 };
-
-// the weight operand of one group for two 16-column tiles.  KN = false: `at` points at term 0 of the group in the row
-// of tile 0's column, rows `ld` apart (tile 1: 16 rows on).  KN = true: `at` points at the lane's 2 columns in the row
-// of the group's term 0, terms `ld` apart: the lane serves column 2 i + ct in column tile ct.
-template <bool KN>
-__device__ __forceinline__ void proj_load_b(const float *at, size_t ld, float (&b)[2][8]) {
-    if constexpr (KN) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const f32x2 v = *reinterpret_cast<const f32x2 *>(at + (size_t)e * ld);
-            b[0][e] = v.x; b[1][e] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            const f32x4 lo = *reinterpret_cast<const f32x4 *>(at + (size_t)(16 * ct) * ld);
-            const f32x4 hi = *reinterpret_cast<const f32x4 *>(at + (size_t)(16 * ct) * ld + 4);
-            b[ct][0] = lo.x; b[ct][1] = lo.y; b[ct][2] = lo.z; b[ct][3] = lo.w;
-            b[ct][4] = hi.x; b[ct][5] = hi.y; b[ct][6] = hi.z; b[ct][7] = hi.w;
-        }
-    }
-}
-
-// the same operand from a bf16 image whose rows hold the reduction terms: `at` as for KN = false; the 16 bytes are the
-// lane's fragment of a column tile
-__device__ __forceinline__ void proj_load_b(const __bf16 *at, size_t ld, bf16x8 (&b)[2]) {
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) b[ct] = *reinterpret_cast<const bf16x8 *>(at + (size_t)(16 * ct) * ld);
-}
-
-__device__ __forceinline__ void proj_load_a(const float *at, float (&a)[8]) {
-    const f32x4 lo = *reinterpret_cast<const f32x4 *>(at);
-    const f32x4 hi = *reinterpret_cast<const f32x4 *>(at + 4);
-    a[0] = lo.x; a[1] = lo.y; a[2] = lo.z; a[3] = lo.w;
-    a[4] = hi.x; a[5] = hi.y; a[6] = hi.z; a[7] = hi.w;
-}
-
-// one group of 32 terms.  BF: the "bf16" arithmetic, one instruction per tile on the same eight registers, rounded and
-// packed pairwise (csrc/t5_common.h)
-template <int RT, bool BF>
-__device__ __forceinline__ void proj_mma(const float (&a)[RT][8], const float (&b)[2][8], f32x4 (&acc)[RT][2]) {
-    if constexpr (BF) {
-        const bf16x8 b0 = pack_bf16x8(b[0]), b1 = pack_bf16x8(b[1]);
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            const bf16x8 ar = pack_bf16x8(a[rt]);
-            acc[rt][0] = mma_group_bf16(ar, b0, acc[rt][0]);
-            acc[rt][1] = mma_group_bf16(ar, b1, acc[rt][1]);
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], b[ct][e], acc[rt][ct], 0, 0, 0);
-    }
-}
-
-// the "bf16" arithmetic on weight fragments that come packed from an image
-template <int RT, bool BF>
-__device__ __forceinline__ void proj_mma(const float (&a)[RT][8], const bf16x8 (&b)[2], f32x4 (&acc)[RT][2]) {
-    static_assert(BF, "weight images belong to the bf16 arithmetic");
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        const bf16x8 ar = pack_bf16x8(a[rt]);
-        acc[rt][0] = mma_group_bf16(ar, b[0], acc[rt][0]);
-        acc[rt][1] = mma_group_bf16(ar, b[1], acc[rt][1]);
-    }
-}
-
-// a finished chain joins the sum of the chains before it; the next chain starts from +0
-template <int RT>
-__device__ __forceinline__ void proj_close(f32x4 (&sum)[RT][2], f32x4 (&run)[RT][2]) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sum[rt][ct][r] = sum[rt][ct][r] + run[rt][ct][r];
-            run[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-}
-
-// keeps a step's loads together and in front of the previous step's matrix instructions (csrc/mlp_small.hip)
-#define PROJ_FENCE __builtin_amdgcn_sched_barrier(0)
 
 // RT: 16-row tiles per workgroup; BF: the "bf16" arithmetic (the operands are rounded as the fragments are packed); IMG:
 // the weights are bf16 images read along their rows (d_x's are the transposed ones)
@@ -184,14 +84,14 @@ __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
     auto load = [&](float (&a)[RT][8], WB &b) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
-            proj_load_a(p.a[seg] + (size_t)arow[rt] * (size_t)p.ld_a[seg] + 32 * g + 8 * kq, a[rt]);
+            load_a(p.a[seg] + (size_t)arow[rt] * (size_t)p.ld_a[seg] + 32 * g + 8 * kq, a[rt]);
         if constexpr (IMG) {       // row c0 + i of the image: the ld terms of the output column's reduction
             const size_t ld = BWD ? (size_t)d_out : (size_t)d_in;
-            proj_load_b(reinterpret_cast<const WT *>(p.w[BWD ? seg : jo]) + (size_t)(c0 + i) * ld + 32 * g + 8 * kq, ld, b);
+            load_b(reinterpret_cast<const WT *>(p.w[BWD ? seg : jo]) + (size_t)(c0 + i) * ld + 32 * g + 8 * kq, ld, b);
         } else {
             const float *at = BWD ? p.w[seg] + (size_t)(32 * g + 8 * kq) * d_in + c0 + 2 * i
                                   : p.w[jo] + (size_t)(c0 + i) * d_in + 32 * g + 8 * kq;
-            proj_load_b<BWD>(at, (size_t)d_in, b);
+            load_b<BWD>(at, (size_t)d_in, b);
         }
         if (++g == ng) g = 0, ++seg;
     };
@@ -207,15 +107,15 @@ __global__ __launch_bounds__(256) void t5_proj_rows_kernel(const ProjRows p) {
     load(a0, b0);
     for (int it = 0; it < total; it += 2) {
         if (it + 1 < total) load(a1, b1);
-        PROJ_FENCE; proj_mma<RT, BF>(a0, b0, run); PROJ_FENCE;
+        T5_FENCE; mma<RT, BF>(a0, b0, run); T5_FENCE;
         if (it + 1 < total) {
             if (it + 2 < total) load(a0, b0);
-            PROJ_FENCE; proj_mma<RT, BF>(a1, b1, run); PROJ_FENCE;
+            T5_FENCE; mma<RT, BF>(a1, b1, run); T5_FENCE;
         }
-        // kProjChainGroups is even: a chain ends behind an odd step, or with the reduction
-        if (((it + 1) & (kProjChainGroups - 1)) == kProjChainGroups - 1 || it + 2 >= total) proj_close<RT>(sum, run);
+        // kChainGroups is even: a chain ends behind an odd step, or with the reduction
+        if (((it + 1) & (kChainGroups - 1)) == kChainGroups - 1 || it + 2 >= total) chain_close<RT>(sum, run);
     }
-    static_assert(kProjChainGroups % 2 == 0, "chains are closed after every second step");
+    static_assert(kChainGroups % 2 == 0, "chains are closed after every second step");
 
     // sum[rt][ct][r]: row 16 rt + 4 kq + r; column 16 ct + i (forward, images) or 2 i + ct (d_x) of the wave's 32
     float *o = p.out[jo] + c0;
@@ -259,7 +159,7 @@ __global__ __launch_bounds__(256) void t5_proj_wgrad_kernel(const ProjWgrad p) {
     float *out = p.dw[job];
     const int a0 = 32 * (tile / (p.d_in >> 5)), b0 = 32 * (tile % (p.d_in >> 5));
 
-    const long long nb = (p.N + kProjWgBlock - 1) / kProjWgBlock;
+    const long long nb = (p.N + kWgBlock - 1) / kWgBlock;
     const long long lo = w * nb / 4, hi = (w + 1) * nb / 4;
     f32x4 tot[2][2], acc[2][2];
 #pragma unroll
@@ -271,7 +171,7 @@ __global__ __launch_bounds__(256) void t5_proj_wgrad_kernel(const ProjWgrad p) {
     auto load = [&](long long b, f32x2 (&pa)[8], f32x2 (&qb)[8]) {
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            const long long n = b * kProjWgBlock + 4 * ks + kq;
+            const long long n = b * kWgBlock + 4 * ks + kq;
             const long long nn = n < p.N ? n : p.N - 1;
             pa[ks] = *reinterpret_cast<const f32x2 *>(pp + (size_t)nn * lp);
             qb[ks] = *reinterpret_cast<const f32x2 *>(qp + (size_t)nn * lq);
@@ -280,7 +180,7 @@ __global__ __launch_bounds__(256) void t5_proj_wgrad_kernel(const ProjWgrad p) {
     auto comp = [&](long long b, f32x2 (&pa)[8], f32x2 (&qb)[8]) {
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            const long long n = b * kProjWgBlock + 4 * ks + kq;
+            const long long n = b * kWgBlock + 4 * ks + kq;
             if (n >= p.N) pa[ks] = qb[ks] = f32x2{0.f, 0.f};
         }
         if constexpr (BF) {
@@ -303,25 +203,16 @@ __global__ __launch_bounds__(256) void t5_proj_wgrad_kernel(const ProjWgrad p) {
                     for (int bt = 0; bt < 2; ++bt)
                         acc[at][bt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ks][at], qb[ks][bt], acc[at][bt], 0, 0, 0);
         }
-        if (((b - lo) & (kProjWgFlush - 1)) == kProjWgFlush - 1) {
-#pragma unroll
-            for (int at = 0; at < 2; ++at)
-#pragma unroll
-                for (int bt = 0; bt < 2; ++bt) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) tot[at][bt][r] = tot[at][bt][r] + acc[at][bt][r];
-                    acc[at][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-        }
+        if (((b - lo) & (kWgFlush - 1)) == kWgFlush - 1) chain_close<2>(tot, acc);
     };
     f32x2 pa0[8], qb0[8], pa1[8], qb1[8];      // two blocks: the next one's loads are in flight over this one's instructions
     if (lo < hi) load(lo, pa0, qb0);
     for (long long b = lo; b < hi; b += 2) {
         if (b + 1 < hi) load(b + 1, pa1, qb1);
-        PROJ_FENCE; comp(b, pa0, qb0); PROJ_FENCE;
+        T5_FENCE; comp(b, pa0, qb0); T5_FENCE;
         if (b + 1 < hi) {
             if (b + 2 < hi) load(b + 2, pa0, qb0);
-            PROJ_FENCE; comp(b + 1, pa1, qb1); PROJ_FENCE;
+            T5_FENCE; comp(b + 1, pa1, qb1); T5_FENCE;
         }
     }
     // acc[at][bt][r]: row 2 (4 kq + r) + at, column 2 i + bt of the tile (the lanes' own column pairs on both sides)
