@@ -406,6 +406,55 @@ int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const f
                            const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *d_q, float *d_k,
                            float *d_v, float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream);
 
+/* The same three calls on PACKED variable-length rows (csrc/t5_attention.hip, the same kernel bodies): R groups, one
+ * K/V per group, whose tokens lie in 2-D tensors without padding.  cu_q and cu_k are int32 [R + 1] cumulative row
+ * tables on the device, either of which may be NULL (not both):
+ *   with cu_k the keys of group b are rows cu_k[b] .. cu_k[b + 1] - 1 of k, v [n_k, H * 64] (row stride ld_kv) and of
+ *     d_k, d_v (dense); with cu_q the same holds for q, out, d_out [n_q, H * 64] (their strides) and d_q (dense);
+ *   NULL is the dense layout above for that side (row b * T + t; n_q = R * Tq, n_k = R * Tk): the cross-attention is
+ *     dense decoder queries over packed K/V.
+ * Tq and Tk are the padded lengths, upper BOUNDS of every group's own: they keep the bias index (j - i), the dropout
+ * element index ((b * H + h) * Tq + i) * Tk + j, the kernel instantiation and the LDS layout of the padded call, and a
+ * group's own lengths give its loops, its row bases and the K/V rows it stages.  A table entry is clamped to [0, n] and a
+ * length to its bound: a bad table gives an empty or a short group, never an address.  Every packed key is valid:
+ * key_mask must be NULL and causal 0 (RQHIP_EARG otherwise; both stay in the signature to say so), beams = 1, no `past`.
+ *   lse: [n_q, H] with cu_q (a token's heads side by side), [R, H, Tq] without.
+ *   d_bias_partial: [R * H, Tq + Tk - 1] as above.
+ *   A group without keys gives out = 0, lse = -inf and d_q = 0; one without queries gives d_k = d_v = 0.
+ * On every valid (group, head, query, key) out, lse, d_q, d_k, d_v and the rows of d_bias_partial have the BITS of the
+ * padded call on the scattered tensors with the prefix key mask (and d_out = 0 on the padded query rows): a masked
+ * key's weight is exactly 0 there, its dS and its share of every sum too, and a skipped key tile is a sum of zeros that
+ * is not added.  Limits: those of rqhip_t5_attention_bwd_supported on the bounds; n_q, n_k < 2^31. */
+int rqhip_t5_attention_packed_supported(int d_kv, int H, int Tq, int Tk);
+int rqhip_t5_attention_packed(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, int64_t R,
+                              int64_t n_q, int64_t n_k, int H, int d_kv, int Tq, int Tk, const int32_t *cu_q,
+                              const int32_t *cu_k, const float *bias_by_delta, int n_delta, int bias_offset,
+                              const uint8_t *key_mask, int causal, float *out, int64_t ld_out, rqhip_stream_t stream);
+int rqhip_t5_attention_packed_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                        int64_t R, int64_t n_q, int64_t n_k, int H, int d_kv, int Tq, int Tk,
+                                        const int32_t *cu_q, const int32_t *cu_k, const float *bias_by_delta,
+                                        int n_delta, int bias_offset, const uint8_t *key_mask, int causal, double p,
+                                        const int64_t *seed, float *out, int64_t ld_out, float *lse,
+                                        rqhip_stream_t stream);
+int rqhip_t5_attention_packed_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                  const float *out, int64_t ld_out, const float *lse, const float *d_out, int64_t ld_do,
+                                  int64_t R, int64_t n_q, int64_t n_k, int H, int d_kv, int Tq, int Tk,
+                                  const int32_t *cu_q, const int32_t *cu_k, const float *bias_by_delta, int n_delta,
+                                  int bias_offset, const uint8_t *key_mask, int causal, double p, const int64_t *seed,
+                                  float *d_q, float *d_k, float *d_v, float *d_bias_by_delta, float *d_bias_partial,
+                                  rqhip_stream_t stream);
+
+/* Between padded [B, T, d] rows and packed [N, d] rows (csrc/rows_pack.hip), fp32, d a multiple of 4
+ * (rqhip_rows_pack_supported), 16-byte accesses.  cu: int32 [B + 1] on the device, clamped as above.
+ *   rqhip_rows_pack: out[cu[b] + t] = x[b, t] for t < cu[b + 1] - cu[b]; rows of out no group covers are not written.
+ *   rqhip_rows_unpack: out[b, t] = x[cu[b] + t] for those t and 0 for the padded tail, in the same launch.
+ * Exact copies; each is the other's backward.  No allocation, copy or sync. */
+int rqhip_rows_pack_supported(int d);
+int rqhip_rows_pack(const float *x, const int32_t *cu, int64_t B, int T, int d, int64_t N, float *out,
+                    rqhip_stream_t stream);
+int rqhip_rows_unpack(const float *x, const int32_t *cu, int64_t B, int T, int d, int64_t N, float *out,
+                      rqhip_stream_t stream);
+
 /* The same attention beyond 256 tokens (csrc/t5_attention_long.hip): inference, training forward and backward for
  * 1 <= Tq, Tk <= 2048 (rqhip_t5_attention_long_supported: d_kv = 64, any H >= 1; shorter lengths are accepted too).  The
  * mathematics, the T5 semantics, q / k / v / out, bias_by_delta, bias_offset, key_mask, causal, the K/V groups (R / Rk

@@ -49,6 +49,8 @@ struct AttArgs {
     const unsigned char *key_mask;  // [Rk, Tk] or null
     const int *anc;     // [R, ld_anc] or null (dense K/V)
     long long ld_anc, slab_rows;
+    const int *cu_q, *cu_k;  // the packed kernels' cumulative row tables [groups + 1], each may be null (that side dense)
+    long long n_q, n_k;      // rows of the packed q / out and k / v tensors
 };
 
 // What the training forward adds to a call: the row log-sum-exp and the dropout of the normalised weights.
@@ -61,26 +63,36 @@ struct AttTrain {
 
 // The dropout decision of element idx = ((r * H + h) * Tq + i) * Tk + j is dropout_keep(seed, idx, thresh) of t5_common.h.
 
-template <int MT, bool TRAIN>
+// PACKED (beams = 1, no key mask, no ancestor table): a.Tq and a.Tk are the padded BOUNDS -- they keep the LDS layout, the
+// bias index and the dropout element index of the padded call -- and the workgroup's own lengths Tq, Tk, read through the
+// cumulative tables, give its loop bounds, its row bases and the K/V rows it stages.
+template <int MT, bool TRAIN, bool PACKED>
 __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
     extern __shared__ float att_lds[];
-    const int ntiles = (a.Tk + 15) >> 4, Tkp = ntiles << 4;
-    float *Ks = att_lds;
-    float *Vs = Ks + (size_t)Tkp * kAttLd;
-    float *madd = Vs + (size_t)Tkp * kAttLd;  // 0: kept, -FLT_MAX: masked, -inf: padding beyond Tk
-    float *bias_s = madd + Tkp;               // [Tq + Tk - 1] of this head, by j - i + Tq - 1
-
     const long long b = blockIdx.x / a.H;
     const int h = blockIdx.x - (int)b * a.H;
     const int tid = threadIdx.x, nthr = blockDim.x;
+
+    int Tq = a.Tq, Tk = a.Tk;                 // this group's own lengths
+    long long kbase = b * a.Tk, qbase = 0;    // first K/V row; first q / out row of a packed q
+    if constexpr (PACKED) {
+        if (a.cu_k) packed_group(a.cu_k, b, a.n_k, a.Tk, kbase, Tk);
+        if (a.cu_q) packed_group(a.cu_q, b, a.n_q, a.Tq, qbase, Tq);
+    }
+    const int ntiles = (Tk + 15) >> 4, Tkp = ntiles << 4;
+    const int TkpL = ((a.Tk + 15) >> 4) << 4;  // the layout's
+    float *Ks = att_lds;
+    float *Vs = Ks + (size_t)TkpL * kAttLd;
+    float *madd = Vs + (size_t)TkpL * kAttLd;  // 0: kept, -FLT_MAX: masked, -inf: padding beyond Tk
+    float *bias_s = madd + TkpL;               // [Tq + Tk - 1] of this head, by j - i + Tq - 1
 
     // ---- stage K, V (zeros beyond Tk: 0 * p must stay 0), the key mask and the head's bias column
     for (int idx = tid; idx < Tkp * 16; idx += nthr) {
         const int j = idx >> 4, c = idx & 15;
         float4 kk = make_float4(0.f, 0.f, 0.f, 0.f), vv = kk;
-        if (j < a.Tk) {
+        if (j < Tk) {
             long long tok;
-            if (a.anc) {
+            if (!PACKED && a.anc) {
                 long long row = b;
                 if (j < a.past) {
                     row = a.anc[b * a.ld_anc + j];
@@ -88,7 +100,7 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
                 }
                 tok = (long long)j * a.slab_rows + row;
             } else {
-                tok = b * a.Tk + j;
+                tok = kbase + j;
             }
             const size_t off = (size_t)tok * (size_t)a.ld_kv + (size_t)h * kAttD + 4 * c;
             kk = *reinterpret_cast<const float4 *>(a.k + off);
@@ -98,19 +110,20 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
         *reinterpret_cast<float4 *>(Vs + j * kAttLd + 4 * c) = vv;
     }
     for (int j = tid; j < Tkp; j += nthr)
-        madd[j] = j >= a.Tk ? -INFINITY : ((a.key_mask && !a.key_mask[b * a.Tk + j]) ? -FLT_MAX : 0.f);
+        madd[j] = j >= Tk ? -INFINITY : ((!PACKED && a.key_mask && !a.key_mask[b * a.Tk + j]) ? -FLT_MAX : 0.f);
     if (a.bias)
         for (int x = tid; x < a.Tq + a.Tk - 1; x += nthr) bias_s[x] = a.bias[(size_t)(a.bias_base + x) * a.H + h];
     __syncthreads();
 
     const int nw = nthr / RQ_WAVE, wave = tid / RQ_WAVE, lane = tid & (RQ_WAVE - 1);
     const int i = lane & 15, g = lane >> 4;
-    const int M = a.beams * a.Tq;
+    const int M = PACKED ? Tq : a.beams * a.Tq;
     for (int qt = wave; qt * 16 < M; qt += nw) {
         const int m = qt * 16 + i;
         const int mc = m < M ? m : M - 1;  // lanes past the last query recompute it and store nothing
-        const int beam = mc / a.Tq, ti = mc - beam * a.Tq;
-        const size_t qrow = (size_t)(b * a.beams + beam) * (size_t)a.Tq + (size_t)ti;
+        const int beam = PACKED ? 0 : mc / a.Tq, ti = mc - beam * a.Tq;
+        const size_t qrow = (PACKED && a.cu_q) ? (size_t)(qbase + ti)
+                                               : (size_t)(b * a.beams + beam) * (size_t)a.Tq + (size_t)ti;
         const float *qp = a.q + qrow * (size_t)a.ld_q + (size_t)h * kAttD + g;
         float qreg[16];
 #pragma unroll
@@ -136,7 +149,7 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
                         sc = -INFINITY;
                     } else {
                         if (a.bias) sc = sc + bias_s[j - ti + a.Tq - 1];
-                        if (ma != 0.f || (a.causal && j > ti + a.past)) sc = sc + -FLT_MAX;
+                        if (ma != 0.f || (!PACKED && a.causal && j > ti + a.past)) sc = sc + -FLT_MAX;
                     }
                     s[mt][r] = sc;
                     mx = fmaxf(mx, sc);
@@ -161,9 +174,14 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
         }
         sum = sum + __shfl_xor(sum, 16, RQ_WAVE);
         sum = sum + __shfl_xor(sum, 32, RQ_WAVE);
+        if constexpr (PACKED) {
+            if (ntiles == 0) sum = 1.f;  // a group without keys: out = 0 and lse = -inf, not 0 / 0
+        }
         if constexpr (TRAIN) {
             const size_t qh = ((size_t)(b * a.beams + beam) * (size_t)a.H + (size_t)h) * (size_t)a.Tq + (size_t)ti;
-            if (m < M && g == 0) t.lse[qh] = mx + logf(sum);
+            // packed q: lse is [n_q, H], a token's heads side by side
+            const size_t lrow = (PACKED && a.cu_q) ? qrow * (size_t)a.H + (size_t)h : qh;
+            if (m < M && g == 0) t.lse[lrow] = mx + logf(sum);
             if (t.thresh) {  // dropout of the normalised weights: the dropped ones leave the product, the sum stays
                 const unsigned long long seed = (unsigned long long)*t.seed;
 #pragma unroll
@@ -210,14 +228,14 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
     }
 }
 
-template <int MT>
+template <int MT, bool PACKED = false>
 __global__ __launch_bounds__(256) void t5_attention_kernel(AttArgs a) {
-    att_body<MT, false>(a, AttTrain{});
+    att_body<MT, false, PACKED>(a, AttTrain{});
 }
 
-template <int MT>
+template <int MT, bool PACKED = false>
 __global__ __launch_bounds__(256) void t5_attention_train_kernel(AttArgs a, AttTrain t) {
-    att_body<MT, true>(a, t);
+    att_body<MT, true, PACKED>(a, t);
 }
 
 size_t att_lds_bytes(int Tq, int Tk, bool bias) {
@@ -277,6 +295,8 @@ struct AttBwdArgs {
     const long long *seed;
     unsigned thresh;
     float inv_keep;
+    const int *cu_q, *cu_k;  // as in AttArgs (the packed kernels)
+    long long n_q, n_k;
 };
 
 constexpr int kAttTileLd = 17;  // row stride of the per-wave 16 x 16 dS scratch
@@ -301,22 +321,30 @@ __host__ __device__ inline AttBwdLds att_bwd_lds(int Tq, int Tk, bool bias, int 
     return l;
 }
 
-template <int MT>
+// PACKED: as in att_body -- a.Tq and a.Tk are the padded bounds (LDS layout, bias index, the partial row's width and
+// the dropout element index), Tq and Tk the workgroup's own lengths.
+template <int MT, bool PACKED = false>
 __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
     extern __shared__ float att_lds[];
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int nw = nthr / RQ_WAVE, wave = tid / RQ_WAVE, lane = tid & (RQ_WAVE - 1);
     const int i = lane & 15, g = lane >> 4;
-    const int ntiles = (a.Tk + 15) >> 4, Tkp = ntiles << 4, Tqp = ((a.Tq + 15) >> 4) << 4;
-    const int Tp = Tqp > Tkp ? Tqp : Tkp, nb = a.bias ? a.Tq + a.Tk - 1 : 0;
+    const long long b = blockIdx.x / a.H;
+    const int h = blockIdx.x - (int)b * a.H;
+    int Tq = a.Tq, Tk = a.Tk;                          // this group's own lengths
+    long long kbase = b * a.Tk, qbase = b * a.Tq;      // first K/V row, first q / d_out / dq row
+    if constexpr (PACKED) {
+        if (a.cu_k) packed_group(a.cu_k, b, a.n_k, a.Tk, kbase, Tk);
+        if (a.cu_q) packed_group(a.cu_q, b, a.n_q, a.Tq, qbase, Tq);
+    }
+    const int ntiles = (Tk + 15) >> 4, Tkp = ntiles << 4, Tqp = ((Tq + 15) >> 4) << 4;
+    const int nb = a.bias ? a.Tq + a.Tk - 1 : 0;
     const AttBwdLds L = att_bwd_lds(a.Tq, a.Tk, a.bias != nullptr, nw);
-    float *Ks = att_lds, *Vs = Ks + (size_t)Tp * kAttLd;  // pass 2: Q and dO
+    float *Ks = att_lds, *Vs = Ks + L.madd / 2;  // two buffers of max(Tqp, Tkp) padded rows; pass 2: Q and dO
     float *madd = att_lds + L.madd, *bias_s = att_lds + L.bias;
     float *mx_s = att_lds + L.mx, *sum_s = att_lds + L.sum, *dd_s = att_lds + L.dd;
     float *dbw = att_lds + L.dbw + (size_t)wave * nb, *tile = att_lds + L.tile + (size_t)wave * 16 * kAttTileLd;
 
-    const long long b = blockIdx.x / a.H;
-    const int h = blockIdx.x - (int)b * a.H;
     const unsigned long long seed = a.thresh ? (unsigned long long)*a.seed : 0ull;
     const unsigned long long idx0 = ((unsigned long long)b * a.H + h) * (unsigned long long)a.Tq;  // + i, then * Tk + j
 
@@ -324,8 +352,8 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
     for (int idx = tid; idx < Tkp * 16; idx += nthr) {
         const int j = idx >> 4, c = idx & 15;
         float4 kk = make_float4(0.f, 0.f, 0.f, 0.f), vv = kk;
-        if (j < a.Tk) {
-            const size_t off = (size_t)(b * a.Tk + j) * (size_t)a.ld_kv + (size_t)h * kAttD + 4 * c;
+        if (j < Tk) {
+            const size_t off = (size_t)(kbase + j) * (size_t)a.ld_kv + (size_t)h * kAttD + 4 * c;
             kk = *reinterpret_cast<const float4 *>(a.k + off);
             vv = *reinterpret_cast<const float4 *>(a.v + off);
         }
@@ -333,15 +361,15 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
         *reinterpret_cast<float4 *>(Vs + j * kAttLd + 4 * c) = vv;
     }
     for (int j = tid; j < Tkp; j += nthr)
-        madd[j] = j >= a.Tk ? -INFINITY : ((a.key_mask && !a.key_mask[b * a.Tk + j]) ? -FLT_MAX : 0.f);
+        madd[j] = j >= Tk ? -INFINITY : ((!PACKED && a.key_mask && !a.key_mask[b * a.Tk + j]) ? -FLT_MAX : 0.f);
     for (int x = tid; x < nb; x += nthr) bias_s[x] = a.bias[(size_t)(a.bias_base + x) * a.H + h];
     for (int x = tid; x < nw * nb; x += nthr) att_lds[L.dbw + x] = 0.f;
     __syncthreads();
 
-    for (int qt = wave; qt * 16 < a.Tq; qt += nw) {
+    for (int qt = wave; qt * 16 < Tq; qt += nw) {
         const int m = qt * 16 + i;
-        const int ti = m < a.Tq ? m : a.Tq - 1;  // lanes past the last query recompute it and contribute nothing
-        const size_t qrow = (size_t)b * (size_t)a.Tq + (size_t)ti;
+        const int ti = m < Tq ? m : Tq - 1;  // lanes past the last query recompute it and contribute nothing
+        const size_t qrow = (size_t)(qbase + ti);
         const float *qp = a.q + qrow * (size_t)a.ld_q + (size_t)h * kAttD + g;
         const float *dop = a.d_out + qrow * (size_t)a.ld_do + (size_t)h * kAttD + g;
         float qreg[16], doreg[16];
@@ -368,7 +396,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
                         sc = -INFINITY;
                     } else {
                         if (a.bias) sc = sc + bias_s[j - ti + a.Tq - 1];
-                        if (ma != 0.f || (a.causal && j > ti)) sc = sc + -FLT_MAX;
+                        if (ma != 0.f || (!PACKED && a.causal && j > ti)) sc = sc + -FLT_MAX;
                     }
                     s[mt][r] = sc;
                     mx = fmaxf(mx, sc);
@@ -420,7 +448,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
         }
         D = D + __shfl_xor(D, 16, RQ_WAVE);
         D = D + __shfl_xor(D, 32, RQ_WAVE);
-        if (m < a.Tq && g == 0) mx_s[m] = mx, sum_s[m] = sum, dd_s[m] = D;
+        if (m < Tq && g == 0) mx_s[m] = mx, sum_s[m] = sum, dd_s[m] = D;
 
         // ---- per key tile: dS, the tile's diagonal sums, dQ
         f32x4 dq[4];
@@ -433,7 +461,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float d = s[mt][r] * (dp[mt][r] - D);
-                    ds[r] = m < a.Tq ? d : 0.f;
+                    ds[r] = m < Tq ? d : 0.f;
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -458,7 +486,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
                 }
             }
         }
-        if (m < a.Tq) {
+        if (m < Tq) {
             float *dqp = a.dq + qrow * (size_t)a.H * kAttD + (size_t)h * kAttD + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
@@ -477,8 +505,8 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
     for (int idx = tid; idx < Tqp * 16; idx += nthr) {
         const int ii = idx >> 4, c = idx & 15;
         float4 qq = make_float4(0.f, 0.f, 0.f, 0.f), dd = qq;
-        if (ii < a.Tq) {
-            const size_t row = (size_t)b * (size_t)a.Tq + (size_t)ii;
+        if (ii < Tq) {
+            const size_t row = (size_t)(qbase + ii);
             qq = *reinterpret_cast<const float4 *>(a.q + row * (size_t)a.ld_q + (size_t)h * kAttD + 4 * c);
             dd = *reinterpret_cast<const float4 *>(a.d_out + row * (size_t)a.ld_do + (size_t)h * kAttD + 4 * c);
         }
@@ -488,10 +516,10 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
     __syncthreads();
 
     // ---- pass 2: lane (g, c) owns key 16 kt + c and, per query tile, queries 16 qt + 4 g + r
-    for (int kt = wave; kt * 16 < a.Tk; kt += nw) {
+    for (int kt = wave; kt * 16 < Tk; kt += nw) {
         const int j = kt * 16 + i;
-        const int jc = j < a.Tk ? j : a.Tk - 1;
-        const size_t krow = (size_t)b * (size_t)a.Tk + (size_t)jc;
+        const int jc = j < Tk ? j : Tk - 1;
+        const size_t krow = (size_t)(kbase + jc);
         const float *kp = a.k + krow * (size_t)a.ld_kv + (size_t)h * kAttD + g;
         const float *vp = a.v + krow * (size_t)a.ld_kv + (size_t)h * kAttD + g;
         float kreg[16], vreg[16];
@@ -501,7 +529,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
         f32x4 dk[4], dv[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int qt = 0; qt * 16 < a.Tq; ++qt) {
+        for (int qt = 0; qt * 16 < Tq; ++qt) {
             f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, pacc = sacc;
             const float *qs = Qs + (16 * qt + i) * kAttLd + g, *dos = dOs + (16 * qt + i) * kAttLd + g;
 #pragma unroll
@@ -513,12 +541,12 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int qi = 16 * qt + 4 * g + r;
-                const int ti = qi < a.Tq ? qi : a.Tq - 1;
+                const int ti = qi < Tq ? qi : Tq - 1;
                 float sc = sacc[r];
                 if (a.bias) sc = sc + bias_s[jc - ti + a.Tq - 1];
-                if (ma != 0.f || (a.causal && j > ti)) sc = sc + -FLT_MAX;
+                if (ma != 0.f || (!PACKED && a.causal && j > ti)) sc = sc + -FLT_MAX;
                 float p = expf(sc - mx_s[ti]) / sum_s[ti];
-                if (qi >= a.Tq || j >= a.Tk) p = 0.f;
+                if (qi >= Tq || j >= Tk) p = 0.f;
                 float dp = pacc[r], pk = p;
                 if (a.thresh) {
                     const bool keep = dropout_keep(seed, (idx0 + ti) * a.Tk + jc, a.thresh);
@@ -538,7 +566,7 @@ __global__ __launch_bounds__(256) void t5_attention_bwd_kernel(AttBwdArgs a) {
                 }
             }
         }
-        if (j < a.Tk) {
+        if (j < Tk) {
             const size_t off = krow * (size_t)a.H * kAttD + (size_t)h * kAttD + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
@@ -640,6 +668,26 @@ int check_att_call(const char *who, bool train, int64_t R, int64_t Rk, int H, in
     return RQHIP_OK;
 }
 
+// What the three packed entry points check beyond check_att_call: the tables and the row counts they index.
+int check_packed_call(const char *who, int64_t R, int64_t n_q, int64_t n_k, int Tq, int Tk, const int32_t *cu_q,
+                      const int32_t *cu_k, const uint8_t *key_mask, int causal) {
+    if (!cu_q && !cu_k) {
+        set_error("%s: no cumulative table (cu_q, cu_k): the dense call is rqhip_t5_attention*", who);
+        return RQHIP_EARG;
+    }
+    if (causal || key_mask) {
+        set_error("%s: a cumulative table goes with neither causal nor key_mask (every packed key is valid)", who);
+        return RQHIP_EARG;
+    }
+    if (n_q < 0 || n_k < 0 || n_q >= (1ll << 31) || n_k >= (1ll << 31) || (!cu_q && n_q != R * Tq) ||
+        (!cu_k && n_k != R * Tk) || n_q > R * Tq || n_k > R * Tk) {
+        set_error("%s: n_q=%lld / n_k=%lld rows do not go with R=%lld groups of at most Tq=%d / Tk=%d (a dense side "
+                  "holds exactly R * T rows; int32 tables)", who, (long long)n_q, (long long)n_k, (long long)R, Tq, Tk);
+        return RQHIP_EARG;
+    }
+    return RQHIP_OK;
+}
+
 }  // namespace
 
 }  // namespace rqhip
@@ -673,6 +721,7 @@ extern "C" int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, 
     a.key_mask = key_mask;
     a.anc = past > 0 ? anc : nullptr;  // at past = 0 the only key is the row's own: the dense form of slab 0
     a.ld_anc = ld_anc, a.slab_rows = slab_rows;
+    a.cu_q = a.cu_k = nullptr, a.n_q = a.n_k = 0;
     if ((int64_t)a.beams * Tq >= (1ll << 24)) {
         set_error("t5_attention: %lld query rows per K/V group", (long long)a.beams * Tq);
         return RQHIP_EUNSUPPORTED;
@@ -715,6 +764,7 @@ extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const 
     a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
     a.key_mask = key_mask;
     a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
+    a.cu_q = a.cu_k = nullptr, a.n_q = a.n_k = 0;
     AttTrain t;
     t.lse = lse, t.seed = reinterpret_cast<const long long *>(seed), t.thresh = thresh;
     t.inv_keep = dropout_scale_f32(p);
@@ -761,6 +811,7 @@ extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float 
         a.key_mask = key_mask;
         a.seed = reinterpret_cast<const long long *>(seed), a.thresh = thresh;
         a.inv_keep = dropout_scale_f32(p);
+        a.cu_q = a.cu_k = nullptr, a.n_q = a.n_k = 0;
         const int threads = (Tq <= 16 && Tk <= 16) ? RQ_WAVE : 4 * RQ_WAVE;
         const size_t lds = att_bwd_lds(Tq, Tk, bias_by_delta != nullptr, threads / RQ_WAVE).total * sizeof(float);
         const int lrc = att_with_mt(Tk, [&](auto mt) {
@@ -768,6 +819,144 @@ extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float 
             return launch_att<t5_attention_bwd_kernel<MT>>(
                 "t5_attention_bwd_kernel", att_bwd_lds(kAttMaxT, att_most_tk(MT), true, 4).total * sizeof(float), R * H,
                 threads, lds, s, a);
+        });
+        if (lrc != RQHIP_OK) return lrc;
+    }
+    if (bias_by_delta) {
+        const long long n = (long long)n_delta * H;
+        hipLaunchKernelGGL(t5_dbias_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_bias_partial, R, H,
+                           nb, bias_offset - (Tq - 1), n_delta, d_bias_by_delta);
+        RQ_CHECK_LAUNCH("t5_dbias_reduce_kernel");
+    }
+    return RQHIP_OK;
+}
+
+// ---- the packed forms: the same kernel bodies, PACKED instantiations (lengths per group through cu_q / cu_k)
+
+extern "C" int rqhip_t5_attention_packed_supported(int d_kv, int H, int Tq, int Tk) {
+    return att_supported(d_kv, H, Tq, Tk);
+}
+
+extern "C" int rqhip_t5_attention_packed(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                         int64_t R, int64_t n_q, int64_t n_k, int H, int d_kv, int Tq, int Tk,
+                                         const int32_t *cu_q, const int32_t *cu_k, const float *bias_by_delta,
+                                         int n_delta, int bias_offset, const uint8_t *key_mask, int causal, float *out,
+                                         int64_t ld_out, rqhip_stream_t stream) {
+    int rc = check_att_call("t5_attention_packed", true, R, R, H, d_kv, Tq, Tk, 0, nullptr, 0, 0, {ld_q, ld_kv, ld_out},
+                            bias_by_delta, n_delta, bias_offset, 0, 0.0);
+    if (rc == RQHIP_OK) rc = check_packed_call("t5_attention_packed", R, n_q, n_k, Tq, Tk, cu_q, cu_k, key_mask, causal);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0 || n_q == 0) return RQHIP_OK;
+    if (any_null(q, out) || (n_k > 0 && any_null(k, v))) {
+        set_error("t5_attention_packed: null pointer (q, k, v, out)");
+        return RQHIP_EARG;
+    }
+    if (!all_aligned16(q, k, v, out)) {
+        set_error("t5_attention_packed: q, k, v and out must be 16-byte aligned");
+        return RQHIP_EARG;
+    }
+    AttArgs a;
+    a.q = q, a.k = k, a.v = v, a.out = out;
+    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
+    a.beams = 1, a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = 0, a.causal = 0;
+    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
+    a.key_mask = nullptr, a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
+    a.cu_q = cu_q, a.cu_k = cu_k, a.n_q = n_q, a.n_k = n_k;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
+    return att_with_mt(Tk, [&](auto mt) {  // the padded call's plan, by the bounds
+        constexpr int MT = decltype(mt)::value;
+        return launch_att<t5_attention_kernel<MT, true>>("t5_attention_kernel (packed)",
+                                                         att_lds_bytes(kAttMaxT, att_most_tk(MT), true), R * H,
+                                                         MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a);
+    });
+}
+
+extern "C" int rqhip_t5_attention_packed_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v,
+                                                   int64_t ld_kv, int64_t R, int64_t n_q, int64_t n_k, int H, int d_kv,
+                                                   int Tq, int Tk, const int32_t *cu_q, const int32_t *cu_k,
+                                                   const float *bias_by_delta, int n_delta, int bias_offset,
+                                                   const uint8_t *key_mask, int causal, double p, const int64_t *seed,
+                                                   float *out, int64_t ld_out, float *lse, rqhip_stream_t stream) {
+    int rc = check_att_call("t5_attention_packed_fwd_train", true, R, R, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
+                            {ld_q, ld_kv, ld_out}, bias_by_delta, n_delta, bias_offset, 0, p);
+    if (rc == RQHIP_OK)
+        rc = check_packed_call("t5_attention_packed_fwd_train", R, n_q, n_k, Tq, Tk, cu_q, cu_k, key_mask, causal);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0 || n_q == 0) return RQHIP_OK;
+    const unsigned thresh = dropout_threshold(p);
+    if (any_null(q, out, lse) || (n_k > 0 && any_null(k, v)) || (thresh && !seed)) {
+        set_error("t5_attention_packed_fwd_train: null pointer (q, k, v, out, lse; seed when p > 0)");
+        return RQHIP_EARG;
+    }
+    if (!all_aligned16(q, k, v, out)) {
+        set_error("t5_attention_packed_fwd_train: q, k, v and out must be 16-byte aligned");
+        return RQHIP_EARG;
+    }
+    AttArgs a;
+    a.q = q, a.k = k, a.v = v, a.out = out;
+    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
+    a.beams = 1, a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = 0, a.causal = 0;
+    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
+    a.key_mask = nullptr, a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
+    a.cu_q = cu_q, a.cu_k = cu_k, a.n_q = n_q, a.n_k = n_k;
+    AttTrain t;
+    t.lse = lse, t.seed = reinterpret_cast<const long long *>(seed), t.thresh = thresh;
+    t.inv_keep = dropout_scale_f32(p);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
+    return att_with_mt(Tk, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        return launch_att<t5_attention_train_kernel<MT, true>>("t5_attention_train_kernel (packed)",
+                                                               att_lds_bytes(kAttMaxT, att_most_tk(MT), true), R * H,
+                                                               MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a, t);
+    });
+}
+
+extern "C" int rqhip_t5_attention_packed_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                             const float *out, int64_t ld_out, const float *lse, const float *d_out,
+                                             int64_t ld_do, int64_t R, int64_t n_q, int64_t n_k, int H, int d_kv, int Tq,
+                                             int Tk, const int32_t *cu_q, const int32_t *cu_k,
+                                             const float *bias_by_delta, int n_delta, int bias_offset,
+                                             const uint8_t *key_mask, int causal, double p, const int64_t *seed,
+                                             float *d_q, float *d_k, float *d_v, float *d_bias_by_delta,
+                                             float *d_bias_partial, rqhip_stream_t stream) {
+    int rc = check_att_call("t5_attention_packed_bwd", true, R, R, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
+                            {ld_q, ld_kv, ld_out, ld_do}, bias_by_delta, n_delta, bias_offset, 0, p);
+    if (rc == RQHIP_OK) rc = check_packed_call("t5_attention_packed_bwd", R, n_q, n_k, Tq, Tk, cu_q, cu_k, key_mask, causal);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0 && !bias_by_delta) return RQHIP_OK;
+    const unsigned thresh = dropout_threshold(p);
+    if ((n_q > 0 && any_null(q, out, lse, d_out, d_q)) || (n_k > 0 && any_null(k, v, d_k, d_v)) || (thresh && !seed) ||
+        (bias_by_delta && any_null(d_bias_by_delta, d_bias_partial))) {
+        set_error("t5_attention_packed_bwd: null pointer (q, k, v, out, lse, d_out, d_q, d_k, d_v; seed when p > 0; "
+                  "d_bias_by_delta and d_bias_partial with a bias table)");
+        return RQHIP_EARG;
+    }
+    if (!all_aligned16(q, k, v, out, d_out, d_q, d_k, d_v)) {
+        set_error("t5_attention_packed_bwd: q, k, v, out, d_out, d_q, d_k and d_v must be 16-byte aligned");
+        return RQHIP_EARG;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nb = Tq + Tk - 1;
+    if (R > 0) {
+        AttBwdArgs a;
+        a.q = q, a.k = k, a.v = v, a.d_out = d_out;
+        a.dq = d_q, a.dk = d_k, a.dv = d_v, a.dbias_part = d_bias_partial;
+        a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_do = ld_do;
+        a.H = H, a.Tq = Tq, a.Tk = Tk, a.causal = 0;
+        a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
+        a.key_mask = nullptr;
+        a.seed = reinterpret_cast<const long long *>(seed), a.thresh = thresh;
+        a.inv_keep = dropout_scale_f32(p);
+        a.cu_q = cu_q, a.cu_k = cu_k, a.n_q = n_q, a.n_k = n_k;
+        const int threads = (Tq <= 16 && Tk <= 16) ? RQ_WAVE : 4 * RQ_WAVE;  // the padded call's, by the bounds
+        const size_t lds = att_bwd_lds(Tq, Tk, bias_by_delta != nullptr, threads / RQ_WAVE).total * sizeof(float);
+        const int lrc = att_with_mt(Tk, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            return launch_att<t5_attention_bwd_kernel<MT, true>>(
+                "t5_attention_bwd_kernel (packed)", att_bwd_lds(kAttMaxT, att_most_tk(MT), true, 4).total * sizeof(float),
+                R * H, threads, lds, s, a);
         });
         if (lrc != RQHIP_OK) return lrc;
     }

@@ -86,6 +86,19 @@ __device__ __forceinline__ f32x4 mma_group_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
+// ---- packed rows (t5_attention.hip's packed kernels, rows_pack.hip)
+
+// Group b of a packed tensor of n rows: rows lo .. lo + len - 1, by the cumulative table cu [groups + 1].  An entry
+// outside [0, n] is clamped and a length beyond the padded bound cut (the rule of seq_batch.hip's offsets): a bad table
+// gives an empty or a short group, never an address.
+__device__ __forceinline__ void packed_group(const int *cu, long long b, long long n, int bound, long long &lo, int &len) {
+    long long first = cu[b], end = cu[b + 1];
+    first = first < 0 ? 0 : (first > n ? n : first);
+    end = end < first ? first : (end > n ? n : end);
+    lo = first;
+    len = (int)(end - first > bound ? bound : end - first);
+}
+
 // ---- the entry points' pointer checks (a null pointer counts as aligned: the null check is a separate one)
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -172,6 +172,21 @@ def seq_window(n_hist: int, u0: int, u1: int, S: int, subsample: bool):
     return start, end - start - 1, end - 1
 
 
+def seq_window_counts(n_hist: Tensor, draws: Optional[Tensor], S: int, subsample: bool) -> Tensor:
+    """`seq_window`'s n_items for many rows at once, on the host: n_hist int64 [B] history lengths, draws int64 [B, 2]
+    the rows' (u0, u1) in [0, 2^62) (not read without subsample) -> int64 [B].  The same integer operations as
+    seq_window, vectorised; data/seq_loader.py uses it to know a batch's valid rows without reading the device."""
+    if S < 2 or bool((n_hist < 0).any()):
+        raise ValueError(f"seq_window_counts: S={S}, negative n_hist: {bool((n_hist < 0).any())}")
+    n_hist = n_hist.to(torch.int64)
+    if not subsample:
+        return n_hist.clamp(max=S)
+    n = n_hist + 1
+    start = draws[:, 0] % ((n - 3).clamp(min=0) + 1)
+    end = torch.minimum(start + 3 + draws[:, 1] % (S - 1), n)
+    return end - start - 1
+
+
 def synthetic_sequences(n_items: int, max_seq_len: int, seed: int = 4321) -> dict:
     """{split: the four CSR tensors} over n_items items: max(64, n_items // 2) users per split, history lengths spread
     over 1 .. 2 * max_seq_len (rows shorter and longer than a window both occur), uniform items."""
@@ -244,13 +259,16 @@ class SeqData(Dataset):
             raise ValueError(f"SeqData: split {self.split!r} is not CSR: userId [U], offsets [U + 1] ascending from 0 to "
                              "len(items), items [nnz], itemId_fut [U]")
         self.item_data = item_matrix
+        # the history lengths stay on the host when `to_device` moves the store (seq_window_counts reads them)
+        self.host_lengths = (self.offsets[1:] - self.offsets[:-1]).cpu()
 
     @property
     def max_seq_len(self) -> int:
         return self._max_seq_len
 
     def to_device(self, device) -> "SeqData":
-        """Make the four tensors resident on `device`; data/seq_loader.py then builds batches there."""
+        """Make the four tensors resident on `device`; data/seq_loader.py then builds batches there.  `host_lengths`,
+        the history lengths, stays a CPU tensor."""
         self.userId, self.offsets, self.items, self.itemId_fut = (
             t.to(device) for t in (self.userId, self.offsets, self.items, self.itemId_fut))
         return self

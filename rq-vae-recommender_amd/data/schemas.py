@@ -14,3 +14,20 @@ TokenizedSeqBatch = collections.namedtuple(
     "TokenizedSeqBatch",
     ["user_ids", "sem_ids", "sem_ids" + FUT_SUFFIX, "seq_mask", "token_type_ids", "token_type_ids" + FUT_SUFFIX],
 )
+
+
+class CountedSeqBatch(TokenizedSeqBatch):
+    """A TokenizedSeqBatch -- the same six fields, `_fields` and positional unpacking -- that also says, on the HOST, how
+    many history items each row holds: `item_counts`, an int64 CPU tensor [B], the number of leading valid item slots of
+    seq_mask's rows.  data/seq_loader.py yields it with host_windows=True; modules/model.py reads it to run the encoder
+    on the valid tokens only (encoder_rows = "packed") without reading the device."""
+
+    def __new__(cls, *args, item_counts=None, **kwargs):
+        self = super().__new__(cls, *args, **kwargs)
+        self.item_counts = item_counts
+        return self
+
+    def _replace(self, **kwargs):
+        out = super()._replace(**kwargs)
+        out.item_counts = self.item_counts
+        return out

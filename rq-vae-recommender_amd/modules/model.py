@@ -38,6 +38,25 @@ and by the encoder pass of `generate`; otherwise the operators run, silently.  i
 the encoder's returned attention mask is then a bool tensor with the operators' truth values.  An id outside the table,
 a device assert of the operators, reads a clamped row and gets no gradient.  The per-step lookup of `generate` is not
 affected.
+`model.encoder_rows = "packed"` (default "padded"; a model-level attribute like head_impl, not in the state dict, any
+other value raises ValueError in `forward`) makes `forward` run the encoder on the VALID tokens only.  A training row is
+padded to max_seq_len items, and the training window law rarely fills it (fill 0.36 on the synthetic histories), yet
+every sub-layer runs on every padded slot, although padding never reaches the loss.  With "packed" the front's output
+[B, T, d] is packed to [N, d], N the batch's valid tokens, by one launch (ops.rows_pack, csrc/rows_pack.hip; its
+backward, ops.rows_unpack, carries the gradient back to the front, which is unchanged), the encoder stack runs on
+[1, N, d] with its attention reading the rows through a cumulative-length table, and the decoder's cross-attention
+reads the packed encoder output (modules/t5.py, "Packed rows").  N must be known on the host WITHOUT reading the
+device -- a sync per step would stop the host from running ahead -- so `forward` packs only when the batch says how
+many items each row holds: a data.schemas.CountedSeqBatch (`item_counts`, int64 CPU [B]: the leading valid item slots of
+each row), as data/seq_loader.py yields with host_windows=True.  It also needs the fused attention to apply to both
+stacks (`T5Stack.packed_rows_active`: attention_impl "hip_train", or "hip" under no_grad; bound within 256 tokens), a row
+width that is a multiple of 4, and at least one token in every row: a row with no item and no user token would attend
+uniformly over its padding in the padded form, which has no packed counterpart.  Otherwise -- a plain
+TokenizedSeqBatch, host tensors, attention_impl = "torch", a longer history, an empty row -- `forward` runs the padded
+path, silently, like every other *_impl.  In eval mode loss and loss_d have the padded fused path's bits; in train mode
+the row-local dropout masks are another sample of the same law.  `generate`, `generate_next_sem_id` and
+`recommend_items` are not affected (their fill is higher and the beams change the cross-attention's grouping: the
+follow-up).  Measurements: profiles/packed_rows.txt.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
@@ -77,12 +96,13 @@ from torch import Tensor
 from data.schemas import TokenizedSeqBatch
 from modules.sid_items import SemIdItemIndex
 from modules.sid_prefix import SemIdPrefixIndex
-from modules.t5 import STACK_ATTRIBUTES, T5Config, T5EncoderModel, T5Stack, checked
+from modules.t5 import STACK_ATTRIBUTES, PackedRows, T5Config, T5EncoderModel, T5Stack, checked
 from rqhip import ops
 from rqhip._lib import RqHipError
-from rqhip.autograd import SidEmbedFunction, SidHeadLossFunction
+from rqhip.autograd import RowsPackFunction, SidEmbedFunction, SidHeadLossFunction
 
 HEAD_IMPLS = ("torch", "hip")
+ENCODER_ROWS = ("padded", "packed")
 EMBED_IMPLS = ("torch", "hip")
 BEAM_IMPLS = ("sample", "exact")
 
@@ -167,6 +187,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.weight_images = "none"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.saved_activations = "fp32"  # or "bf16" (modules/t5.py); handed to both T5 stacks with attention_impl
         self.beam_impl = "sample"  # or "exact": the search of `generate` (module docstring)
+        self.encoder_rows = "padded"  # or "packed": `forward` runs the encoder on the valid tokens only (module docstring)
 
     @property
     def device(self) -> torch.device:
@@ -252,9 +273,52 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return ops.sid_embed_fwd(ids, mask, table, self.num_hierarchies, ld_item, sep, prefix_table, prefix_idx,
                                  need_mask=need_mask)
 
-    def encoder_forward_pass(self, attention_mask, input_ids, user_id=None, *, ld_item=None):
+    def packed_rows_plan(self, batch: TokenizedSeqBatch) -> Optional[PackedRows]:
+        """The packed form of `forward` for this batch (module docstring, `encoder_rows`), or None: the padded path.
+        Built on the host from batch.item_counts alone; the only device work is the upload of the cumulative table."""
+        if self.encoder_rows not in ENCODER_ROWS:
+            raise ValueError(f"encoder_rows must be one of {ENCODER_ROWS}, got {self.encoder_rows!r}")
+        counts = getattr(batch, "item_counts", None)
+        if self.encoder_rows != "packed" or counts is None or not batch.sem_ids.is_cuda:
+            return None
+        B, L = batch.sem_ids.shape[0], self.num_hierarchies
+        S = batch.sem_ids.shape[1] // (L + 1)
+        if counts.is_cuda or counts.dtype != torch.int64 or tuple(counts.shape) != (B,):
+            raise ValueError(f"item_counts must be an int64 CPU tensor [{B}], got {counts.dtype} {tuple(counts.shape)} "
+                             f"on {counts.device}")
+        if B == 0 or int(counts.min()) < 0 or int(counts.max()) > S:
+            return None
+        with_user = batch.user_ids is not None and self.user_embedding is not None
+        if not with_user and int(counts.min()) == 0:
+            return None   # a row without a token: its padded form attends uniformly over its padding
+        per_item = L + (1 if self.sep_token is not None else 0)
+        bound = int(with_user) + S * per_item
+        table = self.item_sid_embedding_table.weight
+        self._push_attention_impl()
+        if not (ops.rows_pack_supported(table.dtype, table.shape[1])
+                and self.encoder.encoder.packed_rows_active(table, bound, bound)
+                and self.t5_decoder.packed_rows_active(table, L + 1, bound)):
+            return None
+        cu = torch.zeros(B + 1, dtype=torch.int32)
+        cu[1:] = torch.cumsum(int(with_user) + counts * per_item, 0)
+        return PackedRows(cu.pin_memory().to(table.device, non_blocking=True), bound, B, int(cu[-1]))
+
+    def _encode(self, inputs_embeds: Tensor, attention_mask, rows: Optional[PackedRows]):
+        """The encoder on the front's output -> (encoder output, its keep-mask); with `rows` on the valid tokens only:
+        one pack launch, then the stack on [1, N, d], whose output needs no mask."""
+        if rows is None:
+            return self.encoder(inputs_embeds=inputs_embeds, attention_mask=attention_mask), attention_mask
+        if torch.is_grad_enabled():
+            packed = RowsPackFunction.apply(inputs_embeds, rows.cu, rows.rows)
+        else:
+            packed = ops.rows_pack(inputs_embeds, rows.cu, rows.rows)
+        return self.encoder.encoder(packed.unsqueeze(0), packed=rows), None
+
+    def encoder_forward_pass(self, attention_mask, input_ids, user_id=None, *, ld_item=None,
+                             rows: Optional[PackedRows] = None):
         """ld_item: columns per item in input_ids and attention_mask, num_hierarchies (the default) or more; columns
-        past num_hierarchies of an item (the tokenizer's dedup column) are not read."""
+        past num_hierarchies of an item (the tokenizer's dedup column) are not read.  rows (`packed_rows_plan`): the
+        encoder runs on the valid tokens only and the result is ([1, N, d], None)."""
         self._push_attention_impl()
         ld_item = self.num_hierarchies if ld_item is None else ld_item
         with_user = user_id is not None and self.user_embedding is not None
@@ -262,7 +326,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
             inputs_embeds, attention_mask = self._hip_embed(
                 input_ids, attention_mask, ld_item, self.sep_token,
                 self.user_embedding.weight if with_user else None, user_id if with_user else None, True)
-            return self.encoder(inputs_embeds=inputs_embeds, attention_mask=attention_mask), attention_mask
+            return self._encode(inputs_embeds, attention_mask, rows)
         if ld_item != self.num_hierarchies:
             input_ids = _strip_dedup_col(input_ids, ld_item, self.num_hierarchies)
             attention_mask = _strip_dedup_col(attention_mask.long(), ld_item, self.num_hierarchies)
@@ -280,12 +344,13 @@ class EncoderDecoderRetrievalModel(nn.Module):
             inputs_embeds = torch.cat([user_embeds.unsqueeze(1), inputs_embeds], dim=1)
             attention_mask = torch.cat(
                 [torch.ones(attention_mask.size(0), 1, device=attention_mask.device), attention_mask], dim=1)
-        encoder_output = self.encoder(inputs_embeds=inputs_embeds, attention_mask=attention_mask)
-        return encoder_output, attention_mask
+        return self._encode(inputs_embeds, attention_mask, rows)
 
     def decoder_forward_pass(self, attention_mask=None, future_ids=None, encoder_output=None,
-                             attention_mask_for_encoder=None, use_cache=False, past_key_values=None, *, ld_item=None):
-        """BOS followed by the embedded future ids (or BOS alone); with a cache (the list this returns when use_cache)
+                             attention_mask_for_encoder=None, use_cache=False, past_key_values=None, *, ld_item=None,
+                             encoder_rows: Optional[PackedRows] = None):
+        """encoder_rows: encoder_output is the packed [1, N, d] of `encoder_forward_pass(rows=...)`.
+        BOS followed by the embedded future ids (or BOS alone); with a cache (the list this returns when use_cache)
         only the last future id is run.  Returns the hidden states, and the self-attention cache when use_cache.
         ld_item: as in encoder_forward_pass, for future_ids and attention_mask."""
         self._push_attention_impl()
@@ -317,7 +382,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
             inputs_embeds = self.bos_token.unsqueeze(0).expand(encoder_output.size(0), 1, -1)
         return self.t5_decoder(inputs_embeds, attention_mask=attention_mask, encoder_hidden_states=encoder_output,
                                encoder_attention_mask=attention_mask_for_encoder,
-                               past_key_values=past_key_values or None, use_cache=use_cache)
+                               past_key_values=past_key_values or None, use_cache=use_cache,
+                               encoder_packed=encoder_rows)
 
     def hip_head_active(self, decoder_output: Tensor) -> bool:
         """Whether `forward` takes the "hip" head path for this decoder output (module docstring)."""
@@ -331,20 +397,23 @@ class EncoderDecoderRetrievalModel(nn.Module):
     def forward(self, batch: TokenizedSeqBatch) -> ModelOutput:
         sem_ids_dim = self.num_hierarchies + 1
         fut_ids = batch.sem_ids_fut[:, : self.num_hierarchies]
+        rows = self.packed_rows_plan(batch)      # None: the padded path (the default)
         if self.hip_embed_active(batch.sem_ids, batch.seq_mask):      # the batch's tensors as they are
             encoder_output, attention_mask_for_encoder = self.encoder_forward_pass(
-                attention_mask=batch.seq_mask, input_ids=batch.sem_ids, user_id=batch.user_ids, ld_item=sem_ids_dim)
+                attention_mask=batch.seq_mask, input_ids=batch.sem_ids, user_id=batch.user_ids, ld_item=sem_ids_dim,
+                rows=rows)
             decoder_output = self.decoder_forward_pass(
                 future_ids=batch.sem_ids_fut, encoder_output=encoder_output,
-                attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False, ld_item=sem_ids_dim)
+                attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False, ld_item=sem_ids_dim,
+                encoder_rows=rows)
         else:
             input_ids = _strip_dedup_col(batch.sem_ids, sem_ids_dim, self.num_hierarchies)
             attention_mask = _strip_dedup_col(batch.seq_mask.long(), sem_ids_dim, self.num_hierarchies)
             encoder_output, attention_mask_for_encoder = self.encoder_forward_pass(
-                attention_mask=attention_mask, input_ids=input_ids, user_id=batch.user_ids)
+                attention_mask=attention_mask, input_ids=input_ids, user_id=batch.user_ids, rows=rows)
             decoder_output = self.decoder_forward_pass(
                 future_ids=fut_ids, encoder_output=encoder_output,
-                attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False)
+                attention_mask_for_encoder=attention_mask_for_encoder, use_cache=False, encoder_rows=rows)
         if self.hip_head_active(decoder_output):
             weights = [m.weight for m in self.decoder_mlp]
             if torch.is_grad_enabled():

@@ -113,6 +113,25 @@ encoder tokens in one alternating run (profiles/t5_attention_long_bf16.txt): one
 against the fp32 arm's 75.3 ms and the operators' 72.1 ms, one `generate` 12.4 against 15.5 and 31.9 ms, at the fp32
 arm's peak memory; the four bf16 kernels take 0.53 of their fp32 twins' device time.
 
+Packed rows.  An encoder forward can run on the valid tokens of variable-length rows alone: `T5Stack.forward(inputs_embeds
+[1, N, d], packed=PackedRows(cu, bound, batch, N))` takes the batch's rows one behind the other, row b at tokens cu[b] ..
+cu[b + 1] - 1 (cu: int32 [batch + 1] on the device, every row at most `bound` tokens, N known to the host), and returns
+[1, N, d]; the decoder reads such an output with `encoder_hidden_states` [1, N, d] and `encoder_packed=` the same record
+(`cross_kv` takes the [1, N, d] tensor as it is).  It is selected by these ARGUMENTS, not by a stack attribute, and
+takes no mask: every packed token is valid.  Only the attention needs the rows' structure: each self-attention of the
+encoder and each cross-attention of the decoder is ONE packed call (ops.t5_attention_packed under no_grad,
+autograd.T5AttentionPackedFunction under grad; csrc/t5_attention.hip), which keeps the padded call's bias index, dropout
+element index, kernel instantiation and LDS layout and shortens each workgroup's loops to its row's own length, so that
+on every valid token it has the bits of the padded call with the prefix key mask.  The glue, the feed-forward and the
+grouped projections run unchanged on the N rows: their kernels take any row count and a row's result does not depend
+on the batch (include/rqhip.h), so in eval mode the loss keeps the padded path's bits (weight gradients sum the rows in
+other groups and differ by rounding).  In train mode a row-local dropout decision is a function of the element's index
+among the N rows, so a packed step draws other masks than a padded one: the same law, another sample.  Packed rows need
+the fused attention this forward would take anyway ("hip_train" under grad; "hip" or "hip_train" without active dropout
+under no_grad; `T5Stack.packed_rows_active`) and every length within the short kernel's 256; elsewhere they raise --
+modules/model.py checks before it packs and runs the padded path instead.  N depends on the data, so a packed forward
+cannot be replayed from a captured graph.
+
 The fused forms take their dropout seeds as int64s drawn on the device with torch.randint (the default generator:
 torch.manual_seed reproduces a run), none in eval mode or at dropout_rate 0.  The fused attention draws one per call.
 With the "hip" glue a stack forward draws once before its first body, one seed per glue call and behind them one per
@@ -127,8 +146,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from rqhip import ops, optim
-from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5AttentionLongFunction, T5FFNFunction,
-                            T5ProjFunction)
+from rqhip.autograd import (T5AddNormFunction, T5AttentionFunction, T5AttentionLongFunction, T5AttentionPackedFunction,
+                            T5FFNFunction, T5ProjFunction)
 
 KV = Tuple[Tensor, Tensor]
 ATTENTION_IMPLS = ("torch", "hip", "hip_train")
@@ -168,6 +187,16 @@ def matmul_forms(arith: str, weight_images: str, saved_activations: str, ffn_act
     saved = bf16 and saved_activations == "bf16" and grad_enabled
     return (ops.T5MatmulForm(arith, images, saved) if ffn_active else None,
             ops.T5MatmulForm(arith, images, False) if proj_active else None)
+
+
+class PackedRows(NamedTuple):
+    """Variable-length rows without their padding (module docstring, "Packed rows"): `batch` rows of at most `bound`
+    tokens lie one behind the other in a [1, N, d] tensor, row b at tokens cu[b] .. cu[b + 1] - 1.  `cu` is an int32
+    [batch + 1] DEVICE tensor; `rows` = N = cu[batch] is the tensor's own size, known to the host without reading it."""
+    cu: Tensor
+    bound: int
+    batch: int
+    rows: int   # N
 
 
 class T5Config:
@@ -463,7 +492,12 @@ class _HipAttention:
 
     def __init__(self, stack: "T5Stack", T: int, attention_mask: Optional[Tensor],
                  encoder_attention_mask: Optional[Tensor], cross_kv: Optional[List[KV]],
-                 cache: Optional[T5DecodeCache], train: bool, plan: MatmulPlan) -> None:
+                 cache: Optional[T5DecodeCache], train: bool, plan: MatmulPlan, packed: Optional[PackedRows] = None,
+                 encoder_packed: Optional[PackedRows] = None) -> None:
+        """packed: the stack's own rows are packed ([1, N, d], T = packed.bound): every self-attention is a packed
+        call with both tables.  encoder_packed: the encoder output is ([1, N, d]): every cross-attention is a packed
+        call of the dense queries over packed K/V.  Neither takes a mask: every packed token is valid."""
+        self.packed, self.encoder_packed = packed, encoder_packed
         self.train = train
         self.plan = plan
         self.long = stack.attention_long_impl == "hip"  # calls the short kernel does not support go to the long one
@@ -491,8 +525,25 @@ class _HipAttention:
         return ops.t5_attention(q, k, v, module.n_heads, bias_by_delta=table, bias_offset=offset, key_mask=key_mask,
                                 causal=causal)
 
+    def _launch_packed(self, module: T5Attention, q: Tensor, k: Tensor, v: Tensor, table: Optional[Tensor], offset: int,
+                       q_rows: Optional[PackedRows], k_rows: PackedRows) -> Tensor:
+        """One packed call (ops.t5_attention_packed, under grad autograd.T5AttentionPackedFunction): k, v [N, inner]
+        by k_rows; q [N, inner] by q_rows, or dense [R, Tq, inner] without."""
+        cu_q, max_q = (None, None) if q_rows is None else (q_rows.cu, q_rows.bound)
+        if self.train:
+            return T5AttentionPackedFunction.apply(q, k, v, table, module.n_heads, offset, cu_q, k_rows.cu, max_q,
+                                                   k_rows.bound, self.p, _draw_seed(self.p, q.device))
+        return ops.t5_attention_packed(q, k, v, module.n_heads, cu_q=cu_q, cu_k=k_rows.cu, max_q=max_q,
+                                       max_k=k_rows.bound, bias_by_delta=table, bias_offset=offset)
+
     def self_attention(self, i: int, module: T5Attention, normed: Tensor) -> Tuple[Tensor, KV]:
         """One launch; with a decode cache the K/V projections go straight into block i's slabs."""
+        if self.packed is not None:
+            q, k, v = _project(self.plan, normed, (module.q, module.k, module.v))       # [1, N, inner]
+            # (squeeze, not [0]: a view in the backward too, where a select would zero-fill and copy its gradient)
+            out = self._launch_packed(module, q.squeeze(0), k.squeeze(0), v.squeeze(0), self.table, self.offset,
+                                      self.packed, self.packed)
+            return _project(self.plan, out.unsqueeze(0), (module.o,))[0], (module._heads(k), module._heads(v))
         if self.cache is None:
             q, k, v = _project(self.plan, normed, (module.q, module.k, module.v))
             out = self._launch(module, q, k, v, self.table, self.offset, self.key_mask, self.causal)
@@ -516,6 +567,9 @@ class _HipAttention:
         # a view of the Linear's output
         k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in self.cross_kv[i])
         q = _project(self.plan, normed, (module.q,))[0]
+        if self.encoder_packed is not None:
+            out = self._launch_packed(module, q, k.squeeze(0), v.squeeze(0), None, 0, None, self.encoder_packed)
+            return _project(self.plan, out, (module.o,))[0]
         return _project(self.plan, self._launch(module, q, k, v, None, 0, self.cross_mask, False), (module.o,))[0]
 
 
@@ -696,6 +750,26 @@ class T5Stack(nn.Module):
                 ops.t5_attention_bwd_supported, x.dtype, query_length, ck.shape[2], long)
         return ok
 
+    def packed_rows_active(self, x: Tensor, query_length: int, key_bound: int) -> bool:
+        """Whether a forward of x (device dtype carrier) can run on packed rows of at most key_bound tokens (module
+        docstring, "Packed rows"): the encoder's own rows (every call has query and key bound key_bound), or the decoder
+        over a packed encoder output (dense self-attention of query_length tokens, cross-attention over key_bound).
+        It takes the fused attention this forward would take anyway -- "hip_train" under grad, "hip" or "hip_train"
+        without dropout under no_grad -- and every length within the short kernel."""
+        cfg = self.config
+        if checked(self, "attention_impl") not in ("hip", "hip_train") or not x.is_cuda:
+            return False
+        if torch.is_grad_enabled():
+            if self.attention_impl != "hip_train":
+                return False
+        elif self.training and cfg.dropout_rate > 0:
+            return False
+        own = ops.t5_attention_bwd_supported if torch.is_grad_enabled() else ops.t5_attention_supported
+        if self.is_decoder:
+            return (own(x.dtype, cfg.d_kv, cfg.num_heads, query_length, query_length)
+                    and ops.t5_attention_packed_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, key_bound))
+        return ops.t5_attention_packed_supported(x.dtype, cfg.d_kv, cfg.num_heads, key_bound, key_bound)
+
     def hip_norm_active(self, x: Tensor) -> bool:
         """Whether a forward of x takes the "hip" norm path (module docstring)."""
         return checked(self, "norm_impl") == "hip" and x.is_cuda and ops.t5_add_norm_supported(x.dtype, self.config.d_model)
@@ -724,9 +798,27 @@ class T5Stack(nn.Module):
         return T5DecodeCache(len(self.block), steps, rows, self.config.num_heads * self.config.d_kv, device)
 
     def _attention_body(self, inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                        past_key_values, cross_kv, decode_cache, plan: MatmulPlan):
-        """The attention body of this forward (module docstring): _HipAttention where it applies, else the operators."""
+                        past_key_values, cross_kv, decode_cache, plan: MatmulPlan, packed: Optional[PackedRows] = None,
+                        encoder_packed: Optional[PackedRows] = None):
+        """The attention body of this forward (module docstring): _HipAttention where it applies, else the operators.
+        Packed rows have no operator form: where the fused attention does not apply they raise."""
         R, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
+        if packed is not None or encoder_packed is not None:
+            rows = packed if packed is not None else encoder_packed
+            if self.is_decoder != (packed is None):
+                raise ValueError("packed rows: an encoder takes `packed`, a decoder `encoder_packed`")
+            if (past_key_values is not None or decode_cache is not None or attention_mask is not None
+                    or encoder_attention_mask is not None):
+                raise ValueError("packed rows take no mask and no cache: every packed token is valid")
+            if rows.cu.numel() != rows.batch + 1 or (packed is not None and (R != 1 or T != rows.rows)):
+                raise ValueError("packed rows: inputs_embeds is [1, N, d] and cu has batch + 1 entries")
+            if not self.packed_rows_active(inputs_embeds, T, rows.bound):
+                raise ValueError('packed rows need the fused attention (attention_impl "hip" / "hip_train", as this '
+                                 f"forward would take it) and every length within 256, got bound {rows.bound}")
+            if self.is_decoder and cross_kv is None:
+                cross_kv = self.cross_kv(encoder_hidden_states, plan)
+            return _HipAttention(self, rows.bound if packed is not None else T, None, None, cross_kv, None,
+                                 train=torch.is_grad_enabled(), plan=plan, packed=packed, encoder_packed=encoder_packed)
         if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
             if self.is_decoder and cross_kv is None:
                 cross_kv = self.cross_kv(encoder_hidden_states, plan)
@@ -769,15 +861,18 @@ class T5Stack(nn.Module):
     def forward(self, inputs_embeds: Tensor, attention_mask: Optional[Tensor] = None,
                 encoder_hidden_states: Optional[Tensor] = None, encoder_attention_mask: Optional[Tensor] = None,
                 past_key_values: Optional[List[KV]] = None, use_cache: bool = False,
-                cross_kv: Optional[List[KV]] = None, decode_cache: Optional[T5DecodeCache] = None):
-        """inputs_embeds [R, T, d]; attention_mask [R, past + T] keep-mask (encoder: [R, T]); encoder_attention_mask
+                cross_kv: Optional[List[KV]] = None, decode_cache: Optional[T5DecodeCache] = None,
+                packed: Optional[PackedRows] = None, encoder_packed: Optional[PackedRows] = None):
+        """packed (encoder): inputs_embeds is [1, N, d], the valid tokens of packed.batch rows, and so is the result;
+        encoder_packed (decoder): encoder_hidden_states is such a tensor (module docstring, "Packed rows").
+        inputs_embeds [R, T, d]; attention_mask [R, past + T] keep-mask (encoder: [R, T]); encoder_attention_mask
         [B, S] keep-mask of the encoder output (B rows, R = B * beams).  Returns the hidden states, and with use_cache
         the per-block self-attention (K, V) including these T positions.  decode_cache ("hip" path, T = 1) holds the
         self-attention history instead of past_key_values: this position's K/V are written into it."""
         self.validate()
         plan = self.matmul_plan(inputs_embeds)  # the images are refreshed here, before the first body
         attention = self._attention_body(inputs_embeds, attention_mask, encoder_hidden_states, encoder_attention_mask,
-                                         past_key_values, cross_kv, decode_cache, plan)
+                                         past_key_values, cross_kv, decode_cache, plan, packed, encoder_packed)
         fused_glue = self.hip_norm_active(inputs_embeds)
         fused_ffn = plan.ffn is not None
         p = float(self.config.dropout_rate) if self.training else 0.0

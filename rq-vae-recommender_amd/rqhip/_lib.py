@@ -115,6 +115,17 @@ SIGNATURES = {
                                             _vp, _int, C.c_double, _vp, _vp, _i64, _vp, _vp]),
     "rqhip_t5_attention_bwd": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int,
                                       _int, _vp, _int, _int, _vp, _int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_attention_packed_supported": (_int, [_int, _int, _int, _int]),
+    "rqhip_t5_attention_packed": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp,
+                                         _int, _int, _vp, _int, _vp, _i64, _vp]),
+    "rqhip_t5_attention_packed_fwd_train": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _vp,
+                                                   _vp, _vp, _int, _int, _vp, _int, C.c_double, _vp, _vp, _i64, _vp, _vp]),
+    "rqhip_t5_attention_packed_bwd": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int,
+                                             _int, _int, _int, _vp, _vp, _vp, _int, _int, _vp, _int, C.c_double, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_rows_pack_supported": (_int, [_int]),
+    "rqhip_rows_pack": (_int, [_vp, _vp, _i64, _int, _int, _i64, _vp, _vp]),
+    "rqhip_rows_unpack": (_int, [_vp, _vp, _i64, _int, _int, _i64, _vp, _vp]),
     "rqhip_t5_attention_long_supported": (_int, [_int, _int, _int, _int]),
     "rqhip_t5_attention_long": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _int, _int, _vp,
                                        _int, _int, _vp, _vp, _i64, _vp]),

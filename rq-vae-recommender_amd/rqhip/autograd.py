@@ -297,6 +297,65 @@ class T5AttentionFunction(torch.autograd.Function):
         return dq, dk, dv, dtable, None, None, None, None, None, None
 
 
+class T5AttentionPackedFunction(torch.autograd.Function):
+    """T5AttentionFunction on packed variable-length rows (ops.t5_attention_packed_fwd_train / _bwd): apply(q, k, v,
+    bias_by_delta or None, n_heads, bias_offset, cu_q or None, cu_k or None, max_q, max_k, p, seed).  A side with its
+    int32 table is 2-D [rows, heads * 64], a side without the dense [groups, T, heads * 64]; max_q / max_k are the padded
+    lengths, whose index laws the bias and the dropout keep.  Saved: q, k, v, out, the row log-sum-exp, the table of the
+    bias, the two cumulative tables and the seed.  Gradients: q, k, v and the bias table."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, bias_by_delta: Optional[Tensor], n_heads: int, bias_offset: int,
+                cu_q: Optional[Tensor], cu_k: Optional[Tensor], max_q: int, max_k: int, p: float,
+                seed: Optional[Tensor]):
+        out, lse = ops.t5_attention_packed_fwd_train(q, k, v, n_heads, cu_q=cu_q, cu_k=cu_k, max_q=max_q, max_k=max_k,
+                                                     bias_by_delta=bias_by_delta, bias_offset=bias_offset, p=p, seed=seed)
+        ctx.save_for_backward(q, k, v, out, lse, bias_by_delta, cu_q, cu_k, seed)
+        ctx.call = (n_heads, bias_offset, max_q, max_k, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        q, k, v, out, lse, table, cu_q, cu_k, seed = ctx.saved_tensors
+        n_heads, bias_offset, max_q, max_k, p = ctx.call
+        dq, dk, dv, dtable = ops.t5_attention_packed_bwd(q, k, v, out, lse, d_out, n_heads, cu_q=cu_q, cu_k=cu_k,
+                                                         max_q=max_q, max_k=max_k, bias_by_delta=table,
+                                                         bias_offset=bias_offset, p=p, seed=seed)
+        return (dq, dk, dv, dtable) + (None,) * 8
+
+
+class RowsPackFunction(torch.autograd.Function):
+    """Padded rows [B, T, d] -> packed rows [N, d] (ops.rows_pack): apply(x, cu, N) with cu the int32 [B + 1] device
+    table and N the host's row count.  Its backward is ops.rows_unpack of the gradient: zero on the padded tails."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, cu: Tensor, N: int):
+        ctx.save_for_backward(cu)
+        ctx.shape = (x.shape[0], x.shape[1])
+        return ops.rows_pack(x, cu, N)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (cu,) = ctx.saved_tensors
+        return ops.rows_unpack(_dense(g), cu, *ctx.shape), None, None
+
+
+class RowsUnpackFunction(torch.autograd.Function):
+    """Packed rows [N, d] -> padded rows [B, T, d] with zero tails (ops.rows_unpack): apply(x, cu, B, T).  Its backward
+    is ops.rows_pack of the gradient."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, cu: Tensor, B: int, T: int):
+        ctx.save_for_backward(cu)
+        ctx.n = x.shape[0]
+        return ops.rows_unpack(x, cu, B, T)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (cu,) = ctx.saved_tensors
+        return ops.rows_pack(_dense(g), cu, ctx.n), None, None, None
+
+
 class T5AttentionLongFunction(torch.autograd.Function):
     """T5AttentionFunction for the lengths beyond its kernel (ops.t5_attention_long_fwd_train / ops.t5_attention_long_bwd,
     up to 2048 tokens): the same arguments and gradients, and a trailing `arith` (ops.T5_ARITHS), the arithmetic of

@@ -851,6 +851,197 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
     return dq, dk, dv, dtable
 
 
+def t5_attention_packed_supported(dtype: torch.dtype, d_kv: int, n_heads: int, Tq: int, Tk: int) -> bool:
+    """Whether the packed attention calls implement these padded BOUNDS (rqhip_t5_attention_packed_supported): fp32,
+    d_kv = 64, Tq and Tk <= 256."""
+    return dtype == torch.float32 and bool(
+        _lib.lib().rqhip_t5_attention_packed_supported(int(d_kv), int(n_heads), int(Tq), int(Tk)))
+
+
+def _packed_side(who: str, t: Tensor, name: str, cu: Optional[Tensor], bound: Optional[int], inner: int):
+    """One side (q or k / v) of a packed attention call -> (tensor, groups, rows, bound).  With its table `cu` (int32
+    [groups + 1], device) the tensor is 2-D [rows, inner] at one row stride and `bound` the padded length; without, it is
+    the dense [groups, T, inner] of t5_attention."""
+    if cu is None:
+        t = _token_rows(t, name)
+        if bound is not None and bound != t.shape[1]:
+            raise RqHipError(f"{who}: dense {name} has {t.shape[1]} tokens per row, not the bound {bound}")
+        if t.shape[2] != inner:
+            raise RqHipError(f"{who}: {name} has {t.shape[2]} columns, not n_heads * 64 = {inner}")
+        return t, t.shape[0], t.shape[0] * t.shape[1], t.shape[1]
+    if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 1 or not cu.is_contiguous():
+        raise RqHipError(f"{who}: the table of {name} must be a contiguous int32 [groups + 1] tensor, got {cu.dtype} "
+                         f"{tuple(cu.shape)}")
+    if bound is None or bound < 1:
+        raise RqHipError(f"{who}: packed {name} needs its padded length (max_q / max_k >= 1)")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != inner:
+        raise RqHipError(f"{who}: packed {name} must be a float32 [rows, n_heads * 64 = {inner}] tensor, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < inner or t.data_ptr() % 16 != 0:
+        t = _aligned16(t.contiguous())
+    return t, cu.numel() - 1, t.shape[0], int(bound)
+
+
+def _packed_attention_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, cu_q: Optional[Tensor],
+                           cu_k: Optional[Tensor], max_q: Optional[int], max_k: Optional[int],
+                           bias_by_delta: Optional[Tensor], key_mask: Optional[Tensor], causal: bool, p: float = 0.0,
+                           seed: Optional[Tensor] = None):
+    """The checks the three packed attention calls share -> (q, k, v, table, R, n_q, n_k, Tq, Tk, inner, seed pointer)."""
+    if cu_q is None and cu_k is None:
+        raise RqHipError(f"{who}: neither cu_q nor cu_k: the dense call is t5_attention")
+    if causal or key_mask is not None:
+        raise RqHipError(f"{who}: a cumulative table goes with neither causal nor key_mask (every packed key is valid)")
+    inner = int(n_heads) * 64
+    q, R, n_q, Tq = _packed_side(who, q, "q", cu_q, max_q, inner)
+    if k.shape != v.shape:
+        raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
+    k, Rk, n_k, Tk = _packed_side(who, k, "k", cu_k, max_k, inner)
+    v = _packed_side(who, v, "v", cu_k, max_k, inner)[0]
+    k_ld, v_ld = (k.stride(-2), v.stride(-2))
+    if k_ld != v_ld:
+        k, v = k.contiguous(), v.contiguous()
+    if Rk != R:
+        raise RqHipError(f"{who}: {R} query groups over {Rk} K/V groups: one K/V per group")
+    if bias_by_delta is not None:
+        bias_by_delta = _f32c(bias_by_delta, "bias_by_delta")
+        if bias_by_delta.dim() != 2 or bias_by_delta.shape[1] != n_heads:
+            raise RqHipError(f"{who}: bias_by_delta must be [n_delta, {n_heads}], got {tuple(bias_by_delta.shape)}")
+    return q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, _dropout_seed(who, seed, p=p)
+
+
+def t5_attention_packed(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, cu_q: Optional[Tensor] = None,
+                        cu_k: Optional[Tensor] = None, max_q: Optional[int] = None, max_k: Optional[int] = None,
+                        bias_by_delta: Optional[Tensor] = None, bias_offset: int = 0, key_mask: Optional[Tensor] = None,
+                        causal: bool = False) -> Tensor:
+    """t5_attention on packed variable-length rows in one launch (rqhip_t5_attention_packed): R groups, one K/V each.
+    With cu_k (int32 [R + 1] on the device) k, v are [n_k, n_heads * 64] and group b's keys the rows cu_k[b] ..
+    cu_k[b + 1] - 1, at most max_k (the padded length); without, k, v are the dense [R, Tk, n_heads * 64].  cu_q / max_q do
+    the same for q and the result.  The bias table is indexed by j - i as in the padded call.  key_mask and causal must
+    stay None / False: they are here to be rejected.  On every valid element the result has the bits of t5_attention on
+    the scattered tensors with the prefix key mask."""
+    _need_gpu(q, k, v, bias_by_delta, key_mask, cu_q, cu_k)
+    who = "t5_attention_packed"
+    q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, _ = _packed_attention_args(
+        who, q, k, v, n_heads, cu_q, cu_k, max_q, max_k, bias_by_delta, key_mask, causal)
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty(q.shape, dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_packed(
+            _ptr(q), int(q.stride(-2)), _ptr(k), _ptr(v), int(k.stride(-2)), R, n_q, n_k, int(n_heads), 64, Tq, Tk,
+            _ptr(cu_q), _ptr(cu_k), _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0],
+            int(bias_offset), None, 0, _ptr(out), inner, _stream())
+        check(rc, "rqhip_t5_attention_packed")
+    return out
+
+
+def t5_attention_packed_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, cu_q: Optional[Tensor] = None,
+                                  cu_k: Optional[Tensor] = None, max_q: Optional[int] = None,
+                                  max_k: Optional[int] = None, bias_by_delta: Optional[Tensor] = None,
+                                  bias_offset: int = 0, key_mask: Optional[Tensor] = None, causal: bool = False,
+                                  p: float = 0.0, seed: Optional[Tensor] = None):
+    """t5_attention_packed for training (rqhip_t5_attention_packed_fwd_train) -> (out, lse); lse is [n_q, n_heads] with
+    cu_q and [R, n_heads, Tq] without.  The dropout decision of weight (b, h, i, j) is the padded call's,
+    t5_attention_dropout_keep(seed, R, H, max_q, max_k, p)[b, h, i, j].  At p = 0 `out` has the bits of
+    t5_attention_packed."""
+    _need_gpu(q, k, v, bias_by_delta, key_mask, cu_q, cu_k, seed)
+    who = "t5_attention_packed_fwd_train"
+    q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, seed_ptr = _packed_attention_args(
+        who, q, k, v, n_heads, cu_q, cu_k, max_q, max_k, bias_by_delta, key_mask, causal, p, seed)
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty(q.shape, dtype=torch.float32, device=dev)
+        lse = torch.empty((n_q, int(n_heads)) if cu_q is not None else (R, int(n_heads), Tq), dtype=torch.float32,
+                          device=dev)
+        rc = _lib.lib().rqhip_t5_attention_packed_fwd_train(
+            _ptr(q), int(q.stride(-2)), _ptr(k), _ptr(v), int(k.stride(-2)), R, n_q, n_k, int(n_heads), 64, Tq, Tk,
+            _ptr(cu_q), _ptr(cu_k), _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0],
+            int(bias_offset), None, 0, float(p), seed_ptr, _ptr(out), inner, _ptr(lse), _stream())
+        check(rc, "rqhip_t5_attention_packed_fwd_train")
+    return out, lse
+
+
+def t5_attention_packed_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, d_out: Tensor, n_heads: int, *,
+                            cu_q: Optional[Tensor] = None, cu_k: Optional[Tensor] = None, max_q: Optional[int] = None,
+                            max_k: Optional[int] = None, bias_by_delta: Optional[Tensor] = None, bias_offset: int = 0,
+                            key_mask: Optional[Tensor] = None, causal: bool = False, p: float = 0.0,
+                            seed: Optional[Tensor] = None):
+    """The gradients of t5_attention_packed_fwd_train in one attention launch (rqhip_t5_attention_packed_bwd) -> (dq in
+    q's layout, dk, dv in k's, dtable [n_delta, n_heads] or None).  The arguments are the forward's, its `out` and `lse`,
+    and d_out in q's layout."""
+    _need_gpu(q, k, v, out, lse, d_out, bias_by_delta, key_mask, cu_q, cu_k, seed)
+    who = "t5_attention_packed_bwd"
+    q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, seed_ptr = _packed_attention_args(
+        who, q, k, v, n_heads, cu_q, cu_k, max_q, max_k, bias_by_delta, key_mask, causal, p, seed)
+    out = _packed_side(who, out, "out", cu_q, Tq, inner)[0]
+    d_out = _packed_side(who, d_out, "d_out", cu_q, Tq, inner)[0]
+    if out.shape != q.shape or d_out.shape != q.shape:
+        raise RqHipError(f"{who}: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q {tuple(q.shape)}")
+    lse = _f32c(lse, "lse")
+    want = (n_q, int(n_heads)) if cu_q is not None else (R, int(n_heads), Tq)
+    if tuple(lse.shape) != want:
+        raise RqHipError(f"{who}: lse must be {list(want)}, got {tuple(lse.shape)}")
+    dev = q.device
+    with torch.cuda.device(dev):
+        dq = torch.empty(q.shape, dtype=torch.float32, device=dev)
+        dk = torch.empty(k.shape, dtype=torch.float32, device=dev)
+        dv = torch.empty(k.shape, dtype=torch.float32, device=dev)
+        dtable = partial = None
+        if bias_by_delta is not None:
+            dtable = torch.empty_like(bias_by_delta)
+            partial = torch.empty((R * int(n_heads), Tq + Tk - 1), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_packed_bwd(
+            _ptr(q), int(q.stride(-2)), _ptr(k), _ptr(v), int(k.stride(-2)), _ptr(out), int(out.stride(-2)), _ptr(lse),
+            _ptr(d_out), int(d_out.stride(-2)), R, n_q, n_k, int(n_heads), 64, Tq, Tk, _ptr(cu_q), _ptr(cu_k),
+            _ptr(bias_by_delta), 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset), None, 0,
+            float(p), seed_ptr, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dtable), _ptr(partial), _stream())
+        check(rc, "rqhip_t5_attention_packed_bwd")
+    return dq, dk, dv, dtable
+
+
+def rows_pack_supported(dtype: torch.dtype, d: int) -> bool:
+    """Whether rows_pack / rows_unpack implement this row width (rqhip_rows_pack_supported): fp32, d a multiple of 4."""
+    return dtype == torch.float32 and bool(_lib.lib().rqhip_rows_pack_supported(int(d)))
+
+
+def _rows_table(who: str, cu: Tensor, B: int) -> None:
+    if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() != B + 1 or not cu.is_contiguous():
+        raise RqHipError(f"{who}: cu must be a contiguous int32 [{B + 1}] tensor, got {cu.dtype} {tuple(cu.shape)}")
+
+
+def rows_pack(x: Tensor, cu: Tensor, N: int) -> Tensor:
+    """Padded rows x [B, T, d] -> packed [N, d] in one launch (rqhip_rows_pack): the first cu[b + 1] - cu[b] tokens of
+    row b land at rows cu[b] ..; cu is an int32 [B + 1] device table with cu[B] = N, and N is the caller's (host) count.
+    Exact copies."""
+    _need_gpu(x, cu)
+    x = _f32c(x, "x")
+    if x.dim() != 3:
+        raise RqHipError(f"rows_pack: x must be [B, T, d], got {tuple(x.shape)}")
+    B, T, d = x.shape
+    _rows_table("rows_pack", cu, B)
+    x = _aligned16(x)
+    with torch.cuda.device(x.device):
+        out = torch.empty((int(N), d), dtype=torch.float32, device=x.device)
+        check(_lib.lib().rqhip_rows_pack(_ptr(x), _ptr(cu), B, T, d, int(N), _ptr(out), _stream()), "rqhip_rows_pack")
+    return out
+
+
+def rows_unpack(x: Tensor, cu: Tensor, B: int, T: int) -> Tensor:
+    """Packed rows x [N, d] -> padded [B, T, d] in one launch (rqhip_rows_unpack), the padded tail of every row zero:
+    the inverse of rows_pack and its backward."""
+    _need_gpu(x, cu)
+    x = _f32c(x, "x")
+    if x.dim() != 2:
+        raise RqHipError(f"rows_unpack: x must be [N, d], got {tuple(x.shape)}")
+    N, d = x.shape
+    _rows_table("rows_unpack", cu, int(B))
+    x = _aligned16(x)
+    with torch.cuda.device(x.device):
+        out = torch.empty((int(B), int(T), d), dtype=torch.float32, device=x.device)
+        check(_lib.lib().rqhip_rows_unpack(_ptr(x), _ptr(cu), int(B), int(T), d, N, _ptr(out), _stream()),
+              "rqhip_rows_unpack")
+    return out
+
+
 # the arithmetics of t5_ffn_*, t5_proj_* and t5_attention_long* (include/rqhip.h): storage is fp32 in both
 T5_ARITHS = ("fp32", "bf16")
 

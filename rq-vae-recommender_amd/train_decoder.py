@@ -29,7 +29,15 @@ What differs:
     not set it.  Reading the bf16 arm's weights from bf16 images, `model.weight_images = "bf16"` (modules/t5.py), is
     a model attribute of the same kind: no parameter here, and amp goes on setting `matmul_arith` alone; the images
     follow every FlatAdamW step through rqhip.optim.generation().  So is `model.saved_activations = "bf16"`
-    (modules/t5.py), which makes the bf16 feed-forward keep bf16 images of its activations for the backward.  push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
+    (modules/t5.py), which makes the bf16 feed-forward keep bf16 images of its activations for the backward.
+  * packed encoder rows.  `encoder_rows` below is a gin-configurable of its own, not a parameter of `train`, whose
+    parameter set stays the reference's plus the six kernel and logging choices (tests/test_seq_batch_host.py pins it).
+    The binding `encoder_rows.mode = "packed"` (default "padded"; a config line, or gin.parse_config from Python) makes
+    `train` set `model.encoder_rows` (modules/model.py) and build both loaders with host_windows=True (data/seq_loader.py): the windows are drawn on the host, every batch says how many items each row
+    holds, and the encoder, the cross-attention K/V and every kernel between them run on the valid tokens only.  The
+    number of rows of such a step depends on the data, so a packed step cannot be captured into a graph.  The
+    checkpoint is the same: it loads into a padded model and back.  configs/decoder_amazon_packed.gin.
+    push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
     reference.
 wandb is optional: with `wandb_logging=True` and no wandb module, metrics are printed.
 The full eval here reports one draw of the sampling beam search; evaluate_decoder.py evaluates a checkpoint with the
@@ -47,7 +55,7 @@ from data.processed import ItemData, RecDataset, SeqData
 from data.seq_loader import TokenizedSeqLoader
 from data.utils import cycle
 from evaluate.metrics import TopKAccumulator
-from modules.model import EncoderDecoderRetrievalModel
+from modules.model import ENCODER_ROWS, EncoderDecoderRetrievalModel
 from modules.scheduler.inv_sqrt import InverseSquareRootScheduler
 from modules.tokenizer.semids import SemanticIdTokenizer
 from modules.utils import parse_config
@@ -83,6 +91,15 @@ def load_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, map_loc
     if lr_scheduler is not None and "scheduler" in state:
         lr_scheduler.load_state_dict(state["scheduler"])
     return state["iter"] + 1
+
+
+@gin.configurable
+def encoder_rows(mode="padded"):
+    """How `train` lays out the encoder's rows (module docstring): "padded", or "packed" -- bound as
+    `encoder_rows.mode = "packed"`, which configs/decoder_amazon_packed.gin adds to configs/decoder_amazon.gin."""
+    if mode not in ENCODER_ROWS:
+        raise ValueError(f"encoder_rows.mode must be one of {ENCODER_ROWS}, got {mode!r}")
+    return mode
 
 
 @gin.configurable
@@ -142,6 +159,7 @@ def train(
             f"amp=True ({mixed_precision_type}): the fused T5 kernels (attention, add/norm, heads, embedding) and the "
             'device optimizer are fp32 only; the feed-forward and projection kernels are fp32 or, with '
             'mixed_precision_type="bf16", bf16-operand')
+    rows = encoder_rows()      # "padded", or "packed" by the binding encoder_rows.mode (validated there)
     if push_vae_to_hf:
         raise NotImplementedError("push_vae_to_hf=True needs the network (huggingface_hub); upload the RQ-VAE checkpoint "
                                   "separately")
@@ -176,8 +194,10 @@ def train(
     tokenizer.precompute_corpus_ids(item_dataset)
 
     # (the loaders check every stored item id against the corpus once, here)
-    train_dataloader = cycle(TokenizedSeqLoader(train_dataset, tokenizer, batch_size, shuffle=True))
-    eval_dataloader = TokenizedSeqLoader(eval_dataset, tokenizer, batch_size, shuffle=True)
+    host_windows = rows == "packed"    # the batches then carry their rows' item counts on the host
+    train_dataloader = cycle(TokenizedSeqLoader(train_dataset, tokenizer, batch_size, shuffle=True,
+                                                host_windows=host_windows))
+    eval_dataloader = TokenizedSeqLoader(eval_dataset, tokenizer, batch_size, shuffle=True, host_windows=host_windows)
 
     model = EncoderDecoderRetrievalModel(
         codebooks=tokenizer.cached_ids[:, :vae_n_layers].contiguous(), num_hierarchies=vae_n_layers,
@@ -186,6 +206,7 @@ def train(
         num_user_bins=num_user_bins).to(device)
     model.attention_impl, model.norm_impl, model.ffn_impl = attention_impl, norm_impl, ffn_impl
     model.head_impl, model.embed_impl = head_impl, embed_impl
+    model.encoder_rows = rows
     if amp:
         model.matmul_arith = "bf16"
 
