@@ -668,22 +668,178 @@ int check_att_call(const char *who, bool train, int64_t R, int64_t Rk, int H, in
     return RQHIP_OK;
 }
 
+// The packed form of a call: the cumulative row tables and row counts the PACKED kernels read, and the key_mask / causal
+// the caller passed, which check_packed_call rejects.  A null descriptor is the padded form.
+struct AttPacked {
+    const int32_t *cu_q, *cu_k;
+    int64_t n_q, n_k;
+    const uint8_t *key_mask;
+    int causal;
+};
+
 // What the three packed entry points check beyond check_att_call: the tables and the row counts they index.
-int check_packed_call(const char *who, int64_t R, int64_t n_q, int64_t n_k, int Tq, int Tk, const int32_t *cu_q,
-                      const int32_t *cu_k, const uint8_t *key_mask, int causal) {
-    if (!cu_q && !cu_k) {
+int check_packed_call(const char *who, int64_t R, int Tq, int Tk, const AttPacked &pk) {
+    if (!pk.cu_q && !pk.cu_k) {
         set_error("%s: no cumulative table (cu_q, cu_k): the dense call is rqhip_t5_attention*", who);
         return RQHIP_EARG;
     }
-    if (causal || key_mask) {
+    if (pk.causal || pk.key_mask) {
         set_error("%s: a cumulative table goes with neither causal nor key_mask (every packed key is valid)", who);
         return RQHIP_EARG;
     }
-    if (n_q < 0 || n_k < 0 || n_q >= (1ll << 31) || n_k >= (1ll << 31) || (!cu_q && n_q != R * Tq) ||
-        (!cu_k && n_k != R * Tk) || n_q > R * Tq || n_k > R * Tk) {
+    if (pk.n_q < 0 || pk.n_k < 0 || pk.n_q >= (1ll << 31) || pk.n_k >= (1ll << 31) || (!pk.cu_q && pk.n_q != R * Tq) ||
+        (!pk.cu_k && pk.n_k != R * Tk) || pk.n_q > R * Tq || pk.n_k > R * Tk) {
         set_error("%s: n_q=%lld / n_k=%lld rows do not go with R=%lld groups of at most Tq=%d / Tk=%d (a dense side "
-                  "holds exactly R * T rows; int32 tables)", who, (long long)n_q, (long long)n_k, (long long)R, Tq, Tk);
+                  "holds exactly R * T rows; int32 tables)", who, (long long)pk.n_q, (long long)pk.n_k, (long long)R, Tq, Tk);
         return RQHIP_EARG;
+    }
+    return RQHIP_OK;
+}
+
+// ---- the three calls behind the six entry points: checks, null and alignment tests, struct fill and launch, each once.
+// `pk`: the packed form, which runs the same kernel bodies in their PACKED instantiations (lengths per group through
+// cu_q / cu_k, the padded call's plan by the bounds).  Its entry points pass Rk = R and key_mask = null, causal = 0 (the
+// caller's are in *pk), and it is checked as the training pair is: one K/V per row.
+
+int att_fwd_call(const char *who, const AttPacked *pk, const float *q, int64_t ld_q, const float *k, const float *v,
+                 int64_t ld_kv, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta,
+                 int n_delta, int bias_offset, const uint8_t *key_mask, int causal, int past, const int32_t *anc,
+                 int64_t ld_anc, int64_t slab_rows, float *out, int64_t ld_out, rqhip_stream_t stream) {
+    int rc = check_att_call(who, pk != nullptr, R, Rk, H, d_kv, Tq, Tk, past, anc, ld_anc, slab_rows, {ld_q, ld_kv, ld_out},
+                            bias_by_delta, n_delta, bias_offset, causal, 0.0);
+    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, Tq, Tk, *pk);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0 || (pk && pk->n_q == 0)) return RQHIP_OK;
+    if (any_null(q, out) || ((!pk || pk->n_k > 0) && any_null(k, v))) {
+        set_error("%s: null pointer (q, k, v, out)", who);
+        return RQHIP_EARG;
+    }
+    if (!all_aligned16(q, k, v, out)) {
+        set_error("%s: q, k, v and out must be 16-byte aligned", who);
+        return RQHIP_EARG;
+    }
+    const AttPacked form = pk ? *pk : AttPacked{};
+    AttArgs a;
+    a.q = q, a.k = k, a.v = v, a.out = out;
+    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
+    a.beams = (int)(R / Rk), a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = past, a.causal = causal != 0;
+    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1) - past;  // table row of the smallest delta j - i - past
+    a.key_mask = key_mask;
+    a.anc = past > 0 ? anc : nullptr;  // at past = 0 the only key is the row's own: the dense form of slab 0
+    a.ld_anc = ld_anc, a.slab_rows = slab_rows;
+    a.cu_q = form.cu_q, a.cu_k = form.cu_k, a.n_q = form.n_q, a.n_k = form.n_k;
+    if ((int64_t)a.beams * Tq >= (1ll << 24)) {
+        set_error("%s: %lld query rows per K/V group", who, (long long)a.beams * Tq);
+        return RQHIP_EUNSUPPORTED;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
+    return att_with_mt(Tk, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        const size_t most = att_lds_bytes(kAttMaxT, att_most_tk(MT), true);
+        const int threads = MT == 1 ? RQ_WAVE : 4 * RQ_WAVE;
+        return pk ? launch_att<t5_attention_kernel<MT, true>>("t5_attention_kernel (packed)", most, Rk * H, threads, lds, s,
+                                                              a)
+                  : launch_att<t5_attention_kernel<MT, false>>("t5_attention_kernel", most, Rk * H, threads, lds, s, a);
+    });
+}
+
+int att_fwd_train_call(const char *who, const AttPacked *pk, const float *q, int64_t ld_q, const float *k, const float *v,
+                       int64_t ld_kv, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta,
+                       int n_delta, int bias_offset, const uint8_t *key_mask, int causal, double p, const int64_t *seed,
+                       float *out, int64_t ld_out, float *lse, rqhip_stream_t stream) {
+    int rc = check_att_call(who, true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0, {ld_q, ld_kv, ld_out}, bias_by_delta,
+                            n_delta, bias_offset, causal, p);
+    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, Tq, Tk, *pk);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0 || (pk && pk->n_q == 0)) return RQHIP_OK;
+    const unsigned thresh = dropout_threshold(p);
+    if (any_null(q, out, lse) || ((!pk || pk->n_k > 0) && any_null(k, v)) || (thresh && !seed)) {
+        set_error("%s: null pointer (q, k, v, out, lse; seed when p > 0)", who);
+        return RQHIP_EARG;
+    }
+    if (!all_aligned16(q, k, v, out)) {
+        set_error("%s: q, k, v and out must be 16-byte aligned", who);
+        return RQHIP_EARG;
+    }
+    const AttPacked form = pk ? *pk : AttPacked{};
+    AttArgs a;
+    a.q = q, a.k = k, a.v = v, a.out = out;
+    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
+    a.beams = 1, a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = 0, a.causal = causal != 0;
+    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
+    a.key_mask = key_mask;
+    a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
+    a.cu_q = form.cu_q, a.cu_k = form.cu_k, a.n_q = form.n_q, a.n_k = form.n_k;
+    AttTrain t;
+    t.lse = lse, t.seed = reinterpret_cast<const long long *>(seed), t.thresh = thresh;
+    t.inv_keep = dropout_scale_f32(p);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
+    return att_with_mt(Tk, [&](auto mt) {  // the inference call's plan
+        constexpr int MT = decltype(mt)::value;
+        const size_t most = att_lds_bytes(kAttMaxT, att_most_tk(MT), true);
+        const int threads = MT == 1 ? RQ_WAVE : 4 * RQ_WAVE;
+        return pk ? launch_att<t5_attention_train_kernel<MT, true>>("t5_attention_train_kernel (packed)", most, R * H,
+                                                                    threads, lds, s, a, t)
+                  : launch_att<t5_attention_train_kernel<MT, false>>("t5_attention_train_kernel", most, R * H, threads,
+                                                                     lds, s, a, t);
+    });
+}
+
+int att_bwd_call(const char *who, const AttPacked *pk, const float *q, int64_t ld_q, const float *k, const float *v,
+                 int64_t ld_kv, const float *out, int64_t ld_out, const float *lse, const float *d_out, int64_t ld_do,
+                 int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta,
+                 int bias_offset, const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *d_q,
+                 float *d_k, float *d_v, float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream) {
+    int rc = check_att_call(who, true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0, {ld_q, ld_kv, ld_out, ld_do}, bias_by_delta,
+                            n_delta, bias_offset, causal, p);
+    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, Tq, Tk, *pk);
+    if (rc != RQHIP_OK) return rc;
+    if (R == 0 && !bias_by_delta) return RQHIP_OK;
+    const unsigned thresh = dropout_threshold(p);
+    // a packed side without rows may be null
+    if (((!pk || pk->n_q > 0) && any_null(q, out, lse, d_out, d_q)) || ((!pk || pk->n_k > 0) && any_null(k, v, d_k, d_v)) ||
+        (thresh && !seed) || (bias_by_delta && any_null(d_bias_by_delta, d_bias_partial))) {
+        set_error("%s: null pointer (q, k, v, out, lse, d_out, d_q, d_k, d_v; seed when p > 0; "
+                  "d_bias_by_delta and d_bias_partial with a bias table)", who);
+        return RQHIP_EARG;
+    }
+    if (!all_aligned16(q, k, v, out, d_out, d_q, d_k, d_v)) {
+        set_error("%s: q, k, v, out, d_out, d_q, d_k and d_v must be 16-byte aligned", who);
+        return RQHIP_EARG;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nb = Tq + Tk - 1;
+    if (R > 0) {
+        const AttPacked form = pk ? *pk : AttPacked{};
+        AttBwdArgs a;
+        a.q = q, a.k = k, a.v = v, a.d_out = d_out;
+        a.dq = d_q, a.dk = d_k, a.dv = d_v, a.dbias_part = d_bias_partial;
+        a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_do = ld_do;
+        a.H = H, a.Tq = Tq, a.Tk = Tk, a.causal = causal != 0;
+        a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
+        a.key_mask = key_mask;
+        a.seed = reinterpret_cast<const long long *>(seed), a.thresh = thresh;
+        a.inv_keep = dropout_scale_f32(p);
+        a.cu_q = form.cu_q, a.cu_k = form.cu_k, a.n_q = form.n_q, a.n_k = form.n_k;
+        const int threads = (Tq <= 16 && Tk <= 16) ? RQ_WAVE : 4 * RQ_WAVE;
+        const size_t lds = att_bwd_lds(Tq, Tk, bias_by_delta != nullptr, threads / RQ_WAVE).total * sizeof(float);
+        const int lrc = att_with_mt(Tk, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            const size_t most = att_bwd_lds(kAttMaxT, att_most_tk(MT), true, 4).total * sizeof(float);
+            return pk ? launch_att<t5_attention_bwd_kernel<MT, true>>("t5_attention_bwd_kernel (packed)", most, R * H,
+                                                                      threads, lds, s, a)
+                      : launch_att<t5_attention_bwd_kernel<MT, false>>("t5_attention_bwd_kernel", most, R * H, threads, lds,
+                                                                       s, a);
+        });
+        if (lrc != RQHIP_OK) return lrc;
+    }
+    if (bias_by_delta) {
+        const long long n = (long long)n_delta * H;
+        hipLaunchKernelGGL(t5_dbias_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_bias_partial, R, H,
+                           nb, bias_offset - (Tq - 1), n_delta, d_bias_by_delta);
+        RQ_CHECK_LAUNCH("t5_dbias_reduce_kernel");
     }
     return RQHIP_OK;
 }
@@ -696,145 +852,21 @@ using namespace rqhip;
 
 extern "C" int rqhip_t5_attention_supported(int d_kv, int H, int Tq, int Tk) { return att_supported(d_kv, H, Tq, Tk); }
 
+extern "C" int rqhip_t5_attention_bwd_supported(int d_kv, int H, int Tq, int Tk) {
+    return att_supported(d_kv, H, Tq, Tk);
+}
+
+extern "C" int rqhip_t5_attention_packed_supported(int d_kv, int H, int Tq, int Tk) {
+    return att_supported(d_kv, H, Tq, Tk);
+}
+
 extern "C" int rqhip_t5_attention(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv, int64_t R,
                                   int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta, int n_delta,
                                   int bias_offset, const uint8_t *key_mask, int causal, int past, const int32_t *anc,
                                   int64_t ld_anc, int64_t slab_rows, float *out, int64_t ld_out,
                                   rqhip_stream_t stream) {
-    const int rc = check_att_call("t5_attention", false, R, Rk, H, d_kv, Tq, Tk, past, anc, ld_anc, slab_rows,
-                                  {ld_q, ld_kv, ld_out}, bias_by_delta, n_delta, bias_offset, causal, 0.0);
-    if (rc != RQHIP_OK) return rc;
-    if (R == 0) return RQHIP_OK;
-    if (any_null(q, k, v, out)) {
-        set_error("t5_attention: null pointer (q, k, v, out)");
-        return RQHIP_EARG;
-    }
-    if (!all_aligned16(q, k, v, out)) {
-        set_error("t5_attention: q, k, v and out must be 16-byte aligned");
-        return RQHIP_EARG;
-    }
-    AttArgs a;
-    a.q = q, a.k = k, a.v = v, a.out = out;
-    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
-    a.beams = (int)(R / Rk), a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = past, a.causal = causal != 0;
-    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1) - past;  // table row of the smallest delta j - i - past
-    a.key_mask = key_mask;
-    a.anc = past > 0 ? anc : nullptr;  // at past = 0 the only key is the row's own: the dense form of slab 0
-    a.ld_anc = ld_anc, a.slab_rows = slab_rows;
-    a.cu_q = a.cu_k = nullptr, a.n_q = a.n_k = 0;
-    if ((int64_t)a.beams * Tq >= (1ll << 24)) {
-        set_error("t5_attention: %lld query rows per K/V group", (long long)a.beams * Tq);
-        return RQHIP_EUNSUPPORTED;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
-    return att_with_mt(Tk, [&](auto mt) {
-        constexpr int MT = decltype(mt)::value;
-        return launch_att<t5_attention_kernel<MT>>("t5_attention_kernel", att_lds_bytes(kAttMaxT, att_most_tk(MT), true),
-                                                   Rk * H, MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a);
-    });
-}
-
-extern "C" int rqhip_t5_attention_bwd_supported(int d_kv, int H, int Tq, int Tk) {
-    return att_supported(d_kv, H, Tq, Tk);
-}
-
-extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
-                                            int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
-                                            const float *bias_by_delta, int n_delta, int bias_offset,
-                                            const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *out,
-                                            int64_t ld_out, float *lse, rqhip_stream_t stream) {
-    const int rc = check_att_call("t5_attention_fwd_train", true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
-                                  {ld_q, ld_kv, ld_out}, bias_by_delta, n_delta, bias_offset, causal, p);
-    if (rc != RQHIP_OK) return rc;
-    if (R == 0) return RQHIP_OK;
-    const unsigned thresh = dropout_threshold(p);
-    if (any_null(q, k, v, out, lse) || (thresh && !seed)) {
-        set_error("t5_attention_fwd_train: null pointer (q, k, v, out, lse; seed when p > 0)");
-        return RQHIP_EARG;
-    }
-    if (!all_aligned16(q, k, v, out)) {
-        set_error("t5_attention_fwd_train: q, k, v and out must be 16-byte aligned");
-        return RQHIP_EARG;
-    }
-    AttArgs a;
-    a.q = q, a.k = k, a.v = v, a.out = out;
-    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
-    a.beams = 1, a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = 0, a.causal = causal != 0;
-    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
-    a.key_mask = key_mask;
-    a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
-    a.cu_q = a.cu_k = nullptr, a.n_q = a.n_k = 0;
-    AttTrain t;
-    t.lse = lse, t.seed = reinterpret_cast<const long long *>(seed), t.thresh = thresh;
-    t.inv_keep = dropout_scale_f32(p);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
-    return att_with_mt(Tk, [&](auto mt) {  // the inference entry point's plan
-        constexpr int MT = decltype(mt)::value;
-        return launch_att<t5_attention_train_kernel<MT>>("t5_attention_train_kernel",
-                                                         att_lds_bytes(kAttMaxT, att_most_tk(MT), true), R * H,
-                                                         MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a, t);
-    });
-}
-
-extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
-                                      const float *out, int64_t ld_out, const float *lse, const float *d_out,
-                                      int64_t ld_do, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
-                                      const float *bias_by_delta, int n_delta, int bias_offset, const uint8_t *key_mask,
-                                      int causal, double p, const int64_t *seed, float *d_q, float *d_k, float *d_v,
-                                      float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream) {
-    const int rc = check_att_call("t5_attention_bwd", true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
-                                  {ld_q, ld_kv, ld_out, ld_do}, bias_by_delta, n_delta, bias_offset, causal, p);
-    if (rc != RQHIP_OK) return rc;
-    if (R == 0 && !bias_by_delta) return RQHIP_OK;
-    const unsigned thresh = dropout_threshold(p);
-    if (any_null(q, k, v, out, lse, d_out, d_q, d_k, d_v) || (thresh && !seed) ||
-        (bias_by_delta && any_null(d_bias_by_delta, d_bias_partial))) {
-        set_error("t5_attention_bwd: null pointer (q, k, v, out, lse, d_out, d_q, d_k, d_v; seed when p > 0; "
-                  "d_bias_by_delta and d_bias_partial with a bias table)");
-        return RQHIP_EARG;
-    }
-    if (!all_aligned16(q, k, v, out, d_out, d_q, d_k, d_v)) {
-        set_error("t5_attention_bwd: q, k, v, out, d_out, d_q, d_k and d_v must be 16-byte aligned");
-        return RQHIP_EARG;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int nb = Tq + Tk - 1;
-    if (R > 0) {
-        AttBwdArgs a;
-        a.q = q, a.k = k, a.v = v, a.d_out = d_out;
-        a.dq = d_q, a.dk = d_k, a.dv = d_v, a.dbias_part = d_bias_partial;
-        a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_do = ld_do;
-        a.H = H, a.Tq = Tq, a.Tk = Tk, a.causal = causal != 0;
-        a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
-        a.key_mask = key_mask;
-        a.seed = reinterpret_cast<const long long *>(seed), a.thresh = thresh;
-        a.inv_keep = dropout_scale_f32(p);
-        a.cu_q = a.cu_k = nullptr, a.n_q = a.n_k = 0;
-        const int threads = (Tq <= 16 && Tk <= 16) ? RQ_WAVE : 4 * RQ_WAVE;
-        const size_t lds = att_bwd_lds(Tq, Tk, bias_by_delta != nullptr, threads / RQ_WAVE).total * sizeof(float);
-        const int lrc = att_with_mt(Tk, [&](auto mt) {
-            constexpr int MT = decltype(mt)::value;
-            return launch_att<t5_attention_bwd_kernel<MT>>(
-                "t5_attention_bwd_kernel", att_bwd_lds(kAttMaxT, att_most_tk(MT), true, 4).total * sizeof(float), R * H,
-                threads, lds, s, a);
-        });
-        if (lrc != RQHIP_OK) return lrc;
-    }
-    if (bias_by_delta) {
-        const long long n = (long long)n_delta * H;
-        hipLaunchKernelGGL(t5_dbias_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_bias_partial, R, H,
-                           nb, bias_offset - (Tq - 1), n_delta, d_bias_by_delta);
-        RQ_CHECK_LAUNCH("t5_dbias_reduce_kernel");
-    }
-    return RQHIP_OK;
-}
-
-// ---- the packed forms: the same kernel bodies, PACKED instantiations (lengths per group through cu_q / cu_k)
-
-extern "C" int rqhip_t5_attention_packed_supported(int d_kv, int H, int Tq, int Tk) {
-    return att_supported(d_kv, H, Tq, Tk);
+    return att_fwd_call("t5_attention", nullptr, q, ld_q, k, v, ld_kv, R, Rk, H, d_kv, Tq, Tk, bias_by_delta, n_delta,
+                        bias_offset, key_mask, causal, past, anc, ld_anc, slab_rows, out, ld_out, stream);
 }
 
 extern "C" int rqhip_t5_attention_packed(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
@@ -842,34 +874,18 @@ extern "C" int rqhip_t5_attention_packed(const float *q, int64_t ld_q, const flo
                                          const int32_t *cu_q, const int32_t *cu_k, const float *bias_by_delta,
                                          int n_delta, int bias_offset, const uint8_t *key_mask, int causal, float *out,
                                          int64_t ld_out, rqhip_stream_t stream) {
-    int rc = check_att_call("t5_attention_packed", true, R, R, H, d_kv, Tq, Tk, 0, nullptr, 0, 0, {ld_q, ld_kv, ld_out},
-                            bias_by_delta, n_delta, bias_offset, 0, 0.0);
-    if (rc == RQHIP_OK) rc = check_packed_call("t5_attention_packed", R, n_q, n_k, Tq, Tk, cu_q, cu_k, key_mask, causal);
-    if (rc != RQHIP_OK) return rc;
-    if (R == 0 || n_q == 0) return RQHIP_OK;
-    if (any_null(q, out) || (n_k > 0 && any_null(k, v))) {
-        set_error("t5_attention_packed: null pointer (q, k, v, out)");
-        return RQHIP_EARG;
-    }
-    if (!all_aligned16(q, k, v, out)) {
-        set_error("t5_attention_packed: q, k, v and out must be 16-byte aligned");
-        return RQHIP_EARG;
-    }
-    AttArgs a;
-    a.q = q, a.k = k, a.v = v, a.out = out;
-    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
-    a.beams = 1, a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = 0, a.causal = 0;
-    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
-    a.key_mask = nullptr, a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
-    a.cu_q = cu_q, a.cu_k = cu_k, a.n_q = n_q, a.n_k = n_k;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
-    return att_with_mt(Tk, [&](auto mt) {  // the padded call's plan, by the bounds
-        constexpr int MT = decltype(mt)::value;
-        return launch_att<t5_attention_kernel<MT, true>>("t5_attention_kernel (packed)",
-                                                         att_lds_bytes(kAttMaxT, att_most_tk(MT), true), R * H,
-                                                         MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a);
-    });
+    const AttPacked pk{cu_q, cu_k, n_q, n_k, key_mask, causal};
+    return att_fwd_call("t5_attention_packed", &pk, q, ld_q, k, v, ld_kv, R, R, H, d_kv, Tq, Tk, bias_by_delta, n_delta,
+                        bias_offset, nullptr, 0, 0, nullptr, 0, 0, out, ld_out, stream);
+}
+
+extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                            int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
+                                            const float *bias_by_delta, int n_delta, int bias_offset,
+                                            const uint8_t *key_mask, int causal, double p, const int64_t *seed, float *out,
+                                            int64_t ld_out, float *lse, rqhip_stream_t stream) {
+    return att_fwd_train_call("t5_attention_fwd_train", nullptr, q, ld_q, k, v, ld_kv, R, Rk, H, d_kv, Tq, Tk, bias_by_delta,
+                              n_delta, bias_offset, key_mask, causal, p, seed, out, ld_out, lse, stream);
 }
 
 extern "C" int rqhip_t5_attention_packed_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v,
@@ -878,39 +894,20 @@ extern "C" int rqhip_t5_attention_packed_fwd_train(const float *q, int64_t ld_q,
                                                    const float *bias_by_delta, int n_delta, int bias_offset,
                                                    const uint8_t *key_mask, int causal, double p, const int64_t *seed,
                                                    float *out, int64_t ld_out, float *lse, rqhip_stream_t stream) {
-    int rc = check_att_call("t5_attention_packed_fwd_train", true, R, R, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
-                            {ld_q, ld_kv, ld_out}, bias_by_delta, n_delta, bias_offset, 0, p);
-    if (rc == RQHIP_OK)
-        rc = check_packed_call("t5_attention_packed_fwd_train", R, n_q, n_k, Tq, Tk, cu_q, cu_k, key_mask, causal);
-    if (rc != RQHIP_OK) return rc;
-    if (R == 0 || n_q == 0) return RQHIP_OK;
-    const unsigned thresh = dropout_threshold(p);
-    if (any_null(q, out, lse) || (n_k > 0 && any_null(k, v)) || (thresh && !seed)) {
-        set_error("t5_attention_packed_fwd_train: null pointer (q, k, v, out, lse; seed when p > 0)");
-        return RQHIP_EARG;
-    }
-    if (!all_aligned16(q, k, v, out)) {
-        set_error("t5_attention_packed_fwd_train: q, k, v and out must be 16-byte aligned");
-        return RQHIP_EARG;
-    }
-    AttArgs a;
-    a.q = q, a.k = k, a.v = v, a.out = out;
-    a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_out = ld_out;
-    a.beams = 1, a.H = H, a.Tq = Tq, a.Tk = Tk, a.past = 0, a.causal = 0;
-    a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
-    a.key_mask = nullptr, a.anc = nullptr, a.ld_anc = 0, a.slab_rows = 0;
-    a.cu_q = cu_q, a.cu_k = cu_k, a.n_q = n_q, a.n_k = n_k;
-    AttTrain t;
-    t.lse = lse, t.seed = reinterpret_cast<const long long *>(seed), t.thresh = thresh;
-    t.inv_keep = dropout_scale_f32(p);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t lds = att_lds_bytes(Tq, Tk, bias_by_delta != nullptr);
-    return att_with_mt(Tk, [&](auto mt) {
-        constexpr int MT = decltype(mt)::value;
-        return launch_att<t5_attention_train_kernel<MT, true>>("t5_attention_train_kernel (packed)",
-                                                               att_lds_bytes(kAttMaxT, att_most_tk(MT), true), R * H,
-                                                               MT == 1 ? RQ_WAVE : 4 * RQ_WAVE, lds, s, a, t);
-    });
+    const AttPacked pk{cu_q, cu_k, n_q, n_k, key_mask, causal};
+    return att_fwd_train_call("t5_attention_packed_fwd_train", &pk, q, ld_q, k, v, ld_kv, R, R, H, d_kv, Tq, Tk,
+                              bias_by_delta, n_delta, bias_offset, nullptr, 0, p, seed, out, ld_out, lse, stream);
+}
+
+extern "C" int rqhip_t5_attention_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                      const float *out, int64_t ld_out, const float *lse, const float *d_out,
+                                      int64_t ld_do, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk,
+                                      const float *bias_by_delta, int n_delta, int bias_offset, const uint8_t *key_mask,
+                                      int causal, double p, const int64_t *seed, float *d_q, float *d_k, float *d_v,
+                                      float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream) {
+    return att_bwd_call("t5_attention_bwd", nullptr, q, ld_q, k, v, ld_kv, out, ld_out, lse, d_out, ld_do, R, Rk, H, d_kv,
+                        Tq, Tk, bias_by_delta, n_delta, bias_offset, key_mask, causal, p, seed, d_q, d_k, d_v,
+                        d_bias_by_delta, d_bias_partial, stream);
 }
 
 extern "C" int rqhip_t5_attention_packed_bwd(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
@@ -921,50 +918,8 @@ extern "C" int rqhip_t5_attention_packed_bwd(const float *q, int64_t ld_q, const
                                              const uint8_t *key_mask, int causal, double p, const int64_t *seed,
                                              float *d_q, float *d_k, float *d_v, float *d_bias_by_delta,
                                              float *d_bias_partial, rqhip_stream_t stream) {
-    int rc = check_att_call("t5_attention_packed_bwd", true, R, R, H, d_kv, Tq, Tk, 0, nullptr, 0, 0,
-                            {ld_q, ld_kv, ld_out, ld_do}, bias_by_delta, n_delta, bias_offset, 0, p);
-    if (rc == RQHIP_OK) rc = check_packed_call("t5_attention_packed_bwd", R, n_q, n_k, Tq, Tk, cu_q, cu_k, key_mask, causal);
-    if (rc != RQHIP_OK) return rc;
-    if (R == 0 && !bias_by_delta) return RQHIP_OK;
-    const unsigned thresh = dropout_threshold(p);
-    if ((n_q > 0 && any_null(q, out, lse, d_out, d_q)) || (n_k > 0 && any_null(k, v, d_k, d_v)) || (thresh && !seed) ||
-        (bias_by_delta && any_null(d_bias_by_delta, d_bias_partial))) {
-        set_error("t5_attention_packed_bwd: null pointer (q, k, v, out, lse, d_out, d_q, d_k, d_v; seed when p > 0; "
-                  "d_bias_by_delta and d_bias_partial with a bias table)");
-        return RQHIP_EARG;
-    }
-    if (!all_aligned16(q, k, v, out, d_out, d_q, d_k, d_v)) {
-        set_error("t5_attention_packed_bwd: q, k, v, out, d_out, d_q, d_k and d_v must be 16-byte aligned");
-        return RQHIP_EARG;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int nb = Tq + Tk - 1;
-    if (R > 0) {
-        AttBwdArgs a;
-        a.q = q, a.k = k, a.v = v, a.d_out = d_out;
-        a.dq = d_q, a.dk = d_k, a.dv = d_v, a.dbias_part = d_bias_partial;
-        a.ld_q = ld_q, a.ld_kv = ld_kv, a.ld_do = ld_do;
-        a.H = H, a.Tq = Tq, a.Tk = Tk, a.causal = 0;
-        a.bias = bias_by_delta, a.bias_base = bias_offset - (Tq - 1);
-        a.key_mask = nullptr;
-        a.seed = reinterpret_cast<const long long *>(seed), a.thresh = thresh;
-        a.inv_keep = dropout_scale_f32(p);
-        a.cu_q = cu_q, a.cu_k = cu_k, a.n_q = n_q, a.n_k = n_k;
-        const int threads = (Tq <= 16 && Tk <= 16) ? RQ_WAVE : 4 * RQ_WAVE;  // the padded call's, by the bounds
-        const size_t lds = att_bwd_lds(Tq, Tk, bias_by_delta != nullptr, threads / RQ_WAVE).total * sizeof(float);
-        const int lrc = att_with_mt(Tk, [&](auto mt) {
-            constexpr int MT = decltype(mt)::value;
-            return launch_att<t5_attention_bwd_kernel<MT, true>>(
-                "t5_attention_bwd_kernel (packed)", att_bwd_lds(kAttMaxT, att_most_tk(MT), true, 4).total * sizeof(float),
-                R * H, threads, lds, s, a);
-        });
-        if (lrc != RQHIP_OK) return lrc;
-    }
-    if (bias_by_delta) {
-        const long long n = (long long)n_delta * H;
-        hipLaunchKernelGGL(t5_dbias_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_bias_partial, R, H,
-                           nb, bias_offset - (Tq - 1), n_delta, d_bias_by_delta);
-        RQ_CHECK_LAUNCH("t5_dbias_reduce_kernel");
-    }
-    return RQHIP_OK;
+    const AttPacked pk{cu_q, cu_k, n_q, n_k, key_mask, causal};
+    return att_bwd_call("t5_attention_packed_bwd", &pk, q, ld_q, k, v, ld_kv, out, ld_out, lse, d_out, ld_do, R, R, H, d_kv,
+                        Tq, Tk, bias_by_delta, n_delta, bias_offset, nullptr, 0, p, seed, d_q, d_k, d_v, d_bias_by_delta,
+                        d_bias_partial, stream);
 }

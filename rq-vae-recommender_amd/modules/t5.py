@@ -127,10 +127,10 @@ grouped projections run unchanged on the N rows: their kernels take any row coun
 on the batch (include/rqhip.h), so in eval mode the loss keeps the padded path's bits (weight gradients sum the rows in
 other groups and differ by rounding).  In train mode a row-local dropout decision is a function of the element's index
 among the N rows, so a packed step draws other masks than a padded one: the same law, another sample.  Packed rows need
-the fused attention this forward would take anyway ("hip_train" under grad; "hip" or "hip_train" without active dropout
-under no_grad; `T5Stack.packed_rows_active`) and every length within the short kernel's 256; elsewhere they raise --
-modules/model.py checks before it packs and runs the padded path instead.  N depends on the data, so a packed forward
-cannot be replayed from a captured graph.
+the fused attention this forward is in anyway (`T5Stack._attention_mode`, which `packed_rows_active` asks as the other two
+attention predicates do) and every length within the short kernel's 256; elsewhere they raise -- modules/model.py checks
+before it packs and runs the padded path instead.  N depends on the data, so a packed forward cannot be replayed from a
+captured graph.
 
 The fused forms take their dropout seeds as int64s drawn on the device with torch.randint (the default generator:
 torch.manual_seed reproduces a run), none in eval mode or at dropout_rate 0.  The fused attention draws one per call.
@@ -498,9 +498,9 @@ class _HipAttention:
         call with both tables.  encoder_packed: the encoder output is ([1, N, d]): every cross-attention is a packed
         call of the dense queries over packed K/V.  Neither takes a mask: every packed token is valid."""
         self.packed, self.encoder_packed = packed, encoder_packed
-        self.train = train
-        self.plan = plan
+        self.train, self.plan = train, plan
         self.long = stack.attention_long_impl == "hip"  # calls the short kernel does not support go to the long one
+        self.long_for = {}  # (Tq, Tk) -> whether that call is a long one
         self.long_arith = stack.attention_arith
         self.long_kw = {} if self.long_arith == "fp32" else {"arith": self.long_arith}  # the keyword only off the default
         self.p = float(stack.config.dropout_rate) if train and stack.training else 0.0
@@ -514,8 +514,10 @@ class _HipAttention:
 
     def _launch(self, module: T5Attention, q: Tensor, k: Tensor, v: Tensor, table: Optional[Tensor], offset: int,
                 key_mask: Optional[Tensor], causal: bool) -> Tensor:
-        long = self.long and not ops.t5_attention_supported(q.dtype, module.d_kv, module.n_heads, q.shape[1],
-                                                            k.shape[1])
+        shape = (q.shape[1], k.shape[1])
+        if self.long and shape not in self.long_for:  # asked once per shape: the self-attention's, the cross-attention's
+            self.long_for[shape] = not ops.t5_attention_supported(q.dtype, module.d_kv, module.n_heads, *shape)
+        long = self.long and self.long_for[shape]
         if self.train:
             call = (q, k, v, table, module.n_heads, offset, key_mask, causal, self.p, _draw_seed(self.p, q.device))
             return T5AttentionLongFunction.apply(*call, self.long_arith) if long else T5AttentionFunction.apply(*call)
@@ -718,30 +720,35 @@ class T5Stack(nn.Module):
         return [(att._heads(outs[2 * i]), att._heads(outs[2 * i + 1])) for i, att in enumerate(atts)]
 
     def _call_supported(self, short, dtype, query_length: int, key_length: int, long: bool) -> bool:
-        """Whether one attention call has a kernel: the existing one (`short`: its support table), else, with `long`,
-        the long one."""
+        """Whether one attention call has a kernel: by `short`, the short kernel's table, else with `long` the long one's."""
         cfg = self.config
         return short(dtype, cfg.d_kv, cfg.num_heads, query_length, key_length) or (
             long and ops.t5_attention_long_supported(dtype, cfg.d_kv, cfg.num_heads, query_length, key_length))
+
+    def _attention_mode(self, x: Tensor) -> Optional[str]:
+        """Which fused attention a forward of x is in, before any length is asked about (module docstring): "train"
+        ("hip_train" under grad), "inference" ("hip" or "hip_train" under no_grad, without active dropout), or None."""
+        if checked(self, "attention_impl") not in ("hip", "hip_train") or not x.is_cuda:
+            return None
+        if torch.is_grad_enabled():
+            return "train" if self.attention_impl == "hip_train" else None
+        return None if self.training and self.config.dropout_rate > 0 else "inference"
 
     def hip_attention_active(self, x: Tensor, query_length: int, key_length: int,
                              cross_length: Optional[int] = None, cached: bool = False) -> bool:
         """Whether a forward of x with these lengths takes the "hip" path (module docstring).  `cached`: the
         self-attention reads a decode cache, which only the existing kernel does."""
         long = checked(self, "attention_long_impl") == "hip"
-        if checked(self, "attention_impl") not in ("hip", "hip_train") or not x.is_cuda or torch.is_grad_enabled():
+        if self._attention_mode(x) != "inference":
             return False
-        if self.training and self.config.dropout_rate > 0:
-            return False
-        ok = self._call_supported(ops.t5_attention_supported, x.dtype, query_length, key_length, long and not cached)
-        if ok and cross_length is not None:
-            ok = self._call_supported(ops.t5_attention_supported, x.dtype, query_length, cross_length, long)
-        return ok
+        short = ops.t5_attention_supported
+        return self._call_supported(short, x.dtype, query_length, key_length, long and not cached) and (
+            cross_length is None or self._call_supported(short, x.dtype, query_length, cross_length, long))
 
     def hip_train_active(self, x: Tensor, query_length: int, cross_kv: Optional[List[KV]]) -> bool:
         """Whether a forward of x under grad takes the "hip_train" path (module docstring)."""
         long = checked(self, "attention_long_impl") == "hip"
-        if self.attention_impl != "hip_train" or not x.is_cuda or not torch.is_grad_enabled():
+        if self._attention_mode(x) != "train":
             return False
         ok = self._call_supported(ops.t5_attention_bwd_supported, x.dtype, query_length, query_length, long)
         if ok and self.is_decoder:
@@ -751,24 +758,16 @@ class T5Stack(nn.Module):
         return ok
 
     def packed_rows_active(self, x: Tensor, query_length: int, key_bound: int) -> bool:
-        """Whether a forward of x (device dtype carrier) can run on packed rows of at most key_bound tokens (module
-        docstring, "Packed rows"): the encoder's own rows (every call has query and key bound key_bound), or the decoder
-        over a packed encoder output (dense self-attention of query_length tokens, cross-attention over key_bound).
-        It takes the fused attention this forward would take anyway -- "hip_train" under grad, "hip" or "hip_train"
-        without dropout under no_grad -- and every length within the short kernel."""
-        cfg = self.config
-        if checked(self, "attention_impl") not in ("hip", "hip_train") or not x.is_cuda:
+        """Whether a forward of x can run on packed rows of at most key_bound tokens (module docstring, "Packed rows"): the
+        encoder's own rows (query and key bound key_bound), or the decoder's dense self-attention of query_length tokens and
+        cross-attention over key_bound.  It takes this forward's fused attention and lengths within the short kernel."""
+        cfg, mode = self.config, self._attention_mode(x)
+        if mode is None:
             return False
-        if torch.is_grad_enabled():
-            if self.attention_impl != "hip_train":
-                return False
-        elif self.training and cfg.dropout_rate > 0:
-            return False
-        own = ops.t5_attention_bwd_supported if torch.is_grad_enabled() else ops.t5_attention_supported
-        if self.is_decoder:
-            return (own(x.dtype, cfg.d_kv, cfg.num_heads, query_length, query_length)
-                    and ops.t5_attention_packed_supported(x.dtype, cfg.d_kv, cfg.num_heads, query_length, key_bound))
-        return ops.t5_attention_packed_supported(x.dtype, cfg.d_kv, cfg.num_heads, key_bound, key_bound)
+        own = ops.t5_attention_bwd_supported if mode == "train" else ops.t5_attention_supported
+        Tq = query_length if self.is_decoder else key_bound  # the packed call's query bound
+        return ((not self.is_decoder or own(x.dtype, cfg.d_kv, cfg.num_heads, Tq, Tq))
+                and ops.t5_attention_packed_supported(x.dtype, cfg.d_kv, cfg.num_heads, Tq, key_bound))
 
     def hip_norm_active(self, x: Tensor) -> bool:
         """Whether a forward of x takes the "hip" norm path (module docstring)."""

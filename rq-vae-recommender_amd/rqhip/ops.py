@@ -699,23 +699,59 @@ def _dropout_seed(who: str, seed: Optional[Tensor], **ps: float) -> Optional[int
     return seed.data_ptr() if live else None
 
 
+def _packed_side(who: str, t: Tensor, name: str, cu: Optional[Tensor], bound: Optional[int], inner: int, copy: bool = True):
+    """One side (q or k / v) of an attention call -> (tensor, groups, rows, bound).  With its table `cu` (int32
+    [groups + 1], device) the tensor is 2-D [rows, inner] at one row stride and `bound` the padded length; without, it is
+    the dense [groups, T, inner] of t5_attention (`copy`: _token_rows')."""
+    if cu is None:
+        t = _token_rows(t, name, copy)
+        if bound is not None and bound != t.shape[1]:
+            raise RqHipError(f"{who}: dense {name} has {t.shape[1]} tokens per row, not the bound {bound}")
+        if t.shape[2] != inner:
+            raise RqHipError(f"{who}: {name} has {t.shape[2]} columns, not n_heads * 64 = {inner}")
+        return t, t.shape[0], t.shape[0] * t.shape[1], t.shape[1]
+    if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 1 or not cu.is_contiguous():
+        raise RqHipError(f"{who}: the table of {name} must be a contiguous int32 [groups + 1] tensor, got {cu.dtype} "
+                         f"{tuple(cu.shape)}")
+    if bound is None or bound < 1:
+        raise RqHipError(f"{who}: packed {name} needs its padded length (max_q / max_k >= 1)")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != inner:
+        raise RqHipError(f"{who}: packed {name} must be a float32 [rows, n_heads * 64 = {inner}] tensor, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < inner or t.data_ptr() % 16 != 0:
+        t = _aligned16(t.contiguous())
+    return t, cu.numel() - 1, t.shape[0], int(bound)
+
+
 def _attention_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, bias_by_delta: Optional[Tensor],
                     key_mask: Optional[Tensor], p: float = 0.0, seed: Optional[Tensor] = None, past: int = 0,
-                    anc: Optional[Tensor] = None):
-    """The checks and copies t5_attention, t5_attention_fwd_train and t5_attention_bwd share (last result: the seed pointer).
-    With `anc` k and v are the position slabs, which are never copied, and the keys are the positions 0 .. past of each row."""
-    q = _token_rows(q, "q")
-    R, Tq, inner = q.shape
-    if inner != n_heads * 64:
-        raise RqHipError(f"{who}: q has {inner} columns, not n_heads * 64 = {n_heads * 64}")
-    if k.shape != v.shape or k.shape[-1] != inner:
+                    anc: Optional[Tensor] = None, packed: Optional[tuple] = None):
+    """The checks and copies the nine attention calls share -> (q, k, v, table, key mask, R, Rk, Tq, Tk, inner, seed
+    pointer, n_q, n_k).  Each side is dense, or packed behind its table: `packed` is a packed call's (cu_q, cu_k, max_q,
+    max_k, causal), and such a call takes one K/V per group and neither mask.  With `anc` k and v are the position slabs,
+    which are never copied, and the keys are the positions 0 .. past of each row."""
+    cu_q = cu_k = max_q = max_k = None
+    if packed is not None:
+        cu_q, cu_k, max_q, max_k, causal = packed
+        if cu_q is None and cu_k is None:
+            raise RqHipError(f"{who}: neither cu_q nor cu_k: the dense call is t5_attention")
+        if causal or key_mask is not None:
+            raise RqHipError(f"{who}: a cumulative table goes with neither causal nor key_mask (every packed key is valid)")
+    inner = int(n_heads) * 64
+    q, R, n_q, Tq = _packed_side(who, q, "q", cu_q, max_q, inner)
+    if packed is not None:
+        if k.shape != v.shape:
+            raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
+    elif k.shape != v.shape or k.shape[-1] != inner:
         raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
-    k, v = _token_rows(k, "k", copy=anc is None), _token_rows(v, "v", copy=anc is None)
-    if k.stride(1) != v.stride(1):
+    k, Rk, n_k, Tk = _packed_side(who, k, "k", cu_k, max_k, inner, anc is None)
+    v = _packed_side(who, v, "v", cu_k, max_k, inner, anc is None)[0]
+    if k.stride(-2) != v.stride(-2):
         if anc is not None:
             raise RqHipError(f"{who}: the k and v slabs must share one row stride")
         k, v = k.contiguous(), v.contiguous()
-    Rk, Tk = k.shape[0], k.shape[1]
+    if packed is not None and Rk != R:
+        raise RqHipError(f"{who}: {R} query groups over {Rk} K/V groups: one K/V per group")
     if anc is not None:
         if (anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < past or anc.stride(1) != 1
                 or k.shape[0] <= past or k.shape[1] < R):
@@ -731,7 +767,39 @@ def _attention_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, bia
             raise RqHipError(f"{who}: key_mask must be bool / uint8 [{Rk}, {Tk}], got {key_mask.dtype} "
                              f"{tuple(key_mask.shape)}")
         key_mask = key_mask.contiguous()
-    return q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _dropout_seed(who, seed, p=p)
+    return q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _dropout_seed(who, seed, p=p), n_q, n_k
+
+
+def _attention_bwd_args(who: str, q: Tensor, out: Tensor, d_out: Tensor, lse: Tensor, lse_shape: tuple,
+                        ml: Optional[Tensor] = None, side: Optional[tuple] = None):
+    """What a backward checks of the forward's `out` and `lse` (and `ml`, the long form's) and of d_out -> (out, d_out,
+    lse, ml).  `side`: a packed call's (cu_q, Tq, inner), out and d_out then being in q's packed-or-dense layout."""
+    if side is None:
+        out, d_out = _token_rows(out, "out"), _token_rows(d_out, "d_out")
+    else:
+        out, d_out = _packed_side(who, out, "out", *side)[0], _packed_side(who, d_out, "d_out", *side)[0]
+    if out.shape != q.shape or d_out.shape != q.shape:
+        raise RqHipError(f"{who}: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q {tuple(q.shape)}")
+    lse = _f32c(lse, "lse")
+    if ml is not None:
+        ml = _f32c(ml, "ml")
+        if tuple(lse.shape) != lse_shape or tuple(ml.shape) != lse_shape + (2,):
+            raise RqHipError(f"{who}: lse must be {list(lse_shape)} and ml {list(lse_shape + (2,))}, got "
+                             f"{tuple(lse.shape)} and {tuple(ml.shape)}")
+    elif tuple(lse.shape) != lse_shape:
+        raise RqHipError(f"{who}: lse must be {list(lse_shape)}, got {tuple(lse.shape)}")
+    return out, d_out, lse, ml
+
+
+def _attention_grads(q: Tensor, k: Tensor, bias_by_delta: Optional[Tensor], scratch: Optional[tuple]):
+    """A backward's outputs on the current device -> (dq like q, dk and dv like k, dtable like the bias table or None,
+    and a float32 buffer of shape `scratch` or None: the short kernels' [R * H, Tq + Tk - 1] partial bias gradients,
+    which go with a table, or the long kernels' workspace)."""
+    dq = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
+    dv = torch.empty(k.shape, dtype=torch.float32, device=q.device)
+    dtable = None if bias_by_delta is None else torch.empty_like(bias_by_delta)
+    return dq, dk, dv, dtable, None if scratch is None else torch.empty(scratch, dtype=torch.float32, device=q.device)
 
 
 def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta: Optional[Tensor] = None,
@@ -746,8 +814,8 @@ def t5_attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_delta
     bias_by_delta [n_delta, n_heads]: table[(j - i - past) + bias_offset] is added.  key_mask [Rk, Tk] bool / uint8
     (0 = masked), causal keeps j <= i + past; masked scores get finfo(float32).min added."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, anc)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _ = _attention_args("t5_attention", q, k, v, n_heads,
-                                                                                bias_by_delta, key_mask, past=past, anc=anc)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _, _, _ = _attention_args(
+        "t5_attention", q, k, v, n_heads, bias_by_delta, key_mask, past=past, anc=anc)
     slab_rows, ld_anc = (0, 0) if anc is None else (k.shape[1], int(anc.stride(0)))
     dev = q.device
     with torch.cuda.device(dev):
@@ -803,7 +871,7 @@ def t5_attention_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bia
     t5_attention_dropout_keep(seed, ...) and scaled by 1 / (1 - p); `seed` is a one-element int64 device tensor the host
     never reads.  At p = 0 `out` has the bits of t5_attention."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr, _, _ = _attention_args(
         "t5_attention_fwd_train", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
     dev = q.device
     with torch.cuda.device(dev):
@@ -824,24 +892,12 @@ def t5_attention_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, 
     dk, dv [R, Tk, inner], dtable [n_delta, n_heads] or None without a bias table).  The arguments are the forward's, its
     `out` and `lse`, and d_out [R, Tq, inner]; the weights are recomputed, the dropout decisions too."""
     _need_gpu(q, k, v, out, lse, d_out, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr, _, _ = _attention_args(
         "t5_attention_bwd", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
-    out, d_out = _token_rows(out, "out"), _token_rows(d_out, "d_out")
-    if out.shape != q.shape or d_out.shape != q.shape:
-        raise RqHipError(f"t5_attention_bwd: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q "
-                         f"{tuple(q.shape)}")
-    lse = _f32c(lse, "lse")
-    if tuple(lse.shape) != (R, int(n_heads), Tq):
-        raise RqHipError(f"t5_attention_bwd: lse must be [{R}, {n_heads}, {Tq}], got {tuple(lse.shape)}")
-    dev = q.device
-    with torch.cuda.device(dev):
-        dq = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
-        dk = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
-        dv = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
-        dtable = partial = None
-        if bias_by_delta is not None:
-            dtable = torch.empty_like(bias_by_delta)
-            partial = torch.empty((R * int(n_heads), Tq + Tk - 1), dtype=torch.float32, device=dev)
+    out, d_out, lse, _ = _attention_bwd_args("t5_attention_bwd", q, out, d_out, lse, (R, int(n_heads), Tq))
+    with torch.cuda.device(q.device):
+        dq, dk, dv, dtable, partial = _attention_grads(
+            q, k, bias_by_delta, None if bias_by_delta is None else (R * int(n_heads), Tq + Tk - 1))
         rc = _lib.lib().rqhip_t5_attention_bwd(
             _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), _ptr(out), int(out.stride(1)), _ptr(lse),
             _ptr(d_out), int(d_out.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk, _ptr(bias_by_delta),
@@ -858,57 +914,6 @@ def t5_attention_packed_supported(dtype: torch.dtype, d_kv: int, n_heads: int, T
         _lib.lib().rqhip_t5_attention_packed_supported(int(d_kv), int(n_heads), int(Tq), int(Tk)))
 
 
-def _packed_side(who: str, t: Tensor, name: str, cu: Optional[Tensor], bound: Optional[int], inner: int):
-    """One side (q or k / v) of a packed attention call -> (tensor, groups, rows, bound).  With its table `cu` (int32
-    [groups + 1], device) the tensor is 2-D [rows, inner] at one row stride and `bound` the padded length; without, it is
-    the dense [groups, T, inner] of t5_attention."""
-    if cu is None:
-        t = _token_rows(t, name)
-        if bound is not None and bound != t.shape[1]:
-            raise RqHipError(f"{who}: dense {name} has {t.shape[1]} tokens per row, not the bound {bound}")
-        if t.shape[2] != inner:
-            raise RqHipError(f"{who}: {name} has {t.shape[2]} columns, not n_heads * 64 = {inner}")
-        return t, t.shape[0], t.shape[0] * t.shape[1], t.shape[1]
-    if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 1 or not cu.is_contiguous():
-        raise RqHipError(f"{who}: the table of {name} must be a contiguous int32 [groups + 1] tensor, got {cu.dtype} "
-                         f"{tuple(cu.shape)}")
-    if bound is None or bound < 1:
-        raise RqHipError(f"{who}: packed {name} needs its padded length (max_q / max_k >= 1)")
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != inner:
-        raise RqHipError(f"{who}: packed {name} must be a float32 [rows, n_heads * 64 = {inner}] tensor, got {t.dtype} "
-                         f"{tuple(t.shape)}")
-    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < inner or t.data_ptr() % 16 != 0:
-        t = _aligned16(t.contiguous())
-    return t, cu.numel() - 1, t.shape[0], int(bound)
-
-
-def _packed_attention_args(who: str, q: Tensor, k: Tensor, v: Tensor, n_heads: int, cu_q: Optional[Tensor],
-                           cu_k: Optional[Tensor], max_q: Optional[int], max_k: Optional[int],
-                           bias_by_delta: Optional[Tensor], key_mask: Optional[Tensor], causal: bool, p: float = 0.0,
-                           seed: Optional[Tensor] = None):
-    """The checks the three packed attention calls share -> (q, k, v, table, R, n_q, n_k, Tq, Tk, inner, seed pointer)."""
-    if cu_q is None and cu_k is None:
-        raise RqHipError(f"{who}: neither cu_q nor cu_k: the dense call is t5_attention")
-    if causal or key_mask is not None:
-        raise RqHipError(f"{who}: a cumulative table goes with neither causal nor key_mask (every packed key is valid)")
-    inner = int(n_heads) * 64
-    q, R, n_q, Tq = _packed_side(who, q, "q", cu_q, max_q, inner)
-    if k.shape != v.shape:
-        raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
-    k, Rk, n_k, Tk = _packed_side(who, k, "k", cu_k, max_k, inner)
-    v = _packed_side(who, v, "v", cu_k, max_k, inner)[0]
-    k_ld, v_ld = (k.stride(-2), v.stride(-2))
-    if k_ld != v_ld:
-        k, v = k.contiguous(), v.contiguous()
-    if Rk != R:
-        raise RqHipError(f"{who}: {R} query groups over {Rk} K/V groups: one K/V per group")
-    if bias_by_delta is not None:
-        bias_by_delta = _f32c(bias_by_delta, "bias_by_delta")
-        if bias_by_delta.dim() != 2 or bias_by_delta.shape[1] != n_heads:
-            raise RqHipError(f"{who}: bias_by_delta must be [n_delta, {n_heads}], got {tuple(bias_by_delta.shape)}")
-    return q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, _dropout_seed(who, seed, p=p)
-
-
 def t5_attention_packed(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, cu_q: Optional[Tensor] = None,
                         cu_k: Optional[Tensor] = None, max_q: Optional[int] = None, max_k: Optional[int] = None,
                         bias_by_delta: Optional[Tensor] = None, bias_offset: int = 0, key_mask: Optional[Tensor] = None,
@@ -921,8 +926,8 @@ def t5_attention_packed(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, cu_q: 
     the scattered tensors with the prefix key mask."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, cu_q, cu_k)
     who = "t5_attention_packed"
-    q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, _ = _packed_attention_args(
-        who, q, k, v, n_heads, cu_q, cu_k, max_q, max_k, bias_by_delta, key_mask, causal)
+    q, k, v, bias_by_delta, _, R, _, Tq, Tk, inner, _, n_q, n_k = _attention_args(
+        who, q, k, v, n_heads, bias_by_delta, key_mask, packed=(cu_q, cu_k, max_q, max_k, causal))
     dev = q.device
     with torch.cuda.device(dev):
         out = torch.empty(q.shape, dtype=torch.float32, device=dev)
@@ -945,8 +950,8 @@ def t5_attention_packed_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int,
     t5_attention_packed."""
     _need_gpu(q, k, v, bias_by_delta, key_mask, cu_q, cu_k, seed)
     who = "t5_attention_packed_fwd_train"
-    q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, seed_ptr = _packed_attention_args(
-        who, q, k, v, n_heads, cu_q, cu_k, max_q, max_k, bias_by_delta, key_mask, causal, p, seed)
+    q, k, v, bias_by_delta, _, R, _, Tq, Tk, inner, seed_ptr, n_q, n_k = _attention_args(
+        who, q, k, v, n_heads, bias_by_delta, key_mask, p, seed, packed=(cu_q, cu_k, max_q, max_k, causal))
     dev = q.device
     with torch.cuda.device(dev):
         out = torch.empty(q.shape, dtype=torch.float32, device=dev)
@@ -970,25 +975,13 @@ def t5_attention_packed_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: T
     and d_out in q's layout."""
     _need_gpu(q, k, v, out, lse, d_out, bias_by_delta, key_mask, cu_q, cu_k, seed)
     who = "t5_attention_packed_bwd"
-    q, k, v, bias_by_delta, R, n_q, n_k, Tq, Tk, inner, seed_ptr = _packed_attention_args(
-        who, q, k, v, n_heads, cu_q, cu_k, max_q, max_k, bias_by_delta, key_mask, causal, p, seed)
-    out = _packed_side(who, out, "out", cu_q, Tq, inner)[0]
-    d_out = _packed_side(who, d_out, "d_out", cu_q, Tq, inner)[0]
-    if out.shape != q.shape or d_out.shape != q.shape:
-        raise RqHipError(f"{who}: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q {tuple(q.shape)}")
-    lse = _f32c(lse, "lse")
-    want = (n_q, int(n_heads)) if cu_q is not None else (R, int(n_heads), Tq)
-    if tuple(lse.shape) != want:
-        raise RqHipError(f"{who}: lse must be {list(want)}, got {tuple(lse.shape)}")
-    dev = q.device
-    with torch.cuda.device(dev):
-        dq = torch.empty(q.shape, dtype=torch.float32, device=dev)
-        dk = torch.empty(k.shape, dtype=torch.float32, device=dev)
-        dv = torch.empty(k.shape, dtype=torch.float32, device=dev)
-        dtable = partial = None
-        if bias_by_delta is not None:
-            dtable = torch.empty_like(bias_by_delta)
-            partial = torch.empty((R * int(n_heads), Tq + Tk - 1), dtype=torch.float32, device=dev)
+    q, k, v, bias_by_delta, _, R, _, Tq, Tk, inner, seed_ptr, n_q, n_k = _attention_args(
+        who, q, k, v, n_heads, bias_by_delta, key_mask, p, seed, packed=(cu_q, cu_k, max_q, max_k, causal))
+    out, d_out, lse, _ = _attention_bwd_args(
+        who, q, out, d_out, lse, (n_q, int(n_heads)) if cu_q is not None else (R, int(n_heads), Tq), side=(cu_q, Tq, inner))
+    with torch.cuda.device(q.device):
+        dq, dk, dv, dtable, partial = _attention_grads(
+            q, k, bias_by_delta, None if bias_by_delta is None else (R * int(n_heads), Tq + Tk - 1))
         rc = _lib.lib().rqhip_t5_attention_packed_bwd(
             _ptr(q), int(q.stride(-2)), _ptr(k), _ptr(v), int(k.stride(-2)), _ptr(out), int(out.stride(-2)), _ptr(lse),
             _ptr(d_out), int(d_out.stride(-2)), R, n_q, n_k, int(n_heads), 64, Tq, Tk, _ptr(cu_q), _ptr(cu_k),
@@ -1135,8 +1128,8 @@ def t5_attention_long(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, bias_by_
     fp32 on unrounded values; all tensors stay float32)."""
     fn, fn_name = _arith_entry("t5_attention_long", arith)
     _need_gpu(q, k, v, bias_by_delta, key_mask)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _ = _attention_args("t5_attention_long", q, k, v, n_heads,
-                                                                                bias_by_delta, key_mask)
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, _, _, _ = _attention_args(
+        "t5_attention_long", q, k, v, n_heads, bias_by_delta, key_mask)
     dev = q.device
     with torch.cuda.device(dev):
         out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
@@ -1157,7 +1150,7 @@ def t5_attention_long_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *
     "bf16" backward only."""
     fn, fn_name = _arith_entry("t5_attention_long_fwd_train", arith)
     _need_gpu(q, k, v, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr, _, _ = _attention_args(
         "t5_attention_long_fwd_train", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
     dev = q.device
     with torch.cuda.device(dev):
@@ -1188,24 +1181,12 @@ def t5_attention_long_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Ten
     rqhip_t5_attention_long_bwd_bf16)."""
     fn, fn_name = _arith_entry("t5_attention_long_bwd", arith)
     _need_gpu(q, k, v, out, lse, ml, d_out, bias_by_delta, key_mask, seed)
-    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr = _attention_args(
+    q, k, v, bias_by_delta, key_mask, R, Rk, Tq, Tk, inner, seed_ptr, _, _ = _attention_args(
         "t5_attention_long_bwd", q, k, v, n_heads, bias_by_delta, key_mask, p, seed)
-    out, d_out = _token_rows(out, "out"), _token_rows(d_out, "d_out")
-    if out.shape != q.shape or d_out.shape != q.shape:
-        raise RqHipError(f"t5_attention_long_bwd: out {tuple(out.shape)} / d_out {tuple(d_out.shape)} do not match q "
-                         f"{tuple(q.shape)}")
-    lse, ml = _f32c(lse, "lse"), _f32c(ml, "ml")
-    if tuple(lse.shape) != (R, int(n_heads), Tq) or tuple(ml.shape) != (R, int(n_heads), Tq, 2):
-        raise RqHipError(f"t5_attention_long_bwd: lse must be [{R}, {n_heads}, {Tq}] and ml [{R}, {n_heads}, {Tq}, 2], "
-                         f"got {tuple(lse.shape)} and {tuple(ml.shape)}")
-    dev = q.device
-    with torch.cuda.device(dev):
-        dq = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
-        dk = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
-        dv = torch.empty((Rk, Tk, inner), dtype=torch.float32, device=dev)
-        dtable = None if bias_by_delta is None else torch.empty_like(bias_by_delta)
+    out, d_out, lse, ml = _attention_bwd_args("t5_attention_long_bwd", q, out, d_out, lse, (R, int(n_heads), Tq), ml)
+    with torch.cuda.device(q.device):
         ws_bytes = t5_attention_long_bwd_workspace_bytes(R, n_heads, Tq, Tk)
-        ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.float32, device=dev)
+        dq, dk, dv, dtable, ws = _attention_grads(q, k, bias_by_delta, ((ws_bytes + 3) // 4,))
         rc = fn(_ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(1)), _ptr(out), int(out.stride(1)), _ptr(lse),
                 _ptr(ml), _ptr(d_out), int(d_out.stride(1)), R, Rk, int(n_heads), 64, Tq, Tk, _ptr(bias_by_delta),
                 0 if bias_by_delta is None else bias_by_delta.shape[0], int(bias_offset), _ptr(key_mask),
