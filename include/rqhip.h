@@ -444,6 +444,25 @@ int rqhip_t5_attention_packed_bwd(const float *q, int64_t ld_q, const float *k, 
                                   float *d_q, float *d_k, float *d_v, float *d_bias_by_delta, float *d_bias_partial,
                                   rqhip_stream_t stream);
 
+/* The cross-attention of a cached decode step over PACKED encoder rows (csrc/t5_attention.hip, the same kernel body),
+ * inference only, ONE launch: the groups of beams of rqhip_t5_attention over the packed K/V of
+ * rqhip_t5_attention_packed.  q and out are dense [R, Tq, H * 64] with R = Rk * beams: query rows b * beams ..
+ * b * beams + beams - 1 read group b, whose keys are rows cu_k[b] .. cu_k[b + 1] - 1 of k, v [n_k, H * 64] (row stride
+ * ld_kv), staged once per (group, head) with the group's own length.  cu_k: int32 [Rk + 1] on the device, required, and
+ * clamped as above (a bad table gives a short group, never an address); Tk is the padded bound of every group.  No bias
+ * table, key mask, causal flag, `past` or ancestor table: a cross-attention has none.
+ *   The kernel instantiation, launch plan and LDS layout are those of the padded call, chosen by the bounds (Tq, Tk).
+ *   With beams = 1 (Rk = R) out has the bits of rqhip_t5_attention_packed(cu_q = NULL); on every query it has the bits of
+ *   rqhip_t5_attention on the scattered K/V [Rk, Tk, H * 64] with the prefix key mask and Rk groups.  A group without
+ *   keys gives out = 0 on its beams' rows.
+ * Limits: those of rqhip_t5_attention_packed_supported on (Tq, Tk); R % Rk == 0; beams * Tq < 2^24; 0 <= n_k <= Rk * Tk
+ * and n_k < 2^31; pointers 16-byte aligned, strides multiples of 4 and >= H * 64.  Outside them RQHIP_EARG /
+ * RQHIP_EUNSUPPORTED with the argument named, before any HIP call.  Deterministic; no allocation, copy, memset or sync.
+ * There is no training pair: under grad a cross-attention has beams = 1 and takes rqhip_t5_attention_packed_fwd_train. */
+int rqhip_t5_attention_packed_beams(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,
+                                    int64_t R, int64_t Rk, int64_t n_k, int H, int d_kv, int Tq, int Tk,
+                                    const int32_t *cu_k, float *out, int64_t ld_out, rqhip_stream_t stream);
+
 /* Between padded [B, T, d] rows and packed [N, d] rows (csrc/rows_pack.hip), fp32, d a multiple of 4
  * (rqhip_rows_pack_supported), 16-byte accesses.  cu: int32 [B + 1] on the device, clamped as above.
  *   rqhip_rows_pack: out[cu[b] + t] = x[b, t] for t < cu[b + 1] - cu[b]; rows of out no group covers are not written.

@@ -19,6 +19,8 @@
 // K/V sources: dense [Rk, Tk, H * 64] (rows b * beams .. b * beams + beams - 1 of q read group b), or, for the cached
 // decode step (Tq = 1, Rk = R), per-position slabs [t][slab_rows, H * 64] through the ancestor table anc [R, past]:
 // key t < past of row r is row anc[r, t] of slab t, key `past` is row r of slab `past`.  Nothing is copied.
+// Or packed [n_k, H * 64] behind a cumulative table (the PACKED instantiations): a group's own length gives its loops,
+// with one K/V per query group, or, for a decode step's cross-attention over packed encoder rows, the beams as above.
 //
 // Fixed reduction orders, no atomics, no host sync: the same bits on every run; graph-capturable once the LDS
 // attribute has been raised by a first eager call, as everywhere in this library.
@@ -63,9 +65,11 @@ struct AttTrain {
 
 // The dropout decision of element idx = ((r * H + h) * Tq + i) * Tk + j is dropout_keep(seed, idx, thresh) of t5_common.h.
 
-// PACKED (beams = 1, no key mask, no ancestor table): a.Tq and a.Tk are the padded BOUNDS -- they keep the LDS layout, the
-// bias index and the dropout element index of the padded call -- and the workgroup's own lengths Tq, Tk, read through the
-// cumulative tables, give its loop bounds, its row bases and the K/V rows it stages.
+// PACKED (no key mask, no ancestor table): a.Tq and a.Tk are the padded BOUNDS -- they keep the LDS layout, the bias
+// index and the dropout element index of the padded call -- and the workgroup's own lengths Tq, Tk, read through the
+// cumulative tables, give its loop bounds, its row bases and the K/V rows it stages.  A packed q has one K/V per group
+// (beams = 1); a dense q over packed K/V (cu_q null) keeps the dense arm's groups of beams: rows b * beams .. of q read
+// the packed group b, staged once with its own length (rqhip_t5_attention_packed_beams; beams = 1 everywhere else).
 template <int MT, bool TRAIN, bool PACKED>
 __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
     extern __shared__ float att_lds[];
@@ -117,13 +121,13 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
 
     const int nw = nthr / RQ_WAVE, wave = tid / RQ_WAVE, lane = tid & (RQ_WAVE - 1);
     const int i = lane & 15, g = lane >> 4;
-    const int M = PACKED ? Tq : a.beams * a.Tq;
+    const bool qpacked = PACKED && a.cu_q;
+    const int M = qpacked ? Tq : a.beams * a.Tq;
     for (int qt = wave; qt * 16 < M; qt += nw) {
         const int m = qt * 16 + i;
         const int mc = m < M ? m : M - 1;  // lanes past the last query recompute it and store nothing
-        const int beam = PACKED ? 0 : mc / a.Tq, ti = mc - beam * a.Tq;
-        const size_t qrow = (PACKED && a.cu_q) ? (size_t)(qbase + ti)
-                                               : (size_t)(b * a.beams + beam) * (size_t)a.Tq + (size_t)ti;
+        const int beam = qpacked ? 0 : mc / a.Tq, ti = mc - beam * a.Tq;
+        const size_t qrow = qpacked ? (size_t)(qbase + ti) : (size_t)(b * a.beams + beam) * (size_t)a.Tq + (size_t)ti;
         const float *qp = a.q + qrow * (size_t)a.ld_q + (size_t)h * kAttD + g;
         float qreg[16];
 #pragma unroll
@@ -180,7 +184,7 @@ __device__ __forceinline__ void att_body(AttArgs a, AttTrain t) {
         if constexpr (TRAIN) {
             const size_t qh = ((size_t)(b * a.beams + beam) * (size_t)a.H + (size_t)h) * (size_t)a.Tq + (size_t)ti;
             // packed q: lse is [n_q, H], a token's heads side by side
-            const size_t lrow = (PACKED && a.cu_q) ? qrow * (size_t)a.H + (size_t)h : qh;
+            const size_t lrow = qpacked ? qrow * (size_t)a.H + (size_t)h : qh;
             if (m < M && g == 0) t.lse[lrow] = mx + logf(sum);
             if (t.thresh) {  // dropout of the normalised weights: the dropped ones leave the product, the sum stays
                 const unsigned long long seed = (unsigned long long)*t.seed;
@@ -675,10 +679,24 @@ struct AttPacked {
     int64_t n_q, n_k;
     const uint8_t *key_mask;
     int causal;
+    bool beams = false;  // rqhip_t5_attention_packed_beams: dense q in groups of R / Rk rows over Rk packed K/V groups
 };
 
-// What the three packed entry points check beyond check_att_call: the tables and the row counts they index.
-int check_packed_call(const char *who, int64_t R, int Tq, int Tk, const AttPacked &pk) {
+// What the packed entry points check beyond check_att_call: the tables and the row counts they index (R groups of
+// queries, Rk of keys: the same number everywhere but in the beams call).
+int check_packed_call(const char *who, int64_t R, int64_t Rk, int Tq, int Tk, const AttPacked &pk) {
+    if (pk.beams) {
+        if (!pk.cu_k) {
+            set_error("%s: cu_k is null: the K/V groups are packed behind their cumulative table", who);
+            return RQHIP_EARG;
+        }
+        if (pk.n_k < 0 || pk.n_k >= (1ll << 31) || pk.n_k > Rk * Tk) {
+            set_error("%s: n_k=%lld rows do not go with Rk=%lld groups of at most Tk=%d (int32 table)", who,
+                      (long long)pk.n_k, (long long)Rk, Tk);
+            return RQHIP_EARG;
+        }
+        return RQHIP_OK;
+    }
     if (!pk.cu_q && !pk.cu_k) {
         set_error("%s: no cumulative table (cu_q, cu_k): the dense call is rqhip_t5_attention*", who);
         return RQHIP_EARG;
@@ -696,18 +714,19 @@ int check_packed_call(const char *who, int64_t R, int Tq, int Tk, const AttPacke
     return RQHIP_OK;
 }
 
-// ---- the three calls behind the six entry points: checks, null and alignment tests, struct fill and launch, each once.
+// ---- the three calls behind the seven entry points: checks, null and alignment tests, struct fill and launch, each once.
 // `pk`: the packed form, which runs the same kernel bodies in their PACKED instantiations (lengths per group through
 // cu_q / cu_k, the padded call's plan by the bounds).  Its entry points pass Rk = R and key_mask = null, causal = 0 (the
-// caller's are in *pk), and it is checked as the training pair is: one K/V per row.
+// caller's are in *pk), and it is checked as the training pair is: one K/V per row -- but for the beams call, which
+// passes its own Rk and is checked as the dense inference call is.
 
 int att_fwd_call(const char *who, const AttPacked *pk, const float *q, int64_t ld_q, const float *k, const float *v,
                  int64_t ld_kv, int64_t R, int64_t Rk, int H, int d_kv, int Tq, int Tk, const float *bias_by_delta,
                  int n_delta, int bias_offset, const uint8_t *key_mask, int causal, int past, const int32_t *anc,
                  int64_t ld_anc, int64_t slab_rows, float *out, int64_t ld_out, rqhip_stream_t stream) {
-    int rc = check_att_call(who, pk != nullptr, R, Rk, H, d_kv, Tq, Tk, past, anc, ld_anc, slab_rows, {ld_q, ld_kv, ld_out},
-                            bias_by_delta, n_delta, bias_offset, causal, 0.0);
-    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, Tq, Tk, *pk);
+    int rc = check_att_call(who, pk && !pk->beams, R, Rk, H, d_kv, Tq, Tk, past, anc, ld_anc, slab_rows,
+                            {ld_q, ld_kv, ld_out}, bias_by_delta, n_delta, bias_offset, causal, 0.0);
+    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, Rk, Tq, Tk, *pk);
     if (rc != RQHIP_OK) return rc;
     if (R == 0 || (pk && pk->n_q == 0)) return RQHIP_OK;
     if (any_null(q, out) || ((!pk || pk->n_k > 0) && any_null(k, v))) {
@@ -750,7 +769,7 @@ int att_fwd_train_call(const char *who, const AttPacked *pk, const float *q, int
                        float *out, int64_t ld_out, float *lse, rqhip_stream_t stream) {
     int rc = check_att_call(who, true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0, {ld_q, ld_kv, ld_out}, bias_by_delta,
                             n_delta, bias_offset, causal, p);
-    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, Tq, Tk, *pk);
+    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, R, Tq, Tk, *pk);
     if (rc != RQHIP_OK) return rc;
     if (R == 0 || (pk && pk->n_q == 0)) return RQHIP_OK;
     const unsigned thresh = dropout_threshold(p);
@@ -794,7 +813,7 @@ int att_bwd_call(const char *who, const AttPacked *pk, const float *q, int64_t l
                  float *d_k, float *d_v, float *d_bias_by_delta, float *d_bias_partial, rqhip_stream_t stream) {
     int rc = check_att_call(who, true, R, Rk, H, d_kv, Tq, Tk, 0, nullptr, 0, 0, {ld_q, ld_kv, ld_out, ld_do}, bias_by_delta,
                             n_delta, bias_offset, causal, p);
-    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, Tq, Tk, *pk);
+    if (rc == RQHIP_OK && pk) rc = check_packed_call(who, R, R, Tq, Tk, *pk);
     if (rc != RQHIP_OK) return rc;
     if (R == 0 && !bias_by_delta) return RQHIP_OK;
     const unsigned thresh = dropout_threshold(p);
@@ -877,6 +896,16 @@ extern "C" int rqhip_t5_attention_packed(const float *q, int64_t ld_q, const flo
     const AttPacked pk{cu_q, cu_k, n_q, n_k, key_mask, causal};
     return att_fwd_call("t5_attention_packed", &pk, q, ld_q, k, v, ld_kv, R, R, H, d_kv, Tq, Tk, bias_by_delta, n_delta,
                         bias_offset, nullptr, 0, 0, nullptr, 0, 0, out, ld_out, stream);
+}
+
+extern "C" int rqhip_t5_attention_packed_beams(const float *q, int64_t ld_q, const float *k, const float *v,
+                                               int64_t ld_kv, int64_t R, int64_t Rk, int64_t n_k, int H, int d_kv, int Tq,
+                                               int Tk, const int32_t *cu_k, float *out, int64_t ld_out,
+                                               rqhip_stream_t stream) {
+    AttPacked pk{nullptr, cu_k, R * (int64_t)Tq, n_k, nullptr, 0};
+    pk.beams = true;
+    return att_fwd_call("t5_attention_packed_beams", &pk, q, ld_q, k, v, ld_kv, R, Rk, H, d_kv, Tq, Tk, nullptr, 0, 0,
+                        nullptr, 0, 0, nullptr, 0, 0, out, ld_out, stream);
 }
 
 extern "C" int rqhip_t5_attention_fwd_train(const float *q, int64_t ld_q, const float *k, const float *v, int64_t ld_kv,

@@ -18,6 +18,13 @@ The tokenizer must give the corpus the checkpoint was trained on: `evaluate` rai
 differ from the checkpoint's `codebooks` buffer, because the model would then search another corpus than the one the
 targets come from.  The fused paths are chosen as in `train`: attention_impl ("hip", the inference kernel with slab
 K/V), norm_impl, ffn_impl, embed_impl; "torch" selects the operators.  `max_batches` stops after that many batches.
+
+Packed encoder rows: `evaluate` reads the binding `encoder_rows.mode` of train_decoder.encoder_rows (the one configurable;
+"padded" by default, validated before any other work).  With "packed" it sets `model.encoder_rows` and builds its loader
+with host_windows=True -- without shuffling and subsampling the same tensors in the same order, each batch also saying
+how many items its rows hold -- and every search runs the encoder, the cross-attention K/V and the decode steps'
+cross-attention on the valid tokens only, with the padded run's metrics (modules/model.py;
+configs/decoder_amazon_eval_packed.gin; profiles/packed_generate.txt).
 """
 import torch
 
@@ -27,7 +34,7 @@ from evaluate.metrics import TopKAccumulator
 from modules.model import EncoderDecoderRetrievalModel
 from modules.tokenizer.semids import SemanticIdTokenizer
 from modules.utils import parse_config
-from train_decoder import load_checkpoint
+from train_decoder import encoder_rows, load_checkpoint
 
 try:
     import gin
@@ -67,6 +74,7 @@ def evaluate(
     embed_impl="hip",
     max_batches=None,
 ):
+    rows = encoder_rows()      # "padded", or "packed" by the binding encoder_rows.mode: validated before any other work
     if checkpoint_path is None:
         raise ValueError("evaluate needs checkpoint_path: a checkpoint written by train_decoder.py")
     if dataset != RecDataset.AMAZON:
@@ -86,7 +94,8 @@ def evaluate(
         rqvae_codebook_normalize=vae_codebook_normalize, rqvae_sim_vq=vae_sim_vq).to(device)
     tokenizer.precompute_corpus_ids(item_dataset)
     corpus = tokenizer.cached_ids[:, :vae_n_layers].contiguous()
-    eval_dataloader = TokenizedSeqLoader(eval_dataset, tokenizer, batch_size, shuffle=False)
+    # packed: the batches carry their rows' item counts on the host; same tensors, same order (no shuffle, no subsampling)
+    eval_dataloader = TokenizedSeqLoader(eval_dataset, tokenizer, batch_size, shuffle=False, host_windows=rows == "packed")
 
     model = EncoderDecoderRetrievalModel(
         codebooks=torch.zeros_like(corpus), num_hierarchies=vae_n_layers, num_embeddings_per_hierarchy=vae_codebook_size,
@@ -101,6 +110,7 @@ def evaluate(
             "(pretrained_rqvae_path) and the same dataset")
     model.attention_impl, model.norm_impl, model.ffn_impl, model.embed_impl = attention_impl, norm_impl, ffn_impl, embed_impl
     model.beam_impl = beam_impl
+    model.encoder_rows = rows
     model.eval()
 
     metrics_accumulator = TopKAccumulator(ks=top_k_eval_list)

@@ -54,13 +54,22 @@ width that is a multiple of 4, and at least one token in every row: a row with n
 uniformly over its padding in the padded form, which has no packed counterpart.  Otherwise -- a plain
 TokenizedSeqBatch, host tensors, attention_impl = "torch", a longer history, an empty row -- `forward` runs the padded
 path, silently, like every other *_impl.  In eval mode loss and loss_d have the padded fused path's bits; in train mode
-the row-local dropout masks are another sample of the same law.  `generate`, `generate_next_sem_id` and
-`recommend_items` are not affected (their fill is higher and the beams change the cross-attention's grouping: the
-follow-up).  Measurements: profiles/packed_rows.txt.
+the row-local dropout masks are another sample of the same law.  Measurements: profiles/packed_rows.txt.
+`generate(..., item_counts=)`, and through it `generate_next_sem_id(batch)` and `recommend_items(batch)` on a
+CountedSeqBatch, run packed by the same attribute and the same plan (`packed_rows_plan`, asked with the decode step's query
+length 1): the front's output is packed by one ops.rows_pack launch, the encoder runs on [1, N, d], `cross_kv` projects
+those N rows, and every decode step is `dec(x, cross_kv=..., decode_cache=slabs, encoder_packed=rows)` without an encoder
+mask, whose cross-attention is ONE ops.t5_attention_packed_beams call per block: the k beams of a user read that user's
+packed row (modules/t5.py, "Packed rows").  The cached self-attention stays on the slabs.  The returned ids and log
+probabilities have the padded run's bits under both beam searches and every *_impl / *_arith attribute.  The same
+fallbacks apply, silently, and one more: where the decode cache's slabs are not taken (`hip_attention_active`), the padded
+path runs.  A packed `generate` cannot be captured into a graph, because N depends on the data.  Measurements:
+profiles/packed_generate.txt.
 Each hierarchy step of `generate` is the decoder on one new token per beam, the head's F.linear and ONE HIP launch
 (ops.beam_step, csrc/beam_step.hip) that does the reference's softmax, multinomial sampling, log, prefix-validity
 mask, sort and gathers.  After the encoder nothing is read back to
-the host and no allocation depends on data, so a whole `generate` can be captured into a graph.
+the host and no allocation depends on data, so a whole padded `generate` can be captured into a graph (a packed one
+cannot: the number N of its encoder rows depends on the data).
 
 Sampling: the reference's `torch.multinomial(probas, n, replacement=False)` is ATen's exponential race
 `topk(p / q, n)` with `q = empty_like(p).exponential_(1)`.  `_exponential_like` draws the same q from the same
@@ -273,22 +282,25 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return ops.sid_embed_fwd(ids, mask, table, self.num_hierarchies, ld_item, sep, prefix_table, prefix_idx,
                                  need_mask=need_mask)
 
-    def packed_rows_plan(self, batch: TokenizedSeqBatch) -> Optional[PackedRows]:
-        """The packed form of `forward` for this batch (module docstring, `encoder_rows`), or None: the padded path.
-        Built on the host from batch.item_counts alone; the only device work is the upload of the cumulative table."""
+    def packed_rows_plan(self, counts: Optional[Tensor], input_ids: Tensor, with_user: bool, *, ld_item: int,
+                         query_length: int) -> Optional[PackedRows]:
+        """The packed form of an encoder pass over input_ids [B, S * ld_item] (module docstring, `encoder_rows`), or None:
+        the padded path.  `forward` asks with the batch's item_counts, its sem_ids as they are (ld_item = L + 1) and the
+        decoder's query length L + 1; `generate` with its own arguments (ld_item = L) and the decode step's query length
+        1.  with_user: the caller passes user ids.  Built on the host from `counts` and the shapes alone; the only
+        device work is the upload of the cumulative table."""
         if self.encoder_rows not in ENCODER_ROWS:
             raise ValueError(f"encoder_rows must be one of {ENCODER_ROWS}, got {self.encoder_rows!r}")
-        counts = getattr(batch, "item_counts", None)
-        if self.encoder_rows != "packed" or counts is None or not batch.sem_ids.is_cuda:
+        if self.encoder_rows != "packed" or counts is None or not input_ids.is_cuda:
             return None
-        B, L = batch.sem_ids.shape[0], self.num_hierarchies
-        S = batch.sem_ids.shape[1] // (L + 1)
+        B, L = input_ids.shape[0], self.num_hierarchies
+        S = input_ids.shape[1] // ld_item
         if counts.is_cuda or counts.dtype != torch.int64 or tuple(counts.shape) != (B,):
             raise ValueError(f"item_counts must be an int64 CPU tensor [{B}], got {counts.dtype} {tuple(counts.shape)} "
                              f"on {counts.device}")
         if B == 0 or int(counts.min()) < 0 or int(counts.max()) > S:
             return None
-        with_user = batch.user_ids is not None and self.user_embedding is not None
+        with_user = with_user and self.user_embedding is not None
         if not with_user and int(counts.min()) == 0:
             return None   # a row without a token: its padded form attends uniformly over its padding
         per_item = L + (1 if self.sep_token is not None else 0)
@@ -297,7 +309,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self._push_attention_impl()
         if not (ops.rows_pack_supported(table.dtype, table.shape[1])
                 and self.encoder.encoder.packed_rows_active(table, bound, bound)
-                and self.t5_decoder.packed_rows_active(table, L + 1, bound)):
+                and self.t5_decoder.packed_rows_active(table, query_length, bound)):
             return None
         cu = torch.zeros(B + 1, dtype=torch.int32)
         cu[1:] = torch.cumsum(int(with_user) + counts * per_item, 0)
@@ -397,7 +409,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
     def forward(self, batch: TokenizedSeqBatch) -> ModelOutput:
         sem_ids_dim = self.num_hierarchies + 1
         fut_ids = batch.sem_ids_fut[:, : self.num_hierarchies]
-        rows = self.packed_rows_plan(batch)      # None: the padded path (the default)
+        rows = self.packed_rows_plan(getattr(batch, "item_counts", None), batch.sem_ids, batch.user_ids is not None,
+                                     ld_item=sem_ids_dim, query_length=sem_ids_dim)   # None: the padded path (the default)
         if self.hip_embed_active(batch.sem_ids, batch.seq_mask):      # the batch's tensors as they are
             encoder_output, attention_mask_for_encoder = self.encoder_forward_pass(
                 attention_mask=batch.seq_mask, input_ids=batch.sem_ids, user_id=batch.user_ids, ld_item=sem_ids_dim,
@@ -432,7 +445,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return ModelOutput(loss=total_loss, logits=None, loss_d=torch.stack(loss_d))
 
     @torch.no_grad()
-    def generate(self, attention_mask, input_ids, user_id=None):
+    def generate(self, attention_mask, input_ids, user_id=None, *, item_counts=None):
         """Beam search over the hierarchy levels: the reference's sampling search (beam_impl = "sample"), or the exact
         constrained search (beam_impl = "exact", module docstring), which replaces the noise draw and ops.beam_step below
         by one ops.beam_topk_step over all K codes per beam and needs k <= K.
@@ -442,6 +455,12 @@ class EncoderDecoderRetrievalModel(nn.Module):
         K/V computed once on the B users) and one ops.beam_step.  With attention_impl = "hip" the self-attention cache
         is a T5DecodeCache instead: each step's K/V are projected straight into that position's slab and the parent
         beams reorder a small ancestor table, never the K/V.
+
+        item_counts (int64 CPU [B], the leading valid item slots of each row of input_ids; a CountedSeqBatch's) with
+        encoder_rows = "packed": the encoder, the cross K/V and every decode step's cross-attention run on the valid
+        tokens only (`packed_rows_plan`; module docstring), with the padded run's bits.  Such a call cannot be captured
+        into a graph: its row count N depends on the data.  Without counts, or wherever the packed form does not apply,
+        the padded path runs, silently.
 
         Returns generated_ids [B, k, num_hierarchies] int64 and log_probas [B, k] fp32 (-inf for beams without a valid
         corpus prefix)."""
@@ -463,17 +482,23 @@ class EncoderDecoderRetrievalModel(nn.Module):
         index = self._prefix_index_for_codebooks()
         index.to(input_ids.device)
 
-        enc_out, enc_mask = self.encoder_forward_pass(attention_mask=attention_mask, input_ids=input_ids,
-                                                      user_id=user_id)
         dec = self.t5_decoder
+        rows = self.packed_rows_plan(item_counts, input_ids, user_id is not None, ld_item=self.num_hierarchies,
+                                     query_length=1)
+        if rows is not None and not dec.hip_attention_active(self.item_sid_embedding_table.weight, 1,
+                                                             self.num_hierarchies, rows.bound, cached=True):
+            rows = None   # the packed decode step lives on the slabs: without them the padded path
+        enc_out, enc_mask = self.encoder_forward_pass(attention_mask=attention_mask, input_ids=input_ids,
+                                                      user_id=user_id, rows=rows)   # packed: ([1, N, d], None)
         cross_kv = dec.cross_kv(enc_out)
-        B = enc_out.shape[0]
+        B = input_ids.shape[0]
+        cross_length = enc_out.shape[1] if rows is None else rows.bound
         K = self.num_embeddings_per_hierarchy
 
         x = self.bos_token.unsqueeze(0).expand(B, 1, -1)
         self_kv: Optional[List] = None
         slabs = None
-        if dec.hip_attention_active(enc_out, 1, self.num_hierarchies, enc_out.shape[1], cached=True):
+        if dec.hip_attention_active(enc_out, 1, self.num_hierarchies, cross_length, cached=True):
             slabs = dec.new_decode_cache(self.num_hierarchies, B * k, enc_out.device)
         ids = scores = None
         for h in range(self.num_hierarchies):
@@ -482,7 +507,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
             if slabs is not None:
                 if h > 0:
                     slabs.reorder(parent)
-                hidden = dec(x, encoder_attention_mask=enc_mask, cross_kv=cross_kv, decode_cache=slabs)
+                hidden = dec(x, encoder_attention_mask=enc_mask, cross_kv=cross_kv, decode_cache=slabs,
+                             encoder_packed=rows)
             else:
                 if h > 0:
                     rows = parent.flatten()
@@ -504,7 +530,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         input_ids = _strip_dedup_col(batch.sem_ids, sem_ids_dim, self.num_hierarchies)
         attention_mask = _strip_dedup_col(batch.seq_mask.long(), sem_ids_dim, self.num_hierarchies)
         generated_ids, log_probas = self.generate(attention_mask=attention_mask, input_ids=input_ids,
-                                                  user_id=batch.user_ids)
+                                                  user_id=batch.user_ids, item_counts=getattr(batch, "item_counts", None))
         return GenerationOutput(sem_ids=generated_ids, log_probas=log_probas)
 
     @torch.no_grad()
@@ -516,7 +542,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
         n_items defaults to top_k_for_generation (at most 256).  With exclude_history the items of batch.sem_ids -- the
         batch's tensor as it is, dedup column included, negative ids being padding -- are never returned.  A user gets
         fewer than n_items items (-1 / -inf padded) when the finite beams' tuples carry fewer.  After the encoder nothing
-        is read back to the host and no allocation depends on data, as in `generate`."""
+        is read back to the host and no allocation depends on data, as in `generate` -- whose packed form (a
+        CountedSeqBatch under encoder_rows = "packed") this call takes too, with the same items and scores."""
         n_items = self.top_k_for_generation if n_items is None else int(n_items)
         generated = self.generate_next_sem_id(batch)
         index = self._item_index_for_codebooks()   # `generate` has moved `codebooks` to the batch's device

@@ -131,6 +131,16 @@ the fused attention this forward is in anyway (`T5Stack._attention_mode`, which 
 attention predicates do) and every length within the short kernel's 256; elsewhere they raise -- modules/model.py checks
 before it packs and runs the padded path instead.  N depends on the data, so a packed forward cannot be replayed from a
 captured graph.
+A decoder forward with `encoder_packed` may also be the cached decode step of a beam search, under no_grad: it takes
+`cross_kv` (of the [1, N, d] encoder output) and a `decode_cache` beside `encoder_packed`, with R = batch * beams query
+rows, rows b * beams .. of which read encoder row b.  Its self-attention stays on the slabs and the short kernel, as
+without packed rows; its cross-attention is ONE ops.t5_attention_packed_beams call per block (csrc/t5_attention.hip, the
+same kernel body: the dense arm's groups of beams over the packed arm's K/V), which on every query has the bits of the
+padded call with the prefix key mask, and at beams = 1 (the first step) those of ops.t5_attention_packed.  The same call
+serves a forward without a cache whose query rows outnumber the encoder rows; with as many query rows as encoder rows
+and no cache the cross-attention is the packed call above.  `packed_rows_active` is asked with the step's query length
+1.  What still raises with packed rows: an `encoder_attention_mask` or `attention_mask`, an operator-format
+`past_key_values`, and grad enabled with beams > 1 or with a decode_cache (there is no backward for the beams).
 
 The fused forms take their dropout seeds as int64s drawn on the device with torch.randint (the default generator:
 torch.manual_seed reproduces a run), none in eval mode or at dropout_rate 0.  The fused attention draws one per call.
@@ -496,7 +506,9 @@ class _HipAttention:
                  encoder_packed: Optional[PackedRows] = None) -> None:
         """packed: the stack's own rows are packed ([1, N, d], T = packed.bound): every self-attention is a packed
         call with both tables.  encoder_packed: the encoder output is ([1, N, d]): every cross-attention is a packed
-        call of the dense queries over packed K/V.  Neither takes a mask: every packed token is valid."""
+        call of the dense queries over packed K/V -- on the cached decode step (`cache`, no_grad), and wherever the
+        query rows outnumber the encoder rows, ONE ops.t5_attention_packed_beams call, the beams of a user as the query
+        rows of its packed row.  Neither takes a mask: every packed token is valid."""
         self.packed, self.encoder_packed = packed, encoder_packed
         self.train, self.plan = train, plan
         self.long = stack.attention_long_impl == "hip"  # calls the short kernel does not support go to the long one
@@ -570,7 +582,13 @@ class _HipAttention:
         k, v = (t.transpose(1, 2).reshape(t.shape[0], t.shape[2], -1) for t in self.cross_kv[i])
         q = _project(self.plan, normed, (module.q,))[0]
         if self.encoder_packed is not None:
-            out = self._launch_packed(module, q, k.squeeze(0), v.squeeze(0), None, 0, None, self.encoder_packed)
+            rows = self.encoder_packed
+            beams = q.shape[0] // rows.batch
+            if self.cache is not None or beams > 1:  # the decode step (no_grad): the beams of a user over its packed row
+                out = ops.t5_attention_packed_beams(q, k.squeeze(0), v.squeeze(0), module.n_heads, cu_k=rows.cu,
+                                                    max_k=rows.bound, beams=beams)
+            else:
+                out = self._launch_packed(module, q, k.squeeze(0), v.squeeze(0), None, 0, None, rows)
             return _project(self.plan, out, (module.o,))[0]
         return _project(self.plan, self._launch(module, q, k, v, None, 0, self.cross_mask, False), (module.o,))[0]
 
@@ -806,17 +824,27 @@ class T5Stack(nn.Module):
             rows = packed if packed is not None else encoder_packed
             if self.is_decoder != (packed is None):
                 raise ValueError("packed rows: an encoder takes `packed`, a decoder `encoder_packed`")
-            if (past_key_values is not None or decode_cache is not None or attention_mask is not None
-                    or encoder_attention_mask is not None):
-                raise ValueError("packed rows take no mask and no cache: every packed token is valid")
+            if past_key_values is not None or attention_mask is not None or encoder_attention_mask is not None:
+                raise ValueError("packed rows take no mask and no operator-format cache (past_key_values): every packed "
+                                 "token is valid, and the cached decode step keeps its history in a decode_cache")
             if rows.cu.numel() != rows.batch + 1 or (packed is not None and (R != 1 or T != rows.rows)):
                 raise ValueError("packed rows: inputs_embeds is [1, N, d] and cu has batch + 1 entries")
+            if packed is not None and decode_cache is not None:
+                raise ValueError("packed rows: a decode_cache belongs to the decoder (`encoder_packed`)")
+            if packed is None and (rows.batch < 1 or R % rows.batch != 0):
+                raise ValueError(f"packed rows: {R} query rows are not a multiple of the {rows.batch} encoder rows")
+            if packed is None and torch.is_grad_enabled() and (R != rows.batch or decode_cache is not None):
+                raise ValueError("packed rows under grad take one encoder row per query row (beams = 1) and no "
+                                 "decode_cache: the beams' cross-attention has no backward")
             if not self.packed_rows_active(inputs_embeds, T, rows.bound):
                 raise ValueError('packed rows need the fused attention (attention_impl "hip" / "hip_train", as this '
                                  f"forward would take it) and every length within 256, got bound {rows.bound}")
+            if decode_cache is not None and (T != 1 or decode_cache.pos >= decode_cache.steps or R > decode_cache.rows):
+                raise ValueError("decode_cache takes one new position per call, within its steps and rows, and no "
+                                 "past_key_values or attention_mask")
             if self.is_decoder and cross_kv is None:
                 cross_kv = self.cross_kv(encoder_hidden_states, plan)
-            return _HipAttention(self, rows.bound if packed is not None else T, None, None, cross_kv, None,
+            return _HipAttention(self, rows.bound if packed is not None else T, None, None, cross_kv, decode_cache,
                                  train=torch.is_grad_enabled(), plan=plan, packed=packed, encoder_packed=encoder_packed)
         if decode_cache is not None or (self.attention_impl != "torch" and past_key_values is None):
             if self.is_decoder and cross_kv is None:

@@ -24,6 +24,11 @@ reports, from the same `generate` call.  Without exclude_history an item hit at 
 position <= p, so every item h@k is at most the tuple h@k; the gap is what tuple collisions hide.  The target item is
 the corpus row with the target's tuple and dedup rank; a target that is no corpus row cannot be scored, so the run
 raises when it meets one (counted on the device, read once at the end with the metrics).  One process, one GPU.
+
+Packed encoder rows: as evaluate_decoder.evaluate, `recommend` reads the binding `encoder_rows.mode` of
+train_decoder.encoder_rows before any other work; with "packed" the loader carries the rows' item counts
+(host_windows=True: the same tensors in the same order) and `model.recommend_items` searches on the valid tokens only,
+returning the padded run's items and scores (configs/decoder_amazon_recommend_packed.gin).
 """
 import torch
 
@@ -34,7 +39,7 @@ from modules.model import EncoderDecoderRetrievalModel
 from modules.tokenizer.semids import SemanticIdTokenizer
 from modules.utils import parse_config
 from rqhip import ops
-from train_decoder import load_checkpoint
+from train_decoder import encoder_rows, load_checkpoint
 
 try:
     import gin
@@ -77,6 +82,7 @@ def recommend(
     exclude_history=True,
     output_path=None,
 ):
+    rows = encoder_rows()      # "padded", or "packed" by the binding encoder_rows.mode: validated before any other work
     if checkpoint_path is None:
         raise ValueError("recommend needs checkpoint_path: a checkpoint written by train_decoder.py")
     if dataset != RecDataset.AMAZON:
@@ -96,7 +102,8 @@ def recommend(
         rqvae_codebook_normalize=vae_codebook_normalize, rqvae_sim_vq=vae_sim_vq).to(device)
     tokenizer.precompute_corpus_ids(item_dataset)
     corpus = tokenizer.cached_ids[:, :vae_n_layers].contiguous()
-    eval_dataloader = TokenizedSeqLoader(eval_dataset, tokenizer, batch_size, shuffle=False)
+    # packed: the batches carry their rows' item counts on the host; same tensors, same order (no shuffle, no subsampling)
+    eval_dataloader = TokenizedSeqLoader(eval_dataset, tokenizer, batch_size, shuffle=False, host_windows=rows == "packed")
 
     model = EncoderDecoderRetrievalModel(
         codebooks=torch.zeros_like(corpus), num_hierarchies=vae_n_layers, num_embeddings_per_hierarchy=vae_codebook_size,
@@ -111,6 +118,7 @@ def recommend(
             "(pretrained_rqvae_path) and the same dataset")
     model.attention_impl, model.norm_impl, model.ffn_impl, model.embed_impl = attention_impl, norm_impl, ffn_impl, embed_impl
     model.beam_impl = beam_impl
+    model.encoder_rows = rows
     model.eval()
 
     item_metrics = TopKAccumulator(ks=top_k_eval_list)

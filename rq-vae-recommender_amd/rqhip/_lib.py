@@ -123,6 +123,8 @@ SIGNATURES = {
     "rqhip_t5_attention_packed_bwd": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int,
                                              _int, _int, _int, _vp, _vp, _vp, _int, _int, _vp, _int, C.c_double, _vp, _vp,
                                              _vp, _vp, _vp, _vp, _vp]),
+    "rqhip_t5_attention_packed_beams": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _vp,
+                                               _vp, _i64, _vp]),
     "rqhip_rows_pack_supported": (_int, [_int]),
     "rqhip_rows_pack": (_int, [_vp, _vp, _i64, _int, _int, _i64, _vp, _vp]),
     "rqhip_rows_unpack": (_int, [_vp, _vp, _i64, _int, _int, _i64, _vp, _vp]),

@@ -939,6 +939,42 @@ def t5_attention_packed(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, cu_q: 
     return out
 
 
+def t5_attention_packed_beams(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, cu_k: Tensor, max_k: int,
+                              beams: int) -> Tensor:
+    """The cross-attention of a cached decode step over packed encoder rows in one launch
+    (rqhip_t5_attention_packed_beams), inference only: q [R, Tq, n_heads * 64] dense, R = groups * beams, rows
+    b * beams .. b * beams + beams - 1 reading group b, whose keys are rows cu_k[b] .. cu_k[b + 1] - 1 of k, v
+    [n_k, n_heads * 64] (cu_k int32 [R // beams + 1] on the device, at most max_k keys a group).  No bias table and no
+    mask.  q and k / v may be views with a larger row stride (the grouped projections' and cross_kv's outputs): nothing
+    is copied.  With beams = 1 the result has the bits of t5_attention_packed(cu_q=None), and on every query those of
+    t5_attention on the scattered k / v with the prefix key mask."""
+    _need_gpu(q, k, v, cu_k)
+    who = "t5_attention_packed_beams"
+    inner, beams = int(n_heads) * 64, int(beams)
+    q, R, _, Tq = _packed_side(who, q, "q", None, None, inner)
+    if beams < 1 or R % beams != 0:
+        raise RqHipError(f"{who}: beams={beams} does not divide the R={R} query rows")
+    if cu_k is None:
+        raise RqHipError(f"{who}: cu_k is required (the dense call is t5_attention)")
+    if k.shape != v.shape:
+        raise RqHipError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
+    k, Rk, n_k, Tk = _packed_side(who, k, "k", cu_k, max_k, inner)
+    v = _packed_side(who, v, "v", cu_k, max_k, inner)[0]
+    if Rk != R // beams:
+        raise RqHipError(f"{who}: the table of k must be a contiguous int32 [R // beams + 1 = {R // beams + 1}] tensor, "
+                         f"got {tuple(cu_k.shape)}")
+    if k.stride(0) != v.stride(0):
+        k, v = k.contiguous(), v.contiguous()
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((R, Tq, inner), dtype=torch.float32, device=dev)
+        rc = _lib.lib().rqhip_t5_attention_packed_beams(
+            _ptr(q), int(q.stride(1)), _ptr(k), _ptr(v), int(k.stride(0)), R, Rk, n_k, int(n_heads), 64, Tq, Tk,
+            _ptr(cu_k), _ptr(out), inner, _stream())
+        check(rc, "rqhip_t5_attention_packed_beams")
+    return out
+
+
 def t5_attention_packed_fwd_train(q: Tensor, k: Tensor, v: Tensor, n_heads: int, *, cu_q: Optional[Tensor] = None,
                                   cu_k: Optional[Tensor] = None, max_q: Optional[int] = None,
                                   max_k: Optional[int] = None, bias_by_delta: Optional[Tensor] = None,

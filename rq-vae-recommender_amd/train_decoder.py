@@ -37,6 +37,11 @@ What differs:
     holds, and the encoder, the cross-attention K/V and every kernel between them run on the valid tokens only.  The
     number of rows of such a step depends on the data, so a packed step cannot be captured into a graph.  The
     checkpoint is the same: it loads into a padded model and back.  configs/decoder_amazon_packed.gin.
+    The binding covers the training steps and the partial evals.  The full eval's beam search stays PADDED in this
+    script, although its batches carry their counts and `model.generate_next_sem_id` would run them packed with the
+    same bits (modules/model.py): tests/test_gpu_packed_model.py pins the packed and pack calls of a packed training
+    run that ends in a full eval, and that pin is kept.  evaluate_decoder.py and recommend.py read the same binding
+    and run the search packed (configs/decoder_amazon_eval_packed.gin, configs/decoder_amazon_recommend_packed.gin).
     push_vae_to_hf=True raises: it needs the network.  Datasets other than AMAZON raise, as in the
     reference.
 wandb is optional: with `wandb_logging=True` and no wandb module, metrics are printed.
@@ -258,9 +263,11 @@ def train(
 
         if (it + 1) % full_eval_every == 0:
             model.eval()
+            model.encoder_rows = "padded"      # the full eval's search stays padded (module docstring)
             for tokenized_data in eval_dataloader:
                 generated = model.generate_next_sem_id(tokenized_data, top_k=True, temperature=1)
                 metrics_accumulator.accumulate(actual=tokenized_data.sem_ids_fut[:, :vae_n_layers], top_k=generated.sem_ids)
+            model.encoder_rows = encoder_rows()
             eval_metrics = metrics_accumulator.reduce()
             print(eval_metrics)
             emit(eval_metrics)

@@ -20,6 +20,13 @@ alternates the two --runs times on one --attention arm and ends with a summary l
 medians and their spread.  --images sets weight_images (modules/t5.py) under `--arith bf16` on the kernel path: "bf16" reads
 the weights of the two "hip" forms from bf16 images; `--images both` alternates "none" and "bf16" --runs times and ends
 with a summary line of the medians over the runs' block medians and their spread.
+--rows sets encoder_rows (modules/model.py) of the kernel path under --attention hip: "packed" runs the encoder, the cross
+K/V and every decode step's cross-attention on the valid tokens only.  It times --batches counted batches of --batch users
+from data.seq_loader.TokenizedSeqLoader(host_windows=True) over the synthetic:12101 histories, cycled: --fill eval = the
+eval split's whole histories (fill about 0.75), --fill train = histories cut by the training window law (about 0.35).
+`--rows padded,packed` alternates the two arms --runs times in one process (the rule of
+profiles/retrieval_train_step_proj.txt) and ends with a summary line: per arm the median over the block medians, their
+spread and the peak allocated memory.  --norm and --embed set norm_impl and embed_impl there.
 
 Device events around each generate after a warm-up; prints one JSON line per path (ms per generate, users/s).
 Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --stats` run of this tool
@@ -28,6 +35,8 @@ Kernel launches per generate come from a separate `rocprofv3 --kernel-trace --st
     python tools/bench_generate.py [--path kernel|reference|both] [--attention torch|hip|both] [--runs 5]
                                    [--proj torch|hip] [--ffn torch|hip] [--arith fp32|bf16|both]
                                    [--images none|bf16|both] [--beam sample|exact|both] [--warmup 3] [--iters 10]
+                                   [--rows padded|packed|padded,packed] [--fill eval|train] [--batch 640] [--batches 4]
+                                   [--norm torch|hip] [--embed torch|hip]
 """
 import argparse
 import json
@@ -108,8 +117,97 @@ def time_path(model, batch, warmup, iters):
     return times[len(times) // 2], times[0]
 
 
+def loader_batches(corpus, B, n, dev, law, seed=0):
+    """n counted batches of B rows from TokenizedSeqLoader(host_windows=True) over the synthetic histories of the corpus'
+    size: law "eval" = the eval split as evaluate_decoder.py reads it (whole histories up to the 20 slots), "train" = the
+    same histories cut by the training window law (subsample).  -> (batches, fill: valid items / item slots)."""
+    from data.processed import RecDataset, SeqData
+    from data.seq_loader import TokenizedSeqLoader
+    from modules.tokenizer.semids import SemanticIdTokenizer
+    N, L = corpus.shape
+    train = law == "train"
+    ds = SeqData(root=f"synthetic:{N}", dataset=RecDataset.AMAZON, is_train=train, subsample=train).to_device(dev)
+    tok = SemanticIdTokenizer(input_dim=16, output_dim=8, hidden_dims=[16], codebook_size=256, n_layers=L, n_cat_feats=0)
+    tok.cached_ids = torch.cat([corpus, torch.zeros(N, 1, dtype=torch.long)], dim=1).to(dev)
+    torch.manual_seed(seed)
+    out = []
+    for batch in TokenizedSeqLoader(ds, tok, B, shuffle=True, host_windows=True):
+        if batch.sem_ids.shape[0] == B:
+            out.append(batch)
+        if len(out) == n:
+            break
+    fill = sum(float(b.item_counts.sum()) for b in out) / (len(out) * B * ds.max_seq_len)
+    return out, fill
+
+
+def rows_block(model, batches, rows, warmup, iters):
+    """One block of one --rows arm -> (ms per generate of the timed calls, peak allocated bytes)."""
+    model.encoder_rows = rows
+    for i in range(warmup):
+        model.generate_next_sem_id(batches[i % len(batches)])
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    times = []
+    for i in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        model.generate_next_sem_id(batches[i % len(batches)])
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return times, torch.cuda.max_memory_allocated()
+
+
+def compare_rows(args, model, dev):
+    """--rows: the arms (encoder_rows of modules/model.py) alternate --runs times in this process over the same counted
+    batches; one line per block, then one summary line: per arm the median of the block medians, their spread
+    (max - min) and the peak memory."""
+    arms = args.rows.split(",")
+    batches, fill = loader_batches(model.codebooks.cpu(), args.batch, args.batches, dev, args.fill)
+    model.attention_impl, model.matmul_arith, model.beam_impl = args.attention, args.arith, args.beam
+    if "packed" in arms:      # a batch that fell back to the padded path, silently, would be timed as packed
+        model.encoder_rows = "packed"
+        L = model.num_hierarchies
+        with torch.no_grad():      # as `generate` asks
+            plans = [model.packed_rows_plan(b.item_counts, b.sem_ids, b.user_ids is not None, ld_item=L + 1,
+                                            query_length=1) for b in batches]
+        if any(plan is None for plan in plans):
+            raise SystemExit("--rows packed: a batch of this run would take the padded path (modules/model.py)")
+    common = {"path": "kernel", "attention": args.attention, "proj": args.proj, "ffn": args.ffn, "norm": args.norm,
+              "embed": args.embed, "arith": args.arith, "beam": args.beam, "batch": args.batch, "fill_law": args.fill,
+              "fill": round(fill, 4), "batches": len(batches)}
+    medians, peaks = {arm: [] for arm in arms}, {arm: 0 for arm in arms}
+    for run in range(args.runs):
+        for arm in arms:
+            times, peak = rows_block(model, batches, arm, args.warmup, args.iters)
+            times.sort()
+            medians[arm].append(times[len(times) // 2])
+            peaks[arm] = max(peaks[arm], peak)
+            print(json.dumps({**common, "rows": arm, "run": run, "ms_per_generate_median": round(medians[arm][-1], 3),
+                              "ms_per_generate_min": round(times[0], 3), "peak_allocated_MiB": round(peak / 2 ** 20, 1),
+                              "iters": args.iters}), flush=True)
+    mid = {arm: sorted(v)[len(v) // 2] for arm, v in medians.items()}
+    print(json.dumps({**common, "rows": args.rows, "runs": args.runs,
+                      **{f"block_medians_{arm}": [round(v, 3) for v in medians[arm]] for arm in arms},
+                      **{f"ms_per_generate_{arm}": round(mid[arm], 3) for arm in arms},
+                      **{f"spread_{arm}": round(max(medians[arm]) - min(medians[arm]), 3) for arm in arms},
+                      **{f"peak_allocated_MiB_{arm}": round(peaks[arm] / 2 ** 20, 1) for arm in arms},
+                      **({"padded_over_packed": round(mid["padded"] / mid["packed"], 4)} if len(arms) == 2 else {}),
+                      "device": torch.cuda.get_device_name(0)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", choices=["padded", "packed", "padded,packed"], default=None,
+                    help="encoder_rows of the kernel path on counted loader batches (--fill); padded,packed alternates the "
+                         "two --runs times and ends with a summary line")
+    ap.add_argument("--fill", choices=["eval", "train"], default="eval",
+                    help="with --rows: whole eval histories (fill about 0.75) or histories cut by the training window law "
+                         "(about 0.35)")
+    ap.add_argument("--batch", type=int, default=640, help="with --rows: users per generate")
+    ap.add_argument("--batches", type=int, default=4, help="with --rows: loader batches, drawn once and cycled")
+    ap.add_argument("--norm", choices=["torch", "hip"], default="torch", help="with --rows: norm_impl")
+    ap.add_argument("--embed", choices=["torch", "hip"], default="torch", help="with --rows: embed_impl")
     ap.add_argument("--path", choices=["kernel", "reference", "both"], default=None,
                     help="default: both, or kernel with --attention both")
     ap.add_argument("--attention", choices=["torch", "hip", "both"], default="torch")
@@ -125,6 +223,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
+    if args.rows is not None:
+        if args.attention != "hip" or args.arith == "both" or args.beam == "both" or args.images != "none" or \
+                args.path not in (None, "kernel"):
+            ap.error("--rows applies to --path kernel with --attention hip, one --arith and one --beam")
+        dev = torch.device("cuda")
+        model, _ = build(dev, B=1)
+        model.proj_impl, model.ffn_impl, model.norm_impl, model.embed_impl = args.proj, args.ffn, args.norm, args.embed
+        compare_rows(args, model, dev)
+        return
     if args.path is None:
         args.path = "kernel" if args.attention == "both" or args.beam != "sample" else "both"
     dev = torch.device("cuda")
